@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — BCD X3D-L train throughput (images/s) on N MI355X, one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one full training iteration of the reference loop (reference
@@ -31,6 +31,7 @@ HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 A_BCD_ELEMS = 159_784_960        # materialised activation elements per sample
 A_SCD_ELEMS = 269_280_000        # same for the SCD path (K=3, T=5; SURVEY.md §8d: 269.28 M)
 A_CC_ELEMS = 170_270_000         # change-captioning encoder (blocks 0-4, K=1; SURVEY.md §8d: 170.27 M; decoder < 0.1 %)
+DUMP_BUDGET_BYTES = 60 * 10**6   # --dump-outputs writes at most this much array data in all (under 64 MB with the .npy headers)
 
 
 def parse():
@@ -68,6 +69,11 @@ def parse():
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="c3d_set_option before the run (A/B of the library's run-time options, e.g. FUSE_WGRAD=1)")
     ap.add_argument("--kernel-table", default="", help="write the per-kernel HIP-event table (JSON) here")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, network output, parameters after "
+                         "the optimiser, their gradients) as DIR/<name>.npy.  That step starts from the seeded weights and a fresh "
+                         "optimiser state (three device copies inside the timed region, < 0.01 %% of it), so every input of it is a "
+                         "function of the arguments and two builds of the library can be compared output for output")
     return ap.parse_args()
 
 
@@ -147,6 +153,29 @@ def cpu_baseline(size, budget_s=45.0):
             "phases_s": {"fwd_loss": round(phase[0], 2), "bwd": round(phase[1], 2), "optimizer": round(phase[2], 3)},
             "sample": f"{done} of the {n_pass} micro-batches of {micro} that make SURVEY 8(d) config 1 (32 {size}x{size} pairs), "
                       f"one train step each (1 warm-up micro-batch, {warm:.1f}s), fp32, torch-CPU eager NCDHW, {cores} threads"}
+
+
+def dump_outputs(dirname, tensors):
+    """`--dump-outputs`: DIR/<name>.npy for each tensor, float64 kept, everything else as float32, DUMP_BUDGET_BYTES in
+    all.  Smallest first, each array may take an equal share of the bytes still free; one that is larger is written as a
+    fixed sample of its flattened elements (ascending indices drawn from RandomState(0), a function of the sizes only),
+    so the same arguments give the same elements in every run and every build.
+    Returns {name: [elements written, elements of the tensor]}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        arr = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        arrays[name] = arr.reshape(1) if arr.ndim == 0 else arr
+    left, written = DUMP_BUDGET_BYTES, {}
+    for i, (name, arr) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        total, keep = arr.size, left // (len(arrays) - i) // arr.itemsize
+        if total > keep:
+            arr = arr.reshape(-1)[np.sort(np.random.RandomState(0).choice(total, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        left -= arr.nbytes
+        written[name] = [int(arr.size), int(total)]
+    return written
 
 
 def pmc_traffic(entry):
@@ -358,6 +387,8 @@ def main():
         caps, caplens = (t.to(dev) for t in synth.synth_captions(a.batch, seed=rank, vocab_size=501))
     else:
         opt = FusedAdam(arena, lr=margs.lr, capturable=True)
+    opts = [opt, dec_opt] if cc else [opt]
+    seeded = [o.arena.flat_param.clone() for o in opts] if a.dump_outputs else None
     meter = ConfuseMatrixMeter(2)
     pre, post, tgt = (t.to(dev) for t in synth.synth_batch(a.batch, a.size, seed=rank))
     if scd:
@@ -468,6 +499,20 @@ def main():
         if state["it"] % 5 == 0:  # reference prints (and syncs on) the loss every 5 iterations
             state["last_loss"] = float(state["loss"])
 
+    def rewind():
+        """--dump-outputs: the synthetic weights and a fresh Adam state again (in-place device copies, no sync), so that the
+        step that follows computes a function of the command line alone.  Without it the dump is not comparable between two
+        runs of ONE build: the chained Adam steps of a run (65 with the default arguments) on this train-mode-BatchNorm
+        network amplify the last-bit differences of the f32 atomics (one step: gradients reproducible to 6e-7) to O(1)
+        differences of the output."""
+        for o, w0 in zip(opts, seeded):
+            o.arena.flat_param.copy_(w0)
+            o.exp_avg.zero_()
+            o.exp_avg_sq.zero_()
+            o.step_count = 0
+        ops.bump_weights_version()
+        torch.default_generator.manual_seed(0)   # the caption decoder draws its dropout seed from torch's CPU generator
+
     # Settling steps (untimed, reported as config.settle_steps): the first process on a freshly leased box runs its first
     # seconds with cold CPU caches and ramping GPU clocks (measured: 35.0 vs 32.8 ms per step, host enqueue 15.9 vs
     # 6.5 ms); a fixed number of extra steps, the same on every rank, before the W warm-up steps the caller asked for.
@@ -490,7 +535,9 @@ def main():
     windows = []
     nwin = a.windows if (a.windows > 1 and world == 1 and a.steps % a.windows == 0) else 1
     for w_ in range(nwin):
-        for _ in range(a.steps // nwin):
+        for k_ in range(a.steps // nwin):
+            if a.dump_outputs and w_ == nwin - 1 and k_ == a.steps // nwin - 1:
+                rewind()   # the last timed step is the one that is dumped
             step()
         if nwin > 1:
             torch.cuda.synchronize()
@@ -518,6 +565,14 @@ def main():
     final_loss = float(state["loss"])
     if not (final_loss == final_loss):
         raise SystemExit("loss is NaN")
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # here, before the kernel-profile step below runs the optimiser once more: what the last TIMED step (run from
+        # the seeded state, see rewind) returned (loss, output) and left behind (parameters after Adam, the gradients it consumed)
+        tensors = {"loss": state["loss"], "output": state["prob"], "params": arena.flat_param, "grads": arena.flat_grad}
+        if cc:
+            tensors.update({"decoder_params": dec_arena.flat_param, "decoder_grads": dec_arena.flat_grad})
+        dumped = dump_outputs(a.dump_outputs, tensors)
 
     ms_per_step = elapsed / a.steps * 1e3
     value = a.batch * world * a.steps / elapsed
@@ -540,7 +595,7 @@ def main():
                    "host_enqueue_ms_per_step": round(t_enqueued / a.steps * 1e3, 3),
                    "ms_per_step_windows": ([round((t_ - p_) / (a.steps // nwin) * 1e3, 3) for p_, t_ in zip([t0] + windows[:-1], windows)]
                                            if nwin > 1 else None)},
-        "dp": dp_diag,
+        "dp": dp_diag, "dumped_outputs": dumped,
         "step_roofline": {"bound": "hbm", "algorithmic_bytes_per_sample": bytes_per_sample,
                           "achieved": round(value / world * bytes_per_sample / 1e9, 1), "peak": HBM_PEAK_GBS,
                           "unit": "GB/s", "frac": round(value / world * bytes_per_sample / 1e9 / HBM_PEAK_GBS, 4)},
