@@ -131,6 +131,26 @@ __global__ __launch_bounds__(256) void scd_label_kernel(const uint8_t* __restric
   }
 }
 
+// BDA labels (reference data/transforms.py:502-526 BDATransforms.random_flip / random_exchange, :541-556 to_tensor;
+// scripts/train_BDA.py:194-195 `label[:, 0].float()`, `torch.prod(label, dim=1).long()`): label u8 [B][H][W][2] =
+// (localisation, damage class) with the two flips of the image pass -> label_loc f32 [B][1][H][W] and
+// label_cls int64 [B][H][W] = localisation x damage class.  The exchange flag swaps the IMAGES only: the labels describe
+// the post-disaster state whichever way round the pair is fed (flags[b][2] is not read here).
+__global__ __launch_bounds__(256) void bda_label_kernel(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ flags,
+                                                        float* __restrict__ loc, int64_t* __restrict__ cls, int B, int H, int W) {
+  const int64_t total = (int64_t)B * H * W;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int x = (int)(i % W);
+    const int64_t r = i / W;
+    const int y = (int)(r % H), b = (int)(r / H);
+    const bool fy = flags && flags[b * 3 + 0], fx = flags && flags[b * 3 + 1];
+    const uint8_t* p = lab + (((int64_t)b * H + (fy ? H - 1 - y : y)) * W + (fx ? W - 1 - x : x)) * 2;
+    const uint8_t l0 = p[0], l1 = p[1];
+    loc[i] = (float)l0;
+    cls[i] = (int64_t)l0 * (int64_t)l1;       // torch.prod of a uint8 tensor accumulates in int64: no wrap
+  }
+}
+
 // Change-captioning image pairs (reference data/dataset.py:411-424 CaptionDataset.__getitem__ + scripts/train_CC.py:466-469
 // transforms.Normalize): img u8 [B][2][3][H][W] (planar, as the HDF5 file stores them) -> pre, post f32 [B][3][H][W] =
 // Normalize(FloatTensor(u8 / 255.)) through a 3 x 256 table built by the HOST with exactly that arithmetic (f64 division,
@@ -160,6 +180,17 @@ extern "C" int c3d_scd_label_preprocess(const uint8_t* label3, const uint8_t* fl
   int64_t grid = ((int64_t)B * H * W + 255) / 256;
   if (grid > 256 * 32) grid = 256 * 32;
   scd_label_kernel<<<dim3((unsigned)grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(label3, flags, out, B, H, W);
+  C3D_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int c3d_bda_label_preprocess(const uint8_t* label2, const uint8_t* flags, float* label_loc, int64_t* label_cls,
+                                        int32_t B, int32_t H, int32_t W, void* stream) {
+  if (!label2 || !label_loc || !label_cls || B <= 0 || H <= 0 || W <= 0) return C3D_E_BADARG;
+  int64_t grid = ((int64_t)B * H * W + 255) / 256;
+  if (grid > 256 * 32) grid = 256 * 32;
+  bda_label_kernel<<<dim3((unsigned)grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(label2, flags, label_loc,
+                                                                                                 label_cls, B, H, W);
   C3D_CHECK_LAUNCH();
   return 0;
 }

@@ -109,6 +109,10 @@ template <int TT> __device__ __forceinline__ void pin_acc(f32x2_t (&a)[TT][2]);
 template <> __device__ __forceinline__ void pin_acc<3>(f32x2_t (&a)[3][2]) {
   asm volatile("" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]) : : "memory");
 }
+template <> __device__ __forceinline__ void pin_acc<4>(f32x2_t (&a)[4][2]) {
+  asm volatile("" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]),
+               "+v"(a[3][1]) : : "memory");
+}
 template <> __device__ __forceinline__ void pin_acc<5>(f32x2_t (&a)[5][2]) {
   asm volatile("" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]),
                "+v"(a[3][1]), "+v"(a[4][0]), "+v"(a[4][1]) : : "memory");
@@ -628,12 +632,15 @@ struct RingPlan {
   // three frames: the `a` rows ride in the slot too and the ring is three slots deep (two tiles ahead); five frames (SCD):
   // a slot is 64 KB, two fit -- one tile ahead, like the register prefetch, but in no registers -- and the `a` rows stay
   // register loads
-  static constexpr bool A_LDS = TT <= 3;
+  // four frames (BDA): a slot is 50 KB of raw rows + 16 KB of `a` rows; three of them do not fit (206 KB), two do (139 KB) --
+  // one tile ahead with the `a` rows in LDS, so no register holds anything of the next tile (the five-frame register kernel
+  // spills; three slots with `a` in registers would be 158 KB and need counted waits that skip the compiler's own loads)
+  static constexpr bool A_LDS = TT <= 4;
   static constexpr int NA = A_LDS ? (TT * 8 * DW_CV + 63) / 64 : 0;   // `a` pieces per wave: TT frames x 8 pixels x 4 vectors
   static constexpr int A_WAVE_BYTES = TT * 8 * DW_CV * 16;
   static constexpr int A_BYTES = A_LDS ? 8 * A_WAVE_BYTES : 0;
   static constexpr int SLOT_BYTES = 2 * NPL * 16 + A_BYTES;
-  static constexpr int R = A_LDS ? 3 : 2;
+  static constexpr int R = TT <= 3 ? 3 : 2;
   static constexpr int AHEAD = R - 1;
   static constexpr int HEAD_BYTES = (27 * 32 + 7 * 32) * 4;
   static constexpr int LDS_BYTES = HEAD_BYTES + R * SLOT_BYTES;
@@ -1044,9 +1051,11 @@ namespace {
 int dispatch_fused(const void* t1, const void* b, const float* coefA, const float* coefB, const float* coefC, const float* w,
                    const void* a, const float* ss_a, const float* mr_a, void* t2, double* dsums, float* dw, const DwGeom& g,
                    int dtype, hipStream_t s, const c3d_bn_fin& fin) {
+  const int tt = dw_frames(g.T);
 #define FB_DISPATCH(TY, S_)                                                                                         \
-  return g.T <= 3 ? launch_fused_t<TY, 3, S_>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin)  \
-                  : launch_fused_t<TY, 5, S_>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
+  return tt == 3 ? launch_fused_t<TY, 3, S_>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin)   \
+       : tt == 4 ? launch_fused_t<TY, 4, S_>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin)   \
+                 : launch_fused_t<TY, 5, S_>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
   if (dtype == C3D_DT_F32) {
     if (g.stride == 1) { FB_DISPATCH(float, 1) }
     FB_DISPATCH(float, 2)
@@ -1056,9 +1065,13 @@ int dispatch_fused(const void* t1, const void* b, const float* coefA, const floa
     // 16-tile walks pay the two-tile ring fill: res4 of the BCD step 65.9 us with the register prefetch, 68.0 us with the
     // ring; the five-frame register kernel spills, its ring variant wins on every map: SCD 663 -> 681 img/s)
     if (C3D_FB_ROWS == 8 && g.stride == 1 && (c3d_option_dw_ring & 1) && ((c3d_option_dw_ring & 8) || g.T > 3 || (long)g.H * g.W >= 64 * 64)) {
-      if (g.T <= 3) {
+      if (tt == 3) {
         if (c3d_option_dw_ring & 4) return launch_ring_t<3, true>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
         return launch_ring_t<3, false>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
+      }
+      if (tt == 4) {
+        if (c3d_option_dw_ring & 4) return launch_ring_t<4, true>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
+        return launch_ring_t<4, false>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
       }
       if (c3d_option_dw_ring & 4) return launch_ring_t<5, true>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
       return launch_ring_t<5, false>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);

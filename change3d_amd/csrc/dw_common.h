@@ -2,6 +2,8 @@
 #pragma once
 #include "common.h"
 
+extern int c3d_option_dw_t4;   // C3D_OPT_DW_T4 (launch_hints.h)
+
 namespace {
 
 constexpr int DW_CV = 4;    // channel vectors (of 8) per workgroup pass = 32 channels
@@ -32,6 +34,10 @@ __device__ __forceinline__ ChunkOrder chunk_order(const int chunks, const int ng
 inline unsigned chunk_order_grid(const int chunks, const long ngroups) {
   return (unsigned)(((ngroups + N_XCD - 1) / N_XCD) * N_XCD * chunks);
 }
+
+// Frame-count instantiation of a clip: three frames (BCD, CC), four (BDA: num_perception_frame = 2), five (SCD).  With
+// C3D_OPT_DW_T4 = 0 a four-frame clip runs on the five-frame instantiation, its fifth frame staged as zeros.
+inline int dw_frames(const int T) { return T <= 3 ? 3 : (T == 4 && c3d_option_dw_t4) ? 4 : 5; }
 
 inline bool geom_ok(const DwGeom& g) {
   if (g.B <= 0 || g.T <= 0 || g.T > DW_MAXT || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.Cp < g.C || (g.Cp & 7))

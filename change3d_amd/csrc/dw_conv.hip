@@ -8,7 +8,7 @@
 //              out = raw conv output b; epilogue = per-(sample,channel) sum / sum-of-squares
 //              (feeds BN_b statistics and the SE squeeze).
 //
-// All T frames of a spatial tile are resident in LDS (T = 3 for BCD, 5 for SCD).  A thread
+// All T frames of a spatial tile are resident in LDS (T = 3 for BCD, 4 for BDA, 5 for SCD).  A thread
 // owns one output pixel and one 8-channel vector for all T frames.
 #include "pw_common.h"  // common.h + device_cus()
 #include "bn_fin.h"
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(TH * TW * DW_CV) void dw_fwd_kernel(
 //   * workgroup = 8x16 output pixels x 32 channels, walks `tiles_per_wg` tiles of one sample keeping
 //     the per-(sample,channel) statistics in registers, with the next tile's raw rows prefetched.
 // PYR = rows per lane: 2 (8 x 16 tiles) for three frames; 1 (4 x 16 tiles) for five frames, whose 8 x 16 tile is 115 KB of
-// LDS = one workgroup per CU (1.3 TB/s); the 4 x 16 tile is 69 KB = two.
+// LDS = one workgroup per CU (1.3 TB/s); the 4 x 16 tile is 69 KB = two.  Four frames (BDA): 92 KB against 55 KB, also 4 x 16.
 constexpr int V2_TW = 16, V2_IW = V2_TW + 2;
 
 __device__ __forceinline__ void lds_ld8v2(const float* p, float (&f)[8]) {
@@ -898,7 +898,7 @@ template <typename T, int TT>
 int launch_fwd_v2s2(const void* x, const float* ss, const float* w, void* y, double* nc, const DwGeom& g,
                     hipStream_t stream, const c3d_bn_fin* fin = nullptr) {
   const size_t lds = (27 * 32 + 64) * sizeof(float) + (size_t)DW_CV * 2 * V2S2Geo<TT>::PLANE * sizeof(float4);
-  if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;   // (five frames: 218 KB -- the v1 kernel)
+  if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;   // (four frames: 174 KB, five: 218 KB -- the v1 kernel on its own frame count)
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2s2_kernel<T, TT, false>),
@@ -985,8 +985,21 @@ int launch_fwd_t(const void* x, const float* ss, const float* w, void* y, double
 template <typename T, int S>
 int launch_fwd(const void* x, const float* ss, const float* w, void* y, double* nc, const DwGeom& g,
                hipStream_t stream) {
-  if (g.T <= 3) return launch_fwd_t<T, S, 3>(x, ss, w, y, nc, g, stream);
+  const int tt = dw_frames(g.T);
+  if (tt == 3) return launch_fwd_t<T, S, 3>(x, ss, w, y, nc, g, stream);
+  if (tt == 4) return launch_fwd_t<T, S, 4>(x, ss, w, y, nc, g, stream);
   return launch_fwd_t<T, S, 5>(x, ss, w, y, nc, g, stream);
+}
+
+// stride-1 v2 kernel on the instantiation of the clip's frame count (three: 8 x 16 tiles; four and five: 4 x 16 tiles, two
+// workgroups per CU -- a four-frame 8 x 16 tile is 92 KB of the 160 KB, one workgroup per CU, like the five-frame one was)
+template <typename T>
+int launch_fwd_v2_frames(const void* x, const float* ss, const float* w, void* y, double* nc, const DwGeom& g,
+                         hipStream_t stream, const c3d_bn_fin* fin = nullptr) {
+  const int tt = dw_frames(g.T);
+  if (tt == 3) return launch_fwd_v2<T, 3>(x, ss, w, y, nc, g, stream, fin);
+  if (tt == 4) return launch_fwd_v2<T, 4>(x, ss, w, y, nc, g, stream, fin);
+  return launch_fwd_v2<T, 5>(x, ss, w, y, nc, g, stream, fin);
 }
 
 }  // namespace
@@ -1005,10 +1018,8 @@ extern "C" int c3d_dw333_fwd(const void* x, const float* ss, const float* w, voi
 #endif
   if (stride == 1) {  // v2 mapping (wave = channel vector, lane = x-strip)
     int rc = C3D_E_UNSUPPORTED;
-    if (dtype == C3D_DT_F32) rc = T <= 3 ? launch_fwd_v2<float, 3>(x, ss, w, y, nc_sums, g, s)
-                                         : launch_fwd_v2<float, 5>(x, ss, w, y, nc_sums, g, s);
-    else if (dtype == C3D_DT_BF16) rc = T <= 3 ? launch_fwd_v2<bf16_t, 3>(x, ss, w, y, nc_sums, g, s)
-                                               : launch_fwd_v2<bf16_t, 5>(x, ss, w, y, nc_sums, g, s);
+    if (dtype == C3D_DT_F32) rc = launch_fwd_v2_frames<float>(x, ss, w, y, nc_sums, g, s);
+    else if (dtype == C3D_DT_BF16) rc = launch_fwd_v2_frames<bf16_t>(x, ss, w, y, nc_sums, g, s);
     else return C3D_E_BADARG;
     if (rc != C3D_E_UNSUPPORTED) return rc;
   }
@@ -1040,10 +1051,8 @@ extern "C" int c3d_dw333_fwd_fin(const void* x, const c3d_bn_fin* fin, const flo
 #endif
   if (!tz && stride == 1 && (dtype == C3D_DT_F32 || dtype == C3D_DT_BF16)) {
     int rc;
-    if (dtype == C3D_DT_F32) rc = T <= 3 ? launch_fwd_v2<float, 3>(x, fin->ss, w, y, nc_sums, g, s, fin)
-                                         : launch_fwd_v2<float, 5>(x, fin->ss, w, y, nc_sums, g, s, fin);
-    else rc = T <= 3 ? launch_fwd_v2<bf16_t, 3>(x, fin->ss, w, y, nc_sums, g, s, fin)
-                     : launch_fwd_v2<bf16_t, 5>(x, fin->ss, w, y, nc_sums, g, s, fin);
+    if (dtype == C3D_DT_F32) rc = launch_fwd_v2_frames<float>(x, fin->ss, w, y, nc_sums, g, s, fin);
+    else rc = launch_fwd_v2_frames<bf16_t>(x, fin->ss, w, y, nc_sums, g, s, fin);
     if (rc != C3D_E_UNSUPPORTED) return rc;
   }
   if (stride == 2 && T <= 3 && (dtype == C3D_DT_F32 || dtype == C3D_DT_BF16) && c3d_knob("C3D_DWF2_V2", 1)) {

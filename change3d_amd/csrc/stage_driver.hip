@@ -943,6 +943,7 @@ int c3d_option_pw_wgrad_v2 = 1;                            // read by pw_wgrad.h
 int c3d_option_pw_cfwd = 3;                                // read by pw_gemm.hip
 int c3d_option_pw_cdg = 3;                                 // read by pw_gemm.hip and c3d_stage_bwd
 int c3d_option_dw_fwd_hv = 5;                              // read by dw_conv.hip
+int c3d_option_dw_t4 = 1;                                  // read by dw_conv.hip / dw_bwd_fused.hip (csrc/dw_common.h)
 
 extern "C" int c3d_set_option(int32_t option, int32_t value) {
   switch (option) {
@@ -954,6 +955,7 @@ extern "C" int c3d_set_option(int32_t option, int32_t value) {
     case C3D_OPT_MASK_IN_DGRAD: g_mask_in_dgrad = value & 3; return 0;
     case C3D_OPT_DW_RING: c3d_option_dw_ring = value & 15; return 0;
     case C3D_OPT_DW_FWD_HV: c3d_option_dw_fwd_hv = value & 7; return 0;
+    case C3D_OPT_DW_T4: c3d_option_dw_t4 = value ? 1 : 0; return 0;
     case C3D_OPT_PW_CFWD: c3d_option_pw_cfwd = value & 3; return 0;
     case C3D_OPT_PW_CDG: c3d_option_pw_cdg = value & 3; return 0;
     case C3D_OPT_PW_WGRAD_V2: c3d_option_pw_wgrad_v2 = value & 1; g_wgrad_chain = (value & 2) ? 0 : 1; return 0;

@@ -351,6 +351,60 @@ extern "C" int c3d_hist2d(const int64_t* a, const int64_t* b, int64_t n_elems, i
   return 0;
 }
 
+// BDA validation (reference scripts/train_BDA.py:102-143 `val`): both confusion matrices of a batch in one pass, in
+// place of two device-to-host copies of the predictions and the numpy bincounts per iteration.
+//   counts[0..3]          cm_loc[2 * gt + pred]: gt = label_loc in {0, 1}, pred = pred_loc > 0.5 (strict, as c3d_confusion2)
+//   counts[4..4 + n*n)    cm_cls[n * gt + pred] over the pixels with label_loc > 0: gt = label_cls in [0, n),
+//                         pred = argmax over the n logits (first maximum wins, a NaN counts as the maximum: torch.argmax)
+//   counts[4 + n*n]       labels outside their range (the reference's Evaluator masks them out silently)
+// Per-wave counters in LDS (a lane's increment is an LDS atomic on its own wave's row), summed over the waves at the end:
+// one 64-bit atomic per non-empty bin and workgroup.  Integer arithmetic only: the result does not depend on the order.
+constexpr int BDA_BINS_MAX = 4 + HIST_MAXN * HIST_MAXN + 1;
+__global__ __launch_bounds__(256) void bda_confusion_kernel(const float* __restrict__ pred_cls, const float* __restrict__ pred_loc,
+                                                            const float* __restrict__ label_loc, const int64_t* __restrict__ label_cls,
+                                                            int64_t n_pix, int64_t HW, int n, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int h[4][BDA_BINS_MAX];
+  const int bins = 4 + n * n + 1;
+  for (int i = threadIdx.x; i < 4 * BDA_BINS_MAX; i += blockDim.x) (&h[0][0])[i] = 0u;
+  __syncthreads();
+  unsigned int* hw = h[threadIdx.x >> 6];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += (int64_t)gridDim.x * blockDim.x) {
+    const float gl = label_loc[i];
+    const int pl = pred_loc[i] > 0.5f ? 1 : 0;
+    if (gl >= 0.f && gl < 2.f) atomicAdd(&hw[2 * (int)gl + pl], 1u);
+    else atomicAdd(&hw[bins - 1], 1u);
+    if (gl > 0.f) {
+      const int64_t b = i / HW, p = i - b * HW;
+      const float* lg = pred_cls + b * n * HW + p;
+      float best = lg[0];
+      int arg = 0;
+      for (int c = 1; c < n; ++c) {
+        const float v = lg[(int64_t)c * HW];
+        if (v > best || (v != v && best == best)) { best = v; arg = c; }
+      }
+      const int64_t gc = label_cls[i];
+      if (gc >= 0 && gc < n) atomicAdd(&hw[4 + (int)gc * n + arg], 1u);
+      else atomicAdd(&hw[bins - 1], 1u);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < bins; i += blockDim.x) {
+    const unsigned long long v = (unsigned long long)h[0][i] + h[1][i] + h[2][i] + h[3][i];
+    if (v) atomicAdd(&counts[i], v);
+  }
+}
+
+extern "C" int c3d_bda_confusion(const float* pred_cls, const float* pred_loc, const float* label_loc, const int64_t* label_cls,
+                                 int64_t B, int32_t n, int64_t HW, unsigned long long* counts, void* stream) {
+  if (!pred_cls || !pred_loc || !label_loc || !label_cls || !counts || B <= 0 || HW <= 0 || n < 1 || n > HIST_MAXN)
+    return C3D_E_BADARG;
+  // (32-bit LDS counters: at most 2^32 - 1 pixels per wave)
+  bda_confusion_kernel<<<grid_for(B * HW, 256, 1024), 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+      pred_cls, pred_loc, label_loc, label_cls, B * HW, HW, n, counts);
+  C3D_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int c3d_abi_version(void) { return 1; }
 extern "C" const char* c3d_build_info(void) { return "change3d_hip gfx950 (MI355X) hipcc " __VERSION__; }
 

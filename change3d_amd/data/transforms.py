@@ -83,6 +83,55 @@ class DeviceSCDBatchTransform:
         return pre, post, labels
 
 
+class BDATransforms(BCDTransforms):
+    """reference data/transforms.py:413-427: same normalisation constants as BCDTransforms.  `get_transform_pipelines`
+    (reference :567-620) composes cv2 geometry (scale, random_crop_resize) with flip / exchange / normalize / to_tensor; the
+    geometry stays on the host, the rest is `DeviceBDABatchTransform`."""
+
+    @classmethod
+    def get_transform_pipelines(cls, args):
+        """(train_transform, val_transform): callables `(image6 u8 [B,H,W,6], label2 u8 [B,H,W,2], rng) -> device tensors`."""
+        mean = getattr(args, "normalize_mean", cls.DEFAULT_MEAN)
+        std = getattr(args, "normalize_std", cls.DEFAULT_STD)
+        state = {}
+
+        def make(train):
+            def transform(image6, label2, rng=None):
+                if "t" not in state:
+                    state["t"] = DeviceBDABatchTransform(torch.device("cuda", torch.cuda.current_device()), mean, std)
+                flags = draw_augmentation_flags(len(image6), rng or np.random.default_rng(), train=train)
+                return state["t"](image6, label2, flags)
+            return transform
+        return make(True), make(False)
+
+
+class DeviceBDABatchTransform:
+    """`(image6 u8 [B,H,W,6], label2 u8 [B,H,W,2], flags u8 [B,3]) -> (pre, post f32 [B,3,H,W], label_loc f32 [B,1,H,W],
+    label_cls int64 [B,H,W])` on the GPU: the tensor side of reference BDATransforms (data/transforms.py:502-556:
+    random_flip, random_exchange -- which swaps the IMAGES only --, normalize, to_tensor) and the label arithmetic of
+    scripts/train_BDA.py:194-195 (`label[:, 0].float()`, `torch.prod(label, dim=1).long()`).  The image runs through the BCD
+    pass (identical arithmetic), the labels through `c3d_bda_label_preprocess`."""
+
+    def __init__(self, device, mean=BCDTransforms.DEFAULT_MEAN, std=BCDTransforms.DEFAULT_STD):
+        self.image = DeviceBatchTransform(device, mean, std)
+        self.device = self.image.device
+
+    def __call__(self, image6, label2, flags=None):
+        label2 = torch.as_tensor(label2).to(self.device, non_blocking=True).contiguous()
+        if label2.dtype != torch.uint8 or label2.dim() != 4 or label2.shape[-1] != 2:
+            raise ValueError("label2 must be uint8 [B, H, W, 2] (localisation, damage class)")
+        B, H, W = label2.shape[:3]
+        if flags is not None:
+            flags = torch.as_tensor(flags).to(self.device, non_blocking=True).contiguous()
+            if flags.dtype != torch.uint8 or tuple(flags.shape) != (B, 3):
+                raise ValueError("flags must be uint8 [B, 3]")
+        pre, post, _ = self.image(image6, None, flags)
+        label_loc = torch.empty((B, 1, H, W), dtype=torch.float32, device=self.device)
+        label_cls = torch.empty((B, H, W), dtype=torch.int64, device=self.device)
+        ops.bda_label_preprocess(label2, flags, label_loc, label_cls, B, H, W)
+        return pre, post, label_loc, label_cls
+
+
 def cc_normalize_table(mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """f32 [3, 256]: Normalize(mean, std)(FloatTensor(u8 / 255.)) for every byte value, with the reference's own
     arithmetic (data/dataset.py:413: numpy u8 / 255. is a float64 division, rounded to f32 by FloatTensor;

@@ -1,0 +1,6 @@
+"""reference `data/transforms.py` import path -> change3d_amd.data.transforms (see ../README.md)."""
+from change3d_amd.data.transforms import *  # noqa: F401,F403
+from change3d_amd.data import transforms as _impl
+
+__all__ = [n for n in dir(_impl) if not n.startswith("_")]
+globals().update({n: getattr(_impl, n) for n in __all__})

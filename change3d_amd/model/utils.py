@@ -430,6 +430,122 @@ class SCDHistogram:
         return scd_scores_from_hist(self.matrix())
 
 
+class Evaluator(object):
+    """Confusion-matrix scores of reference model/utils.py:379-479 (`Evaluator`), same attribute and method names (its
+    spelling `Damage_F1_socore` included): `confusion_matrix[gt, pred]` as np.longlong, filled from host arrays by
+    `add_batch` -- or, in this package's `val`, handed the device counts of `c3d_bda_confusion` by `BDAEvaluator`."""
+
+    def __init__(self, num_class):
+        self.num_class = num_class
+        self.confusion_matrix = np.zeros((self.num_class,) * 2, dtype=np.longlong)
+
+    def Pixel_Accuracy(self):
+        return np.diag(self.confusion_matrix).sum() / self.confusion_matrix.sum()
+
+    def Pixel_Accuracy_Class(self):
+        Acc = np.diag(self.confusion_matrix) / (self.confusion_matrix.sum(axis=1) + 1e-7)
+        return np.nanmean(Acc), Acc
+
+    def Pixel_Precision_Rate(self):
+        assert self.confusion_matrix.shape[0] == 2
+        return self.confusion_matrix[1, 1] / (self.confusion_matrix[0, 1] + self.confusion_matrix[1, 1])
+
+    def Pixel_Recall_Rate(self):
+        assert self.confusion_matrix.shape[0] == 2
+        return self.confusion_matrix[1, 1] / (self.confusion_matrix[1, 0] + self.confusion_matrix[1, 1])
+
+    def Pixel_F1_score(self):
+        assert self.confusion_matrix.shape[0] == 2
+        Rec, Pre = self.Pixel_Recall_Rate(), self.Pixel_Precision_Rate()
+        return 2 * Rec * Pre / (Rec + Pre)
+
+    def calculate_per_class_metrics(self):
+        TPs = np.diag(self.confusion_matrix)[1:]   # class 0 excluded
+        FNs = np.sum(self.confusion_matrix, axis=1)[1:] - TPs
+        FPs = np.sum(self.confusion_matrix, axis=0)[1:] - TPs
+        return TPs, FNs, FPs
+
+    def Damage_F1_socore(self):
+        TPs, FNs, FPs = self.calculate_per_class_metrics()
+        precisions = TPs / (TPs + FPs + 1e-7)
+        recalls = TPs / (TPs + FNs + 1e-7)
+        return 2 * (precisions * recalls) / (precisions + recalls + 1e-7)
+
+    def Mean_Intersection_over_Union(self):
+        cm = self.confusion_matrix
+        return np.nanmean(np.diag(cm) / (np.sum(cm, axis=1) + np.sum(cm, axis=0) - np.diag(cm) + 1e-7))
+
+    def Intersection_over_Union(self):
+        cm = self.confusion_matrix
+        return cm[1, 1] / (cm[0, 1] + cm[1, 0] + cm[1, 1])
+
+    def Kappa_coefficient(self):
+        cm = self.confusion_matrix
+        num_total = np.sum(cm)
+        observed_accuracy = np.trace(cm) / num_total
+        expected_accuracy = np.sum(np.sum(cm, axis=0) / num_total * np.sum(cm, axis=1) / num_total)
+        return (observed_accuracy - expected_accuracy) / (1 - expected_accuracy)
+
+    def Frequency_Weighted_Intersection_over_Union(self):
+        cm = self.confusion_matrix
+        freq = np.sum(cm, axis=1) / np.sum(cm)
+        iu = np.diag(cm) / (np.sum(cm, axis=1) + np.sum(cm, axis=0) - np.diag(cm))
+        return (freq[freq > 0] * iu[freq > 0]).sum()
+
+    def _generate_matrix(self, gt_image, pre_image):
+        mask = (gt_image >= 0) & (gt_image < self.num_class)
+        label = self.num_class * gt_image[mask].astype("int64") + pre_image[mask]
+        count = np.bincount(label, minlength=self.num_class ** 2)
+        return count.reshape(self.num_class, self.num_class)
+
+    def add_batch(self, gt_image, pre_image):
+        assert gt_image.shape == pre_image.shape
+        self.confusion_matrix += self._generate_matrix(gt_image, pre_image)
+
+    def reset(self):
+        self.confusion_matrix = np.zeros((self.num_class,) * 2)
+
+
+def bda_scores(evaluator_loc, evaluator_cls):
+    """The five numbers of reference scripts/train_BDA.py:135-138, in the same float64 arithmetic:
+    (loc_f1, harmonic mean of the damage F1s, 0.3 * loc + 0.7 * harmonic, per-class damage F1s)."""
+    loc_f1_score = evaluator_loc.Pixel_F1_score()
+    damage_f1_score = evaluator_cls.Damage_F1_socore()
+    harmonic_mean_f1 = len(damage_f1_score) / np.sum(1.0 / damage_f1_score)
+    oaf1 = 0.3 * loc_f1_score + 0.7 * harmonic_mean_f1
+    return loc_f1_score, harmonic_mean_f1, oaf1, damage_f1_score
+
+
+class BDAEvaluator:
+    """Both confusion matrices of the BDA validation loop (reference scripts/train_BDA.py:102-133) accumulated ON THE DEVICE
+    by `c3d_bda_confusion`: the reference copies both predictions to the host every iteration and bincounts in numpy; here
+    4 + n*n + 1 integers are read back once, in `evaluators()`, which returns two reference-shaped `Evaluator`s (`loc`,
+    `cls`) holding the device counts."""
+
+    def __init__(self, num_class, device):
+        self.n = int(num_class)
+        self.counts = torch.zeros(4 + self.n * self.n + 1, dtype=torch.int64, device=device)
+
+    def reset(self):
+        self.counts.zero_()
+
+    def add_batch(self, pred_cls, pred_loc, label_loc, label_cls):
+        ops.bda_confusion(pred_cls.detach().float().contiguous(), pred_loc.detach().float().contiguous(),
+                          label_loc.float().contiguous(), label_cls.to(torch.int64).contiguous(), self.counts)
+
+    def evaluators(self, strict=True):
+        h = self.counts.cpu().numpy()
+        if strict and h[-1] != 0:
+            raise ValueError(f"{int(h[-1])} label values outside [0, 2) / [0, {self.n}) in the BDA validation counts")
+        loc, cls = Evaluator(2), Evaluator(self.n)
+        loc.confusion_matrix = h[:4].reshape(2, 2).astype(np.longlong)
+        cls.confusion_matrix = h[4:4 + self.n * self.n].reshape(self.n, self.n).astype(np.longlong)
+        return loc, cls
+
+    def scores(self):
+        return bda_scores(*self.evaluators())
+
+
 def _cal_kappa(hist):
     """reference model/utils.py:330-342."""
     if hist.sum() == 0:

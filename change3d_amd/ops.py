@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib as L
-from ._lib import (OPT_CONVT_MFMA, OPT_DW_FWD_HV, OPT_DW_RING, OPT_FOLD_SE, OPT_FUSE_WGRAD, OPT_MASK_IN_DGRAD, OPT_PW_CDG, OPT_PW_CFWD, OPT_PW_WGRAD_V2, OPT_SIDE_STREAM, OPT_STEM_MFMA, STAGE_NO_WEIGHT_IMAGES, STAGE_SEPARATE_FINALIZE,  # noqa: F401
+from ._lib import (OPT_CONVT_MFMA, OPT_DW_FWD_HV, OPT_DW_RING, OPT_DW_T4, OPT_FOLD_SE, OPT_FUSE_WGRAD, OPT_MASK_IN_DGRAD, OPT_PW_CDG, OPT_PW_CFWD, OPT_PW_WGRAD_V2, OPT_SIDE_STREAM, OPT_STEM_MFMA, STAGE_NO_WEIGHT_IMAGES, STAGE_SEPARATE_FINALIZE,  # noqa: F401
                    STAGE_SEPARATE_RESIDUAL, STAGE_SEPARATE_WGRAD)
 from ._lib import (DT_BF16, DT_F32, EPI_ADD, EPI_STATS, EPI_STORE, EPI_SWISH_SE_BWD, PRO_AFFINE2,  # noqa: F401
                    PRO_BN_SE_SWISH, PRO_NONE, ROWS_DENSE, ROWS_FRAME, ROWS_S2SHIFT, ROWS_STRIDE2, SC_BN,
@@ -566,6 +566,19 @@ def hist2d(a, b, n, hist):
     _launch("c3d_hist2d", a.numel() * 16, L.lib().c3d_hist2d, _p(a), _p(b), a.numel(), n, _p(hist), _stream())
 
 
+def bda_confusion(pred_cls, pred_loc, label_loc, label_cls, counts):
+    """counts (uint64-as-int64 [4 + n*n + 1], device) += localisation matrix | damage matrix over label_loc > 0 | out-of-range
+    labels, of one batch (include/change3d_hip.h: c3d_bda_confusion)."""
+    B, n = pred_cls.shape[0], pred_cls.shape[1]
+    HW = pred_cls.numel() // (B * n)
+    assert pred_cls.is_contiguous() and pred_loc.is_contiguous() and label_loc.is_contiguous() and label_cls.is_contiguous()
+    assert pred_cls.dtype == torch.float32 and pred_loc.dtype == torch.float32 and label_loc.dtype == torch.float32
+    assert label_cls.dtype == torch.int64 and counts.dtype == torch.int64 and counts.numel() == 4 + n * n + 1
+    assert pred_loc.numel() == B * HW and label_loc.numel() == B * HW and label_cls.numel() == B * HW
+    _launch("c3d_bda_confusion", B * HW * (n * 4 + 16), L.lib().c3d_bda_confusion, _p(pred_cls), _p(pred_loc), _p(label_loc),
+            _p(label_cls), B, n, HW, _p(counts), _stream())
+
+
 # ------------------------------------------------------------------------------ stage driver
 class StageBinding:
     """ctypes descriptor (include/change3d_hip.h: c3d_stage_desc) of one residual stage, bound to the tensors of
@@ -703,6 +716,11 @@ def bcd_preprocess(image6, label, flags, mean6, std6, pre, post, label_out, B, H
 def scd_label_preprocess(label3, flags, out, B, H, W):
     _launch("c3d_scd_label_preprocess", B * H * W * (3 + 24), L.lib().c3d_scd_label_preprocess, _p(label3), _p(flags), _p(out),
             B, H, W, _stream())
+
+
+def bda_label_preprocess(label2, flags, label_loc, label_cls, B, H, W):
+    _launch("c3d_bda_label_preprocess", B * H * W * (2 + 12), L.lib().c3d_bda_label_preprocess, _p(label2), _p(flags),
+            _p(label_loc), _p(label_cls), B, H, W, _stream())
 
 
 def cc_preprocess(img, swap, lut, pre, post, B, H, W):

@@ -112,6 +112,29 @@ def synth_scd_labels(batch, size=256, seed=0, num_class=7):
     return torch.from_numpy(np.stack([maps[0], maps[1], change], axis=1).astype(np.int64))
 
 
+def synth_bda_labels(batch, size=256, seed=0, num_class=5):
+    """xBD-shaped labels as the data set holds them before the transforms: (B,S,S,2) uint8 = (localisation in {0,1}, damage
+    class).  Blocky building footprints cover a minority of the pixels; inside them the damage class is 1..num_class-1
+    (every class occurs in every sample: the first num_class-1 footprints take the classes in turn), outside it is 0."""
+    rng = np.random.default_rng(3000 + seed)
+    lab = np.zeros((batch, size, size, 2), dtype=np.uint8)
+    lo, hi = max(size // 16, 1), max(size // 5, 2)
+    for b in range(batch):
+        n_build = (num_class - 1) + int(rng.integers(1, 4))
+        for k in range(n_build):
+            h, w = int(rng.integers(lo, hi)), int(rng.integers(lo, hi))
+            y0, x0 = int(rng.integers(0, size - h)), int(rng.integers(0, size - w))
+            cls = 1 + k % (num_class - 1) if k < num_class - 1 else int(rng.integers(1, num_class))
+            if k < num_class - 1:      # a corner pixel of the first footprints is never painted over: every class survives
+                y0, x0 = (k * (size // num_class)) % (size - h), 0 if k % 2 == 0 else size - w
+            lab[b, y0:y0 + h, x0:x0 + w, 0] = 1
+            lab[b, y0:y0 + h, x0:x0 + w, 1] = cls
+        for k in range(num_class - 1):   # re-stamp one pixel per class after all footprints are drawn
+            y, x = (k * (size // num_class)) % size, (0 if k % 2 == 0 else size - 1)
+            lab[b, y, x] = (1, 1 + k)
+    return torch.from_numpy(lab)
+
+
 def synth_tensor(shape, seed, scale=1.0):
     rng = np.random.default_rng(seed)
     return torch.from_numpy((rng.standard_normal(shape) * scale).astype(np.float32))

@@ -397,6 +397,15 @@ int c3d_confusion2(const float* prob, const float* target, int64_t n, unsigned l
  * hist[a*n + b] += #{i : a[i] == a, b[i] == b} for 0 <= a < n (a = prediction, b = label; int64 device arrays), n <= 16;
  * hist has n*n + 1 u64 slots, the last one counts pairs whose b is outside [0, n) (numpy would raise there).        */
 int c3d_hist2d(const int64_t* a, const int64_t* b, int64_t n_elems, int32_t n, unsigned long long* hist, void* stream);
+/* BDA validation (reference scripts/train_BDA.py:102-143 `val`: `pred_loc.cpu().numpy() > 0.5`, `torch.argmax(pred_cls,
+ * dim=1).cpu().numpy()`, `[label_loc > 0]`, model/utils.py:466-475 Evaluator._generate_matrix / add_batch, twice per
+ * iteration): pred_cls f32 [B][n][HW] logits, pred_loc f32 [B][1][HW] probabilities, label_loc f32 [B][HW], label_cls int64
+ * [B][HW], all contiguous; n <= 16.  counts (u64 [4 + n*n + 1], device, ACCUMULATED into):
+ *   [2*gt + pred]     localisation matrix, pred = pred_loc > 0.5 (strict);
+ *   [4 + n*gt + pred] damage matrix of argmax (first maximum wins) over the pixels with label_loc > 0;
+ *   [4 + n*n]         labels outside [0, 2) / [0, n), which the reference's Evaluator drops silently.                 */
+int c3d_bda_confusion(const float* pred_cls, const float* pred_loc, const float* label_loc, const int64_t* label_cls, int64_t B,
+                      int32_t n, int64_t HW, unsigned long long* counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * SCD losses.  Logits are f32 NCHW views: element (b, c, p) at
@@ -441,6 +450,14 @@ int c3d_bcd_preprocess(const uint8_t* image6, const uint8_t* label, const uint8_
  * class maps.  The SCD image goes through c3d_bcd_preprocess (same 6-channel arithmetic, label = NULL).             */
 int c3d_scd_label_preprocess(const uint8_t* label3, const uint8_t* flags, int64_t* out, int32_t B, int32_t H, int32_t W,
                              void* stream);
+/* BDA labels (reference data/transforms.py:502-526 BDATransforms.random_flip / random_exchange, :541-556 to_tensor;
+ * scripts/train_BDA.py:194-195 `label[:, 0].float()`, `torch.prod(label, dim=1).long()`): label2 u8 [B][H][W][2] =
+ * (localisation, damage class), flags u8 [B][3] as for the image pass (NULL = none) -> label_loc f32 [B][1][H][W],
+ * label_cls int64 [B][H][W] = localisation x damage class (int64 product, as torch.prod of a uint8 tensor).  The two flips
+ * apply; the exchange flag swaps the images only (BDATransforms.random_exchange leaves the label alone).  The BDA image
+ * goes through c3d_bcd_preprocess (label = NULL).                                                                    */
+int c3d_bda_label_preprocess(const uint8_t* label2, const uint8_t* flags, float* label_loc, int64_t* label_cls, int32_t B,
+                             int32_t H, int32_t W, void* stream);
 /* Change-captioning pairs (reference data/dataset.py:411-424, scripts/train_CC.py:466-469): img u8 [B][2][3][H][W] ->
  * pre, post f32 [B][3][H][W] = lut[channel][u8] (the host builds the 3 x 256 table with the reference's own arithmetic:
  * Normalize(FloatTensor(u8 / 255.))); swap u8 [B] or NULL exchanges the pair.  H*W % 4 == 0.                        */
@@ -570,10 +587,16 @@ int c3d_side_join(void* stream);
  *                         workgroup-cooperative kernels (csrc/pw_cdgrad.hip) where they apply -- all three stage widths of
  *                         X3D-L, the 216-wide layers included, which the wave-private kernel's fused variant (accumulator
  *                         image in LDS) left to separate c3d_pw_wgrad launches; c3d_stage_bwd then asks for the fused form
- *                         there too.  Data gradients bit-identical, sums / dW to f32 rounding.  Default 3                  */
+ *                         there too.  Data gradients bit-identical, sums / dW to f32 rounding.  Default 3
+ *   C3D_OPT_DW_T4       : four-frame clips (T = 4: building damage assessment, num_perception_frame = 2) run on four-frame
+ *                         instantiations of c3d_dw333_fwd / c3d_dw333_bwd_fused (csrc/dw_conv.hip, csrc/dw_bwd_fused.hip): LDS
+ *                         tile, staging slots, tap loops and accumulators sized for four frames, the bf16 stride-1 backward on
+ *                         an LDS-DMA ring of two slots with the `a` rows in LDS.  0 = T = 4 runs on the five-frame (SCD)
+ *                         instantiation with a zero fifth frame.  Same tap order per output: outputs and data gradients
+ *                         bit-identical, statistics / dW to f32 rounding.  T <= 3 and T = 5 are not affected.  Default 1   */
 enum { C3D_OPT_SIDE_STREAM = 0, C3D_OPT_STEM_MFMA = 1, C3D_OPT_CONVT_MFMA = 2, C3D_OPT_FUSE_WGRAD = 3, C3D_OPT_FOLD_SE = 4,
        C3D_OPT_MASK_IN_DGRAD = 5, C3D_OPT_DW_RING = 6, C3D_OPT_PW_WGRAD_V2 = 7, C3D_OPT_DW_FWD_HV = 8, C3D_OPT_PW_CFWD = 9,
-       C3D_OPT_PW_CDG = 10 };
+       C3D_OPT_PW_CDG = 10, C3D_OPT_DW_T4 = 11 };
 int c3d_set_option(int32_t option, int32_t value);
 /* Per-launch profile of the stage driver: between c3d_prof_begin and c3d_prof_end every kernel c3d_stage_fwd /
  * c3d_stage_bwd enqueue is bracketed by a HIP event pair on its launch stream and billed its algorithmic bytes
