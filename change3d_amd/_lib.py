@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("C3D_LIB") or os.path.join(_HERE, "lib", "libchange3d_
 DT_F32, DT_BF16 = 0, 1
 PRO_NONE, PRO_BN_SE_SWISH, PRO_AFFINE2 = 0, 1, 2
 EPI_STORE, EPI_STATS, EPI_SWISH_SE_BWD, EPI_ADD = 0, 1, 2, 3
+AUG_NONE, AUG_BCD, AUG_SCD, AUG_BDA = 0, 1, 2, 3
 ROWS_DENSE, ROWS_FRAME, ROWS_STRIDE2, ROWS_S2SHIFT = 0, 1, 2, 3
 SC_NONE, SC_IDENTITY, SC_BN, SC_RAW = 0, 1, 2, 3
 STAT_STRIPES = 16
@@ -137,6 +138,7 @@ SIGNATURES = {
     "c3d_scd_label_preprocess": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "c3d_bda_label_preprocess": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "c3d_cc_preprocess": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "c3d_augment_gather": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "c3d_cap_embed_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_embed_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_dropout": (i32, [vp, vp, i64, i32, f32, C.c_uint64, i32, vp]),

@@ -1,9 +1,17 @@
-"""MI355X-native mirror of the tensor-side half of the reference's `data/transforms.py` (reference
-data/transforms.py:100-154) for the BCD train step: the reference runs random_flip -> random_exchange ->
-normalize -> to_tensor per sample on the host (numpy / cv2) inside DataLoader workers; here the raw uint8 batch is
-copied to HBM once and ONE HIP pass (`c3d_bcd_preprocess`, csrc/data_ops.hip) produces the normalised float
-tensors `Trainer.update_bcd` consumes.  Geometry-changing transforms (scale / resize / random_crop_resize) stay on
-the host side of the boundary (they are cv2 interpolation, outside SURVEY.md section 8).
+"""MI355X-native mirror of the reference's `data/transforms.py` (reference data/transforms.py:100-207).  The reference
+runs its chain per sample on the host (numpy / cv2) inside DataLoader workers; here the raw uint8 data stays in HBM and
+HIP passes (csrc/data_ops.hip) produce the normalised float tensors `Trainer.update_*` consumes:
+
+  * `c3d_bcd_preprocess` / `c3d_scd_label_preprocess` / `c3d_bda_label_preprocess` behind the `Device*BatchTransform`
+    classes: random_flip -> random_exchange -> normalize -> to_tensor over a raw batch the caller hands in (the synthetic
+    loaders of the script mirrors);
+  * `c3d_augment_gather` behind `resident.DeviceAugmentLoader`: the whole training recipe normalize -> scale ->
+    random_crop_resize -> random_flip -> random_exchange -> to_tensor, gathered from a resident file data set
+    (`resident.ResidentStore`), driven by the per-epoch table `draw_augmentation_table` draws and
+    `validate_augment_table` checks on the host before it is uploaded.
+
+Nothing runs on the host per step.  The aspect-preserving `resize` of the reference is used by none of its pipelines and
+has no mirror.
 
 `BCDTransforms.DEFAULT_MEAN/STD` and `IMAGENET_MEAN/STD` are the reference's constants."""
 import numpy as np
@@ -25,6 +33,53 @@ def draw_augmentation_flags(batch, rng, train=True):
     if not train:
         return np.zeros((batch, 3), dtype=np.uint8)
     return (rng.random((batch, 3)) < 0.5).astype(np.uint8)
+
+
+AUG_COLUMNS = ("index", "do_crop", "x1", "y1", "flip0", "flip1", "exchange", "reserved")
+
+
+def crop_area_of(in_width):
+    """reference data/transforms.py:185: `int(7.0 / 224.0 * args.in_width)`."""
+    return int(7.0 / 224.0 * in_width)
+
+
+def draw_augmentation_table(indices, rng, crop_area, train=True):
+    """int32 [len(indices), 8] = (index, do_crop, x1, y1, flip0, flip1, exchange, 0) for `c3d_augment_gather`, drawn with a
+    numpy Generator as the reference's random_crop_resize / random_flip / random_exchange draw per sample
+    (data/transforms.py:79-124): p = 0.5 for the crop with x1, y1 uniform on [0, crop_area] INCLUSIVE (`random.randint`),
+    p = 0.5 for each flip and for the exchange.  The validation transform draws nothing: only the index column is set."""
+    indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+    table = np.zeros((len(indices), 8), dtype=np.int32)
+    table[:, 0] = indices
+    if train and len(indices):
+        n = len(indices)
+        table[:, 1] = rng.random(n) < 0.5
+        table[:, 2] = rng.integers(0, crop_area + 1, size=n)
+        table[:, 3] = rng.integers(0, crop_area + 1, size=n)
+        table[:, 2:4] *= table[:, 1:2]                   # offsets only where the crop fires
+        table[:, 4:7] = rng.random((n, 3)) < 0.5
+    return table
+
+
+def validate_augment_table(table, n_store, height, width):
+    """Host-side check of a table BEFORE it is uploaded (the kernel cannot refuse device data; it only clamps): int32
+    [B, 8], 0 <= index < n_store, 0 <= x1 with 2 * x1 < width, 0 <= y1 with 2 * y1 < height, flags in {0, 1}."""
+    table = np.asarray(table)
+    if table.dtype != np.int32 or table.ndim != 2 or table.shape[1] != 8:
+        raise ValueError(f"augmentation table must be int32 [B, 8], got {table.dtype} {table.shape}")
+    if len(table) == 0:
+        return table
+    if table[:, 0].min() < 0 or table[:, 0].max() >= n_store:
+        raise ValueError(f"augmentation table index out of range [0, {n_store}): "
+                         f"min {int(table[:, 0].min())}, max {int(table[:, 0].max())}")
+    if table[:, 2].min() < 0 or 2 * int(table[:, 2].max()) >= width:
+        raise ValueError(f"crop offset x1 must satisfy 0 <= x1 and 2 * x1 < {width}: got {int(table[:, 2].min())}..{int(table[:, 2].max())}")
+    if table[:, 3].min() < 0 or 2 * int(table[:, 3].max()) >= height:
+        raise ValueError(f"crop offset y1 must satisfy 0 <= y1 and 2 * y1 < {height}: got {int(table[:, 3].min())}..{int(table[:, 3].max())}")
+    flags = table[:, [1, 4, 5, 6]]
+    if flags.min() < 0 or flags.max() > 1:
+        raise ValueError("do_crop / flip0 / flip1 / exchange must be 0 or 1")
+    return table
 
 
 class DeviceBatchTransform:
@@ -85,8 +140,9 @@ class DeviceSCDBatchTransform:
 
 class BDATransforms(BCDTransforms):
     """reference data/transforms.py:413-427: same normalisation constants as BCDTransforms.  `get_transform_pipelines`
-    (reference :567-620) composes cv2 geometry (scale, random_crop_resize) with flip / exchange / normalize / to_tensor; the
-    geometry stays on the host, the rest is `DeviceBDABatchTransform`."""
+    (reference :567-620) composes cv2 geometry (scale, random_crop_resize) with flip / exchange / normalize / to_tensor.  This
+    batch-level pair covers flip / exchange / normalize / to_tensor (`DeviceBDABatchTransform`); the full recipe over a
+    file data set is `resident.DeviceAugmentLoader`."""
 
     @classmethod
     def get_transform_pipelines(cls, args):

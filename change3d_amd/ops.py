@@ -728,6 +728,14 @@ def cc_preprocess(img, swap, lut, pre, post, B, H, W):
             B, H, W, _stream())
 
 
+def augment_gather(store, label_store, table, mean6, std6, pre, post, label_a, label_b, scratch, task, N, Hs, Ws, B, H, W):
+    """c3d_augment_gather: one launch (two through `scratch` when a table meets a store size other than H x W).  `table` is a
+    DEVICE int32 [B, 8]; validate its host copy with data.transforms.validate_augment_table before the upload."""
+    lb = {L.AUG_NONE: 0, L.AUG_BCD: 1 + 4, L.AUG_SCD: 3 + 24, L.AUG_BDA: 2 + 12}[task]
+    _launch("c3d_augment_gather", B * H * W * (6 + 24 + lb), L.lib().c3d_augment_gather, _p(store), _p(label_store), _p(table),
+            _p(mean6), _p(std6), _p(pre), _p(post), _p(label_a), _p(label_b), _p(scratch), task, N, Hs, Ws, B, H, W, _stream())
+
+
 def build_clip(pre, post, frames, clip, B, K, H, W):
     _launch("c3d_build_clip", clip.numel() * 8, L.lib().c3d_build_clip, _p(pre), _p(post), _p(frames), _p(clip), B, K, H, W,
             _stream())

@@ -4,8 +4,9 @@ scripts/train_BCD.py:92-154 `val`, :157-237 `train`, :240-383 `trainValidate`, :
 Same flags, same loop order (LR update -> update_bcd -> BCEDiceLoss -> binarise ->
 zero_grad/backward/step -> loss/metrics), same Adam hyper-parameters, checkpoint layout and
 "validate on the test split, skip epoch 0" behaviour.  Differences, all deliberate:
-  * file datasets / cv2 augmentation are out of scope: `--dataset SYNTH-CD`
-    (default) draws LEVIR-CD-shaped synthetic pairs with the reference's normalisation;
+  * `--dataset SYNTH-CD` (default) draws LEVIR-CD-shaped synthetic pairs with the reference's normalisation; any
+    other name reads `--file_root/{train,val,test}/{t1,t2,label}` once into an HBM-resident uint8 store and runs the
+    reference's whole transform chain in one kernel per step (change3d_amd/data/resident.py, c3d_augment_gather);
   * the model is `change3d_amd.model.Trainer` (HIP kernels), the optimizer the fused Adam;
   * the per-iteration confusion matrix is accumulated on the GPU (4 integers come back per
     epoch instead of two label maps per iteration) and `torch.cuda.empty_cache()` is not called;
@@ -67,6 +68,12 @@ class SyntheticBCDLoader:
 
 
 def create_data_loaders(args, rank=0):
+    if not args.dataset.startswith("SYNTH"):
+        from change3d_amd.data.dataset import BCDDataset
+        from change3d_amd.data.resident import build_file_loaders
+        train, val, test = build_file_loaders(args, BCDDataset, "bcd", torch.device("cuda", torch.cuda.current_device()),
+                                              rank, int(os.environ.get("WORLD_SIZE", "1")))
+        return train, val, test, len(train)
     train = SyntheticBCDLoader(args.synthetic_pairs, args.batch_size, args.in_height, seed=10 + rank, drop_last=True, train=True)
     val = SyntheticBCDLoader(max(args.batch_size, args.synthetic_pairs // 8), args.batch_size, args.in_height, seed=5)
     test = SyntheticBCDLoader(max(args.batch_size, args.synthetic_pairs // 8), args.batch_size, args.in_height, seed=6)
@@ -176,7 +183,8 @@ def trainValidate(args):
 def build_parser():
     p = ArgumentParser()
     p.add_argument("--dataset", default="SYNTH-CD", help="any name containing 'CD' selects the BCD head")
-    p.add_argument("--file_root", default="", help="unused (file datasets are out of scope)")
+    p.add_argument("--file_root", default="", help="data set root with train/val/test splits (read when --dataset is not SYNTH*)")
+    p.add_argument("--resident_gb", type=float, default=16.0, help="keep the decoded uint8 store in HBM up to this size")
     p.add_argument("--in_height", type=int, default=256)
     p.add_argument("--in_width", type=int, default=256)
     p.add_argument("--num_perception_frame", type=int, default=1)

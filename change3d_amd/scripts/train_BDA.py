@@ -8,9 +8,10 @@ same loop order and loss composition
     loss = CrossEntropyLoss2d(ignore_index=0)(pred_cls, label_cls) + BCEDiceLoss(pred_loc, label_loc.unsqueeze(1))
 same Adam hyper-parameters, log columns, checkpoint layout and "validate on the test split, skip epoch 0" behaviour.
 Differences, all deliberate:
-  * an xBD file data set and the cv2 geometry transforms are out of scope: `--synthetic` (the only data source) draws
-    xBD-shaped synthetic pairs and labels; flips, exchange, normalisation and the label arithmetic run on the device
-    (`DeviceBDABatchTransform`: c3d_bcd_preprocess + c3d_bda_label_preprocess);
+  * `--synthetic` draws xBD-shaped synthetic pairs and labels; flips, exchange, normalisation and the label arithmetic run
+    on the device (`DeviceBDABatchTransform`: c3d_bcd_preprocess + c3d_bda_label_preprocess).  Without it
+    `--file_root/{train,val,test}/{t1,t2,label1,label2}` is decoded once into an HBM-resident uint8 store and the
+    reference's whole transform chain runs in one kernel per step (change3d_amd/data/resident.py, c3d_augment_gather);
   * the model is `change3d_amd.model.Trainer` (HIP kernels, T = 4 clips on the four-frame depthwise kernels), the optimizer
     the fused Adam over a ParamArena;
   * `val` accumulates both confusion matrices on the device (`BDAEvaluator`: c3d_bda_confusion) and reads 4 + n*n + 1
@@ -71,7 +72,15 @@ class SyntheticBDALoader:
 
 def create_data_loaders(args, rank=0):
     if not args.synthetic:
-        raise SystemExit("train_BDA: an xBD file data set is out of scope here; run with --synthetic")
+        if not os.path.isdir(args.file_root):
+            raise SystemExit(f"train_BDA: --file_root {args.file_root} is not a directory; point it at an xBD tree with "
+                             f"train/val/test splits or run with --synthetic")
+        from change3d_amd.data.dataset import BDADataset
+        from change3d_amd.data.resident import build_file_loaders
+        train, val, test = build_file_loaders(args, BDADataset, "bda", torch.device("cuda", torch.cuda.current_device()),
+                                              rank, int(os.environ.get("WORLD_SIZE", "1")))
+        print(f"For each epoch, we have {len(train)} batches.")
+        return train, val, test, len(train)
     mk = lambda n, seed, **kw: SyntheticBDALoader(n, args.batch_size, args.in_height, args.num_class, seed, **kw)  # noqa: E731
     train = mk(args.synthetic_pairs, 10 + rank, drop_last=True, train=True)
     val = mk(max(args.batch_size, args.synthetic_pairs // 8), 5)
@@ -195,7 +204,8 @@ def trainValidate(args):
 def build_parser():
     p = ArgumentParser()
     p.add_argument("--dataset", default="xBD", help="Dataset selection | xBD |")
-    p.add_argument("--file_root", default="path/to/xBD", help="unused (a file data set is out of scope)")
+    p.add_argument("--file_root", default="path/to/xBD", help="xBD root with train/val/test splits (read unless --synthetic)")
+    p.add_argument("--resident_gb", type=float, default=16.0, help="keep the decoded uint8 store in HBM up to this size")
     p.add_argument("--in_height", type=int, default=256)
     p.add_argument("--in_width", type=int, default=256)
     p.add_argument("--num_perception_frame", type=int, default=2)
@@ -211,7 +221,7 @@ def build_parser():
     p.add_argument("--resume", default=None)
     p.add_argument("--log_file", default="train_val_log.txt")
     p.add_argument("--gpu_id", default=0, type=int)
-    p.add_argument("--synthetic", action="store_true", help="train on synthetic xBD-shaped pairs (the only data source here)")
+    p.add_argument("--synthetic", action="store_true", help="train on synthetic xBD-shaped pairs instead of --file_root")
     p.add_argument("--synthetic_pairs", type=int, default=240, help="pairs per synthetic epoch")
     p.add_argument("--act_dtype", choices=["f32", "bf16"], default="bf16")
     return p

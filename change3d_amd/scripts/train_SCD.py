@@ -8,9 +8,11 @@ Same loop order and loss composition
          + BCEDiceLoss(change_mask, label_change)                                 (:227)
          + ChangeSimilarity(pre_mask[:, 1:], post_mask[:, 1:], label_change)      (:228)
 same Adam hyper-parameters (:323-329) and the per-iteration semantic accuracy of `model/utils.py:313-319`
-(`accuracy(pred * change, label)`), computed on the device.  As in `train_BCD.py` of this package the
-file datasets / cv2 augmentation are out of scope: `--dataset SYNTH-SECOND` draws SECOND-shaped synthetic
-pairs (K=3 perception frames, 7 classes).  Under torch.distributed.run it trains data-parallel.
+(`accuracy(pred * change, label)`), computed on the device.  `--dataset SYNTH-SECOND` (default) draws SECOND-shaped
+synthetic pairs (K=3 perception frames, 7 classes); any other name reads
+`--file_root/{train,val,test}/{t1,t2,label1,label2,change}` once into an HBM-resident uint8 store, runs the reference's
+whole transform chain in one kernel per step (change3d_amd/data/resident.py, c3d_augment_gather) and validates on the
+test split after every epoch.  Under torch.distributed.run it trains data-parallel.
 """
 import os
 import sys
@@ -147,7 +149,13 @@ def trainValidate(args):
     args.act_dtype = torch.bfloat16 if args.act_dtype == "bf16" else torch.float32
     model = Trainer(args).cuda()
     broadcast_module_state(model)
-    loader = SyntheticSCDLoader(args.synthetic_pairs, args.batch_size, args.in_height, args.num_class, seed=10 + args.rank)
+    test_loader = None
+    if args.dataset.startswith("SYNTH"):
+        loader = SyntheticSCDLoader(args.synthetic_pairs, args.batch_size, args.in_height, args.num_class, seed=10 + args.rank)
+    else:
+        from change3d_amd.data.dataset import SCDDataset
+        from change3d_amd.data.resident import build_file_loaders
+        loader, _, test_loader = build_file_loaders(args, SCDDataset, "scd", torch.device("cuda", local), args.rank, world)
     max_batches = len(loader)
     args.max_epochs = int(np.ceil(args.max_steps / max_batches))
     arena, sync = setup_data_parallel(model, torch.device("cuda", local))
@@ -161,6 +169,8 @@ def trainValidate(args):
             if args.val_pairs > 0:   # rank 0 validates on its own BatchNorm statistics (the ones a checkpoint would hold)
                 vl = SyntheticSCDLoader(args.val_pairs, min(args.batch_size, args.val_pairs), args.in_height, args.num_class, seed=5)
                 val(args, vl, model)
+            if test_loader is not None:
+                val(args, test_loader, model)
         host_barrier()   # the other ranks wait (on the host) for rank 0's validation pass before the next exchange / teardown
     if world > 1:
         dist.destroy_process_group()
@@ -169,6 +179,9 @@ def trainValidate(args):
 def build_parser():
     p = ArgumentParser()
     p.add_argument("--dataset", default="SYNTH-SECOND")
+    p.add_argument("--file_root", default="", help="data set root with train/val/test splits (read when --dataset is not SYNTH*)")
+    p.add_argument("--num_workers", type=int, default=4)
+    p.add_argument("--resident_gb", type=float, default=16.0, help="keep the decoded uint8 store in HBM up to this size")
     p.add_argument("--in_height", type=int, default=256)
     p.add_argument("--in_width", type=int, default=256)
     p.add_argument("--num_perception_frame", type=int, default=3)

@@ -463,6 +463,31 @@ int c3d_bda_label_preprocess(const uint8_t* label2, const uint8_t* flags, float*
  * Normalize(FloatTensor(u8 / 255.))); swap u8 [B] or NULL exchanges the pair.  H*W % 4 == 0.                        */
 int c3d_cc_preprocess(const uint8_t* img, const uint8_t* swap, const float* lut, float* pre, float* post, int32_t B,
                       int32_t H, int32_t W, void* stream);
+/* File data sets: gather + the whole training transform chain of the BCD / SCD / BDA recipes (reference
+ * data/transforms.py:166-207 and its two siblings: normalize -> scale -> random_crop_resize -> random_flip ->
+ * random_exchange -> to_tensor) in one pass over a uint8 store that stays in HBM.
+ *   store        u8 [N][Hs][Ws][6] (pre | post, HWC) at an even address; addressed with 64-bit offsets
+ *   label_store  u8 [N][Hs][Ws][L], L = 1 (BCD) / 3 (SCD) / 2 (BDA); NULL with task = C3D_AUG_NONE
+ *   table        i32 [B][8] DEVICE = (index, do_crop, x1, y1, flip0, flip1, exchange, reserved) per output sample; NULL =
+ *                index b and no augmentation (the validation transform; needs B <= N).  The caller validates its host copy
+ *                (0 <= index < N, 2 * x1 < W, 2 * y1 < H); the kernel clamps the index, the offsets and every source
+ *                coordinate, so no table content can address memory outside the stores.
+ *   mean6, std6  f32 [6] DEVICE vectors, as for c3d_bcd_preprocess
+ * Outputs: pre, post f32 [B][3][H][W]; by task: BCD label_a = f32 [B][1][H][W] = ceil(u8 / 255); SCD label_a = int64
+ * [B][3][H][W] (an exchange swaps the two class maps); BDA label_a = label_loc f32 [B][1][H][W], label_b = label_cls int64
+ * [B][H][W] = loc x class (the exchange leaves both alone); label_b is NULL for the other tasks.
+ * Source window: the whole Hs x Ws image (scale; the identity when Hs == H && Ws == W), or with do_crop
+ * [y1 : H - y1, x1 : W - x1] of the image already scaled to H x W, resized back to H x W.  Images: cv2.INTER_LINEAR on the
+ * normalised f32 image (coordinate (d + 0.5) * (src / dst) - 0.5, f32 floor and fraction, clamped with fraction 0 at the
+ * borders, horizontal lerp on both rows, then vertical; fraction 0 copies the tap, so a zero table at the store's own size
+ * reproduces the three plain passes bit for bit).  Labels: cv2.INTER_NEAREST with the exact quotient min(d * src / dst, src - 1).
+ * With a table AND a store size other than H x W the reference resamples twice, and so does this entry: launch 1 scales
+ * into `scratch` (f32 [2][B][3][H][W], required in that case only), launch 2 crops / flips / exchanges from it.  Every
+ * other case is one launch.  W % 4 == 0 and Ws <= 1232 (C3D_E_UNSUPPORTED otherwise).                                  */
+enum { C3D_AUG_NONE = 0, C3D_AUG_BCD = 1, C3D_AUG_SCD = 2, C3D_AUG_BDA = 3 };
+int c3d_augment_gather(const uint8_t* store, const uint8_t* label_store, const int32_t* table, const float* mean6,
+                       const float* std6, float* pre, float* post, void* label_a, void* label_b, float* scratch,
+                       int32_t task, int32_t N, int32_t Hs, int32_t Ws, int32_t B, int32_t H, int32_t W, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
