@@ -460,20 +460,9 @@ extern "C" int c3d_bn_se_finalize(const double* nc, int32_t B, double cnt_per_sa
   const int Cw = C + ((8 - (C & 31)) & 31);
   const size_t lds = w1 ? ((size_t)B * C + (size_t)9 * B * Cr + (size_t)Cr * Cw + (size_t)C * Cr) * sizeof(float) : 0;
   if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
-  if (lds > 64 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bn_se_finalize_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
-  }
-  bn_se_finalize_kernel<<<dim3(w1 ? SE_SLICES : 1), dim3(SE_THREADS), lds, reinterpret_cast<hipStream_t>(stream)>>>(
-      nc, B, cnt_per_sample, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, C, Cp,
-      training, w1, b1, w2, b2, Cr, ss, mr, gate, hid);
-  C3D_CHECK_LAUNCH();
-  return 0;
+  return c3d_launch_lds<bn_se_finalize_kernel>(
+      dim3(w1 ? SE_SLICES : 1), dim3(SE_THREADS), lds, reinterpret_cast<hipStream_t>(stream), nc, B, cnt_per_sample, gamma,
+      beta, running_mean, running_var, num_batches_tracked, momentum, eps, C, Cp, training, w1, b1, w2, b2, Cr, ss, mr, gate, hid);
 }
 
 extern "C" int c3d_bn_bwd_coef(const double* dsums, int32_t stripes, double count, const float* gamma, const float* mr, int32_t C,
@@ -495,20 +484,9 @@ extern "C" int c3d_se_bn_bwd_coef(const double* nc3, const double* ncf, int32_t 
   if (w1 && (!w2 || !gate || !hid || !dw1 || !db1 || !dw2 || !db2 || Cr <= 0)) return C3D_E_BADARG;
   const size_t lds = w1 ? ((size_t)3 * B * C + (size_t)2 * B * Cr + (size_t)C * Cr + (8 * Cr <= C ? 0 : (size_t)8 * B * Cr)) * sizeof(float) : 0;
   if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
-  if (lds > 64 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&se_bn_bwd_coef_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
-  }
-  se_bn_bwd_coef_kernel<<<dim3(w1 ? SE_SLICES : 1), dim3(SE_THREADS), lds, reinterpret_cast<hipStream_t>(stream)>>>(
-      nc3, ncf, B, cnt_per_sample, gamma, mr, ss, C, Cp, w1, w2, gate, hid, Cr, coefA, coefC, coefB, dgamma, dbeta,
-      dw1, db1, dw2, db2);
-  C3D_CHECK_LAUNCH();
-  return 0;
+  return c3d_launch_lds<se_bn_bwd_coef_kernel>(
+      dim3(w1 ? SE_SLICES : 1), dim3(SE_THREADS), lds, reinterpret_cast<hipStream_t>(stream), nc3, ncf, B, cnt_per_sample, gamma,
+      mr, ss, C, Cp, w1, w2, gate, hid, Cr, coefA, coefC, coefB, dgamma, dbeta, dw1, db1, dw2, db2);
 }
 
 #ifdef C3D_SE_CLOCK

@@ -476,16 +476,8 @@ extern "C" int c3d_cap_attn_fwd(const void* q, const void* k, const void* v, int
   const int qsplit = Lq >= 16 ? 4 : 1;   // query rows of a (sample, head) over 4 workgroups
   if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  CAP_DISPATCH(dtype, (attn_fwd_kernel<float><<<dim3(B * H, qsplit), 256, lds, s>>>((const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, (float*)o, ldo, P, B, H, Lq, Lk, hd, scale, causal, p, seed)),
-               (attn_fwd_kernel<bf16_t><<<dim3(B * H, qsplit), 256, lds, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, (bf16_t*)o, ldo, P, B, H, Lq, Lk, hd, scale, causal, p, seed)));
-  C3D_CHECK_LAUNCH();
-  return 0;
+  CAP_DISPATCH(dtype, return c3d_launch_lds<attn_fwd_kernel<float>>(dim3(B * H, qsplit), 256, lds, s, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, (float*)o, ldo, P, B, H, Lq, Lk, hd, scale, causal, p, seed),
+               return c3d_launch_lds<attn_fwd_kernel<bf16_t>>(dim3(B * H, qsplit), 256, lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, (bf16_t*)o, ldo, P, B, H, Lq, Lk, hd, scale, causal, p, seed));
 }
 
 extern "C" int c3d_cap_attn_bwd(const void* q, const void* k, const void* v, int32_t ldq, int32_t ldk, int32_t ldv, const void* dout,
@@ -497,16 +489,8 @@ extern "C" int c3d_cap_attn_bwd(const void* q, const void* k, const void* v, int
   const size_t lds = ((size_t)2 * Lk * hs + (size_t)2 * Lq * hs + (size_t)Lq * Lk) * sizeof(float);
   if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  CAP_DISPATCH(dtype, (attn_bwd_kernel<float><<<B * H, 256, lds, s>>>((const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, (const float*)dout, ldo, P, (float*)dq, (float*)dk, (float*)dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, scale, p, seed)),
-               (attn_bwd_kernel<bf16_t><<<B * H, 256, lds, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, (const bf16_t*)dout, ldo, P, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, scale, p, seed)));
-  C3D_CHECK_LAUNCH();
-  return 0;
+  CAP_DISPATCH(dtype, return c3d_launch_lds<attn_bwd_kernel<float>>(B * H, 256, lds, s, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, (const float*)dout, ldo, P, (float*)dq, (float*)dk, (float*)dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, scale, p, seed),
+               return c3d_launch_lds<attn_bwd_kernel<bf16_t>>(B * H, 256, lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, (const bf16_t*)dout, ldo, P, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, scale, p, seed));
 }
 
 extern "C" int c3d_cap_ce_fwd(const void* logits, const int64_t* caps, const int64_t* declen, double* acc2, float* lse, float* loss,

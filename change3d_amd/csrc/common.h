@@ -128,3 +128,17 @@ inline int c3d_knob(const char* name, int dflt) {
     hipError_t e_ = hipGetLastError();                       \
     if (e_ != hipSuccess) return (int)e_;                    \
   } while (0)
+
+// Launch of a kernel that opts into more dynamic LDS than the 64 KB default (up to the CU's 160 KB).  The limit is raised
+// by the kernel's first launch: the function-local static is initialised by that call -- thread-safe by the language
+// (forward launches come from the caller's thread, backward ones from autograd's) -- and its error is remembered and
+// returned by every later call, which makes no runtime call besides the launch.  "Once" is once per process, which is
+// right while a rank owns one device (parallel.py: one rank per GPU).  Returns what C3D_CHECK_LAUNCH would.
+template <auto Kernel, class... Args>
+int c3d_launch_lds(const dim3 grid, const dim3 block, const size_t lds, hipStream_t stream, const Args&... args) {
+  static const hipError_t raised =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (raised != hipSuccess) return (int)raised;
+  Kernel<<<grid, block, lds, stream>>>(args...);
+  return (int)hipGetLastError();
+}

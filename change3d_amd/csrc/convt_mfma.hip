@@ -405,16 +405,9 @@ int launch_fwd(const void* in, const float* w, const float* bias, const void* sk
   size_t stage = (size_t)4 * 2 * 32 * C * sizeof(float);
   if (stage < (size_t)C * (C * 16 + 2) * sizeof(bf16_t)) stage = (size_t)C * (C * 16 + 2) * sizeof(bf16_t);   // the raw weights, first
   const size_t lds = (size_t)4 * NT * KS * 64 * 16 + stage;
-  static bool attr = false;
-  if (!attr && lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&convt_fwd_mfma_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return C3D_E_UNSUPPORTED;
-    attr = true;
-  }
   const int64_t wave_tiles = (int64_t)B * h * ((wd + 15) / 16);
   const int grid = persistent_grid((wave_tiles + 3) / 4, C <= 24 ? 6 : 2);
-  convt_fwd_mfma_kernel<C><<<grid, 256, lds, st>>>((const bf16_t*)in, w, bias, (const bf16_t*)skip, skip_bstride, (bf16_t*)out, B, h, wd);
-  C3D_CHECK_LAUNCH();
-  return 0;
+  return c3d_launch_lds<convt_fwd_mfma_kernel<C>>(grid, 256, lds, st, (const bf16_t*)in, w, bias, (const bf16_t*)skip, skip_bstride, (bf16_t*)out, B, h, wd);
 }
 
 template <int C>
@@ -423,16 +416,9 @@ int launch_bwd_data(const void* dout, const float* w, void* din, int B, int h, i
   size_t stage = (size_t)4 * (4 * 34 * C + 8) * sizeof(bf16_t);
   if (stage < (size_t)C * (C * 16 + 2) * sizeof(bf16_t)) stage = (size_t)C * (C * 16 + 2) * sizeof(bf16_t);
   const size_t lds = (size_t)NT * KS * 64 * 16 + stage;
-  static bool attr = false;
-  if (!attr && lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&convt_bwd_data_mfma_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return C3D_E_UNSUPPORTED;
-    attr = true;
-  }
   const int64_t wave_tiles = (int64_t)B * h * ((wd + 15) / 16);
   const int grid = persistent_grid((wave_tiles + 3) / 4, C <= 24 ? 6 : 2);
-  convt_bwd_data_mfma_kernel<C><<<grid, 256, lds, st>>>((const bf16_t*)dout, w, (bf16_t*)din, B, h, wd);
-  C3D_CHECK_LAUNCH();
-  return 0;
+  return c3d_launch_lds<convt_bwd_data_mfma_kernel<C>>(grid, 256, lds, st, (const bf16_t*)dout, w, (bf16_t*)din, B, h, wd);
 }
 
 template <int C>
@@ -445,14 +431,9 @@ template <int C>
 int launch_wgrad(const void* t, const void* dcur, float* dw, float* ws, int B, int h, int wd, hipStream_t st) {
   constexpr int CP = C + 2;
   const size_t lds = (size_t)(WG_TH * WG_TW + WG_PH * WG_PW) * CP * 2;
-  static bool attr = false;
-  if (!attr && lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&convt_wgrad_mfma_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return C3D_E_UNSUPPORTED;
-    attr = true;
-  }
   const int grid = wgrad_grid<C>(B, h, wd);
-  convt_wgrad_mfma_kernel<C><<<grid, 256, lds, st>>>((const bf16_t*)t, (const bf16_t*)dcur, ws, B, h, wd);
-  C3D_CHECK_LAUNCH();
+  const int rc = c3d_launch_lds<convt_wgrad_mfma_kernel<C>>(grid, 256, lds, st, (const bf16_t*)t, (const bf16_t*)dcur, ws, B, h, wd);
+  if (rc) return rc;
   const int n = 16 * C * C;
   convt_wgrad_reduce_kernel<<<(n + 31) / 32, 256, 0, st>>>(ws, dw, grid, C);
   C3D_CHECK_LAUNCH();

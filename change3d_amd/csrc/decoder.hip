@@ -408,23 +408,13 @@ extern "C" int c3d_convT4s2_fwd(const void* in, const float* w, const float* bia
   const int nthr = (CT_QH * CT_QW / 2) * G;
   dim3 grid(((wd + CT_QW - 1) / CT_QW) * ((h + CT_QH - 1) / CT_QH), 4, B);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&convT_fwd_kernel<float>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&convT_fwd_kernel<bf16_t>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
   if (dtype == C3D_DT_F32)
-    convT_fwd_kernel<float><<<grid, nthr, lds, s>>>((const float*)in, w, bias, (const float*)skip, skip_bstride,
-                                                     (float*)out, B, h, wd, C);
-  else if (dtype == C3D_DT_BF16)
-    convT_fwd_kernel<bf16_t><<<grid, nthr, lds, s>>>((const bf16_t*)in, w, bias, (const bf16_t*)skip, skip_bstride,
-                                                      (bf16_t*)out, B, h, wd, C);
-  else return C3D_E_BADARG;
-  C3D_CHECK_LAUNCH();
-  return 0;
+    return c3d_launch_lds<convT_fwd_kernel<float>>(grid, nthr, lds, s, (const float*)in, w, bias, (const float*)skip, skip_bstride,
+                                                   (float*)out, B, h, wd, C);
+  if (dtype == C3D_DT_BF16)
+    return c3d_launch_lds<convT_fwd_kernel<bf16_t>>(grid, nthr, lds, s, (const bf16_t*)in, w, bias, (const bf16_t*)skip,
+                                                    skip_bstride, (bf16_t*)out, B, h, wd, C);
+  return C3D_E_BADARG;
 }
 
 extern "C" int c3d_convT4s2_bwd_data(const void* dout, const float* w, void* din, int32_t B, int32_t h, int32_t wd,
@@ -440,21 +430,11 @@ extern "C" int c3d_convT4s2_bwd_data(const void* dout, const float* w, void* din
   if (nthr > 1024) return C3D_E_UNSUPPORTED;
   dim3 grid(((wd + CT_QW - 1) / CT_QW) * ((h + CT_QH - 1) / CT_QH), B);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&convT_bwd_data_kernel<float>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&convT_bwd_data_kernel<bf16_t>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
   if (dtype == C3D_DT_F32)
-    convT_bwd_data_kernel<float><<<grid, nthr, lds, s>>>((const float*)dout, w, (float*)din, B, h, wd, C);
-  else if (dtype == C3D_DT_BF16)
-    convT_bwd_data_kernel<bf16_t><<<grid, nthr, lds, s>>>((const bf16_t*)dout, w, (bf16_t*)din, B, h, wd, C);
-  else return C3D_E_BADARG;
-  C3D_CHECK_LAUNCH();
-  return 0;
+    return c3d_launch_lds<convT_bwd_data_kernel<float>>(grid, nthr, lds, s, (const float*)dout, w, (float*)din, B, h, wd, C);
+  if (dtype == C3D_DT_BF16)
+    return c3d_launch_lds<convT_bwd_data_kernel<bf16_t>>(grid, nthr, lds, s, (const bf16_t*)dout, w, (bf16_t*)din, B, h, wd, C);
+  return C3D_E_BADARG;
 }
 
 extern "C" int c3d_col_sum(const void* x, float* out, int64_t M, int32_t C, int32_t Cp, int32_t dtype,

@@ -976,112 +976,65 @@ __global__ __launch_bounds__(FB_NTHR) void dw_bwd_ring_kernel(
 }
 
 template <int TT, bool SPREAD>
-int launch_ring_t(const void* t1, const void* bb, const float* cA, const float* cB, const float* cC, const float* w,
-                  const void* a, const float* ss_a, const float* mr_a, void* t2, double* dsums, float* dw,
-                  const DwGeom& g, hipStream_t stream, const c3d_bn_fin& fin) {
+int launch_ring_t(const DwBwdCall& c) {
   typedef RingPlan<TT> P;
   static_assert(P::LDS_BYTES <= 160 * 1024, "ring does not fit");
   static_assert((size_t)P::R * P::SLOT_BYTES >= (size_t)27 * (FB_NTHR + 48) * sizeof(float), "dump region");
   static_assert((P::AHEAD - 1) * (2 * P::SL + P::NA) <= 12, "fb_wait_vm covers counts up to 12");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_bwd_ring_kernel<TT, SPREAD>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  const DwGeom& g = c.g;
   const int ntiles = ((g.W + FB_TW - 1) / FB_TW) * ((g.H + FB_TH - 1) / FB_TH);
-  const int chunks = (g.Cp + DW_CV * 8 - 1) / (DW_CV * 8);
-  static const int env_tpw = c3d_env("C3D_DWBF_TPW") ? atoi(c3d_env("C3D_DWBF_TPW")) : 0;
-  static const int env_max = c3d_env("C3D_DWBF_MAX") ? atoi(c3d_env("C3D_DWBF_MAX")) : 64;
-  int tpw = env_max;
-  while (tpw > 4 && (long)((ntiles + tpw - 1) / tpw) * chunks * g.B < 85L * device_cus() / 100) tpw >>= 1;
-  if (env_tpw > 0) tpw = env_tpw;
-  if (tpw > ntiles) tpw = ntiles;
-  dim3 grid(chunk_order_grid(chunks, (long)((ntiles + tpw - 1) / tpw) * g.B));
-  dw_bwd_ring_kernel<TT, SPREAD><<<grid, dim3(FB_NTHR), P::LDS_BYTES, stream>>>(
-      reinterpret_cast<const bf16_t*>(t1), reinterpret_cast<const bf16_t*>(bb), cA, cB, cC, w, reinterpret_cast<const bf16_t*>(a),
-      ss_a, mr_a, reinterpret_cast<bf16_t*>(t2), dsums, dw, g, tpw, fin);
-  C3D_CHECK_LAUNCH();
-  return 0;
+  const DwWalk wk = dw_walk(g, ntiles, c3d_knob("C3D_DWBF_MAX", 64), 4, 85L * device_cus() / 100, "C3D_DWBF_TPW");
+  return c3d_launch_lds<dw_bwd_ring_kernel<TT, SPREAD>>(
+      dim3(wk.grid), dim3(FB_NTHR), P::LDS_BYTES, c.stream, reinterpret_cast<const bf16_t*>(c.t1),
+      reinterpret_cast<const bf16_t*>(c.b), c.cA, c.cB, c.cC, c.w, reinterpret_cast<const bf16_t*>(c.a), c.ss_a, c.mr_a,
+      reinterpret_cast<bf16_t*>(c.t2), c.dsums, c.dw, g, wk.tpw, c.fin);
 }
 
 template <typename T, int TT, int S>
-int launch_fused_t(const void* t1, const void* bb, const float* cA, const float* cB, const float* cC, const float* w,
-                   const void* a, const float* ss_a, const float* mr_a, void* t2, double* dsums, float* dw,
-                   const DwGeom& g, hipStream_t stream, const c3d_bn_fin& fin) {
+int launch_fused_t(const DwBwdCall& c) {
   constexpr int NI = TT * FB_DH * FB_DW * DW_CV;
   const size_t lds = (27 * 32 + 7 * 32) * sizeof(float) + (size_t)2 * 2 * NI * sizeof(float4);
   static_assert((size_t)2 * 2 * NI * sizeof(float4) >= (size_t)27 * (FB_NTHR + 48) * sizeof(float), "dump region");
   if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_bwd_fused_kernel<T, TT, S>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  const DwGeom& g = c.g;
   const int ntiles = ((g.W + FB_TW * S - 1) / (FB_TW * S)) * ((g.H + FB_TH * S - 1) / (FB_TH * S));
-  const int chunks = (g.Cp + DW_CV * 8 - 1) / (DW_CV * 8);
   // one 512-thread workgroup is resident per CU: a walk amortises the weight-gradient flush (~3 us) and pipelines the
   // loads; short enough for ~2 rounds of workgroups (C3D_DWBF_TPW: tuning knob)
-  static const int env_tpw = c3d_env("C3D_DWBF_TPW") ? atoi(c3d_env("C3D_DWBF_TPW")) : 0;
   // measured on MI355X (B=32 bf16 step, side stream on): 4 / 8 / 16 / 32 / 64 tiles -> 32.9 / 31.3 / 30.6 / 30.4 / 31.2 ms
   // (12, 24: +0.3..1.2 ms -- ragged last groups)
   // -> the longest walk that still gives (almost) every CU a workgroup: 16 / 32 / 32 tiles for the 32x32 / 64x64 / 128x128 stages
   // (round 5, re-swept at 23.2 ms per step: cap 16 / 32 / 64 / 128 tiles -> 23.42 / 23.18 / 22.95 / 23.15 ms; with the narrower
   // side-stream weight gradient, three interleaved repeats: 22.90 against 23.39 ms for the old pair of defaults)
-  static const int env_max = c3d_env("C3D_DWBF_MAX") ? atoi(c3d_env("C3D_DWBF_MAX")) : 64;
-  int tpw = env_max / (S * S) * (8 / FB_TH);   // a stride-2 tile is four pixels per thread; (half-height tiles: twice as many)
+  // a stride-2 tile is four pixels per thread; (half-height tiles: twice as many)
+  const int start = c3d_knob("C3D_DWBF_MAX", 64) / (S * S) * (8 / FB_TH);
   constexpr int WGC = 512 / FB_NTHR;           // workgroups resident per CU
-  while (tpw > 4 && (long)((ntiles + tpw - 1) / tpw) * chunks * g.B < 85L * WGC * device_cus() / 100) tpw >>= 1;
-  if (env_tpw > 0) tpw = env_tpw;
-  if (tpw > ntiles) tpw = ntiles;
-  dim3 grid(chunk_order_grid(chunks, (long)((ntiles + tpw - 1) / tpw) * g.B));
-  dw_bwd_fused_kernel<T, TT, S><<<grid, dim3(FB_NTHR), lds, stream>>>(
-      reinterpret_cast<const T*>(t1), reinterpret_cast<const T*>(bb), cA, cB, cC, w, reinterpret_cast<const T*>(a),
-      ss_a, mr_a, reinterpret_cast<T*>(t2), dsums, dw, g, tpw, fin);
-  C3D_CHECK_LAUNCH();
-  return 0;
+  const DwWalk wk = dw_walk(g, ntiles, start, 4, 85L * WGC * device_cus() / 100, "C3D_DWBF_TPW");
+  return c3d_launch_lds<dw_bwd_fused_kernel<T, TT, S>>(
+      dim3(wk.grid), dim3(FB_NTHR), lds, c.stream, reinterpret_cast<const T*>(c.t1), reinterpret_cast<const T*>(c.b), c.cA, c.cB,
+      c.cC, c.w, reinterpret_cast<const T*>(c.a), c.ss_a, c.mr_a, reinterpret_cast<T*>(c.t2), c.dsums, c.dw, g, wk.tpw, c.fin);
 }
 
-}  // namespace
-
-namespace {
-int dispatch_fused(const void* t1, const void* b, const float* coefA, const float* coefB, const float* coefC, const float* w,
-                   const void* a, const float* ss_a, const float* mr_a, void* t2, double* dsums, float* dw, const DwGeom& g,
-                   int dtype, hipStream_t s, const c3d_bn_fin& fin) {
-  const int tt = dw_frames(g.T);
-#define FB_DISPATCH(TY, S_)                                                                                         \
-  return tt == 3 ? launch_fused_t<TY, 3, S_>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin)   \
-       : tt == 4 ? launch_fused_t<TY, 4, S_>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin)   \
-                 : launch_fused_t<TY, 5, S_>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
-  if (dtype == C3D_DT_F32) {
-    if (g.stride == 1) { FB_DISPATCH(float, 1) }
-    FB_DISPATCH(float, 2)
-  }
-  if (dtype == C3D_DT_BF16) {
-    // LDS-DMA ring kernels (bit 2: requests spread over the tap walk; bit 3: three-frame maps under 64 x 64 too -- their
-    // 16-tile walks pay the two-tile ring fill: res4 of the BCD step 65.9 us with the register prefetch, 68.0 us with the
-    // ring; the five-frame register kernel spills, its ring variant wins on every map: SCD 663 -> 681 img/s)
-    if (C3D_FB_ROWS == 8 && g.stride == 1 && (c3d_option_dw_ring & 1) && ((c3d_option_dw_ring & 8) || g.T > 3 || (long)g.H * g.W >= 64 * 64)) {
-      if (tt == 3) {
-        if (c3d_option_dw_ring & 4) return launch_ring_t<3, true>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
-        return launch_ring_t<3, false>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
-      }
-      if (tt == 4) {
-        if (c3d_option_dw_ring & 4) return launch_ring_t<4, true>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
-        return launch_ring_t<4, false>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
-      }
-      if (c3d_option_dw_ring & 4) return launch_ring_t<5, true>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
-      return launch_ring_t<5, false>(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, s, fin);
-    }
-    if (g.stride == 1) { FB_DISPATCH(bf16_t, 1) }
-    FB_DISPATCH(bf16_t, 2)
-  }
-#undef FB_DISPATCH
-  return C3D_E_BADARG;
+template <typename T>
+int dispatch_fused_t(const DwBwdCall& c) {
+  return with_frames(c.g.T, [&c](auto n) {
+    return c.g.stride == 1 ? launch_fused_t<T, decltype(n)::value, 1>(c) : launch_fused_t<T, decltype(n)::value, 2>(c);
+  });
 }
+
+int dispatch_fused(const DwBwdCall& c, const int dtype) {
+  const DwGeom& g = c.g;
+  if (dtype == C3D_DT_F32) return dispatch_fused_t<float>(c);
+  if (dtype != C3D_DT_BF16) return C3D_E_BADARG;
+  // LDS-DMA ring kernels (bit 2: requests spread over the tap walk; bit 3: three-frame maps under 64 x 64 too -- their
+  // 16-tile walks pay the two-tile ring fill: res4 of the BCD step 65.9 us with the register prefetch, 68.0 us with the
+  // ring; the five-frame register kernel spills, its ring variant wins on every map: SCD 663 -> 681 img/s)
+  if (C3D_FB_ROWS == 8 && g.stride == 1 && (c3d_option_dw_ring & 1) && ((c3d_option_dw_ring & 8) || g.T > 3 || (long)g.H * g.W >= 64 * 64))
+    return with_frames(g.T, [&c](auto n) {
+      return (c3d_option_dw_ring & 4) ? launch_ring_t<decltype(n)::value, true>(c) : launch_ring_t<decltype(n)::value, false>(c);
+    });
+  return dispatch_fused_t<bf16_t>(c);
+}
+
 }  // namespace
 
 extern "C" int c3d_dw333_bwd_fused(const void* t1, const void* b, const float* coefA, const float* coefB,
@@ -1089,11 +1042,11 @@ extern "C" int c3d_dw333_bwd_fused(const void* t1, const void* b, const float* c
                                    const float* mr_a, void* t2, double* dsums, float* dw, int32_t B, int32_t T,
                                    int32_t H, int32_t W, int32_t C, int32_t Cp, int32_t stride, int32_t dtype, void* stream) {
   if (stride != 1 && stride != 2) return C3D_E_UNSUPPORTED;
-  DwGeom g{B, T, H, W, (H - 1) / stride + 1, (W - 1) / stride + 1, C, Cp, stride};
+  const DwGeom g = dw_geom(B, T, H, W, C, Cp, stride);
   if (!t1 || !b || !coefA || !coefB || !coefC || !w || !a || !ss_a || !mr_a || !t2 || !dsums || !dw || !geom_ok(g))
     return C3D_E_BADARG;
-  return dispatch_fused(t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g, dtype,
-                        reinterpret_cast<hipStream_t>(stream), c3d_bn_fin{});
+  return dispatch_fused(DwBwdCall{t1, b, coefA, coefB, coefC, w, a, ss_a, mr_a, t2, dsums, dw, g,
+                                  reinterpret_cast<hipStream_t>(stream), c3d_bn_fin{}}, dtype);
 }
 
 extern "C" int c3d_dw333_bwd_fused_fin(const void* t1, const void* b, const c3d_bn_fin* fin_b, const float* w, const void* a,
@@ -1101,11 +1054,11 @@ extern "C" int c3d_dw333_bwd_fused_fin(const void* t1, const void* b, const c3d_
                                        int32_t T, int32_t H, int32_t W, int32_t C, int32_t Cp, int32_t stride, int32_t dtype,
                                        void* stream) {
   if (stride != 1 && stride != 2) return C3D_E_UNSUPPORTED;
-  DwGeom g{B, T, H, W, (H - 1) / stride + 1, (W - 1) / stride + 1, C, Cp, stride};
+  const DwGeom g = dw_geom(B, T, H, W, C, Cp, stride);
   if (!t1 || !b || !w || !a || !ss_a || !mr_a || !t2 || !dsums || !dw || !geom_ok(g)) return C3D_E_BADARG;
   if (!fin_b || !fin_b->sums || fin_b->batch != B || !fin_b->gamma || !fin_b->mr || !(fin_b->count > 0)) return C3D_E_BADARG;
-  return dispatch_fused(t1, b, nullptr, nullptr, nullptr, w, a, ss_a, mr_a, t2, dsums, dw, g, dtype,
-                        reinterpret_cast<hipStream_t>(stream), *fin_b);
+  return dispatch_fused(DwBwdCall{t1, b, nullptr, nullptr, nullptr, w, a, ss_a, mr_a, t2, dsums, dw, g,
+                                  reinterpret_cast<hipStream_t>(stream), *fin_b}, dtype);
 }
 
 #ifdef C3D_PW_CLOCK

@@ -1,6 +1,8 @@
 // Pieces shared by the depthwise 3x3x3 translation units (dw_conv.hip, dw_bwd_fused.hip).
 #pragma once
 #include "common.h"
+#include "../../include/change3d_hip.h"   // c3d_bn_fin
+#include <type_traits>
 
 extern int c3d_option_dw_t4;   // C3D_OPT_DW_T4 (launch_hints.h)
 
@@ -38,6 +40,63 @@ inline unsigned chunk_order_grid(const int chunks, const long ngroups) {
 // Frame-count instantiation of a clip: three frames (BCD, CC), four (BDA: num_perception_frame = 2), five (SCD).  With
 // C3D_OPT_DW_T4 = 0 a four-frame clip runs on the five-frame instantiation, its fifth frame staged as zeros.
 inline int dw_frames(const int T) { return T <= 3 ? 3 : (T == 4 && c3d_option_dw_t4) ? 4 : 5; }
+
+// f(std::integral_constant<int, N>{}) with N = dw_frames(T): the one frame ladder of the depthwise launchers
+template <class F> auto with_frames(const int T, F&& f) {
+  switch (dw_frames(T)) {
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 5>{});
+  }
+}
+
+// the one place Ho / Wo are computed (a stride that is not positive is left for geom_ok to reject)
+inline DwGeom dw_geom(const int B, const int T, const int H, const int W, const int C, const int Cp, const int stride) {
+  const int s = stride > 0 ? stride : 1;
+  return DwGeom{B, T, H, W, (H - 1) / s + 1, (W - 1) / s + 1, C, Cp, stride};
+}
+inline int dw_chunks(const DwGeom& g) { return (g.Cp + DW_CV * 8 - 1) / (DW_CV * 8); }   // 32-channel chunks
+
+// Walk length of a tile-walking workgroup and the chunk_order_grid extent that goes with it: from `start` tiles, halved
+// while more than `floor` and the grid would hold fewer than `wanted` workgroups; then the tuning knob (when named and
+// positive), then the clamp to the tile count.
+struct DwWalk {
+  int tpw;
+  unsigned grid;
+};
+inline DwWalk dw_walk(const DwGeom& g, const int ntiles, const int start, const int floor, const long wanted, const char* knob) {
+  const int chunks = dw_chunks(g);
+  int tpw = start;
+  while (tpw > floor && (long)((ntiles + tpw - 1) / tpw) * chunks * g.B < wanted) tpw >>= 1;
+  if (knob && c3d_knob(knob, 0) > 0) tpw = c3d_knob(knob, 0);
+  if (tpw > ntiles) tpw = ntiles;
+  return DwWalk{tpw, chunk_order_grid(chunks, (long)((ntiles + tpw - 1) / tpw) * g.B)};
+}
+
+// One forward / one fused-backward call, built by the extern "C" entry point and passed down to the launcher.
+// fin == nullptr (forward) / a zeroed fin (backward) is the form without the folded BatchNorm finalize.
+struct DwFwdCall {
+  const void* x;
+  const float* ss;
+  const float* w;
+  void* y;
+  double* nc;
+  DwGeom g;
+  hipStream_t stream;
+  const c3d_bn_fin* fin;
+};
+struct DwBwdCall {
+  const void *t1, *b;
+  const float *cA, *cB, *cC, *w;
+  const void* a;
+  const float *ss_a, *mr_a;
+  void* t2;
+  double* dsums;
+  float* dw;
+  DwGeom g;
+  hipStream_t stream;
+  c3d_bn_fin fin;
+};
 
 inline bool geom_ok(const DwGeom& g) {
   if (g.B <= 0 || g.T <= 0 || g.T > DW_MAXT || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.Cp < g.C || (g.Cp & 7))

@@ -548,71 +548,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HV ? 2 : 1,
   }
 }
 
-template <typename T, int TT>
-int launch_fwd_v2(const void* x, const float* ss, const float* w, void* y, double* nc, const DwGeom& g,
-                  hipStream_t stream, const c3d_bn_fin* fin = nullptr) {
-  const size_t lds = (27 * 32 + 64) * sizeof(float) + (size_t)DW_CV * 2 * V2Geo<TT>::PLANE * sizeof(float4);
-  if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2_kernel<T, TT, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  constexpr int V2_TH = V2Geo<TT>::TH;
-  const int ntiles = ((g.W + V2_TW - 1) / V2_TW) * ((g.H + V2_TH - 1) / V2_TH);
-  int tpw = 16 * 2 / V2Geo<TT>::PYR;  // swept on MI355X: 1:427us 4:255 8:240 16:233 32:250 (stage-1 shape)
-  // ...but a walk is a serial chain (~5.5 us per tile): keep ~2 workgroups per CU in the grid
-  // (the 64x64 / 32x32 stages launched 256 / 224 workgroups of 16 / 8 tiles: one per CU, 98 / 52 us)
-  const int chunks_ = (g.Cp + DW_CV * 8 - 1) / (DW_CV * 8);
-  // measured best: 16 / 8 / 4 tiles for the 128x128 / 64x64 / 32x32 stages = ~2 workgroups per CU, and
-  // never fewer than 4 tiles (the prefetch pipeline needs a walk)
-  while (tpw > 4 && (long)((ntiles + tpw - 1) / tpw) * chunks_ * g.B < 2L * device_cus()) tpw >>= 1;
-  if (const char* e = c3d_env("C3D_DW_TPW")) tpw = atoi(e) > 0 ? atoi(e) : tpw;  // tuning knob
-  if (tpw > ntiles) tpw = ntiles;
-  dim3 grid(chunk_order_grid((g.Cp + DW_CV * 8 - 1) / (DW_CV * 8), (long)((ntiles + tpw - 1) / tpw) * g.B));
+// `c.fin ? *c.fin : zeroed`: the kernels take the folded finalize by value
+inline c3d_bn_fin fwd_fin(const DwFwdCall& c) {
   c3d_bn_fin f0;
   std::memset(&f0, 0, sizeof(f0));
+  return c.fin ? *c.fin : f0;
+}
+
+template <typename T, int TT>
+int launch_fwd_v2(const DwFwdCall& c) {
+  const DwGeom& g = c.g;
+  const size_t lds = (27 * 32 + 64) * sizeof(float) + (size_t)DW_CV * 2 * V2Geo<TT>::PLANE * sizeof(float4);
+  if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
+  constexpr int V2_TH = V2Geo<TT>::TH;
+  const int ntiles = ((g.W + V2_TW - 1) / V2_TW) * ((g.H + V2_TH - 1) / V2_TH);
+  // start: swept on MI355X: 1:427us 4:255 8:240 16:233 32:250 (stage-1 shape)
+  // ...but a walk is a serial chain (~5.5 us per tile): keep ~2 workgroups per CU in the grid
+  // (the 64x64 / 32x32 stages launched 256 / 224 workgroups of 16 / 8 tiles: one per CU, 98 / 52 us)
+  // measured best: 16 / 8 / 4 tiles for the 128x128 / 64x64 / 32x32 stages = ~2 workgroups per CU, and
+  // never fewer than 4 tiles (the prefetch pipeline needs a walk)
+  const DwWalk wk = dw_walk(g, ntiles, 16 * 2 / V2Geo<TT>::PYR, 4, 2L * device_cus(), "C3D_DW_TPW");
   // packed slot descriptors (bf16): the largest tile-relative element offset in 22 bits, the tensor in 2^31 elements
   const size_t rel_max = (((size_t)(g.T - 1) * g.H + V2Geo<TT>::IH) * g.W + V2_IW) * g.Cp + g.Cp;
   const bool pk = sizeof(T) == 2 && rel_max < ((size_t)1 << 22) && (size_t)g.B * g.T * g.H * g.W * g.Cp < ((size_t)1 << 31);
   // half-vector lanes (C3D_OPT_DW_FWD_HV: bit 0 bf16 storage, bit 1 f32 storage), three frames
   constexpr bool HVT = TT == 3;
   const bool hv = HVT && (c3d_option_dw_fwd_hv & (sizeof(T) == 2 ? 1 : 2)) != 0;
-  if (hv) {
-    static bool attr_hv = false;
-    if (!attr_hv) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2_kernel<T, TT, false, HVT>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2_kernel<T, TT, sizeof(T) == 2, HVT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr_hv = true;
-    }
-    if (pk)
-      dw_fwd_v2_kernel<T, TT, sizeof(T) == 2, HVT><<<grid, dim3(256), lds, stream>>>(reinterpret_cast<const T*>(x), ss, w,
-                                                                                    reinterpret_cast<T*>(y), nc, g, tpw, fin ? *fin : f0);
-    else
-      dw_fwd_v2_kernel<T, TT, false, HVT><<<grid, dim3(256), lds, stream>>>(reinterpret_cast<const T*>(x), ss, w,
-                                                                            reinterpret_cast<T*>(y), nc, g, tpw, fin ? *fin : f0);
-  } else if (pk) {
-    static bool attr_pk = false;
-    if (!attr_pk) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2_kernel<T, TT, sizeof(T) == 2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr_pk = true;
-    }
-    dw_fwd_v2_kernel<T, TT, sizeof(T) == 2><<<grid, dim3(256), lds, stream>>>(reinterpret_cast<const T*>(x), ss, w,
-                                                                             reinterpret_cast<T*>(y), nc, g, tpw, fin ? *fin : f0);
-  } else {
-    dw_fwd_v2_kernel<T, TT, false><<<grid, dim3(256), lds, stream>>>(reinterpret_cast<const T*>(x), ss, w,
-                                                                     reinterpret_cast<T*>(y), nc, g, tpw, fin ? *fin : f0);
-  }
-  C3D_CHECK_LAUNCH();
-  return 0;
+  // PKT / HVT instead of `true`: the f32 and the four- / five-frame launchers name no instantiation they never take
+  constexpr bool PKT = sizeof(T) == 2;
+  const auto go = [&](auto pk_, auto hv_) {
+    return c3d_launch_lds<dw_fwd_v2_kernel<T, TT, decltype(pk_)::value, decltype(hv_)::value>>(
+        dim3(wk.grid), dim3(256), lds, c.stream, reinterpret_cast<const T*>(c.x), c.ss, c.w, reinterpret_cast<T*>(c.y), c.nc, g,
+        wk.tpw, fwd_fin(c));
+  };
+  constexpr std::false_type off{};
+  if (hv) return pk ? go(std::bool_constant<PKT>{}, std::bool_constant<HVT>{}) : go(off, std::bool_constant<HVT>{});
+  return pk ? go(std::bool_constant<PKT>{}, off) : go(off, off);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -895,58 +866,28 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void dw_fwd_v2s2_kernel(const T* __
 }
 
 template <typename T, int TT>
-int launch_fwd_v2s2(const void* x, const float* ss, const float* w, void* y, double* nc, const DwGeom& g,
-                    hipStream_t stream, const c3d_bn_fin* fin = nullptr) {
+int launch_fwd_v2s2(const DwFwdCall& c) {
+  const DwGeom& g = c.g;
   const size_t lds = (27 * 32 + 64) * sizeof(float) + (size_t)DW_CV * 2 * V2S2Geo<TT>::PLANE * sizeof(float4);
   if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;   // (four frames: 174 KB, five: 218 KB -- the v1 kernel on its own frame count)
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2s2_kernel<T, TT, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2s2_kernel<T, TT, sizeof(T) == 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const int ntiles = ((g.Wo + S2_TW - 1) / S2_TW) * ((g.Ho + S2_TH - 1) / S2_TH);
-  const int chunks = (g.Cp + DW_CV * 8 - 1) / (DW_CV * 8);
-  int tpw = c3d_knob("C3D_DWF2_TPW", 16);   // one workgroup per CU (LDS): ~2 rounds of workgroups, >= 4 tiles for the prefetch
-  while (tpw > 4 && (long)((ntiles + tpw - 1) / tpw) * chunks * g.B < 2L * device_cus()) tpw >>= 1;
-  if (tpw > ntiles) tpw = ntiles;
-  dim3 grid(chunk_order_grid(chunks, (long)((ntiles + tpw - 1) / tpw) * g.B));
-  c3d_bn_fin f0;
-  std::memset(&f0, 0, sizeof(f0));
+  // one workgroup per CU (LDS): ~2 rounds of workgroups, >= 4 tiles for the prefetch (the knob is the START of the walk)
+  const DwWalk wk = dw_walk(g, ntiles, c3d_knob("C3D_DWF2_TPW", 16), 4, 2L * device_cus(), nullptr);
   // packed slot descriptors (bf16): the largest tile-relative element offset / 8 in 21 bits, the tensor in 2^31 elements
   const size_t rel_max = (((size_t)(g.T - 1) * g.H + S2_IH) * g.W + S2_IW) * g.Cp + g.Cp;
   const bool pk = sizeof(T) == 2 && (rel_max >> 3) < ((size_t)1 << 21) && (size_t)g.B * g.T * g.H * g.W * g.Cp < ((size_t)1 << 31);
   // eight waves on the tile (C3D_OPT_DW_FWD_HV bit 2), bf16 storage
   constexpr bool W8T = sizeof(T) == 2;
-  if (W8T && (c3d_option_dw_fwd_hv & 4)) {
-    static bool attr_w8 = false;
-    if (!attr_w8) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2s2_kernel<T, TT, false, W8T>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_v2s2_kernel<T, TT, W8T, W8T>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr_w8 = true;
-    }
-    if (pk)
-      dw_fwd_v2s2_kernel<T, TT, W8T, W8T><<<grid, dim3(512), lds, stream>>>(reinterpret_cast<const T*>(x), ss, w,
-                                                                           reinterpret_cast<T*>(y), nc, g, tpw, fin ? *fin : f0);
-    else
-      dw_fwd_v2s2_kernel<T, TT, false, W8T><<<grid, dim3(512), lds, stream>>>(reinterpret_cast<const T*>(x), ss, w,
-                                                                             reinterpret_cast<T*>(y), nc, g, tpw, fin ? *fin : f0);
-  } else if (pk)
-    dw_fwd_v2s2_kernel<T, TT, sizeof(T) == 2><<<grid, dim3(256), lds, stream>>>(reinterpret_cast<const T*>(x), ss, w,
-                                                                               reinterpret_cast<T*>(y), nc, g, tpw, fin ? *fin : f0);
-  else
-    dw_fwd_v2s2_kernel<T, TT, false><<<grid, dim3(256), lds, stream>>>(reinterpret_cast<const T*>(x), ss, w,
-                                                                       reinterpret_cast<T*>(y), nc, g, tpw, fin ? *fin : f0);
-  C3D_CHECK_LAUNCH();
-  return 0;
+  const bool w8 = W8T && (c3d_option_dw_fwd_hv & 4);
+  const auto go = [&](auto pk_, auto w8_) {
+    return c3d_launch_lds<dw_fwd_v2s2_kernel<T, TT, decltype(pk_)::value, decltype(w8_)::value>>(
+        dim3(wk.grid), dim3(decltype(w8_)::value ? 512 : 256), lds, c.stream, reinterpret_cast<const T*>(c.x), c.ss, c.w,
+        reinterpret_cast<T*>(c.y), c.nc, g, wk.tpw, fwd_fin(c));
+  };
+  constexpr std::false_type off{};
+  constexpr std::bool_constant<W8T> bf16{};   // packed descriptors and eight waves are bf16-storage variants
+  if (w8) return pk ? go(bf16, bf16) : go(off, bf16);
+  return pk ? go(bf16, off) : go(off, off);
 }
 
 template <typename T, int S> struct DwTile;  // forward / wgrad output tile per workgroup
@@ -954,52 +895,60 @@ template <typename T> struct DwTile<T, 1> { static constexpr int TH = 8, TW = 8;
 template <typename T> struct DwTile<T, 2> { static constexpr int TH = 4, TW = 8; };
 
 template <typename T, int S, int TT>
-int launch_fwd_t(const void* x, const float* ss, const float* w, void* y, double* nc, const DwGeom& g,
-                 hipStream_t stream) {
+int launch_fwd_t(const DwFwdCall& c) {
+  const DwGeom& g = c.g;
   constexpr int TH = DwTile<T, S>::TH, TW = DwTile<T, S>::TW;
   constexpr int IH = (TH - 1) * S + 3, IW = (TW - 1) * S + 3, NTHR = TH * TW * DW_CV;
   const size_t lds = (27 * 32 + (NTHR / 64) * DW_CV * 16) * sizeof(float) +
                      (size_t)g.T * IH * IW * 32 * sizeof(typename LdsStore<T>::type);
   if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_kernel<T, S, TH, TW, TT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const int ntiles = ((g.Wo + TW - 1) / TW) * ((g.Ho + TH - 1) / TH);
-  const int chunks = (g.Cp + DW_CV * 8 - 1) / (DW_CV * 8);
-  static const int env_tpw = c3d_env("C3D_DWF1_TPW") ? atoi(c3d_env("C3D_DWF1_TPW")) : 0;
-  int tpw = 8;   // no prefetch in this kernel: the walk only amortises the weight staging and the statistics flush
-  while (tpw > 1 && (long)((ntiles + tpw - 1) / tpw) * chunks * g.B < 2L * device_cus()) tpw >>= 1;   // swept: 8 is best
-  if (env_tpw > 0) tpw = env_tpw;
-  if (tpw > ntiles) tpw = ntiles;
-  dim3 grid(chunk_order_grid(chunks, (long)((ntiles + tpw - 1) / tpw) * g.B));
-  dw_fwd_kernel<T, S, TH, TW, TT><<<grid, dim3(NTHR), lds, stream>>>(
-      reinterpret_cast<const T*>(x), ss, w, reinterpret_cast<T*>(y), nc, g, tpw);
-  C3D_CHECK_LAUNCH();
-  return 0;
+  // no prefetch in this kernel: the walk only amortises the weight staging and the statistics flush (swept: 8 is best)
+  const DwWalk wk = dw_walk(g, ntiles, 8, 1, 2L * device_cus(), "C3D_DWF1_TPW");
+  return c3d_launch_lds<dw_fwd_kernel<T, S, TH, TW, TT>>(dim3(wk.grid), dim3(NTHR), lds, c.stream, reinterpret_cast<const T*>(c.x),
+                                                         c.ss, c.w, reinterpret_cast<T*>(c.y), c.nc, g, wk.tpw);
 }
 
-template <typename T, int S>
-int launch_fwd(const void* x, const float* ss, const float* w, void* y, double* nc, const DwGeom& g,
-               hipStream_t stream) {
-  const int tt = dw_frames(g.T);
-  if (tt == 3) return launch_fwd_t<T, S, 3>(x, ss, w, y, nc, g, stream);
-  if (tt == 4) return launch_fwd_t<T, S, 4>(x, ss, w, y, nc, g, stream);
-  return launch_fwd_t<T, S, 5>(x, ss, w, y, nc, g, stream);
-}
-
-// stride-1 v2 kernel on the instantiation of the clip's frame count (three: 8 x 16 tiles; four and five: 4 x 16 tiles, two
-// workgroups per CU -- a four-frame 8 x 16 tile is 92 KB of the 160 KB, one workgroup per CU, like the five-frame one was)
+// The order of attempts: Toeplitz experiment (instrumented build) -> stride-1 v2 -> stride-2 polyphase -> the v1 kernel.
+// A call with a folded BatchNorm finalize (c.fin) that reaches a kernel without the fold runs c3d_bn_finalize first.
 template <typename T>
-int launch_fwd_v2_frames(const void* x, const float* ss, const float* w, void* y, double* nc, const DwGeom& g,
-                         hipStream_t stream, const c3d_bn_fin* fin = nullptr) {
-  const int tt = dw_frames(g.T);
-  if (tt == 3) return launch_fwd_v2<T, 3>(x, ss, w, y, nc, g, stream, fin);
-  if (tt == 4) return launch_fwd_v2<T, 4>(x, ss, w, y, nc, g, stream, fin);
-  return launch_fwd_v2<T, 5>(x, ss, w, y, nc, g, stream, fin);
+int dispatch_fwd_t(DwFwdCall c) {
+  const DwGeom& g = c.g;
+  const auto unfold = [&c, &g]() {   // the separate finalize launch, then the plain form
+    const c3d_bn_fin* fin = c.fin;
+    c.fin = nullptr;
+    return c3d_bn_finalize(fin->sums, C3D_STAT_STRIPES, fin->count, fin->gamma, fin->beta, fin->running_mean, fin->running_var,
+                           fin->nbt, fin->momentum, fin->eps, g.C, g.Cp, fin->training, fin->ss, fin->mr, c.stream);
+  };
+#ifdef C3D_TUNING
+  if (g.stride == 1 && sizeof(T) == 2 && g.T <= 3 && c3d_dw_toeplitz_enabled()) {   // matrix-core kernel (dw_toeplitz.hip)
+    const int rcf = c.fin ? unfold() : 0;
+    if (rcf) return rcf;
+    const int rc = c3d_dw333_fwd_toeplitz(c.x, c.ss, c.w, c.y, c.nc, g.B, g.T, g.H, g.W, g.C, g.Cp, c.stream);
+    if (rc != C3D_E_UNSUPPORTED) { if (rc == 0) C3D_CHECK_LAUNCH(); return rc; }
+  }
+#endif
+  if (g.stride == 1) {  // v2 mapping (wave = channel vector, lane = x-strip) on the instantiation of the clip's frame count
+    // (three: 8 x 16 tiles; four and five: 4 x 16 tiles, two workgroups per CU -- a four-frame 8 x 16 tile is 92 KB of
+    // the 160 KB, one workgroup per CU, like the five-frame one was)
+    const int rc = with_frames(g.T, [&c](auto n) { return launch_fwd_v2<T, decltype(n)::value>(c); });
+    if (rc != C3D_E_UNSUPPORTED) return rc;
+  }
+  if (g.stride == 2 && g.T <= 3 && c3d_knob("C3D_DWF2_V2", 1)) {   // polyphase v2: three frames only (the tile fits LDS)
+    const int rc = launch_fwd_v2s2<T, 3>(c);
+    if (rc != C3D_E_UNSUPPORTED) return rc;
+  }
+  const int rcf = c.fin ? unfold() : 0;   // no folded kernel for this shape
+  if (rcf) return rcf;
+  return with_frames(g.T, [&c, &g](auto n) {
+    return g.stride == 1 ? launch_fwd_t<T, 1, decltype(n)::value>(c) : launch_fwd_t<T, 2, decltype(n)::value>(c);
+  });
+}
+
+int dispatch_fwd(const DwFwdCall& c, const int dtype) {
+  if (dtype == C3D_DT_F32) return dispatch_fwd_t<float>(c);
+  if (dtype == C3D_DT_BF16) return dispatch_fwd_t<bf16_t>(c);
+  return C3D_E_BADARG;
 }
 
 }  // namespace
@@ -1007,63 +956,16 @@ int launch_fwd_v2_frames(const void* x, const float* ss, const float* w, void* y
 extern "C" int c3d_dw333_fwd(const void* x, const float* ss, const float* w, void* y, double* nc_sums, int32_t B,
                              int32_t T, int32_t H, int32_t W, int32_t C, int32_t Cp, int32_t stride, int32_t dtype,
                              void* stream) {
-  DwGeom g{B, T, H, W, (H - 1) / (stride > 0 ? stride : 1) + 1, (W - 1) / (stride > 0 ? stride : 1) + 1, C, Cp, stride};
+  const DwGeom g = dw_geom(B, T, H, W, C, Cp, stride);
   if (!x || !ss || !w || !y || !geom_ok(g)) return C3D_E_BADARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#ifdef C3D_TUNING
-  if (stride == 1 && dtype == C3D_DT_BF16 && T <= 3 && c3d_dw_toeplitz_enabled()) {   // matrix-core kernel (dw_toeplitz.hip)
-    const int rc = c3d_dw333_fwd_toeplitz(x, ss, w, y, nc_sums, B, T, H, W, C, Cp, s);
-    if (rc != C3D_E_UNSUPPORTED) { if (rc == 0) C3D_CHECK_LAUNCH(); return rc; }
-  }
-#endif
-  if (stride == 1) {  // v2 mapping (wave = channel vector, lane = x-strip)
-    int rc = C3D_E_UNSUPPORTED;
-    if (dtype == C3D_DT_F32) rc = launch_fwd_v2_frames<float>(x, ss, w, y, nc_sums, g, s);
-    else if (dtype == C3D_DT_BF16) rc = launch_fwd_v2_frames<bf16_t>(x, ss, w, y, nc_sums, g, s);
-    else return C3D_E_BADARG;
-    if (rc != C3D_E_UNSUPPORTED) return rc;
-  }
-  if (stride == 2 && T <= 3 && c3d_knob("C3D_DWF2_V2", 1)) {   // polyphase v2 (three frames: the tile fits LDS)
-    int rc = C3D_E_UNSUPPORTED;
-    if (dtype == C3D_DT_F32) rc = launch_fwd_v2s2<float, 3>(x, ss, w, y, nc_sums, g, s);
-    else if (dtype == C3D_DT_BF16) rc = launch_fwd_v2s2<bf16_t, 3>(x, ss, w, y, nc_sums, g, s);
-    else return C3D_E_BADARG;
-    if (rc != C3D_E_UNSUPPORTED) return rc;
-  }
-  if (dtype == C3D_DT_F32) return stride == 1 ? launch_fwd<float, 1>(x, ss, w, y, nc_sums, g, s)
-                                              : launch_fwd<float, 2>(x, ss, w, y, nc_sums, g, s);
-  if (dtype == C3D_DT_BF16) return stride == 1 ? launch_fwd<bf16_t, 1>(x, ss, w, y, nc_sums, g, s)
-                                               : launch_fwd<bf16_t, 2>(x, ss, w, y, nc_sums, g, s);
-  return C3D_E_BADARG;
+  return dispatch_fwd(DwFwdCall{x, ss, w, y, nc_sums, g, reinterpret_cast<hipStream_t>(stream), nullptr}, dtype);
 }
 
 extern "C" int c3d_dw333_fwd_fin(const void* x, const c3d_bn_fin* fin, const float* w, void* y, double* nc_sums,
                                  int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t Cp, int32_t stride,
                                  int32_t dtype, void* stream) {
   if (!fin || !fin->sums || !fin->ss || !fin->gamma || !fin->beta || !fin->training) return C3D_E_BADARG;
-  DwGeom g{B, T, H, W, (H - 1) / (stride > 0 ? stride : 1) + 1, (W - 1) / (stride > 0 ? stride : 1) + 1, C, Cp, stride};
+  const DwGeom g = dw_geom(B, T, H, W, C, Cp, stride);
   if (!x || !w || !y || !geom_ok(g)) return C3D_E_BADARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#ifdef C3D_TUNING
-  const bool tz = stride == 1 && dtype == C3D_DT_BF16 && T <= 3 && c3d_dw_toeplitz_enabled();
-#else
-  const bool tz = false;
-#endif
-  if (!tz && stride == 1 && (dtype == C3D_DT_F32 || dtype == C3D_DT_BF16)) {
-    int rc;
-    if (dtype == C3D_DT_F32) rc = launch_fwd_v2_frames<float>(x, fin->ss, w, y, nc_sums, g, s, fin);
-    else rc = launch_fwd_v2_frames<bf16_t>(x, fin->ss, w, y, nc_sums, g, s, fin);
-    if (rc != C3D_E_UNSUPPORTED) return rc;
-  }
-  if (stride == 2 && T <= 3 && (dtype == C3D_DT_F32 || dtype == C3D_DT_BF16) && c3d_knob("C3D_DWF2_V2", 1)) {
-    const int rc = dtype == C3D_DT_F32 ? launch_fwd_v2s2<float, 3>(x, fin->ss, w, y, nc_sums, g, s, fin)
-                                       : launch_fwd_v2s2<bf16_t, 3>(x, fin->ss, w, y, nc_sums, g, s, fin);
-    if (rc != C3D_E_UNSUPPORTED) return rc;
-  }
-  // no folded kernel for this shape: the separate launch, then the plain kernel
-  const int rc = c3d_bn_finalize(fin->sums, C3D_STAT_STRIPES, fin->count, fin->gamma, fin->beta, fin->running_mean,
-                                 fin->running_var, fin->nbt, fin->momentum, fin->eps, C, Cp, fin->training, fin->ss,
-                                 fin->mr, stream);
-  if (rc) return rc;
-  return c3d_dw333_fwd(x, fin->ss, w, y, nc_sums, B, T, H, W, C, Cp, stride, dtype, stream);
+  return dispatch_fwd(DwFwdCall{x, fin->ss, w, y, nc_sums, g, reinterpret_cast<hipStream_t>(stream), fin}, dtype);
 }

@@ -347,13 +347,6 @@ static unsigned long long* tz_clk_buffer() {
 template <int NCH>
 static int tz_launch(const void* x, const float* ss, const float* w, void* y, double* nc, const Geom& g, hipStream_t s) {
   const size_t lds = (size_t)NCH * PLANE_B + 64 + 2 * NCH * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_fwd_tz_kernel<NCH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const int groups = (g.Cp + NCH - 1) / NCH;
   const int nitems = g.B * ((g.H + TS - 1) / TS) * ((g.W + TS - 1) / TS);
   int walkers = (NCH == 16 ? 256 : 512) / groups;     // one (16 channels) or two (8 channels) workgroups per CU
@@ -361,11 +354,9 @@ static int tz_launch(const void* x, const float* ss, const float* w, void* y, do
   if (walkers > nitems) walkers = nitems;
   static const int env_w = c3d_env("C3D_DW_TZ_WALKERS") ? atoi(c3d_env("C3D_DW_TZ_WALKERS")) : 0;
   if (env_w > 0) walkers = env_w < nitems ? env_w : nitems;
-  dw_fwd_tz_kernel<NCH><<<dim3(walkers, groups), NTHR, lds, s>>>(reinterpret_cast<const bf16_t*>(x), ss, w,
-                                                               reinterpret_cast<bf16_t*>(y), nc, g, walkers,
-                                                               c3d_env("C3D_DW_TZ_DBG") ? atoi(c3d_env("C3D_DW_TZ_DBG")) : 0,
-                                                               tz_clk_buffer());
-  return 0;
+  return c3d_launch_lds<dw_fwd_tz_kernel<NCH>>(dim3(walkers, groups), NTHR, lds, s, reinterpret_cast<const bf16_t*>(x), ss, w,
+                                               reinterpret_cast<bf16_t*>(y), nc, g, walkers,
+                                               c3d_env("C3D_DW_TZ_DBG") ? atoi(c3d_env("C3D_DW_TZ_DBG")) : 0, tz_clk_buffer());
 }
 
 int c3d_dw333_fwd_toeplitz(const void* x, const float* ss, const float* w, void* y, double* nc, int B, int T, int H, int W,

@@ -410,15 +410,7 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
 
 template <int KS, int NTW, int NPW, int NQW, int RP, int RQ, int K2>
 int cd_launch(const c3d_pw_args& a, const CdPlan& L, dim3 grid, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_cdg_a_kernel<KS, NTW, NPW, NQW, RP, RQ, K2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  pw_cdg_a_kernel<KS, NTW, NPW, NQW, RP, RQ, K2><<<grid, dim3(CD_THREADS), lds, s>>>(a, L);
-  return 0;
+  return c3d_launch_lds<pw_cdg_a_kernel<KS, NTW, NPW, NQW, RP, RQ, K2>>(grid, dim3(CD_THREADS), lds, s, a, L);
 }
 
 // shape -> instantiation: 0 = none.  1: 216 -> 96 (32 x 32 stage), 2: 108 -> 48, 3: 54 -> 24
@@ -803,15 +795,7 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
 
 template <int KS, int NPW, int NQW, int K2>
 int cc_launch(const c3d_pw_args& a, const CcPlan& L, dim3 grid, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_cdg_c_kernel<KS, NPW, NQW, K2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  pw_cdg_c_kernel<KS, NPW, NQW, K2><<<grid, dim3(CD_THREADS), lds, s>>>(a, L);
-  return 0;
+  return c3d_launch_lds<pw_cdg_c_kernel<KS, NPW, NQW, K2>>(grid, dim3(CD_THREADS), lds, s, a, L);
 }
 
 // 1: 96 -> 216 (32 x 32 stage), 2: 48 -> 108, 3: 24 -> 54

@@ -343,15 +343,7 @@ __global__ __launch_bounds__(CF_THREADS) void pw_cfwd_kernel(const c3d_pw_args a
 
 template <int PRO, int NTW, int KS>
 int cf_launch(const c3d_pw_args& a, const CfPlan& L, dim3 grid, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_cfwd_kernel<PRO, NTW, KS, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  pw_cfwd_kernel<PRO, NTW, KS, true><<<grid, dim3(CF_THREADS), lds, s>>>(a, L);
-  return 0;
+  return c3d_launch_lds<pw_cfwd_kernel<PRO, NTW, KS, true>>(grid, dim3(CF_THREADS), lds, s, a, L);
 }
 
 }  // namespace

@@ -1257,13 +1257,6 @@ int launch_pw_d(const c3d_pw_args& a, hipStream_t stream) {
   PwLaunch L;
   size_t lds = 0;
   if (!plan_pw<T, NT, PRO, EPI, WAVES, WG>(a, L, lds)) return C3D_E_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_gemm_kernel<T, NT, PRO, EPI, WAVES, DENSE, WG>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const int64_t tiles = (a.M + 15) >> 4;
   int occ = (int)((160 * 1024) / lds);
   if (occ > 32 / WAVES) occ = 32 / WAVES;
@@ -1289,8 +1282,8 @@ int launch_pw_d(const c3d_pw_args& a, hipStream_t stream) {
   }
   static const int fsm = c3d_env("C3D_PW_FLUSH_SHFL") ? atoi(c3d_env("C3D_PW_FLUSH_SHFL")) : 0;   // tuning knob (measured: no gain)
   L.flush_shuffle_max = fsm;
-  pw_gemm_kernel<T, NT, PRO, EPI, WAVES, DENSE, WG><<<dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream>>>(a, L);
-  C3D_CHECK_LAUNCH();
+  const int rc = c3d_launch_lds<pw_gemm_kernel<T, NT, PRO, EPI, WAVES, DENSE, WG>>(dim3((unsigned)blocks), dim3(WAVES * 64), lds, stream, a, L);
+  if (rc) return rc;
   if (WG == C3D_WG_SWISH || WG == C3D_WG_ROWS)   // partials [blocks][K][N] -> dw[n*w_sn + k*w_sk] (+=), fixed order
     return c3d_detail_pw_wgrad_reduce(a.wg_ws, a.wg_dw, a.K, a.N, (int)blocks, a.w_sk, a.w_sn, stream);
   return 0;

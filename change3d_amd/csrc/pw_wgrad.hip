@@ -418,18 +418,10 @@ __global__ __launch_bounds__(256) void pw_wgrad_reduce_kernel(const float* __res
 
 constexpr int WGRAD_MAX_PARTS = 512;
 
-// One instantiation: sets the LDS attribute once, launches.
+// One instantiation.
 template <typename T, bool HASP2, bool QD, int TN, int TK>
 int launch_wgrad_inst(const c3d_pw_wgrad_args& a, dim3 grid, size_t lds, int tpw, int WN, int WK, int MT, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_kernel<T, HASP2, QD, TN, TK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  pw_wgrad_kernel<T, HASP2, QD, TN, TK><<<grid, dim3(WG_THREADS), lds, stream>>>(a, tpw, WN, WK, MT);
-  return 0;
+  return c3d_launch_lds<pw_wgrad_kernel<T, HASP2, QD, TN, TK>>(grid, dim3(WG_THREADS), lds, stream, a, tpw, WN, WK, MT);
 }
 
 // Instantiated per-wave tile grids (TN x TK): a launch takes the smallest that covers its ceil(NT / WN) x ceil(KT / WK).

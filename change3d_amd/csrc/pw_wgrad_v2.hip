@@ -426,15 +426,7 @@ __global__ __launch_bounds__(W2_THREADS) void pw_wgrad_v2_kernel(const c3d_pw_wg
 
 template <bool HASP2, bool QSW, int TN, int TK, bool IL>
 int w2_launch_il(const c3d_pw_wgrad_args& a, const W2Plan& L, const W2Red& red, dim3 grid, size_t lds, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_wgrad_v2_kernel<HASP2, QSW, TN, TK, IL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  pw_wgrad_v2_kernel<HASP2, QSW, TN, TK, IL><<<grid, dim3(W2_THREADS), lds, stream>>>(a, L, red);
-  return 0;
+  return c3d_launch_lds<pw_wgrad_v2_kernel<HASP2, QSW, TN, TK, IL>>(grid, dim3(W2_THREADS), lds, stream, a, L, red);
 }
 template <bool HASP2, bool QSW, int TN, int TK>
 int w2_launch_inst(const c3d_pw_wgrad_args& a, const W2Plan& L, const W2Red& red, dim3 grid, size_t lds, hipStream_t stream) {

@@ -518,23 +518,11 @@ extern "C" int c3d_stem_bwd_wx(const float* x, const float* w_t, const void* dv,
   const int tpw = 1;
   dim3 grid(ntiles, bsplit);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_bwd_wx_kernel<float>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_bwd_wx_kernel<bf16_t>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e1 != hipSuccess) return (int)e1;
-    if (e2 != hipSuccess) return (int)e2;
-    attr_set = true;
-  }
   if (dtype == C3D_DT_F32)
-    stem_bwd_wx_kernel<float><<<grid, SW_THREADS, lds, s>>>(x, w_t, (const float*)dv, dw_t, dP, g, t_first,
-                                                             n_frames, per_sample, tpw);
-  else if (dtype == C3D_DT_BF16)
-    stem_bwd_wx_kernel<bf16_t><<<grid, SW_THREADS, lds, s>>>(x, w_t, (const bf16_t*)dv, dw_t, dP, g, t_first,
-                                                              n_frames, per_sample, tpw);
-  else return C3D_E_BADARG;
-  C3D_CHECK_LAUNCH();
-  return 0;
+    return c3d_launch_lds<stem_bwd_wx_kernel<float>>(grid, SW_THREADS, lds, s, x, w_t, (const float*)dv, dw_t, dP, g, t_first,
+                                                     n_frames, per_sample, tpw);
+  if (dtype == C3D_DT_BF16)
+    return c3d_launch_lds<stem_bwd_wx_kernel<bf16_t>>(grid, SW_THREADS, lds, s, x, w_t, (const bf16_t*)dv, dw_t, dP, g, t_first,
+                                                      n_frames, per_sample, tpw);
+  return C3D_E_BADARG;
 }

@@ -772,28 +772,11 @@ int wx_t(const float* x, const float* w_t, const void* dv, float* dw_t, float* d
     // bf16 storage: both gradients on the bf16 matrix cores (c3d_set_option(C3D_OPT_STEM_MFMA, 1) keeps the f32-MFMA kernel)
     size_t lb = ((size_t)TT * IHW * SC + 8 + (size_t)TT * IHW * 4 + 8) * sizeof(bf16_t);
     if (lb < 4 * 32 * 32 * sizeof(float)) lb = 4 * 32 * 32 * sizeof(float);
-    static bool attr_b = false;
-    if (!attr_b) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_bwd_wx_bf16_kernel<TT>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr_b = true;
-    }
-    stem_bwd_wx_bf16_kernel<TT><<<dim3(ntiles, bsplit), NTHR, lb, s>>>(x, w_t, reinterpret_cast<const bf16_t*>(dv), dw_t, dP, g,
-                                                                      t_first, n_frames, per_sample);
-    C3D_CHECK_LAUNCH();
-    return 0;
+    return c3d_launch_lds<stem_bwd_wx_bf16_kernel<TT>>(dim3(ntiles, bsplit), NTHR, lb, s, x, w_t, reinterpret_cast<const bf16_t*>(dv),
+                                                       dw_t, dP, g, t_first, n_frames, per_sample);
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_bwd_wx_mfma_kernel<T, TT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  stem_bwd_wx_mfma_kernel<T, TT><<<dim3(ntiles, bsplit), NTHR, lds, s>>>(x, w_t, reinterpret_cast<const T*>(dv), dw_t, dP,
-                                                                        g, t_first, n_frames, per_sample);
-  return 0;
+  return c3d_launch_lds<stem_bwd_wx_mfma_kernel<T, TT>>(dim3(ntiles, bsplit), NTHR, lds, s, x, w_t, reinterpret_cast<const T*>(dv),
+                                                        dw_t, dP, g, t_first, n_frames, per_sample);
 }
 
 #define STEM_DISPATCH(FN, ...)                                                         \
