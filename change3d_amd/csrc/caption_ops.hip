@@ -389,10 +389,13 @@ __global__ __launch_bounds__(256) void cap_ce_bwd_kernel(const T* __restrict__ l
   }
 }
 
-// ---- gradient clipping by value (reference model/utils.py:481-491 clip_gradient) over a flat buffer
+// ---- gradient clipping by value (reference model/utils.py:481-491 clip_gradient) over a flat buffer.  NaN stays NaN, as
+// torch's clamp_ keeps it: fmaxf / fminf return their non-NaN operand and would turn a diverged gradient into -limit
 __global__ void clamp_kernel(float* __restrict__ g, int64_t n, float lim) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    g[i] = fminf(fmaxf(g[i], -lim), lim);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float v = g[i];
+    g[i] = v != v ? v : fminf(fmaxf(v, -lim), lim);
+  }
 }
 
 inline int grid_for(int64_t n, int block = 256) {

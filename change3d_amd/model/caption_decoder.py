@@ -14,8 +14,9 @@ csrc/pw_wide.hip) behind one autograd function:
     pred = wdc(drop(x))  ->  (B, L, vocab), sorted by caption length
 
 Dropout masks come from a counter-based generator (seed drawn from torch's CPU generator per call), so train-mode
-results are reproducible under `torch.manual_seed` but are NOT bit-comparable with torch's CPU dropout stream; parity
-tests run with dropout 0 (tests/test_cc_gpu.py).
+results are reproducible under `torch.manual_seed` but are NOT bit-comparable with torch's CPU dropout stream: the oracle
+parity tests run with dropout 0 (tests/test_cc_gpu.py); with dropout on, tests/test_caption_ops_gpu.py reads the device's
+masks back and compares against a float64 restatement that applies the same masks.
 """
 import copy
 import math
@@ -154,6 +155,44 @@ def _mha_used_params(m):
     return [m.in_proj_weight, m.in_proj_bias, m.out_proj.weight, m.out_proj.bias]
 
 
+# Dropout sites of one training step, in forward order: "pos" (position encoding), then per layer "attn1" (self-attention
+# weights), "drop1", "attn2" (cross-attention weights), "drop3", and "out" (dropout_layer before wdc).
+_LAYER_SITES = {"attn1": 1, "drop1": 2, "attn2": 3, "drop3": 4}
+
+
+def dropout_seed(seed, site, layer=0):
+    """Seed of one dropout site from the step's base seed: the ONE schedule forward and backward both read, so the mask a
+    backward kernel regenerates is the forward's by construction."""
+    if site == "pos":
+        return seed
+    if site == "out":
+        return seed + 7
+    return seed + 1000 * (layer + 1) + _LAYER_SITES[site]
+
+
+ATTN_LDS_LIMIT = 160 * 1024      # bytes of LDS c3d_cap_attn_fwd / c3d_cap_attn_bwd accept (csrc/caption_ops.hip)
+
+
+def attn_lds_bytes(Lq, Lk, hd):
+    """(forward, backward) dynamic-LDS bytes of the attention kernels for one (sample, head): the forward stages K, V, the
+    query rows and one probability row per wave; the backward holds the whole [Lq][Lk] matrix."""
+    hs = hd | 1
+    return 4 * (2 * Lk * hs + Lq * hs + 4 * Lk), 4 * (2 * Lk * hs + 2 * Lq * hs + Lq * Lk)
+
+
+def check_attention_geometry(L, S, hd, backward):
+    """Refuse, before anything is launched, a caption length L / memory length S whose attention does not fit the kernels'
+    LDS budget.  The backward budget is the tighter one: without this check a training step would run its whole forward
+    and fail inside loss.backward()."""
+    for what, Lk in (("self-attention", L), ("cross-attention", S)):
+        fwd, bwd = attn_lds_bytes(L, Lk, hd)
+        for which, need in (("forward", fwd), ("backward", bwd))[:2 if backward else 1]:
+            if need > ATTN_LDS_LIMIT:
+                raise NotImplementedError(
+                    f"caption decoder: the {what} {which} kernel needs {need} bytes of LDS for L = {L} caption tokens over "
+                    f"S = {S} memory tokens at head width {hd}; the limit is {ATTN_LDS_LIMIT}. Shorten S or L.")
+
+
 class _CaptionFn(torch.autograd.Function):
     """Whole decoder forward / backward (embedding .. vocabulary logits) as one autograd node."""
 
@@ -172,28 +211,28 @@ class _CaptionFn(torch.autograd.Function):
         Dp, V = cpad(D), dec.vocab_size
         R = L * B
         scale = 1.0 / math.sqrt(hd)
-        mem = memory.detach().to(act).contiguous().view(S * B, D)
         if Dp != D:
             raise NotImplementedError("embed_dim must be a multiple of 8")
+        check_attention_geometry(L, S, hd, backward=train)
+        mem = memory.detach().to(act).contiguous().view(S * B, D)
         tok = caps.detach().contiguous()
         x = torch.empty((R, Dp), dtype=act, device=dev)
         pe = dec.position_encoding.pe.view(-1, D)
-        ops.cap_embed_fwd(tok, dec.vocab_embedding.weight, pe, x, B, L, D, V, p_pos, seed, dt)
+        ops.cap_embed_fwd(tok, dec.vocab_embedding.weight, pe, x, B, L, D, V, p_pos, dropout_seed(seed, "pos"), dt)
         saved = []
         for li, layer in enumerate(dec.transformer.layers):
             sa, ca = layer.self_attn, layer.multihead_attn2
-            sd = seed + 1000 * (li + 1)
             # ---- causal self-attention
             qkv = torch.empty((R, 3 * D), dtype=act, device=dev)
             ops.linear_fwd(x, sa.in_proj_weight, sa.in_proj_bias, qkv, R, D, 3 * D, dt)
             P1 = torch.empty((H * B, L, L), dtype=torch.float32, device=dev)
             o1 = torch.empty((R, Dp), dtype=act, device=dev)
-            ops.cap_attn_fwd(qkv, qkv, qkv, 3 * D, 3 * D, 3 * D, o1, Dp, P1, B, H, L, L, hd, scale, True, p_attn, sd + 1, dt,
-                             q_off=0, k_off=D, v_off=2 * D)
+            ops.cap_attn_fwd(qkv, qkv, qkv, 3 * D, 3 * D, 3 * D, o1, Dp, P1, B, H, L, L, hd, scale, True, p_attn,
+                             dropout_seed(seed, "attn1", li), dt, q_off=0, k_off=D, v_off=2 * D)
             a1 = torch.empty((R, Dp), dtype=act, device=dev)
             ops.linear_fwd(o1, sa.out_proj.weight, sa.out_proj.bias, a1, R, D, D, dt)
             if p_attn > 0:
-                ops.cap_dropout(a1, a1, R, D, p_attn, sd + 2, dt)           # dropout1
+                ops.cap_dropout(a1, a1, R, D, p_attn, dropout_seed(seed, "drop1", li), dt)
             x1 = torch.empty((R, Dp), dtype=act, device=dev)
             mr1 = torch.empty((R, 2), dtype=torch.float32, device=dev)
             ops.cap_layernorm_fwd(x, a1, layer.norm1, x1, mr1, R, D, dt)
@@ -204,12 +243,12 @@ class _CaptionFn(torch.autograd.Function):
             ops.linear_fwd(mem, ca.in_proj_weight[D:], ca.in_proj_bias[D:], kv2, S * B, D, 2 * D, dt)
             P2 = torch.empty((H * B, L, S), dtype=torch.float32, device=dev)
             o2 = torch.empty((R, Dp), dtype=act, device=dev)
-            ops.cap_attn_fwd(q2, kv2, kv2, Dp, 2 * D, 2 * D, o2, Dp, P2, B, H, L, S, hd, scale, False, p_attn, sd + 3, dt,
-                             k_off=0, v_off=D)
+            ops.cap_attn_fwd(q2, kv2, kv2, Dp, 2 * D, 2 * D, o2, Dp, P2, B, H, L, S, hd, scale, False, p_attn,
+                             dropout_seed(seed, "attn2", li), dt, k_off=0, v_off=D)
             a2 = torch.empty((R, Dp), dtype=act, device=dev)
             ops.linear_fwd(o2, ca.out_proj.weight, ca.out_proj.bias, a2, R, D, D, dt)
             if p_attn > 0:
-                ops.cap_dropout(a2, a2, R, D, p_attn, sd + 4, dt)           # dropout3
+                ops.cap_dropout(a2, a2, R, D, p_attn, dropout_seed(seed, "drop3", li), dt)
             x2 = torch.empty((R, Dp), dtype=act, device=dev)
             mr2 = torch.empty((R, 2), dtype=torch.float32, device=dev)
             ops.cap_layernorm_fwd(x1, a2, layer.norm2, x2, mr2, R, D, dt)
@@ -218,7 +257,7 @@ class _CaptionFn(torch.autograd.Function):
         xd = x
         if p_out > 0:
             xd = torch.empty_like(x)
-            ops.cap_dropout(x, xd, R, D, p_out, seed + 7, dt)               # dropout_layer
+            ops.cap_dropout(x, xd, R, D, p_out, dropout_seed(seed, "out"), dt)
         Vp = cpad(V)
         logits = torch.empty((R, Vp), dtype=act, device=dev)
         ops.linear_fwd(xd, dec.wdc.weight, dec.wdc.bias, logits, R, D, V, dt)
@@ -237,13 +276,12 @@ class _CaptionFn(torch.autograd.Function):
         dx = torch.empty((R, Dp), dtype=act, device=dev)
         ops.linear_bwd(xd, dec.wdc.weight, dl, dx, ops.grad_of(dec.wdc.weight), ops.grad_of(dec.wdc.bias), R, D, V, dt)
         if p_out > 0:
-            ops.cap_dropout(dx, dx, R, D, p_out, seed + 7, dt)
+            ops.cap_dropout(dx, dx, R, D, p_out, dropout_seed(seed, "out"), dt)
         dmem = torch.zeros((S * B, Dp), dtype=act, device=dev)
         first_mem = True
         for li in range(len(saved) - 1, -1, -1):
             layer = dec.transformer.layers[li]
             sa, ca = layer.self_attn, layer.multihead_attn2
-            sd = seed + 1000 * (li + 1)
             x0, qkv, P1, o1, a1, mr1, x1, q2, kv2, P2, o2, a2, mr2 = saved[li]
             # ---- x2 = LN2(x1 + a2)
             d12 = torch.empty((R, Dp), dtype=act, device=dev)        # gradient of x1 (residual) == gradient of a2
@@ -251,13 +289,13 @@ class _CaptionFn(torch.autograd.Function):
             da2 = d12
             if p_attn > 0:
                 da2 = torch.empty_like(d12)
-                ops.cap_dropout(d12, da2, R, D, p_attn, sd + 4, dt)
+                ops.cap_dropout(d12, da2, R, D, p_attn, dropout_seed(seed, "drop3", li), dt)
             do2 = torch.empty((R, Dp), dtype=act, device=dev)
             ops.linear_bwd(o2, ca.out_proj.weight, da2, do2, ops.grad_of(ca.out_proj.weight), ops.grad_of(ca.out_proj.bias), R, D, D, dt)
             dq2 = torch.empty((R, Dp), dtype=act, device=dev)
             dkv2 = torch.empty((S * B, 2 * D), dtype=act, device=dev)
             ops.cap_attn_bwd(q2, kv2, kv2, Dp, 2 * D, 2 * D, do2, Dp, P2, dq2, dkv2, dkv2, Dp, 2 * D, 2 * D, B, H, L, S, hd, scale,
-                             p_attn, sd + 3, dt, k_off=0, v_off=D, dk_off=0, dv_off=D)
+                             p_attn, dropout_seed(seed, "attn2", li), dt, k_off=0, v_off=D, dk_off=0, dv_off=D)
             gw, gb = ops.grad_of(ca.in_proj_weight), ops.grad_of(ca.in_proj_bias)
             # memory projection: d mem += dkv2 @ W_kv ; parameter gradients into the [D:] rows
             ops.linear_bwd(mem, ca.in_proj_weight[D:], dkv2, dmem, gw[D:], gb[D:], S * B, D, 2 * D, dt,
@@ -272,17 +310,18 @@ class _CaptionFn(torch.autograd.Function):
             da1 = d01
             if p_attn > 0:
                 da1 = torch.empty_like(d01)
-                ops.cap_dropout(d01, da1, R, D, p_attn, sd + 2, dt)
+                ops.cap_dropout(d01, da1, R, D, p_attn, dropout_seed(seed, "drop1", li), dt)
             do1 = torch.empty((R, Dp), dtype=act, device=dev)
             ops.linear_bwd(o1, sa.out_proj.weight, da1, do1, ops.grad_of(sa.out_proj.weight), ops.grad_of(sa.out_proj.bias), R, D, D, dt)
             dqkv = torch.empty((R, 3 * D), dtype=act, device=dev)
             ops.cap_attn_bwd(qkv, qkv, qkv, 3 * D, 3 * D, 3 * D, do1, Dp, P1, dqkv, dqkv, dqkv, 3 * D, 3 * D, 3 * D, B, H, L, L, hd,
-                             scale, p_attn, sd + 1, dt, q_off=0, k_off=D, v_off=2 * D, dq_off=0, dk_off=D, dv_off=2 * D)
+                             scale, p_attn, dropout_seed(seed, "attn1", li), dt, q_off=0, k_off=D, v_off=2 * D, dq_off=0, dk_off=D,
+                             dv_off=2 * D)
             dx0 = torch.empty((R, Dp), dtype=act, device=dev)
             ops.linear_bwd(x0, sa.in_proj_weight, dqkv, dx0, ops.grad_of(sa.in_proj_weight), ops.grad_of(sa.in_proj_bias), R, D, 3 * D,
                            dt, accumulate_dx=d01)
             dx = dx0
-        ops.cap_embed_bwd(tok, dx, ops.grad_of(dec.vocab_embedding.weight), B, L, D, V, p_pos, seed, dt)
+        ops.cap_embed_bwd(tok, dx, ops.grad_of(dec.vocab_embedding.weight), B, L, D, V, p_pos, dropout_seed(seed, "pos"), dt)
         gmem = dmem.view(S, B, Dp)[:, :, :D].to(mem_dtype) if ctx.needs_input_grad[0] else None
         return (gmem, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
 

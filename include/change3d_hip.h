@@ -655,7 +655,9 @@ int c3d_stage_saved(const c3d_stage_desc* d, int32_t blk, const char* name, int6
  * storage dtype; the linear layers run on c3d_pw_gemm / c3d_pw_wgrad (bias through c3d_pw_args.bias, bias gradient
  * through c3d_col_sum).  Dropout masks are counter-based: (seed, element index) -> keep/drop, regenerated in backward.
  * ------------------------------------------------------------------------------------ */
-/* out[l*B+b] = dropout_p(emb[tokens[b][l]] + pe[l]); tokens int64 [B][L]; emb f32 [V][D]; pe f32 [>=L][D]        */
+/* out[l*B+b] = dropout_p(emb[tokens[b][l]] + pe[l]); tokens int64 [B][L]; emb f32 [V][D]; pe f32 [>=L][D].  A token
+ * outside [0, V) is clamped to the nearest valid row (0 or V-1), in the forward and in the gradient alike: no read or
+ * atomic ever leaves the table.  Padding columns of out are written as 0.                                          */
 int c3d_cap_embed_fwd(const int64_t* tokens, const float* emb, const float* pe, void* out, int32_t B, int32_t L,
                       int32_t D, int32_t V, float p, uint64_t seed, int32_t dtype, void* stream);
 /* demb[tokens[b][l]] += dropout-mask * dout[l*B+b]   (f32 atomics)                                                */
@@ -671,7 +673,12 @@ int c3d_cap_layernorm_bwd(const void* x, const void* a, const void* dy, const fl
                           float* dgamma, float* dbeta, int64_t rows, int32_t D, int32_t dtype, void* stream);
 /* multi-head attention, one workgroup per (sample, head): q/k/v/o rows (l*B+b) with leading dimensions ld* (elements),
  * head h at column h*hd; P f32 [H*B][Lq][Lk] = softmax(scale*q.k^T (+causal mask)) BEFORE dropout (saved for backward);
- * o = dropout_p(P) v.                                                                                             */
+ * o = dropout_p(P) v.  hd <= 64 (C3D_E_BADARG beyond).  Each (sample, head) lives in LDS, with hs = hd | 1:
+ *   forward  4 * (2*Lk*hs + Lq*hs + 4*Lk)      bytes,
+ *   backward 4 * (2*Lk*hs + 2*Lq*hs + Lq*Lk)   bytes (the whole [Lq][Lk] matrix),
+ * and either entry returns C3D_E_UNSUPPORTED, writing nothing, above 160 KB.  The backward limit is the tighter one (Lq 52,
+ * hd 24: Lk <= 376 against Lk <= 734): a caller that trains must check the backward size before it runs the forward
+ * (model/caption_decoder.py check_attention_geometry).                                                             */
 int c3d_cap_attn_fwd(const void* q, const void* k, const void* v, int32_t ldq, int32_t ldk, int32_t ldv, void* o, int32_t ldo,
                      float* P, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, float scale, int32_t causal,
                      float p, uint64_t seed, int32_t dtype, void* stream);
@@ -684,13 +691,18 @@ int c3d_cap_attn_bwd(const void* q, const void* k, const void* v, int32_t ldq, i
  * a step counts iff l < declen[b] (int64 [B]) and target != ignore_index; loss = mean; lse f32 [L*B];
  * acc2 f64 [3] = (sum of the negative log-likelihoods, counted steps, top-1 hits = caption_accuracy(scores, targets, 1)
  * of reference model/utils.py:493-507 before its percentage scaling).  A counted step whose target lies outside [0, V)
- * makes the loss NaN (torch.nn.CrossEntropyLoss trips a device assert there): never silently ignored.              */
+ * makes the loss NaN (torch.nn.CrossEntropyLoss trips a device assert there): never silently ignored.  The last step
+ * (l = L-1) has no target and never counts.  When NO step counts (every declen 0, or every target ignore_index) the loss
+ * is 0, acc2 = (0, 0, 0) and c3d_cap_ce_bwd writes a zero gradient -- torch's mean over nothing would be NaN; here such a
+ * batch is a step without a decoder update, not a poisoned one.                                                    */
 int c3d_cap_ce_fwd(const void* logits, const int64_t* caps, const int64_t* declen, double* acc2, float* lse, float* loss,
                    int32_t B, int32_t L, int32_t V, int64_t ignore_index, int32_t dtype, void* stream);
 int c3d_cap_ce_bwd(const void* logits, const int64_t* caps, const int64_t* declen, const double* acc2, const float* lse,
                    const float* dloss, void* dlogits, int32_t B, int32_t L, int32_t V, int64_t ignore_index, int32_t dtype,
                    void* stream);
-/* clip_gradient (reference model/utils.py:481-491): g = clamp(g, -limit, limit) over a flat f32 gradient buffer     */
+/* clip_gradient (reference model/utils.py:481-491): g = clamp(g, -limit, limit) over a flat f32 gradient buffer with
+ * torch.clamp_'s semantics: +-inf go to the limit, NaN stays NaN (clipping never hides a diverged gradient);
+ * limit <= 0 or NaN is C3D_E_BADARG.                                                                               */
 int c3d_clamp_(float* g, int64_t n, float limit, void* stream);
 
 #ifdef __cplusplus

@@ -846,3 +846,91 @@ def test_pw_gemm_checks_the_folded_block_output_backward_arguments_without_a_lau
     assert call(a) == -1
     a = base(); a.wg_mode = 4                     # not a mode
     assert call(a) == -1
+
+
+def test_caption_reference_equals_oracle_decoder():
+    """tests/caption_reference.py::decoder_forward / packed_ce (matmul + softmax, the yardstick of the dropout-on GPU tests) is
+    the same function as oracle.caption.CaptionDecoder + cc_loss (nn.MultiheadAttention, nn.LayerNorm, packed F.cross_entropy)
+    when nothing is dropped: float64, train mode, p = 0 -- logits, loss and every gradient to 1e-9 relative."""
+    import caption_reference as R
+    from oracle import caption as oc, synth
+    V, S, B = 203, 37, 3
+    args = synth.make_cc_args(size=64, vocab_size=V, dropout=0.0)
+    ora = oc.CaptionDecoder(args)
+    sd = synth.synth_state_dict(ora, seed=9)
+    sd["position_encoding.pe"] = ora.state_dict()["position_encoding.pe"].clone()
+    ora.load_state_dict(sd)
+    ora = ora.double().train()
+    ora.position_encoding.dropout.p = 0.0
+    mem = synth.synth_tensor((S, B, 192), 11).double()
+    caps, caplens = synth.synth_captions(B, seed=4, vocab_size=V)
+    m_o = mem.clone().requires_grad_(True)
+    scores, caps_sorted, dl, sort_ind = ora(m_o, caps, caplens)
+    l_o, _, _ = oc.cc_loss(scores, caps_sorted, dl)
+    l_o.backward()
+    sd64 = {k: v.double().requires_grad_(True) for k, v in sd.items() if v.is_floating_point()}
+    m_r = mem.clone().requires_grad_(True)
+    all_kept = {"pos": torch.ones(52, B, 192), (1, "attn2"): torch.ones(B, 8, 52, S)}     # all-ones masks = no mask
+    logits = R.decoder_forward(sd64, m_r, caps, all_kept, args.n_head, p_attn=0.0)
+    l_r, n, _ = R.packed_ce(logits, caps, caplens.reshape(-1) - 1, 0)
+    l_r.backward()
+    rel = lambda a, b: ((a - b).abs().max() / b.abs().max()).item()  # noqa: E731
+    assert n == sum(dl)
+    assert rel(logits.permute(1, 0, 2)[sort_ind].detach(), scores.detach()) < 1e-9
+    assert abs(l_r.item() - l_o.item()) < 1e-9 * abs(l_o.item())
+    assert rel(m_r.grad, m_o.grad) < 1e-9
+    checked = 0
+    for name, p in ora.named_parameters():
+        if p.grad is None:
+            assert sd64[name].grad is None, name
+        else:
+            assert rel(sd64[name].grad, p.grad) < 1e-9, name
+            checked += 1
+    assert checked == 3 + 3 * 12
+    # a mask is really applied: dropping everything before wdc leaves the bias
+    none_kept = R.decoder_forward(sd64, m_r, caps, {"out": torch.zeros(52, B, 192)}, args.n_head, p_out=0.1)
+    assert torch.equal(none_kept.detach(), sd64["wdc.bias"].detach().expand(52, B, V))
+
+
+def test_caption_reference_ops_equal_torch():
+    """The per-op float64 restatements against torch's own modules (float64)."""
+    import caption_reference as R
+    g = torch.Generator().manual_seed(3)
+    x, a = torch.randn(7, 20, generator=g, dtype=torch.float64) + 3, torch.randn(7, 20, generator=g, dtype=torch.float64)
+    ln = torch.nn.LayerNorm(20).double()
+    with torch.no_grad():
+        ln.weight.copy_(torch.randn(20, generator=g)); ln.bias.copy_(torch.randn(20, generator=g))
+    y, mean, rstd = R.layernorm(x, a, ln.weight, ln.bias, ln.eps)
+    assert torch.allclose(y, ln(x + a), rtol=1e-12, atol=1e-12) and torch.allclose(mean, (x + a).mean(-1))
+    q_, k, v = (torch.randn(2, 3, 5, 8, generator=g, dtype=torch.float64) for _ in range(3))
+    P, o = R.attention(q_, k, v, 0.3, True)
+    want = torch.nn.functional.scaled_dot_product_attention(q_, k, v, is_causal=True, scale=0.3)
+    assert torch.allclose(o, want, rtol=1e-12, atol=1e-12) and torch.allclose(P.sum(-1), torch.ones(2, 3, 5, dtype=torch.float64))
+    assert (P[..., torch.triu(torch.ones(5, 5, dtype=torch.bool), 1)] == 0).all()
+    keep = torch.rand(2, 3, 5, 5, generator=g) < 0.5
+    _, od = R.attention(q_, k, v, 0.3, True, keep, 0.5)
+    assert torch.allclose(od, (P * keep * 2.0) @ v, rtol=1e-12, atol=1e-12)
+    assert R.keep_scale(0.0) == 1.0 and abs(R.keep_scale(0.1) - 1 / 0.9) < 1e-7
+
+
+def test_caption_dropout_seed_schedule_and_attention_budget():
+    """The seed schedule forward and backward share (values pinned: changing them changes every trained run under a fixed
+    torch seed), and the up-front refusal of a geometry the attention backward cannot take (pure arithmetic, no device)."""
+    from change3d_amd.model.caption_decoder import ATTN_LDS_LIMIT, attn_lds_bytes, check_attention_geometry, dropout_seed
+    s = 123456
+    assert dropout_seed(s, "pos") == s and dropout_seed(s, "out") == s + 7
+    assert [dropout_seed(s, site, 2) for site in ("attn1", "drop1", "attn2", "drop3")] == [s + 3001, s + 3002, s + 3003, s + 3004]
+    seeds = [dropout_seed(s, "pos"), dropout_seed(s, "out")] + [dropout_seed(s, site, li) for li in range(3)
+                                                                for site in ("attn1", "drop1", "attn2", "drop3")]
+    assert len(set(seeds)) == 14
+    with pytest.raises(KeyError):
+        dropout_seed(s, "drop2", 0)
+    assert attn_lds_bytes(52, 400, 24) == (91600, 173600) and ATTN_LDS_LIMIT == 160 * 1024
+    check_attention_geometry(52, 256, 24, backward=True)        # the training geometry
+    check_attention_geometry(52, 400, 24, backward=False)       # forward only (beam search / eval): taken
+    with pytest.raises(NotImplementedError, match=r"cross-attention backward .*L = 52 .*S = 400"):
+        check_attention_geometry(52, 400, 24, backward=True)
+    with pytest.raises(NotImplementedError, match=r"cross-attention forward .*S = 900"):
+        check_attention_geometry(52, 900, 24, backward=False)
+    with pytest.raises(NotImplementedError, match=r"self-attention backward .*L = 200"):
+        check_attention_geometry(200, 16, 24, backward=True)
