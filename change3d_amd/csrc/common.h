@@ -134,11 +134,17 @@ inline int c3d_knob(const char* name, int dflt) {
 // (forward launches come from the caller's thread, backward ones from autograd's) -- and its error is remembered and
 // returned by every later call, which makes no runtime call besides the launch.  "Once" is once per process, which is
 // right while a rank owns one device (parallel.py: one rank per GPU).  Returns what C3D_CHECK_LAUNCH would.
+// It also notes which kernel it launched (the kernel's host-side handle: one pointer store per launch and thread, host only):
+// a dispatcher that answers C3D_E_UNSUPPORTED falls through to another kernel without telling its caller, so a test asks
+// afterwards (c3d_last_kernel) to know what it compared.
+inline thread_local const void* c3d_last_launch = nullptr;
+
 template <auto Kernel, class... Args>
 int c3d_launch_lds(const dim3 grid, const dim3 block, const size_t lds, hipStream_t stream, const Args&... args) {
   static const hipError_t raised =
       hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (raised != hipSuccess) return (int)raised;
+  c3d_last_launch = reinterpret_cast<const void*>(Kernel);
   Kernel<<<grid, block, lds, stream>>>(args...);
   return (int)hipGetLastError();
 }

@@ -15,6 +15,7 @@
 #include "launch_hints.h"
 #include <cstdio>
 #include <cstring>
+#include <cxxabi.h>
 #include <deque>
 #include <mutex>
 #include <vector>
@@ -519,6 +520,32 @@ extern "C" int c3d_stage_ws_bytes(const c3d_stage_desc* d, int64_t* ws_fwd_bytes
   if (y_bytes) *y_bytes = (int64_t)P.y_bytes;
   if (dx_bytes) *dx_bytes = (int64_t)P.dx_bytes;
   return 0;
+}
+
+// The runtime knows the mangled device name of every registered kernel by its host handle; demangled, that is
+// "void (anonymous namespace)::dw_fwd_v2_kernel<unsigned short, 3, true, true>(unsigned short const*, ...)" (bf16_t is unsigned
+// short): return type, namespace and parameter list are cut, the template arguments stay.
+extern "C" const char* c3d_last_kernel(void) {
+  static thread_local char name[256];
+  name[0] = 0;
+  if (!c3d_last_launch) return name;
+  const char* mangled = hipKernelNameRefByPtr(c3d_last_launch, nullptr);
+  if (!mangled) return name;
+  int status = 0;
+  char* d = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+  const char* s = d ? d : mangled;
+  if (!strncmp(s, "void ", 5)) s += 5;
+  static const char anon[] = "(anonymous namespace)::";
+  size_t o = 0;
+  for (int depth = 0; *s && o + 1 < sizeof(name);) {
+    if (!strncmp(s, anon, sizeof(anon) - 1)) { s += sizeof(anon) - 1; continue; }
+    if (*s == '(' && depth == 0) break;   // the parameter list
+    depth += (*s == '<') - (*s == '>');
+    name[o++] = *s++;
+  }
+  name[o] = 0;
+  free(d);
+  return name;
 }
 
 extern "C" int c3d_stage_saved(const c3d_stage_desc* d, int32_t blk, const char* name, int64_t* offset, int64_t* bytes) {

@@ -142,6 +142,12 @@ def set_option(option, value):
     L.check(L.lib().c3d_set_option(int(option), int(value)), "c3d_set_option")
 
 
+def last_kernel():
+    """Name, with template arguments, of the kernel this thread launched last through the library's large-LDS launcher
+    (c3d_last_kernel): how a test knows which kernel a dispatcher picked."""
+    return L.lib().c3d_last_kernel().decode()
+
+
 def side_run(fn, *tensors):
     """Run `fn` (kernel launches) on the side stream after everything issued so far on the current
     stream.  Only inside an autograd backward pass (that is where the join callback can be queued: one

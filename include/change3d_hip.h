@@ -647,6 +647,13 @@ int c3d_stage_fwd_folded(const c3d_stage_desc* d, const void* fold, const void* 
 /* byte offsets (into ws_fwd) and sizes of what block `blk` stored: name is one of "a","b","c","sc","mr_a","mr_b",
  * "mr_c","mr_sc","ss_a","ss_b","ss_c","ss_sc","gate" -- test / debug access (returns C3D_E_BADARG if absent). */
 int c3d_stage_saved(const c3d_stage_desc* d, int32_t blk, const char* name, int64_t* offset, int64_t* bytes);
+/* name of the kernel the calling thread launched last through the library's large-LDS launcher (every pointwise GEMM,
+ * weight-gradient, depthwise, stem, decoder and attention kernel goes through it), with its template arguments as the
+ * demangler spells them (bf16 storage is `unsigned short`), e.g. "dw_fwd_v2_kernel<unsigned short, 3, true, true>"; ""
+ * before the first launch.  Host-only, test / debug: the dispatchers fall through to another kernel where one does not
+ * apply, and this is how a test knows which one it measured.  The string belongs to the calling thread and is valid until
+ * its next call.                                                                                                     */
+const char* c3d_last_kernel(void);
 
 /* ------------------------------------------------------------------------------------
  * Caption decoder of the change-captioning path (reference model/caption_decoder.py:526-613 CaptionDecoder, :316-423

@@ -134,6 +134,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     declared = set(re.findall(r"\b(c3d_[A-Za-z0-9_]+)\s*\(", header))
     assert declared == set(names), declared ^ set(names)
     assert b"gfx950" in _lib.lib().c3d_build_info()
+    assert _lib.lib().c3d_last_kernel() == b""      # host-only: nothing launched in this process, no runtime call made
 
 
 def test_product_path_fails_loudly_without_gpu():

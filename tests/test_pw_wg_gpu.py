@@ -277,17 +277,21 @@ def test_cooperative_conv_a_data_and_weight_gradient(Ci, Cin, M, mask):
                 ops.pw_gemm(t2d, wd, dx, wg_mode=ops.WG_MASKSUM, wg_x3=yd, **sums, **base)
             else:
                 ops.pw_gemm(t2d, wd, dx, **base)
+            kernel = ops.last_kernel()
             ops.pw_wgrad(t2d, yd, dw, M=M, K=Cin, N=Ci, dw_sn=Cin, dw_sk=1, dtype=dt, p2=ad, p_coef=coef)
         else:
             ops.pw_gemm(t2d, wd, dx, wg_mode=ops.WG_ROWS, wg_dw=dw, wg_x3=yd, wg_mask_out=mask, **sums, **base)
+            kernel = ops.last_kernel()
         torch.cuda.synchronize()
-        return dx, dw, s
+        return dx, dw, s, kernel
 
     try:
-        dx0, dw0, s0 = run(0)
-        dx1, dw1, s1 = run(1)
+        dx0, dw0, s0, k0 = run(0)
+        dx1, dw1, s1, k1 = run(1)
     finally:
         ops.set_option(ops.OPT_PW_CDG, 3)
+    # the two legs ran two kernels (c3d_pw_gemm falls back silently where the cooperative kernel does not apply)
+    assert k0.startswith("pw_gemm_kernel<") and k1.startswith("pw_cdg_a_kernel<"), (k0, k1)
     assert torch.isfinite(dx1.float()).all() and dx1.float().abs().max().item() > 0
     assert torch.equal(dx0.view(torch.int16), dx1.view(torch.int16)), f"{int((dx0.view(torch.int16) != dx1.view(torch.int16)).sum())} elements of dx differ"
     if mask:
@@ -339,19 +343,22 @@ def test_cooperative_conv_c_data_and_weight_gradient(Co, Ci, rows, B, ragged, ga
         dw = torch.ones((Co, Ci), dtype=torch.float32, device=DEV)
         if opt == 0 and Co > 48:      # no fused form in the first kernel
             ops.pw_gemm(gd, wd, t1, stats=nc3, **base)
+            kernel = ops.last_kernel()
             kw = dict(q_gate=gt) if gated else {}
             ops.pw_wgrad(gd, bd, dw, M=M, K=Ci, N=Co, dw_sn=Ci, dw_sk=1, dtype=dt, p2=cd, p_coef=coef, q_mode=ops.PRO_BN_SE_SWISH, q_ss=ss,
                          rows_per_sample=rows, **kw)
         else:
             ops.pw_gemm(gd, wd, t1, stats=nc3, wg_mode=ops.WG_SWISH, wg_dw=dw, **base)
+            kernel = ops.last_kernel()
         torch.cuda.synchronize()
-        return t1, nc3, dw
+        return t1, nc3, dw, kernel
 
     try:
-        t1_0, nc_0, dw_0 = run(0)
-        t1_1, nc_1, dw_1 = run(3)
+        t1_0, nc_0, dw_0, k0 = run(0)
+        t1_1, nc_1, dw_1, k1 = run(3)
     finally:
         ops.set_option(ops.OPT_PW_CDG, 3)
+    assert k0.startswith("pw_gemm_kernel<") and k1.startswith("pw_cdg_c_kernel<"), (k0, k1)
     assert torch.isfinite(t1_1.float()).all() and t1_1.float().abs().max().item() > 0
     # Same operands, same instruction chain (both disassemblies read: packed fma / mul, v_exp, v_rcp in the same association): the
     # results are equal bit for bit on the two narrower layers; at 96 -> 216 ONE element in ~600 000 comes out one bf16 ulp apart
