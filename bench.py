@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — BCD X3D-L train throughput (images/s) on N MI355X, one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one full training iteration of the reference loop (reference
@@ -10,8 +10,10 @@ poly-LR update, Trainer.update_bcd forward (train-mode BN), BCE+Dice, zero_grad,
 gradient all-reduce (N>1), Adam, thresholded confusion-matrix update.  Workload = BASELINE.json
 configs[1]: BCD X3D-L, bf16 activations, B=32 per GPU, 256x256 pairs, T=3.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed, algorithmic
-bytes) and `cpu_baseline` (the CPU oracle = port of the reference path, timed on host cores).
+Prints ONE JSON line (rank 0).  A plain run does what the headline `value` needs and nothing else: set-up, settling and
+warm-up steps, the K timed steps, `--dump-outputs`, the line.  `--full` adds, after the timed steps and without touching
+them, `roofline` (dominant kernel, HIP-event timed in one extra step, algorithmic bytes), `also` (short SCD / CC / BCD-f32
+runs, a process each) and `cpu_baseline` (the CPU oracle = port of the reference path, timed on host cores).
 """
 import argparse
 import contextlib
@@ -34,7 +36,7 @@ A_CC_ELEMS = 170_270_000         # change-captioning encoder (blocks 0-4, K=1; S
 DUMP_BUDGET_BYTES = 60 * 10**6   # --dump-outputs writes at most this much array data in all (under 64 MB with the .npy headers)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -53,10 +55,15 @@ def parse():
                     help="host: every step starts from a pinned uint8 host batch (H2D copy + device input pipeline inside the "
                          "timed region) -- the PCIe-inclusive rate quoted in DESIGN.md, never the headline value")
     ap.add_argument("--settle", type=int, default=-1, help="untimed settling steps before the warm-up (default: 40 when --steps >= 10)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also take everything else this benchmark reports: the per-kernel HIP-event "
+                         "profile of one extra step (`roofline`, `--kernel-table`), the short SCD / CC / BCD-f32 runs (`also`) and the "
+                         "CPU oracle on the host cores (`cpu_baseline`); about a minute more.  Off by default: a plain run sets up, "
+                         "warms up, times the steps, writes `--dump-outputs` and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave `cpu_baseline` out")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="with --full: leave the per-kernel profile step (`roofline`) out")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the short SCD / CC / BCD-f32 runs the default command appends as `also` (BASELINE configs[3], [4]; "
+                    help="with --full: skip the short SCD / CC / BCD-f32 runs appended as `also` (BASELINE configs[3], [4]; "
                          "the parity-grade f32 path's price)")
     ap.add_argument("--windows", type=int, default=1,
                     help="split the K timed steps into this many equal windows (a device sync between them) and report each "
@@ -68,13 +75,26 @@ def parse():
                          "launch-readiness check of the multi-GPU path, never a measurement")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="c3d_set_option before the run (A/B of the library's run-time options, e.g. FUSE_WGRAD=1)")
-    ap.add_argument("--kernel-table", default="", help="write the per-kernel HIP-event table (JSON) here")
+    ap.add_argument("--kernel-table", default="", help="with --full: write the per-kernel HIP-event table (JSON) here")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (loss, network output, parameters after "
                          "the optimiser, their gradients) as DIR/<name>.npy.  That step starts from the seeded weights and a fresh "
                          "optimiser state (three device copies inside the timed region, < 0.01 %% of it), so every input of it is a "
                          "function of the arguments and two builds of the library can be compared output for output")
-    return ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.kernel_table and (not a.full or a.no_kernel_profile):
+        ap.error("--kernel-table is written by the per-kernel profile step: add --full (and drop --no-kernel-profile)")
+    return a
+
+
+def extra_legs(a, world=1):
+    """What a run measures besides its headline value, all of it after the timed steps: nothing unless `--full` is given.
+    kernel_profile = one extra eager step under HIP events (`roofline`, `--kernel-table`); also = the SCD / CC / BCD-f32
+    child runs, appended to the default workload only; cpu_baseline = the CPU oracle on the host cores."""
+    return {"kernel_profile": a.full and not a.no_kernel_profile,
+            "also": (a.full and not a.no_also and world == 1 and a.task == "bcd" and a.dtype == "bf16" and a.input == "device"
+                     and not a.graph),
+            "cpu_baseline": a.full and not a.no_cpu_baseline and world == 1}
 
 
 def usable_cores():
@@ -202,7 +222,7 @@ def pmc_traffic(entry):
 
 
 def also_runs(a):
-    """Short runs of the other workloads BASELINE.json names, each in its own process after the headline measurement
+    """`--full`: short runs of the other workloads BASELINE.json names, each in its own process after the headline measurement
     (30 timed steps in three windows of 10 after 40 settling + 5 warm-up steps -- `value` is the 30-step mean, the per-window
     ms/step give min / median; 120 s per child and 300 s in all, so the headline line is never held up for long; a run whose
     windows disagree by more than 5 % is measured once more and the better-agreeing run is kept, with the other recorded): SCD (configs[3], B=16, T=5), CC (configs[4], B=16) in bf16, and the BCD workload on the
@@ -216,7 +236,7 @@ def also_runs(a):
             res[key] = {"error": "skipped: the auxiliary runs' wall budget was spent"}
             continue
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "30", "--warmup", "5", "--size", str(a.size),
-               "--no-cpu-baseline", "--no-kernel-profile", "--no-also", "--windows", "3"] + extra
+               "--windows", "3"] + extra   # plain runs: the headline figure of each and nothing more
         try:
             best = None
             for attempt in (0, 1):
@@ -589,7 +609,7 @@ def main():
                                f"+bwd+{'clip+2xAdam' if cc else 'Adam'})",
                    "global_batch": a.batch * world, "parallelism": f"dp{world}", "dist_world_size": dist_world,
                    "dist_backend": (dist.get_backend() if world > 1 else None),
-                   "hip_graph": graph is not None, "settle_steps": settle, "input": "resident in HBM" if a.input == "device" else
+                   "hip_graph": graph is not None, "full": a.full, "settle_steps": settle, "input": "resident in HBM" if a.input == "device" else
                    "pinned uint8 host batch: H2D + device input pipeline every step (PCIe-inclusive, not the headline)",
                    "final_loss": round(final_loss, 5),
                    "host_enqueue_ms_per_step": round(t_enqueued / a.steps * 1e3, 3),
@@ -601,8 +621,10 @@ def main():
                           "unit": "GB/s", "frac": round(value / world * bytes_per_sample / 1e9 / HBM_PEAK_GBS, 4)},
     }
 
+    # ---- `--full` only, from here to the print: a plain run has its line already
     # ---- dominant kernel, timed live with HIP events on the launch stream (one extra eager step)
-    if rank == 0 and not a.no_kernel_profile:
+    legs = extra_legs(a, world)
+    if rank == 0 and legs["kernel_profile"]:
         net.encoder.x3d.blocks[3].post_backward = None
         net.encoder.x3d.blocks[4].post_backward = None
         # this extra step runs on rank 0 ONLY: no collective may be issued from it (a peer-less all-reduce would block
@@ -648,9 +670,9 @@ def main():
         for r in rows:
             print(f"[kernels] {r['kernel']:24s} x{r['launches']:4d} {r['ms_total']:9.3f} ms {r['GBps']:8.1f} GB/s",
                   file=sys.stderr)
-    if rank == 0 and world == 1 and not a.no_also and a.task == "bcd" and a.dtype == "bf16" and a.input == "device" and not a.graph:
+    if rank == 0 and legs["also"]:
         out["also"] = also_runs(a)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and legs["cpu_baseline"]:
         out["cpu_baseline"] = cpu_baseline(a.size) if not (scd or cc) else None   # the CPU leg times the BCD oracle only
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -341,6 +341,43 @@ def test_bench_refuses_a_world_size_mismatch():
     assert out.returncode != 0 and "WORLD_SIZE=1" in out.stderr and not out.stdout.strip()
 
 
+def test_bench_measures_the_headline_alone_unless_full_is_given():
+    """A plain `bench.py --gpus 1 --steps N --warmup W [--dump-outputs DIR]` takes no per-kernel profile step, starts no
+    SCD / CC / BCD-f32 child run and does not time the CPU oracle; `--full` brings all three back, each still to be left out by
+    its `--no-...` option, the child runs beside the default workload only as before; `--kernel-table` needs the profile step."""
+    import bench
+    nothing = {"kernel_profile": False, "also": False, "cpu_baseline": False}
+    for argv in ([], ["--gpus", "1", "--steps", "20", "--warmup", "5"], ["--steps", "20", "--warmup", "5", "--dump-outputs", "d"],
+                 ["--task", "scd"], ["--dtype", "f32"], ["--no-cpu-baseline", "--no-kernel-profile", "--no-also"]):
+        a = bench.parse(argv)
+        assert a.full is False and bench.extra_legs(a) == nothing, argv
+    everything = {"kernel_profile": True, "also": True, "cpu_baseline": True}
+    assert bench.extra_legs(bench.parse(["--full"])) == everything
+    assert bench.extra_legs(bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--dump-outputs", "d"])) == everything
+    for opt, leg in (("--no-kernel-profile", "kernel_profile"), ("--no-also", "also"), ("--no-cpu-baseline", "cpu_baseline")):
+        assert bench.extra_legs(bench.parse(["--full", opt])) == dict(everything, **{leg: False})
+    for argv in (["--task", "scd"], ["--task", "cc"], ["--dtype", "f32"], ["--input", "host"], ["--graph"]):
+        assert bench.extra_legs(bench.parse(["--full"] + argv)) == dict(everything, also=False), argv
+    assert bench.extra_legs(bench.parse(["--full", "--gpus", "2"]), world=2) == dict(everything, also=False, cpu_baseline=False)
+    assert bench.parse(["--full", "--kernel-table", "kt.json"]).kernel_table == "kt.json"
+    for argv in (["--kernel-table", "kt.json"], ["--full", "--no-kernel-profile", "--kernel-table", "kt.json"]):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)
+    # the child runs of `also` are plain runs themselves: no option of theirs may ask for more
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    child = src[src.index("def also_runs("):src.index("def self_launch(")]
+    assert '"--full"' not in child
+
+
+def test_bench_kernel_table_is_refused_without_full(tmp_path):
+    """The table is written by the `--full` profile step: asking for it in a plain run is an error, not an empty file."""
+    import subprocess
+    kt = tmp_path / "kt.json"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--kernel-table", str(kt)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--full" in r.stderr and not r.stdout.strip() and not kt.exists()
+
+
 def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path):
     """bench.py --dump-outputs: float32 / float64 .npy files, small arrays whole, a large one as the same sample of
     its elements in every call, the byte budget kept in all."""

@@ -257,3 +257,47 @@ def test_bench_self_launch_two_ranks_on_one_gpu(task):
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["config"]["dist_world_size"] == 2 and d["config"]["dist_backend"] == "gloo"
     assert d["config"]["global_batch"] == 4 and d["value"] > 0 and np.isfinite(d["config"]["final_loss"])
+
+
+def test_bench_plain_run_prints_the_headline_only_and_full_adds_the_rest(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]` does what its headline figure needs; the
+    per-kernel profile step (`roofline`, `--kernel-table`), the SCD / CC / BCD-f32 child runs (`also`) and the CPU oracle
+    (`cpu_baseline`) come with `--full`, after the timed steps: the two runs' lines agree on everything that describes the
+    headline measurement, and their dumped last timed steps agree."""
+    _need_gpu()
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "64", "--batch", "2"]
+    extras = ("roofline", "kernel_time_ms_eager_step", "also", "cpu_baseline")
+
+    def run(tag, more):
+        r = subprocess.run(base + ["--dump-outputs", str(tmp_path / tag)] + more, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout          # stdout carries exactly the JSON line
+        return json.loads(lines[0]), r.stderr
+
+    plain, err = run("plain", [])
+    assert not any(k in plain for k in extras), sorted(plain)
+    assert "[kernels]" not in err and plain["config"]["full"] is False
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "images/s" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "bf16" and plain["steps"] == 3 and plain["warmup"] == 1 and plain["step_roofline"]["frac"] > 0
+
+    kt = tmp_path / "kt.json"
+    full, err = run("full", ["--full", "--kernel-table", str(kt)])
+    assert all(k in full for k in extras), sorted(full)
+    assert "[kernels]" in err and full["config"]["full"] is True
+    assert full["roofline"]["kernel"].startswith("c3d_") and full["roofline"]["launches_per_step"] > 0
+    assert full["kernel_time_ms_eager_step"] > 0 and json.load(open(kt))["kernels"]
+    assert sorted(full["also"]) == ["bcd_f32", "cc", "scd"]
+    for key, d in full["also"].items():
+        assert "error" not in d and d["value"] > 0 and d["steps"] == 30 and len(d["ms_per_step_windows"]) == 3, (key, d)
+    assert full["also"]["bcd_f32"]["dtype"] == "f32" and full["cpu_baseline"]["value"] > 0
+    # the headline part of the line: same keys, same description of the job, whichever kind of run
+    assert sorted(k for k in full if k not in extras) == sorted(plain)
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "dtype", "data", "scaling", "dumped_outputs"):
+        assert full[k] == plain[k], k
+    assert {k: v for k, v in full["config"].items() if k not in ("full", "host_enqueue_ms_per_step", "final_loss")} == \
+           {k: v for k, v in plain["config"].items() if k not in ("full", "host_enqueue_ms_per_step", "final_loss")}
+    for name in ("loss", "output", "params", "grads"):
+        x, y = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert x.shape == y.shape and np.allclose(x, y, rtol=1e-4, atol=1e-5), name
+

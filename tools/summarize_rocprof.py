@@ -49,8 +49,8 @@ def find(d, pat):
 def main():
     root, tag = sys.argv[1], sys.argv[2]
     # ---- kernel stats (default run: side stream on; "_serial": side stream off)
-    for sub, suffix, cmd in (("prof_stats", "", "python bench.py --no-cpu-baseline"),
-                             ("prof_stats_serial", "_serial", "C3D_WGRAD_SIDE=0 python bench.py --no-cpu-baseline")):
+    for sub, suffix, cmd in (("prof_stats", "", "python bench.py --full --no-cpu-baseline --no-also"),
+                             ("prof_stats_serial", "_serial", "C3D_WGRAD_SIDE=0 python bench.py --full --no-cpu-baseline --no-also")):
       f = find(os.path.join(root, sub), "*kernel_stats.csv")
       if f:
           rows = list(csv.DictReader(open(f)))
@@ -62,7 +62,7 @@ def main():
           out = [{"entry": e, "calls": c, "total_ms": round(t / 1e6, 3), "avg_us": round(t / c / 1e3, 2)}
                  for e, (c, t) in sorted(agg.items(), key=lambda kv: -kv[1][1])]
           json.dump({"source": "rocprofv3 --kernel-trace --stats -- " + cmd,
-                     "note": "all launches of the run (python bench.py --no-also: 40 settling + 5 warm-up + 20 timed steps + 2 set-up / per-kernel profile steps through the stage driver = 67 steps)",
+                     "note": "all launches of the run (40 settling + 5 warm-up + 20 timed steps + 2 set-up / per-kernel profile steps through the stage driver = 67 steps)",
                      "by_entry": out,
                      "top_kernels": [{"name": r["Name"][:160], "calls": int(r["Calls"]),
                                       "avg_us": round(float(r["AverageNs"]) / 1e3, 2),
