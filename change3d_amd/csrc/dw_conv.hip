@@ -21,8 +21,6 @@
 #include <cstdlib>
 #include <cstring>
 
-thread_local int c3d_side_launch = 0;
-
 namespace {
 
 template <typename T> struct LdsStore;  // tile element type in LDS

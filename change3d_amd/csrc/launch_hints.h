@@ -4,14 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/change3d_hip.h"
 
-// Set by the stage driver around launches it places on its side stream.  Single-round kernels (one long-running
-// workgroup per CU for the whole launch) read it to leave CUs free: a side kernel that occupies every CU keeps EVERY
-// kernel of the data-gradient chain that becomes ready meanwhile -- including its 1-8 workgroup coefficient kernels --
-// waiting for its whole duration (measured on MI355X, B=32 bf16: depthwise weight gradient on 128 instead of 256
-// workgroups: step 35.6 -> 34.1 ms, and the 40 us stall around c3d_se_bn_bwd_coef disappears).
-// The pointwise weight gradient takes 7/8 of the CUs in the same situation (round 2: 256 -> 192 workgroups: 32.43 -> 31.69 ms; round 5: 192 -> 160: 23.18 -> 22.86 ms,
-// then -- with c3d_block_out_bwd folded into the conv_a data gradient: nothing small left to run beside a narrow grid -- 160 -> 224: 22.70 -> 22.29 ms;
-// profiles/r02_side_stream_width_final.json, csrc/pw_wgrad.hip).
+// Set by the stage driver around launches it places on its side stream; read by pw_wgrad_cap (pw_common.h), defined in pw_wgrad.hip
 extern thread_local int c3d_side_launch;
 
 // c3d_set_option (stage_driver.hip): kernel-family selectors with a parity test between the two implementations
@@ -23,14 +16,16 @@ extern int c3d_option_dw_fwd_hv;     // C3D_OPT_DW_FWD_HV: stride-1 three-frame 
 extern int c3d_option_dw_t4;         // C3D_OPT_DW_T4: four-frame clips (BDA) on the TT = 4 instantiations of the depthwise kernels (0: the five-frame ones)
 extern int c3d_option_pw_cfwd;       // C3D_OPT_PW_CFWD: conv_c forward of the training path on csrc/pw_cfwd.hip
 extern int c3d_option_pw_cdg;        // C3D_OPT_PW_CDG: conv_a (bit 0) / conv_c (bit 1) data + weight gradient on csrc/pw_cdgrad.hip
-int c3d_detail_pw_cdg_a(const c3d_pw_args* args, void* stream);
-bool c3d_detail_pw_cdg_a_supported(int Kp, int Np, int64_t M);
-int c3d_detail_pw_cdg_c(const c3d_pw_args* args, void* stream);
-bool c3d_detail_pw_cdg_c_supported(int Kp, int Np, int64_t M, int64_t rows_per_sample);
-// Set by the stage driver around a c3d_pw_gemm call: the cooperative kernel then leaves its weight-gradient partials in
-// wg_ws WITHOUT launching the reducer and reports their count in c3d_cdg_parts (0: another kernel ran, which reduced on its
-// own) -- the driver launches the reducer on its side stream (c3d_detail_pw_wgrad_reduce).
-extern thread_local int c3d_cdg_defer_reduce, c3d_cdg_parts;
+// The cooperative conv_a / conv_c data + weight gradient (pw_cdgrad.hip).  _shape: does the kernel hold the layer (workspace
+// plans, made before any pointer exists); _accepts: does the launch function take exactly these arguments -- the stage driver
+// skips the separate weight-gradient launch on it.  parts_out != NULL: the partials stay in wg_ws, their count is reported
+// and the caller launches c3d_detail_pw_wgrad_reduce; NULL: the reducer follows on `stream`.
+bool c3d_detail_pw_cdg_a_shape(int Kp, int Np, int64_t M);
+bool c3d_detail_pw_cdg_c_shape(int Kp, int Np, int64_t M, int64_t rows_per_sample);
+bool c3d_detail_pw_cdg_a_accepts(const c3d_pw_args* args);
+bool c3d_detail_pw_cdg_c_accepts(const c3d_pw_args* args);
+int c3d_detail_pw_cdg_a(const c3d_pw_args* args, int* parts_out, void* stream);
+int c3d_detail_pw_cdg_c(const c3d_pw_args* args, int* parts_out, void* stream);
 int c3d_detail_pw_wgrad_reduce(const float* ws, float* dw, int N, int K, int parts, int sn, int sk, hipStream_t stream);   // pw_wgrad.hip
 extern int c3d_option_pw_wgrad_v2;  // C3D_OPT_PW_WGRAD_V2: 1 = c3d_pw_wgrad of bf16 dense rows on csrc/pw_wgrad_v2.hip, 0 = pw_wgrad.hip's kernel
-void c3d_detail_pw_wgrad_v2_drop();  // forget pending partials of a chained c3d_pw_wgrad launch WITHOUT reducing them (start of a stage pass)
+void c3d_detail_pw_wgrad_v2_forget(const float* ws);   // pending partials of a chained c3d_pw_wgrad launch that sit in `ws`: forgotten, NOT reduced

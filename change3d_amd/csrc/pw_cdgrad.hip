@@ -25,12 +25,10 @@
 #include "common.h"
 #include "../../include/change3d_hip.h"
 #include "pw_common.h"
+#include "pw_coop.h"
 #include "launch_hints.h"
 #include "bn_fin.h"
 #include <cstdlib>
-#include <cstring>
-
-thread_local int c3d_cdg_defer_reduce = 0, c3d_cdg_parts = 0;
 
 #ifdef C3D_CD_CLOCK
 // Debug build only (tools/r6/cdg_clock.py): s_memtime stamps of wave 0 per workgroup of the conv_c kernel -- [0] entry, [1]
@@ -48,7 +46,6 @@ extern "C" int c3d_debug_cd_clock(unsigned long long* out) {
 namespace {
 
 constexpr int CD_THREADS = 512;
-constexpr uint32_t CD_OOB = 0x80000000u;
 constexpr int CD_MAX_PARTS = 512;     // = PW_WG_MAX_PARTS: the fused-variant workspace holds this many K x N partials
 
 struct CdPlan {
@@ -62,30 +59,6 @@ struct CdPlan {
   int par_off, dump_off;     // A | B | C [Kp] each, mean | rstd [Np] each; dump
 };
 
-typedef uint32_t cd_u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* cd_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* cd_glb_ptr_t;
-typedef short cd_s16x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) cd_s16x4_t* cd_lds_s16x4_ptr_t;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t cd_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, p ? (int)bytes : 0, 0x00020000);
-}
-__device__ __forceinline__ uint4 cd_load(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  const cd_u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ void cd_cvt(const uint4& v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ void cd_ld8(const float* p, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
 
 // KS: k-steps of 32 of the data gradient (Kpad / 32); NTW: its output tiles (16 channels) per wave; NPW x NQW: weight-
 // gradient tiles (P channels x y_prev channels) per wave; RP / RQ: 16-byte items per thread and tile of the P streams / of
@@ -108,12 +81,12 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
   int t1 = t0 + L.tiles_per_wg;
   if (t1 > tiles) t1 = tiles;
   const uint32_t row_hi = (uint32_t)(t1 * MT < M32 ? t1 * MT : M32);
-  const __amdgpu_buffer_rsrc_t rX = cd_rsrc(a.x, row_hi * (uint32_t)Kp * 2u);
-  const __amdgpu_buffer_rsrc_t rX2 = cd_rsrc(a.x2, row_hi * (uint32_t)Kp * 2u);
-  const __amdgpu_buffer_rsrc_t rQ = cd_rsrc(a.wg_x3, row_hi * (uint32_t)Np * 2u);
-  const __amdgpu_buffer_rsrc_t rE1 = cd_rsrc(a.e1, (uint32_t)M32 * (uint32_t)Np * 2u);
-  const __amdgpu_buffer_rsrc_t rC1 = cd_rsrc(a.add_sums ? a.add_c : nullptr, (uint32_t)M32 * (uint32_t)Np * 2u);
-  const __amdgpu_buffer_rsrc_t rY = cd_rsrc(a.y, (uint32_t)M32 * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rX = co_rsrc(a.x, row_hi * (uint32_t)Kp * 2u);
+  const __amdgpu_buffer_rsrc_t rX2 = co_rsrc(a.x2, row_hi * (uint32_t)Kp * 2u);
+  const __amdgpu_buffer_rsrc_t rQ = co_rsrc(a.wg_x3, row_hi * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rE1 = co_rsrc(a.e1, (uint32_t)M32 * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rC1 = co_rsrc(a.add_sums ? a.add_c : nullptr, (uint32_t)M32 * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rY = co_rsrc(a.y, (uint32_t)M32 * (uint32_t)Np * 2u);
 
   // ---- item maps: item i = tid + 512 r of a tile <-> (row = i / G, vector = i % G); its bytes sit at tile base + 16 i
   int p_desc[RP], q_desc[RQ];
@@ -126,7 +99,7 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
       const int row = __float2int_rz(((float)i + 0.5f) * invG);
       const bool ok = i < MT * Gq;
       p_desc[r] = ok ? (row << 5) | (i - row * Gq) : 0;
-      p_go[r] = ok ? (uint32_t)i * 16u : CD_OOB;
+      p_go[r] = ok ? (uint32_t)i * 16u : CO_OOB;
     }
 #pragma unroll
     for (int r = 0; r < RQ; ++r) {
@@ -134,7 +107,7 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
       const int row = __float2int_rz(((float)i + 0.5f) * invN);
       const bool ok = i < MT * Gn;
       q_desc[r] = ok ? (row << 5) | (i - row * Gn) : 0;
-      q_go[r] = ok ? (uint32_t)i * 16u : CD_OOB;
+      q_go[r] = ok ? (uint32_t)i * 16u : CO_OOB;
     }
   }
   const bool p_last = (wave * 64 + CD_THREADS * (RP - 1)) < MT * Gq;   // (wave-uniform: the last round has an item for this wave)
@@ -144,9 +117,9 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
   {
     const uint32_t bp = (uint32_t)t0 * tbp, bq = (uint32_t)t0 * tbq;
 #pragma unroll
-    for (int r = 0; r < RP; ++r) { rawp[r] = cd_load(rX, p_go[r] + bp); rawp2[r] = cd_load(rX2, p_go[r] + bp); }
+    for (int r = 0; r < RP; ++r) { rawp[r] = co_load(rX, p_go[r] + bp); rawp2[r] = co_load(rX2, p_go[r] + bp); }
 #pragma unroll
-    for (int r = 0; r < RQ; ++r) rawq[r] = cd_load(rQ, q_go[r] + bq);
+    for (int r = 0; r < RQ; ++r) rawq[r] = co_load(rQ, q_go[r] + bq);
   }
 
   // ---- lane maps of the data gradient and of its epilogue (csrc/pw_cfwd.hip)
@@ -162,9 +135,9 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
   // and lane, a tile ahead
   uint4 e1r[NPASS], c1r[NPASS];
 #define CD_EOFF(TILE, P) ((act_o && (P) * RPO + rr_o < 16 && (TILE) * MT + wr * 16 + (P) * RPO + rr_o < M32)                        \
-                              ? ((uint32_t)((TILE) * MT + wr * 16 + (P) * RPO + rr_o) * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CD_OOB)
+                              ? ((uint32_t)((TILE) * MT + wr * 16 + (P) * RPO + rr_o) * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CO_OOB)
 #pragma unroll
-  for (int p = 0; p < NPASS; ++p) { const uint32_t o = t0 < t1 ? CD_EOFF(t0, p) : CD_OOB; e1r[p] = cd_load(rE1, o); c1r[p] = cd_load(rC1, o); }
+  for (int p = 0; p < NPASS; ++p) { const uint32_t o = t0 < t1 ? CD_EOFF(t0, p) : CO_OOB; e1r[p] = co_load(rE1, o); c1r[p] = co_load(rC1, o); }
 
   // ---- weight image -> LDS (LDS-DMA, 1 KB per wave instruction; the chunk order rotated by the workgroup index)
   {
@@ -177,7 +150,7 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
       if (r >= nchunk) r -= nchunk;
       const int off = r * 1024 + lane * 16;
       if (off < wbytes)
-        __builtin_amdgcn_global_load_lds((cd_glb_ptr_t)(src + off), (cd_lds_ptr_t)(smem + L.w_off + r * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((co_glb_ptr_t)(src + off), (co_lds_ptr_t)(smem + L.w_off + r * 1024), 16, 0, 0);
     }
   }
   // all four tiles zeroed once: the padding columns are never written again (k padding of P: 0 x weight row; channel padding
@@ -231,24 +204,24 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
     _Pragma("unroll") for (int r = 0; r < RP; ++r) {                                                                \
       if (r == RP - 1 && !p_last) continue;                                                                         \
       const int row = p_desc[r] >> 5, v = p_desc[r] & 31;                                                           \
-      bf16_t* dst = p_go[r] != CD_OOB ? (CP) + row * KL + v * 8 : dump;                                             \
+      bf16_t* dst = p_go[r] != CO_OOB ? (CP) + row * KL + v * 8 : dump;                                             \
       float f[8], f2[8], cA[8], cB[8], cC[8];                                                                       \
-      cd_cvt(rawp[r], f); cd_cvt(rawp2[r], f2);                                                                     \
-      cd_ld8(Pp + v * 8, cA); cd_ld8(Pp + Kp + v * 8, cB); cd_ld8(Pp + 2 * Kp + v * 8, cC);                         \
+      co_cvt(rawp[r], f); co_cvt(rawp2[r], f2);                                                                     \
+      co_ld8(Pp + v * 8, cA); co_ld8(Pp + Kp + v * 8, cB); co_ld8(Pp + 2 * Kp + v * 8, cC);                         \
       /* a row past the tensor's end is zero x A + B: zeroed by a bit mask (`real ? fma : 0` compiles to a branch) */ \
       const uint32_t keep = rowg0_ + row < M32 ? 0xffffffffu : 0u;                                                  \
       _Pragma("unroll") for (int e = 0; e < 8; ++e)                                                                 \
         f[e] = __uint_as_float(__float_as_uint(fmaf(cA[e], f[e], fmaf(cC[e], f2[e], cB[e]))) & keep);               \
       Vec8<bf16_t>::store(dst, f);                                                                                  \
-      rawp[r] = cd_load(rX, p_go[r] + bpn_);   /* (past this workgroup's last row: zeros, no memory access) */       \
-      rawp2[r] = cd_load(rX2, p_go[r] + bpn_);                                                                      \
+      rawp[r] = co_load(rX, p_go[r] + bpn_);   /* (past this workgroup's last row: zeros, no memory access) */       \
+      rawp2[r] = co_load(rX2, p_go[r] + bpn_);                                                                      \
     }                                                                                                               \
     _Pragma("unroll") for (int r = 0; r < RQ; ++r) {                                                                \
       if (r == RQ - 1 && !q_last) continue;                                                                         \
       const int row = q_desc[r] >> 5, v = q_desc[r] & 31;                                                           \
-      bf16_t* dst = q_go[r] != CD_OOB ? (CQ) + row * QL + v * 8 : dump;                                             \
+      bf16_t* dst = q_go[r] != CO_OOB ? (CQ) + row * QL + v * 8 : dump;                                             \
       *reinterpret_cast<uint4*>(dst) = rawq[r];                                                                     \
-      rawq[r] = cd_load(rQ, q_go[r] + bqn_);                                                                        \
+      rawq[r] = co_load(rQ, q_go[r] + bqn_);                                                                        \
     }                                                                                                               \
   }
   // data gradient of one tile: A = weight fragment (packed image), B = data fragment (row-major P tile)
@@ -270,13 +243,13 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
       const bf16_t* pb_ = (CA) + k2 * 32 * KL + pl;                                                                 \
       const bf16_t* qb_ = (CQ) + k2 * 32 * QL + ql;                                                                 \
       _Pragma("unroll") for (int i = 0; i < NPW; ++i) {                                                             \
-        const cd_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_lds_s16x4_ptr_t)(pb_ + i * 16));        \
-        const cd_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_lds_s16x4_ptr_t)(pb_ + 16 * KL + i * 16)); \
+        const co_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(pb_ + i * 16));        \
+        const co_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(pb_ + 16 * KL + i * 16)); \
         pa[i] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7));               \
       }                                                                                                             \
       _Pragma("unroll") for (int j = 0; j < NQW; ++j) {                                                             \
-        const cd_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_lds_s16x4_ptr_t)(qb_ + j * 16));        \
-        const cd_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_lds_s16x4_ptr_t)(qb_ + 16 * QL + j * 16)); \
+        const co_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(qb_ + j * 16));        \
+        const co_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(qb_ + 16 * QL + j * 16)); \
         qb[j] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7));               \
       }                                                                                                             \
       _Pragma("unroll") for (int i = 0; i < NPW; ++i)                                                               \
@@ -302,8 +275,8 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
       const uint4 rawo = *reinterpret_cast<const uint4*>(Os + rowc * NLW + v_o * 8);                                \
       const uint4 x3 = *reinterpret_cast<const uint4*>((CQ) + (wr * 16 + rowc) * QL + (act_o ? cvec : 0) * 8);      \
       float f[8], rv[8], cv[8], eM[8], eR[8];                                                                       \
-      cd_cvt(rawo, f); cd_cvt(e1r[p], rv); cd_cvt(c1r[p], cv);                                                      \
-      cd_ld8(Ep + (act_o ? cvec : 0) * 8, eM); cd_ld8(Ep + Np + (act_o ? cvec : 0) * 8, eR);                        \
+      co_cvt(rawo, f); co_cvt(e1r[p], rv); co_cvt(c1r[p], cv);                                                      \
+      co_ld8(Ep + (act_o ? cvec : 0) * 8, eM); co_ld8(Ep + Np + (act_o ? cvec : 0) * 8, eR);                        \
       const uint32_t xw[4] = {x3.x, x3.y, x3.z, x3.w};                                                              \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                               \
         const uint32_t hx = (xw[j >> 1] >> ((j & 1) * 16)) & 0xffffu;                                               \
@@ -315,10 +288,10 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_a_kernel(const c3d_pw_args 
         s0[j] += gq; s1[j] = fmaf(gq, (cv[j] - eM[j]) * eR[j], s1[j]);                                              \
       }                                                                                                             \
       const uint4 pk = make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])); \
-      __builtin_amdgcn_raw_buffer_store_b128(cd_u32x4_t{pk.x, pk.y, pk.z, pk.w}, rY,                                \
-                                             ok ? ((uint32_t)m * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CD_OOB, 0, 0); \
-      const uint32_t no_ = (NEXT_ON) ? CD_EOFF((TILE) + 1, p) : CD_OOB;                                             \
-      e1r[p] = cd_load(rE1, no_); c1r[p] = cd_load(rC1, no_);                                                       \
+      __builtin_amdgcn_raw_buffer_store_b128(co_u32x4_t{pk.x, pk.y, pk.z, pk.w}, rY,                                \
+                                             ok ? ((uint32_t)m * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CO_OOB, 0, 0); \
+      const uint32_t no_ = (NEXT_ON) ? CD_EOFF((TILE) + 1, p) : CO_OOB;                                             \
+      e1r[p] = co_load(rE1, no_); c1r[p] = co_load(rC1, no_);                                                       \
     }                                                                                                               \
   }
 
@@ -422,11 +395,19 @@ int cd_variant(int Kp, int Np) {
   return 0;
 }
 
-int cd_plan(const c3d_pw_args& a, CdPlan& L, int64_t& blocks, size_t& lds) {
-  const int var = cd_variant(a.Kp, a.Np);
-  if (!var) return 0;
-  const int Kpad = (a.Kp + 31) / 32 * 32, KS = Kpad / 32, ntn = (a.Np + 15) >> 4;
-  L.img_rows = (ntn <= 2 ? 2 : ntn <= 4 ? 4 : ntn <= 7 ? 7 : 14) * 16;
+// What a launch needs beside its arguments: instantiation (0: the kernel does not take the call), plan, grid, LDS bytes
+template <typename PlanT> struct CdgLaunch { int var = 0; PlanT L; int64_t blocks = 0; size_t lds = 0; };
+
+// Shape layer: all the stage driver's workspace plan can ask (c3d_detail_pw_cdg_a_shape); the launch asks cd_accept, which
+// ends here.
+CdgLaunch<CdPlan> cd_plan(int Kp, int Np, int64_t M) {
+  CdgLaunch<CdPlan> R;
+  CdPlan& L = R.L;
+  if (Kp <= 0 || Np <= 0 || (Kp & 7) || (Np & 7) || M < 1024 || !pw_fits_u32(M + 512, Kp, Np, 2)) return R;
+  const int var = cd_variant(Kp, Np);
+  if (!var) return R;
+  const int Kpad = (Kp + 31) / 32 * 32, KS = Kpad / 32, ntn = (Np + 15) >> 4;
+  L.img_rows = pw_nt_bucket(Np) * 16;
   int NTW;
   // (216 -> 96: 32-row tiles, 2 row slabs x 4 column groups of two output tiles -- the fourth group is padding: with 64-row tiles
   // the prefetch registers of three row streams beside 48 weight-gradient accumulators spilled, and LDS was full)
@@ -436,26 +417,37 @@ int cd_plan(const c3d_pw_args& a, CdPlan& L, int64_t& blocks, size_t& lds) {
   L.MT = 16 * L.WR;
   L.KL = Kpad + 8;
   L.QL = ntn * 16 + 8;
-  const int64_t tiles = (a.M + L.MT - 1) / L.MT;
-  blocks = device_cus();
-  if (blocks > (tiles + 1) / 2) blocks = (tiles + 1) / 2;
-  if (blocks > CD_MAX_PARTS) blocks = CD_MAX_PARTS;
-  if (blocks < 1) blocks = 1;
-  const int tpw = (int)((tiles + blocks - 1) / blocks);
-  blocks = (tiles + tpw - 1) / tpw;
-  L.tiles_per_wg = tpw;
+  const PwWalk walk = pw_walk((M + L.MT - 1) / L.MT, device_cus() < CD_MAX_PARTS ? device_cus() : CD_MAX_PARTS, 2);
+  R.blocks = walk.blocks;
+  L.tiles_per_wg = walk.tiles_per_wg;
   auto al = [](size_t v) { return (v + 1023) / 1024 * 1024; };
   size_t off = 0;
   L.w_off = 0; off += al((size_t)KS * 4 * L.img_rows * 16);
   L.a_off = (int)off; L.a_bytes = (int)al((size_t)L.MT * L.KL * 2); off += 2 * (size_t)L.a_bytes;
   L.q_off = (int)off; L.q_bytes = (int)al((size_t)L.MT * L.QL * 2); off += 2 * (size_t)L.q_bytes;
-  if (2 * (size_t)L.a_bytes + 2 * (size_t)L.q_bytes < (size_t)8 * 16 * 64 * 4) return 0;   // (the statistics dump at the end reuses the tiles)
+  if (2 * (size_t)L.a_bytes + 2 * (size_t)L.q_bytes < (size_t)8 * 16 * 64 * 4) return R;   // (the statistics dump at the end reuses the tiles)
   L.os_wave = 16 * (NTW * 16 + 8) * 2; L.os_off = (int)off; off += al((size_t)8 * L.os_wave);
-  L.par_off = (int)off; off += al(((size_t)3 * a.Kp + 2 * a.Np) * 4);
+  L.par_off = (int)off; off += al(((size_t)3 * Kp + 2 * Np) * 4);
   L.dump_off = (int)off; off += (size_t)CD_THREADS * 16;
-  if (off > 160 * 1024) return 0;
-  lds = off;
-  return var;
+  if (off > 160 * 1024) return R;
+  R.lds = off;
+  R.var = var;
+  return R;
+}
+
+// What the two kernels share of the argument layer: bf16 dense rows, BatchNorm backward on load (coefficients rebuilt from the
+// producer's completed sums, or read from memory), the packed weight image, a weight gradient to leave
+bool cdg_common_args(const c3d_pw_args& a) {
+  if (a.dtype != C3D_DT_BF16 || a.row_mode != C3D_ROWS_DENSE || a.pro_mode != C3D_PRO_AFFINE2) return false;
+  if (!a.w_img || !a.x2 || !a.e1 || !a.wg_dw || !a.wg_ws || a.pro_out || a.bias || a.fin.ticket) return false;
+  return a.fin.sums ? (a.fin.training == 0 && a.fin.mr && a.fin.gamma) : a.pro_p != nullptr;
+}
+
+// Argument layer: does pw_cdg_a_kernel take exactly this call?
+CdgLaunch<CdPlan> cd_accept(const c3d_pw_args& a) {
+  if (!cdg_common_args(a) || a.epi_mode != C3D_EPI_ADD || a.wg_mode != C3D_WG_ROWS || a.res_mode != 0 || !a.wg_x3) return {};
+  if (a.add_sums && (!a.add_c || !a.add_mr || !a.wg_mask_out)) return {};
+  return cd_plan(a.Kp, a.Np, a.M);
 }
 
 
@@ -507,10 +499,10 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
   int t1 = t0 + L.tiles_per_wg;
   if (t1 > tiles) t1 = tiles;
   const uint32_t row_hi = (uint32_t)(t1 * MT < M32 ? t1 * MT : M32);
-  const __amdgpu_buffer_rsrc_t rX = cd_rsrc(a.x, row_hi * (uint32_t)Kp * 2u);
-  const __amdgpu_buffer_rsrc_t rX2 = cd_rsrc(a.x2, row_hi * (uint32_t)Kp * 2u);
-  const __amdgpu_buffer_rsrc_t rE1 = cd_rsrc(a.e1, (uint32_t)M32 * (uint32_t)Np * 2u);
-  const __amdgpu_buffer_rsrc_t rY = cd_rsrc(a.y, (uint32_t)M32 * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rX = co_rsrc(a.x, row_hi * (uint32_t)Kp * 2u);
+  const __amdgpu_buffer_rsrc_t rX2 = co_rsrc(a.x2, row_hi * (uint32_t)Kp * 2u);
+  const __amdgpu_buffer_rsrc_t rE1 = co_rsrc(a.e1, (uint32_t)M32 * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rY = co_rsrc(a.y, (uint32_t)M32 * (uint32_t)Np * 2u);
   const uint32_t rps = (uint32_t)a.rows_per_sample;
 
   // ---- item map of the P streams (one round: MT x Kp / 8 <= 512 items)
@@ -520,14 +512,14 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
     const int row = __float2int_rz(((float)tid + 0.5f) * (1.0f / (float)Gq));
     const bool ok = tid < MT * Gq;
     p_desc = ok ? (row << 5) | (tid - row * Gq) : 0;
-    p_go = ok ? (uint32_t)tid * 16u : CD_OOB;
+    p_go = ok ? (uint32_t)tid * 16u : CO_OOB;
   }
   const uint32_t tbp = (uint32_t)(MT * Kp * 2);
   // two tiles of the row streams in flight (the waves of these kernels are parked ~50 % of their cycles with one): register set
   // s holds tile t0 + s (+ 2, + 4 ..); the tile loop is unrolled by two so that the sets are named statically
   uint4 rawp[2], rawp2[2];
 #pragma unroll
-  for (int s_ = 0; s_ < 2; ++s_) { rawp[s_] = cd_load(rX, p_go + (uint32_t)(t0 + s_) * tbp); rawp2[s_] = cd_load(rX2, p_go + (uint32_t)(t0 + s_) * tbp); }
+  for (int s_ = 0; s_ < 2; ++s_) { rawp[s_] = co_load(rX, p_go + (uint32_t)(t0 + s_) * tbp); rawp2[s_] = co_load(rX2, p_go + (uint32_t)(t0 + s_) * tbp); }
 
   // ---- lane maps of the data gradient and of its epilogue
   const int wr = wave % L.WR, wc = wave / L.WR;
@@ -541,11 +533,11 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
   const int cve = act_o ? cvec : 0;                       // (parameter / gate reads of lanes beyond the row stay inside the arrays)
   uint4 e1r[2][NPASS];
 #define CC_EOFF(TILE, P) ((act_o && (TILE) < t1 && (TILE) * MT + wr * 16 + (P) * RPO + rr_o < M32)                                                \
-                              ? ((uint32_t)((TILE) * MT + wr * 16 + (P) * RPO + rr_o) * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CD_OOB)
+                              ? ((uint32_t)((TILE) * MT + wr * 16 + (P) * RPO + rr_o) * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CO_OOB)
 #pragma unroll
   for (int s_ = 0; s_ < 2; ++s_)
 #pragma unroll
-    for (int p = 0; p < NPASS; ++p) e1r[s_][p] = cd_load(rE1, CC_EOFF(t0 + s_, p));
+    for (int p = 0; p < NPASS; ++p) e1r[s_][p] = co_load(rE1, CC_EOFF(t0 + s_, p));
 
   // ---- weight image -> LDS
   {
@@ -558,7 +550,7 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
       if (r >= nchunk) r -= nchunk;
       const int off = r * 1024 + lane * 16;
       if (off < wbytes)
-        __builtin_amdgcn_global_load_lds((cd_glb_ptr_t)(src + off), (cd_lds_ptr_t)(smem + L.w_off + r * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((co_glb_ptr_t)(src + off), (co_lds_ptr_t)(smem + L.w_off + r * 1024), 16, 0, 0);
     }
   }
   // the five tiles zeroed once (k padding of P; columns of q sg nobody writes)
@@ -623,16 +615,16 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
     const int rowg0_ = (TILE) * MT;                                                                                 \
     const uint32_t bpn_ = (uint32_t)((TILE) + 2) * tbp;   /* the slot is requested again for the tile after the next */  \
     const int row = p_desc >> 5, v = p_desc & 31;                                                                   \
-    bf16_t* dst = p_go != CD_OOB ? (CP) + row * KL + v * 8 : dump;                                                  \
+    bf16_t* dst = p_go != CO_OOB ? (CP) + row * KL + v * 8 : dump;                                                  \
     float f[8], f2[8], cA[8], cB[8], cC[8];                                                                         \
-    cd_cvt(rawp[S], f); cd_cvt(rawp2[S], f2);                                                                       \
-    cd_ld8(Pp + v * 8, cA); cd_ld8(Pp + Kp + v * 8, cB); cd_ld8(Pp + 2 * Kp + v * 8, cC);                           \
+    co_cvt(rawp[S], f); co_cvt(rawp2[S], f2);                                                                       \
+    co_ld8(Pp + v * 8, cA); co_ld8(Pp + Kp + v * 8, cB); co_ld8(Pp + 2 * Kp + v * 8, cC);                           \
     const uint32_t keep = rowg0_ + row < M32 ? 0xffffffffu : 0u;                                                    \
     _Pragma("unroll") for (int e = 0; e < 8; ++e)                                                                   \
       f[e] = __uint_as_float(__float_as_uint(fmaf(cA[e], f[e], fmaf(cC[e], f2[e], cB[e]))) & keep);                 \
     Vec8<bf16_t>::store(dst, f);                                                                                    \
-    rawp[S] = cd_load(rX, p_go + bpn_);                                                                             \
-    rawp2[S] = cd_load(rX2, p_go + bpn_);                                                                           \
+    rawp[S] = co_load(rX, p_go + bpn_);                                                                             \
+    rawp2[S] = co_load(rX2, p_go + bpn_);                                                                           \
   }
 #define CC_MULT(CA)                                                                                                 \
   {                                                                                                                 \
@@ -658,13 +650,13 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
       const bf16_t* pb_ = (CA) + k2 * 32 * KL + pl;                                                                 \
       const bf16_t* qb_ = (CQ) + k2 * 32 * QL + ql;                                                                 \
       _Pragma("unroll") for (int i = 0; i < NPW; ++i) {                                                             \
-        const cd_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_lds_s16x4_ptr_t)(pb_ + i * 16));        \
-        const cd_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_lds_s16x4_ptr_t)(pb_ + 16 * KL + i * 16)); \
+        const co_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(pb_ + i * 16));        \
+        const co_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(pb_ + 16 * KL + i * 16)); \
         pa[i] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7));               \
       }                                                                                                             \
       _Pragma("unroll") for (int j = 0; j < NQW; ++j) {                                                             \
-        const cd_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_lds_s16x4_ptr_t)(qb_ + j * 16));        \
-        const cd_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((cd_lds_s16x4_ptr_t)(qb_ + 16 * QL + j * 16)); \
+        const co_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(qb_ + j * 16));        \
+        const co_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(qb_ + 16 * QL + j * 16)); \
         qb[j] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7));               \
       }                                                                                                             \
       _Pragma("unroll") for (int i = 0; i < NPW; ++i)                                                               \
@@ -685,7 +677,7 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
       const uint32_t keep = ok ? 0xffffffffu : 0u;                                                                  \
       const uint4 rawo = *reinterpret_cast<const uint4*>(Os + row * NLW + v_o * 8);                                 \
       float f[8], bv[8], qs[8];                                                                                     \
-      cd_cvt(rawo, f); cd_cvt(e1r[S][p], bv);                                                                       \
+      co_cvt(rawo, f); co_cvt(e1r[S][p], bv);                                                                       \
       /* four channels at a time, the halves and the passes in program order (sched_barrier): the 7 x 8 temporaries of a whole   \
          vector beside the weight-gradient accumulators spilled 77 registers at 96 -> 216 */                       \
       _Pragma("unroll") for (int h = 0; h < 8; h += 4) {                                                            \
@@ -711,10 +703,10 @@ __global__ __launch_bounds__(CD_THREADS) void pw_cdg_c_kernel(const c3d_pw_args 
         __builtin_amdgcn_sched_barrier(0);                                                                          \
       }                                                                                                             \
       const uint4 pk = make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])); \
-      __builtin_amdgcn_raw_buffer_store_b128(cd_u32x4_t{pk.x, pk.y, pk.z, pk.w}, rY,                                \
-                                             ok ? ((uint32_t)m * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CD_OOB, 0, 0); \
+      __builtin_amdgcn_raw_buffer_store_b128(co_u32x4_t{pk.x, pk.y, pk.z, pk.w}, rY,                                \
+                                             ok ? ((uint32_t)m * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CO_OOB, 0, 0); \
       Vec8<bf16_t>::store((CQ) + (wr * 16 + row) * QL + cvec * 8, qs);                                              \
-      e1r[S][p] = cd_load(rE1, CC_EOFF((TILE) + 2, p));                                                             \
+      e1r[S][p] = co_load(rE1, CC_EOFF((TILE) + 2, p));                                                             \
     }                                                                                                               \
   }
 
@@ -807,119 +799,91 @@ int cc_variant(int Kp, int Np) {
   return 0;
 }
 
-int cc_plan(const c3d_pw_args& a, CcPlan& L, int64_t& blocks, size_t& lds) {
-  const int var = cc_variant(a.Kp, a.Np);
-  if (!var) return 0;
-  const int Kpad = (a.Kp + 31) / 32 * 32, KS = Kpad / 32, ntn = (a.Np + 15) >> 4;
-  L.img_rows = (ntn <= 2 ? 2 : ntn <= 4 ? 4 : ntn <= 7 ? 7 : 14) * 16;
+// Shape layer of the conv_c kernel (a tile lies inside one sample: rows_per_sample belongs to the shape)
+CdgLaunch<CcPlan> cc_plan(int Kp, int Np, int64_t M, int64_t rows_per_sample) {
+  CdgLaunch<CcPlan> R;
+  CcPlan& L = R.L;
+  if (Kp <= 0 || Np <= 0 || (Kp & 7) || (Np & 7) || M < 1024 || !pw_fits_u32(M + 512, Kp, Np, 2)) return R;
+  const int var = cc_variant(Kp, Np);
+  if (!var) return R;
+  const int Kpad = (Kp + 31) / 32 * 32, KS = Kpad / 32;
+  L.img_rows = pw_nt_bucket(Np) * 16;
   if (var == 1) { L.WR = 2; L.WC = 4; L.QG = 4; }
   else if (var == 2) { L.WR = 4; L.WC = 2; L.QG = 8; }
   else { L.WR = 8; L.WC = 1; L.QG = 4; }
   L.MT = 16 * L.WR;
-  if ((L.MT * (a.Kp >> 3)) > CD_THREADS) return 0;
-  if (a.rows_per_sample <= 0 || a.rows_per_sample % L.MT) return 0;   // a tile inside one sample
+  if ((L.MT * (Kp >> 3)) > CD_THREADS) return R;
+  if (rows_per_sample <= 0 || rows_per_sample % L.MT) return R;   // a tile inside one sample
   L.KL = Kpad + 8;
   L.QL = L.WC * 4 * 16 + 8;
-  const int64_t tiles = (a.M + L.MT - 1) / L.MT;
-  blocks = device_cus();
-  if (blocks > (tiles + 1) / 2) blocks = (tiles + 1) / 2;
-  if (blocks > CD_MAX_PARTS) blocks = CD_MAX_PARTS;
-  if (blocks < 1) blocks = 1;
-  const int tpw = (int)((tiles + blocks - 1) / blocks);
-  blocks = (tiles + tpw - 1) / tpw;
-  L.tiles_per_wg = tpw;
+  const PwWalk walk = pw_walk((M + L.MT - 1) / L.MT, device_cus() < CD_MAX_PARTS ? device_cus() : CD_MAX_PARTS, 2);
+  R.blocks = walk.blocks;
+  L.tiles_per_wg = walk.tiles_per_wg;
   auto al = [](size_t v) { return (v + 1023) / 1024 * 1024; };
   size_t off = 0;
   L.w_off = 0; off += al((size_t)KS * 4 * L.img_rows * 16);
   L.a_off = (int)off; L.a_bytes = (int)al((size_t)L.MT * L.KL * 2); off += 3 * (size_t)L.a_bytes;
   L.q_off = (int)off; L.q_bytes = (int)al((size_t)L.MT * L.QL * 2); off += 2 * (size_t)L.q_bytes;
   L.os_wave = 16 * (4 * 16 + 8) * 2; L.os_off = (int)off; off += al((size_t)8 * L.os_wave);
-  L.par_off = (int)off; off += al(((size_t)3 * a.Kp + 5 * a.Np) * 4);
+  L.par_off = (int)off; off += al(((size_t)3 * Kp + 5 * Np) * 4);
   L.red_off = (int)off; off += al((size_t)8 * 24 * 8 * 4);
   L.dump_off = (int)off; off += (size_t)CD_THREADS * 16;
-  if (off > 160 * 1024) return 0;
-  lds = off;
-  return var;
+  if (off > 160 * 1024) return R;
+  R.lds = off;
+  R.var = var;
+  return R;
+}
+
+CdgLaunch<CcPlan> cc_accept(const c3d_pw_args& a) {
+  if (!cdg_common_args(a) || a.epi_mode != C3D_EPI_SWISH_SE_BWD || a.wg_mode != C3D_WG_SWISH) return {};
+  if (!a.epi_p || !a.epi_q || !a.stats || a.add_sums) return {};
+  return cc_plan(a.Kp, a.Np, a.M, a.rows_per_sample);
+}
+
+// The weight-gradient partials of a launch on `blocks` workgroups: left for the caller (parts_out) or reduced here, in fixed
+// order, by the reducer of the first kernel's fused variant
+int cdg_finish(const c3d_pw_args& a, int64_t blocks, int* parts_out, hipStream_t s) {
+  if (parts_out) { *parts_out = (int)blocks; return 0; }
+  return c3d_detail_pw_wgrad_reduce(a.wg_ws, a.wg_dw, a.K, a.N, (int)blocks, a.w_sk, a.w_sn, s);
 }
 
 }  // namespace
 
-// Host-side check for the stage driver: would c3d_detail_pw_cdg_a take this layer (bf16, dense rows, res_mode 0)?
-__attribute__((visibility("hidden"))) bool c3d_detail_pw_cdg_a_supported(int Kp, int Np, int64_t M) {
-  if (Kp <= 0 || Np <= 0 || (Kp & 7) || (Np & 7)) return false;
-  if (M < 1024 || (M + 512) * (int64_t)(Kp > Np ? Kp : Np) * 2 >= ((int64_t)1 << 31)) return false;
-  c3d_pw_args a;
-  std::memset(&a, 0, sizeof(a));
-  a.M = M; a.K = a.Kp = Kp; a.N = a.Np = Np;
-  CdPlan L;
-  int64_t blocks = 0;
-  size_t lds = 0;
-  return cd_plan(a, L, blocks, lds) != 0;
-}
+__attribute__((visibility("hidden"))) bool c3d_detail_pw_cdg_a_shape(int Kp, int Np, int64_t M) { return cd_plan(Kp, Np, M).var != 0; }
+__attribute__((visibility("hidden"))) bool c3d_detail_pw_cdg_a_accepts(const c3d_pw_args* args) { return cd_accept(*args).var != 0; }
 
 // Returns C3D_E_UNSUPPORTED for what it does not take (c3d_pw_gemm then runs the first kernel's fused variant).
-__attribute__((visibility("hidden"))) int c3d_detail_pw_cdg_a(const c3d_pw_args* args, void* stream) {
+__attribute__((visibility("hidden"))) int c3d_detail_pw_cdg_a(const c3d_pw_args* args, int* parts_out, void* stream) {
   const c3d_pw_args& a = *args;
-  if (a.dtype != C3D_DT_BF16 || a.row_mode != C3D_ROWS_DENSE || a.pro_mode != C3D_PRO_AFFINE2 || a.epi_mode != C3D_EPI_ADD ||
-      a.wg_mode != C3D_WG_ROWS || a.res_mode != 0)
-    return C3D_E_UNSUPPORTED;
-  if (!a.w_img || !a.x2 || !a.e1 || !a.wg_x3 || !a.wg_dw || !a.wg_ws || a.pro_out || a.bias || a.fin.ticket) return C3D_E_UNSUPPORTED;
-  if (a.fin.sums ? (a.fin.training != 0 || !a.fin.mr || !a.fin.gamma) : !a.pro_p) return C3D_E_UNSUPPORTED;
-  if (a.add_sums && (!a.add_c || !a.add_mr || !a.wg_mask_out)) return C3D_E_UNSUPPORTED;
-  if (a.M < 1024 || (a.M + 512) * (int64_t)(a.Kp > a.Np ? a.Kp : a.Np) * 2 >= ((int64_t)1 << 31)) return C3D_E_UNSUPPORTED;
-  CdPlan L;
-  int64_t blocks = 0;
-  size_t lds = 0;
-  const int var = cd_plan(a, L, blocks, lds);
-  if (!var) return C3D_E_UNSUPPORTED;
+  const CdgLaunch<CdPlan> R = cd_accept(a);
+  if (!R.var) return C3D_E_UNSUPPORTED;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)blocks);
+  const dim3 grid((unsigned)R.blocks);
   int rc = C3D_E_UNSUPPORTED;
-  if (var == 1) rc = cd_launch<7, 2, 4, 3, 2, 1, 1>(a, L, grid, lds, s);        // 216 -> 96: 14 x 6 weight-gradient tiles, 4 x 3 per wave
-  else if (var == 2) rc = cd_launch<4, 3, 1, 3, 4, 2, 4>(a, L, grid, lds, s);   // 108 -> 48: 7 x 3, 1 x 3 per wave
-  else if (var == 3) rc = cd_launch<2, 2, 1, 1, 2, 1, 4>(a, L, grid, lds, s);   // 54 -> 24: 4 x 2, 1 x 1 per wave
+  if (R.var == 1) rc = cd_launch<7, 2, 4, 3, 2, 1, 1>(a, R.L, grid, R.lds, s);        // 216 -> 96: 14 x 6 weight-gradient tiles, 4 x 3 per wave
+  else if (R.var == 2) rc = cd_launch<4, 3, 1, 3, 4, 2, 4>(a, R.L, grid, R.lds, s);   // 108 -> 48: 7 x 3, 1 x 3 per wave
+  else if (R.var == 3) rc = cd_launch<2, 2, 1, 1, 2, 1, 4>(a, R.L, grid, R.lds, s);   // 54 -> 24: 4 x 2, 1 x 1 per wave
   if (rc != 0) return rc;
   C3D_CHECK_LAUNCH();
-  if (c3d_cdg_defer_reduce) { c3d_cdg_parts = (int)blocks; return 0; }   // (the stage driver reduces on its side stream)
-  return c3d_detail_pw_wgrad_reduce(a.wg_ws, a.wg_dw, a.K, a.N, (int)blocks, a.w_sk, a.w_sn, s);
+  return cdg_finish(a, R.blocks, parts_out, s);
 }
 
-// conv_c: host-side check for the stage driver, and the launch
-__attribute__((visibility("hidden"))) bool c3d_detail_pw_cdg_c_supported(int Kp, int Np, int64_t M, int64_t rows_per_sample) {
-  if (Kp <= 0 || Np <= 0 || (Kp & 7) || (Np & 7)) return false;
-  if (M < 1024 || (M + 512) * (int64_t)(Kp > Np ? Kp : Np) * 2 >= ((int64_t)1 << 31)) return false;
-  c3d_pw_args a;
-  std::memset(&a, 0, sizeof(a));
-  a.M = M; a.K = a.Kp = Kp; a.N = a.Np = Np; a.rows_per_sample = rows_per_sample;
-  CcPlan L;
-  int64_t blocks = 0;
-  size_t lds = 0;
-  return cc_plan(a, L, blocks, lds) != 0;
+__attribute__((visibility("hidden"))) bool c3d_detail_pw_cdg_c_shape(int Kp, int Np, int64_t M, int64_t rows_per_sample) {
+  return cc_plan(Kp, Np, M, rows_per_sample).var != 0;
 }
+__attribute__((visibility("hidden"))) bool c3d_detail_pw_cdg_c_accepts(const c3d_pw_args* args) { return cc_accept(*args).var != 0; }
 
-__attribute__((visibility("hidden"))) int c3d_detail_pw_cdg_c(const c3d_pw_args* args, void* stream) {
+__attribute__((visibility("hidden"))) int c3d_detail_pw_cdg_c(const c3d_pw_args* args, int* parts_out, void* stream) {
   const c3d_pw_args& a = *args;
-  if (a.dtype != C3D_DT_BF16 || a.row_mode != C3D_ROWS_DENSE || a.pro_mode != C3D_PRO_AFFINE2 || a.epi_mode != C3D_EPI_SWISH_SE_BWD ||
-      a.wg_mode != C3D_WG_SWISH)
-    return C3D_E_UNSUPPORTED;
-  if (!a.w_img || !a.x2 || !a.e1 || !a.epi_p || !a.epi_q || !a.stats || !a.wg_dw || !a.wg_ws || a.pro_out || a.bias || a.fin.ticket ||
-      a.add_sums)
-    return C3D_E_UNSUPPORTED;
-  if (a.fin.sums ? (a.fin.training != 0 || !a.fin.mr || !a.fin.gamma) : !a.pro_p) return C3D_E_UNSUPPORTED;
-  if (a.M < 1024 || (a.M + 512) * (int64_t)(a.Kp > a.Np ? a.Kp : a.Np) * 2 >= ((int64_t)1 << 31)) return C3D_E_UNSUPPORTED;
-  CcPlan L;
-  int64_t blocks = 0;
-  size_t lds = 0;
-  const int var = cc_plan(a, L, blocks, lds);
-  if (!var) return C3D_E_UNSUPPORTED;
+  const CdgLaunch<CcPlan> R = cc_accept(a);
+  if (!R.var) return C3D_E_UNSUPPORTED;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)blocks);
+  const dim3 grid((unsigned)R.blocks);
   int rc = C3D_E_UNSUPPORTED;
-  if (var == 1) rc = cc_launch<3, 3, 4, 1>(a, L, grid, lds, s);        // 96 -> 216: 6 x 14 weight-gradient tiles, 3 x 4 per wave
-  else if (var == 2) rc = cc_launch<2, 3, 1, 2>(a, L, grid, lds, s);   // 48 -> 108: 3 x 7, 3 x 1 per wave
-  else if (var == 3) rc = cc_launch<1, 1, 1, 4>(a, L, grid, lds, s);   // 24 -> 54: 2 x 4, 1 x 1 per wave
+  if (R.var == 1) rc = cc_launch<3, 3, 4, 1>(a, R.L, grid, R.lds, s);        // 96 -> 216: 6 x 14 weight-gradient tiles, 3 x 4 per wave
+  else if (R.var == 2) rc = cc_launch<2, 3, 1, 2>(a, R.L, grid, R.lds, s);   // 48 -> 108: 3 x 7, 3 x 1 per wave
+  else if (R.var == 3) rc = cc_launch<1, 1, 1, 4>(a, R.L, grid, R.lds, s);   // 24 -> 54: 2 x 4, 1 x 1 per wave
   if (rc != 0) return rc;
   C3D_CHECK_LAUNCH();
-  if (c3d_cdg_defer_reduce) { c3d_cdg_parts = (int)blocks; return 0; }
-  return c3d_detail_pw_wgrad_reduce(a.wg_ws, a.wg_dw, a.K, a.N, (int)blocks, a.w_sk, a.w_sn, s);
+  return cdg_finish(a, R.blocks, parts_out, s);
 }

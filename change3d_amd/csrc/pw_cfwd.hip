@@ -25,6 +25,7 @@
 #include "common.h"
 #include "../../include/change3d_hip.h"
 #include "pw_common.h"
+#include "pw_coop.h"
 #include "launch_hints.h"
 #include "bn_fin.h"
 #include <cstdlib>
@@ -47,7 +48,6 @@ namespace {
 constexpr int CF_THREADS = 512;
 constexpr int CF_SE_NS = 4;          // samples a workgroup's rows may span with the in-kernel SE gate (= PW_SE_NS)
 constexpr int CF_SE_CR = 32;         // hidden units at most (= PW_SE_CR)
-constexpr uint32_t CF_OOB = 0x80000000u;
 
 struct CfPlan {
   int MT, WR, WC;            // rows per tile = 16 WR; wave grid WR x WC = 8
@@ -61,28 +61,6 @@ struct CfPlan {
   int ns;
 };
 
-typedef uint32_t cf_u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* cf_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* cf_glb_ptr_t;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t cf_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, p ? (int)bytes : 0, 0x00020000);
-}
-__device__ __forceinline__ uint4 cf_load(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  const cf_u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ void cf_cvt(const uint4& v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ void cf_ld8(const float* p, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
 
 // PRO: C3D_PRO_BN_SE_SWISH (conv_c) or C3D_PRO_AFFINE2 with the fused residual output (conv_a: the operand is
 // y = relu(bn_c(c) + shortcut) of the previous block, written out once -- c3d_pw_args.pro_out); NTW: output tiles (16 channels)
@@ -111,10 +89,10 @@ __global__ __launch_bounds__(CF_THREADS) void pw_cfwd_kernel(const c3d_pw_args a
   int t1 = t0 + L.tiles_per_wg;
   if (t1 > tiles) t1 = tiles;
   const uint32_t row_hi = (uint32_t)(t1 * MT < M32 ? t1 * MT : M32);
-  const __amdgpu_buffer_rsrc_t rX = cf_rsrc(a.x, row_hi * (uint32_t)Kp * 2u);
-  [[maybe_unused]] const __amdgpu_buffer_rsrc_t rX2 = cf_rsrc(AFF ? a.x2 : nullptr, row_hi * (uint32_t)Kp * 2u);
-  [[maybe_unused]] const __amdgpu_buffer_rsrc_t rPO = cf_rsrc(AFF ? a.pro_out : nullptr, row_hi * (uint32_t)Kp * 2u);
-  const __amdgpu_buffer_rsrc_t rY = cf_rsrc(a.y, (uint32_t)M32 * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rX = co_rsrc(a.x, row_hi * (uint32_t)Kp * 2u);
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t rX2 = co_rsrc(AFF ? a.x2 : nullptr, row_hi * (uint32_t)Kp * 2u);
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t rPO = co_rsrc(AFF ? a.pro_out : nullptr, row_hi * (uint32_t)Kp * 2u);
+  const __amdgpu_buffer_rsrc_t rY = co_rsrc(a.y, (uint32_t)M32 * (uint32_t)Np * 2u);
 
   // ---- item map: item i = tid + 512 r of a tile <-> (row = i / Gq, vector = i % Gq); its bytes sit at tile base + 16 i
   int q_desc[CF_R];
@@ -127,7 +105,7 @@ __global__ __launch_bounds__(CF_THREADS) void pw_cfwd_kernel(const c3d_pw_args a
       const int row = __float2int_rz(((float)i + 0.5f) * invG);
       const bool ok = i < MT * Gq;
       q_desc[r] = ok ? (row << 5) | (i - row * Gq) : 0;
-      q_go[r] = ok ? (uint32_t)i * 16u : CF_OOB;
+      q_go[r] = ok ? (uint32_t)i * 16u : CO_OOB;
     }
   }
   const bool q_last = (wave * 64 + CF_THREADS * (CF_R - 1)) < MT * Gq;   // (wave-uniform: the last round has an item for this wave)
@@ -138,8 +116,8 @@ __global__ __launch_bounds__(CF_THREADS) void pw_cfwd_kernel(const c3d_pw_args a
     const uint32_t b0 = (uint32_t)t0 * tbq;
 #pragma unroll
     for (int r = 0; r < CF_R; ++r) {
-      raw[r] = cf_load(rX, q_go[r] + b0);
-      if (AFF) raw2[AFF ? r : 0] = cf_load(rX2, q_go[r] + b0);
+      raw[r] = co_load(rX, q_go[r] + b0);
+      if (AFF) raw2[AFF ? r : 0] = co_load(rX2, q_go[r] + b0);
     }
   }
 
@@ -155,7 +133,7 @@ __global__ __launch_bounds__(CF_THREADS) void pw_cfwd_kernel(const c3d_pw_args a
       if (r >= nchunk) r -= nchunk;
       const int off = r * 1024 + lane * 16;
       if (off < wbytes)
-        __builtin_amdgcn_global_load_lds((cf_glb_ptr_t)(src + off), (cf_lds_ptr_t)(smem + L.w_off + r * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((co_glb_ptr_t)(src + off), (co_lds_ptr_t)(smem + L.w_off + r * 1024), 16, 0, 0);
     }
   }
   const uint32_t rps = a.rows_per_sample > 0 ? (uint32_t)a.rows_per_sample : 1u;
@@ -217,33 +195,33 @@ __global__ __launch_bounds__(CF_THREADS) void pw_cfwd_kernel(const c3d_pw_args a
     _Pragma("unroll") for (int r = 0; r < CF_R; ++r) {                                                              \
       if (r == CF_R - 1 && !q_last) continue;                                                                       \
       const int row = q_desc[r] >> 5, v = q_desc[r] & 31;                                                           \
-      bf16_t* dst = q_go[r] != CF_OOB ? (CQ) + row * KL + v * 8 : dump;                                             \
+      bf16_t* dst = q_go[r] != CO_OOB ? (CQ) + row * KL + v * 8 : dump;                                             \
       float f[8], sc[8], sh[8];                                                                                     \
-      cf_cvt(raw[r], f);                                                                                            \
-      cf_ld8(Pp + v * 8, sc); cf_ld8(Pp + Kp + v * 8, sh);                                                          \
+      co_cvt(raw[r], f);                                                                                            \
+      co_ld8(Pp + v * 8, sc); co_ld8(Pp + Kp + v * 8, sh);                                                          \
       if constexpr (AFF) {                                                                                          \
         /* y = relu(bn_c(c) + shortcut) in the association of c3d_block_out_fwd (fmaf(f2, 1, 0) is f2), zero past the  \
            tensor's end; the bf16 rounding of y that is stored is the operand the GEMM reads */                     \
         float f2[8];                                                                                                \
-        cf_cvt(raw2[AFF ? r : 0], f2);                                                                              \
+        co_cvt(raw2[AFF ? r : 0], f2);                                                                              \
         const uint32_t keep = rowg0_ + row < M32 ? 0xffffffffu : 0u;                                                \
         _Pragma("unroll") for (int e = 0; e < 8; ++e)                                                               \
           f[e] = __uint_as_float(__float_as_uint(fmaxf(fmaf(f[e], sc[e], sh[e]) + fmaf(f2[e], 1.f, 0.f), 0.f)) & keep); \
         const uint4 pk = make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])); \
         *reinterpret_cast<uint4*>(dst) = pk;                                                                        \
-        __builtin_amdgcn_raw_buffer_store_b128(cf_u32x4_t{pk.x, pk.y, pk.z, pk.w}, rPO,                             \
-                                               (q_go[r] != CF_OOB && keep) ? q_go[r] + bq_ : CF_OOB, 0, 0);         \
-        raw2[AFF ? r : 0] = cf_load(rX2, q_go[r] + bqn_);                                                           \
+        __builtin_amdgcn_raw_buffer_store_b128(co_u32x4_t{pk.x, pk.y, pk.z, pk.w}, rPO,                             \
+                                               (q_go[r] != CO_OOB && keep) ? q_go[r] + bq_ : CO_OOB, 0, 0);         \
+        raw2[AFF ? r : 0] = co_load(rX2, q_go[r] + bqn_);                                                           \
       } else {                                                                                                      \
         float g[8];                                                                                                 \
-        cf_ld8(GsC_ + ((gate_on && rowg0_ + row >= bound_) ? Kp : 0) + v * 8, g);                                   \
+        co_ld8(GsC_ + ((gate_on && rowg0_ + row >= bound_) ? Kp : 0) + v * 8, g);                                   \
         _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                             \
           const float q = g[e] * fmaf(f[e], sc[e], sh[e]);                                                          \
           f[e] = q * sigmoid_t<bf16_t>(q);                                                                          \
         }                                                                                                           \
         Vec8<bf16_t>::store(dst, f);                                                                                \
       }                                                                                                             \
-      raw[r] = cf_load(rX, q_go[r] + bqn_);   /* (past this workgroup's last row: zeros, no memory access) */        \
+      raw[r] = co_load(rX, q_go[r] + bqn_);   /* (past this workgroup's last row: zeros, no memory access) */        \
     }                                                                                                               \
   }
 #define CF_MULT(CA)                                                                                                 \
@@ -270,15 +248,15 @@ __global__ __launch_bounds__(CF_THREADS) void pw_cfwd_kernel(const c3d_pw_args a
       const uint4 rawo = *reinterpret_cast<const uint4*>(Os + (row < 16 ? row : 0) * NLW + v_o * 8);                \
       if constexpr (STATS) {                                                                                        \
         float fo[8];                                                                                                \
-        cf_cvt(rawo, fo);                                                                                           \
+        co_cvt(rawo, fo);                                                                                           \
         const uint32_t keep = ok ? 0xffffffffu : 0u;                                                                \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                             \
           const float fv = __uint_as_float(__float_as_uint(fo[j]) & keep);                                          \
           s0[j] += fv; s1[j] += fv * fv;                                                                            \
         }                                                                                                           \
       }                                                                                                             \
-      __builtin_amdgcn_raw_buffer_store_b128(cf_u32x4_t{rawo.x, rawo.y, rawo.z, rawo.w}, rY,                        \
-                                             ok ? ((uint32_t)m * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CF_OOB, 0, 0); \
+      __builtin_amdgcn_raw_buffer_store_b128(co_u32x4_t{rawo.x, rawo.y, rawo.z, rawo.w}, rY,                        \
+                                             ok ? ((uint32_t)m * (uint32_t)Np + (uint32_t)cvec * 8u) * 2u : CO_OOB, 0, 0); \
     }                                                                                                               \
   }
 
@@ -346,6 +324,52 @@ int cf_launch(const c3d_pw_args& a, const CfPlan& L, dim3 grid, size_t lds, hipS
   return c3d_launch_lds<pw_cfwd_kernel<PRO, NTW, KS, true>>(grid, dim3(CF_THREADS), lds, s, a, L);
 }
 
+// Shape layer: conv_a (aff) or conv_c form, (Kp, Np, M, rows per sample, in-kernel SE gate or not) -> output tiles per wave
+// (0: this kernel does not hold the shape), plan, grid, LDS bytes
+int cf_plan(bool aff, bool se_gate, int Kp, int Np, int64_t M, int64_t rows_per_sample, CfPlan& L, int64_t& blocks, size_t& lds) {
+  if (Kp > 224 || Np > 224 || M < 1024 || !pw_fits_u32(M + 512, Kp, Np, 2)) return 0;
+  const int Kpad = (Kp + 31) / 32 * 32, KS = Kpad / 32, Gq = Kp >> 3;
+  const int ntn = (Np + 15) >> 4;
+  L.img_rows = pw_nt_bucket(Np) * 16;
+  // wave grid: row slabs x output-tile groups.  conv_c: 4 x 2 (3 tiles each) for 5..6 output tiles, else 8 x 1; conv_a: 4 x 2
+  // (7 tiles each) for 8..14 tiles, else 8 x 1 with 7 / 4 tiles
+  int NTW;
+  if (aff) {
+    if (ntn > 7) { L.WR = 4; L.WC = 2; NTW = 7; }
+    else { L.WR = 8; L.WC = 1; NTW = ntn > 4 ? 7 : 4; }
+  } else {
+    if (ntn > 6) return 0;
+    if (ntn > 3) { L.WR = 4; L.WC = 2; NTW = 3; }
+    else { L.WR = 8; L.WC = 1; NTW = ntn < 2 ? 2 : ntn; }
+  }
+  L.MT = 16 * L.WR;
+  const int rounds = (aff || KS <= 2) ? 2 : 4;
+  if ((L.MT * Gq + CF_THREADS - 1) / CF_THREADS > rounds) return 0;
+  if (!aff && rows_per_sample < L.MT) return 0;   // a tile touches at most two samples
+  L.KL = Kpad + 8;
+  // the narrowest layers (K <= 64, N <= 64: under 128 registers and 80 KB of LDS) run TWO workgroups per CU, out of phase with
+  // each other: conv_c on the 128 x 128 maps 73.9 -> 59.7 us per launch (its byte floor: 50), conv_a there unchanged (at its floor)
+  const PwWalk walk = pw_walk((M + L.MT - 1) / L.MT, (int64_t)device_cus() * ((KS <= 2 && ntn <= 4) ? 2 : 1), 2);
+  blocks = walk.blocks;
+  L.tiles_per_wg = walk.tiles_per_wg;
+  const int64_t rows_wg = (int64_t)walk.tiles_per_wg * L.MT;
+  L.ns = se_gate ? (int)((rows_wg + rows_per_sample - 2) / rows_per_sample + 1) : 1;
+  if (L.ns > CF_SE_NS) return 0;
+  auto al = [](size_t v) { return (v + 1023) / 1024 * 1024; };
+  size_t off = 0;
+  L.w_off = 0; off += al((size_t)KS * 4 * L.img_rows * 16);
+  L.a_off = (int)off; L.a_bytes = (int)al((size_t)L.MT * L.KL * 2); off += 2 * (size_t)L.a_bytes;
+  L.os_wave = 16 * (NTW * 16 + 8) * 2; L.os_off = (int)off; off += al((size_t)8 * L.os_wave);
+  // (the statistics dump at the end -- 8 waves x [16][64] f32 -- reuses the converted tiles and the staging rows behind them)
+  if (off - L.a_off < (size_t)8 * 16 * 64 * 4) off = L.a_off + (size_t)8 * 16 * 64 * 4;
+  L.par_off = (int)off; off += al((size_t)2 * Kp * 4);
+  L.gate_off = (int)off; off += al((size_t)L.ns * (Kp + CF_SE_CR) * 4);
+  L.dump_off = (int)off; off += (size_t)CF_THREADS * 16;
+  if (off > 160 * 1024) return 0;
+  lds = off;
+  return NTW;
+}
+
 }  // namespace
 
 // Returns C3D_E_UNSUPPORTED for what it does not take (c3d_pw_gemm then runs the first kernel).
@@ -364,63 +388,23 @@ __attribute__((visibility("hidden"))) int c3d_detail_pw_cfwd(const c3d_pw_args* 
       return C3D_E_UNSUPPORTED;
     if (!a.se_w1 && a.pro_gate) return C3D_E_UNSUPPORTED;   // gates given in memory (a separate finalize launch made them): first kernel
   }
-  if (a.Kp > 224 || a.Np > 224 || a.M < 1024) return C3D_E_UNSUPPORTED;
-  if ((a.M + 512) * (int64_t)(a.Kp > a.Np ? a.Kp : a.Np) * 2 >= ((int64_t)1 << 31)) return C3D_E_UNSUPPORTED;
-  const int Kpad = (a.Kp + 31) / 32 * 32, KS = Kpad / 32, Gq = a.Kp >> 3;
-  const int ntn = (a.Np + 15) >> 4;
   CfPlan L;
-  L.img_rows = (ntn <= 2 ? 2 : ntn <= 4 ? 4 : ntn <= 7 ? 7 : 14) * 16;
-  // wave grid: row slabs x output-tile groups.  conv_c: 4 x 2 (3 tiles each) for 5..6 output tiles, else 8 x 1; conv_a: 4 x 2
-  // (7 tiles each) for 8..14 tiles, else 8 x 1 with 7 / 4 tiles
-  int NTW;
-  if (aff) {
-    if (ntn > 7) { L.WR = 4; L.WC = 2; NTW = 7; }
-    else { L.WR = 8; L.WC = 1; NTW = ntn > 4 ? 7 : 4; }
-  } else {
-    if (ntn > 6) return C3D_E_UNSUPPORTED;
-    if (ntn > 3) { L.WR = 4; L.WC = 2; NTW = 3; }
-    else { L.WR = 8; L.WC = 1; NTW = ntn < 2 ? 2 : ntn; }
-  }
-  L.MT = 16 * L.WR;
-  const int rounds = (aff || KS <= 2) ? 2 : 4;
-  if ((L.MT * Gq + CF_THREADS - 1) / CF_THREADS > rounds) return C3D_E_UNSUPPORTED;
-  if (!aff && a.rows_per_sample < L.MT) return C3D_E_UNSUPPORTED;   // a tile touches at most two samples
-  L.KL = Kpad + 8;
-  const int64_t tiles = (a.M + L.MT - 1) / L.MT;
-  int64_t blocks = device_cus();
-  // the narrowest layers (K <= 64, N <= 64: under 128 registers and 80 KB of LDS) run TWO workgroups per CU, out of phase with
-  // each other: conv_c on the 128 x 128 maps 73.9 -> 59.7 us per launch (its byte floor: 50), conv_a there unchanged (at its floor)
-  if (KS <= 2 && ntn <= 4) blocks *= 2;
-  if (blocks > (tiles + 1) / 2) blocks = (tiles + 1) / 2;
-  if (blocks < 1) blocks = 1;
-  const int tpw = (int)((tiles + blocks - 1) / blocks);
-  blocks = (tiles + tpw - 1) / tpw;
-  L.tiles_per_wg = tpw;
-  const int64_t rows_wg = (int64_t)tpw * L.MT;
-  L.ns = (!aff && a.se_w1) ? (int)((rows_wg + a.rows_per_sample - 2) / a.rows_per_sample + 1) : 1;
-  if (L.ns > CF_SE_NS) return C3D_E_UNSUPPORTED;
-  auto al = [](size_t v) { return (v + 1023) / 1024 * 1024; };
-  size_t off = 0;
-  L.w_off = 0; off += al((size_t)KS * 4 * L.img_rows * 16);
-  L.a_off = (int)off; L.a_bytes = (int)al((size_t)L.MT * L.KL * 2); off += 2 * (size_t)L.a_bytes;
-  L.os_wave = 16 * (NTW * 16 + 8) * 2; L.os_off = (int)off; off += al((size_t)8 * L.os_wave);
-  // (the statistics dump at the end -- 8 waves x [16][64] f32 -- reuses the converted tiles and the staging rows behind them)
-  if (off - L.a_off < (size_t)8 * 16 * 64 * 4) off = L.a_off + (size_t)8 * 16 * 64 * 4;
-  L.par_off = (int)off; off += al((size_t)2 * a.Kp * 4);
-  L.gate_off = (int)off; off += al((size_t)L.ns * (a.Kp + CF_SE_CR) * 4);
-  L.dump_off = (int)off; off += (size_t)CF_THREADS * 16;
-  if (off > 160 * 1024) return C3D_E_UNSUPPORTED;
+  int64_t blocks = 0;
+  size_t lds = 0;
+  const int NTW = cf_plan(aff, !aff && a.se_w1, a.Kp, a.Np, a.M, a.rows_per_sample, L, blocks, lds);
+  if (!NTW) return C3D_E_UNSUPPORTED;
+  const int KS = (a.Kp + 31) / 32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)blocks);
   int rc = C3D_E_UNSUPPORTED;
   if (!aff) {
-    if (NTW == 3 && KS == 7) rc = cf_launch<C3D_PRO_BN_SE_SWISH, 3, 7>(a, L, grid, off, s);
-    else if (NTW == 3 && KS == 4) rc = cf_launch<C3D_PRO_BN_SE_SWISH, 3, 4>(a, L, grid, off, s);
-    else if (NTW == 2 && KS == 2) rc = cf_launch<C3D_PRO_BN_SE_SWISH, 2, 2>(a, L, grid, off, s);
+    if (NTW == 3 && KS == 7) rc = cf_launch<C3D_PRO_BN_SE_SWISH, 3, 7>(a, L, grid, lds, s);
+    else if (NTW == 3 && KS == 4) rc = cf_launch<C3D_PRO_BN_SE_SWISH, 3, 4>(a, L, grid, lds, s);
+    else if (NTW == 2 && KS == 2) rc = cf_launch<C3D_PRO_BN_SE_SWISH, 2, 2>(a, L, grid, lds, s);
   } else {
-    if (NTW == 7 && KS == 3) rc = cf_launch<C3D_PRO_AFFINE2, 7, 3>(a, L, grid, off, s);        // res4: 96 -> 216
-    else if (NTW == 7 && KS == 2) rc = cf_launch<C3D_PRO_AFFINE2, 7, 2>(a, L, grid, off, s);   // res3: 48 -> 108
-    else if (NTW == 4 && KS == 1) rc = cf_launch<C3D_PRO_AFFINE2, 4, 1>(a, L, grid, off, s);   // res2: 24 -> 54
+    if (NTW == 7 && KS == 3) rc = cf_launch<C3D_PRO_AFFINE2, 7, 3>(a, L, grid, lds, s);        // res4: 96 -> 216
+    else if (NTW == 7 && KS == 2) rc = cf_launch<C3D_PRO_AFFINE2, 7, 2>(a, L, grid, lds, s);   // res3: 48 -> 108
+    else if (NTW == 4 && KS == 1) rc = cf_launch<C3D_PRO_AFFINE2, 4, 1>(a, L, grid, lds, s);   // res2: 24 -> 54
   }
   if (rc != 0) return rc;
   C3D_CHECK_LAUNCH();

@@ -29,11 +29,10 @@ __attribute__((visibility("hidden"))) int c3d_detail_pw_cfwd(const c3d_pw_args* 
 // ------------------------------------------------------------------------------------------ weight images
 namespace {
 
-// (NT, KL) of the narrow kernel for a padded shape: dispatch_nt's buckets and pw_gemm_kernel's KL
+// (NT, KL) of the narrow kernel for a padded shape: pw_nt_bucket and pw_gemm_kernel's KL
 bool pw_img_geom(int Np, int Kp, int dtype, int& NT, int& KL, int& esz) {
   if (Kp <= 0 || Np <= 0 || Kp > 224 || Np > 224 || (Kp & 7) || (Np & 7)) return false;
-  const int nt = (Np + 15) / 16;
-  NT = nt <= 2 ? 2 : nt <= 4 ? 4 : nt <= 7 ? 7 : 14;
+  NT = pw_nt_bucket(Np);
   if (dtype == C3D_DT_BF16) {
     KL = (Kp + Mma<bf16_t>::KSTEP - 1) / Mma<bf16_t>::KSTEP * Mma<bf16_t>::KSTEP + Mma<bf16_t>::KPAD; esz = 2;
   } else if (dtype == C3D_DT_F32) {
@@ -146,16 +145,14 @@ extern "C" int c3d_pw_gemm(const c3d_pw_args* args, void* stream) {
     if (wide) return C3D_E_UNSUPPORTED;
   }
   if (wide) return c3d_detail_pw_gemm_wide(args, stream);
-  // the wave-private-tile kernels address rows with 32-bit byte offsets into bounds-checked buffer resources (offset 2^31 =
-  // "nowhere"): every tensor of the call must stay under 2 GiB
-  if ((int64_t)a.M * (a.Kp > a.Np ? a.Kp : a.Np) * (a.dtype == C3D_DT_F32 ? 4 : 2) >= ((int64_t)1 << 31)) return C3D_E_UNSUPPORTED;
+  if (!pw_fits_u32(a.M, a.Kp, a.Np, a.dtype == C3D_DT_F32 ? 4 : 2)) return C3D_E_UNSUPPORTED;
   if (a.wg_mode == C3D_WG_ROWS && (c3d_option_pw_cdg & 1)) {
     // conv_a data gradient + weight gradient: the workgroup-cooperative kernel (csrc/pw_cdgrad.hip) where it applies
-    const int rcd = c3d_detail_pw_cdg_a(args, stream);
+    const int rcd = c3d_detail_pw_cdg_a(args, nullptr, stream);
     if (rcd != C3D_E_UNSUPPORTED) return rcd;
   }
   if (a.wg_mode == C3D_WG_SWISH && (c3d_option_pw_cdg & 2)) {
-    const int rcd = c3d_detail_pw_cdg_c(args, stream);   // conv_c data gradient + weight gradient, cooperative (csrc/pw_cdgrad.hip)
+    const int rcd = c3d_detail_pw_cdg_c(args, nullptr, stream);   // conv_c data gradient + weight gradient, cooperative (csrc/pw_cdgrad.hip)
     if (rcd != C3D_E_UNSUPPORTED) return rcd;
   }
   if (a.wg_mode != C3D_WG_NONE) return c3d_detail_pw_gemm_wg(args, stream);

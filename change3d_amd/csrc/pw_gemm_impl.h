@@ -1313,7 +1313,7 @@ int launch_pw(const c3d_pw_args& a, hipStream_t stream) {
 
 template <typename T, int PRO, int EPI>
 int dispatch_nt(const c3d_pw_args& a, hipStream_t stream) {
-  const int nt = (a.Np + 15) / 16;
+  const int nt = (a.Np + 15) / 16;   // (the ladder is pw_nt_bucket, pw_common.h, spelled as template arguments)
   if (nt <= 2) return launch_pw<T, 2, PRO, EPI>(a, stream);
   if (nt <= 4) return launch_pw<T, 4, PRO, EPI>(a, stream);
   if (nt <= 7) return launch_pw<T, 7, PRO, EPI>(a, stream);

@@ -424,13 +424,9 @@ int launch_wgrad_inst(const c3d_pw_wgrad_args& a, dim3 grid, size_t lds, int tpw
   return c3d_launch_lds<pw_wgrad_kernel<T, HASP2, QD, TN, TK>>(grid, dim3(WG_THREADS), lds, stream, a, tpw, WN, WK, MT);
 }
 
-// Instantiated per-wave tile grids (TN x TK): a launch takes the smallest that covers its ceil(NT / WN) x ceil(KT / WK).
-struct WgInst { int tn, tk; };
-constexpr WgInst WG_INSTS[] = {{1, 1}, {2, 2}, {3, 4}, {4, 3}, {4, 4}};
-
 template <typename T, bool HASP2, bool QD>
 int launch_wgrad_pick2(const c3d_pw_wgrad_args& a, int inst, dim3 grid, size_t lds, int tpw, int WN, int WK, int MT, hipStream_t s) {
-  switch (inst) {
+  switch (inst) {   // PW_WG_INSTS (pw_common.h)
     case 0: return launch_wgrad_inst<T, HASP2, QD, 1, 1>(a, grid, lds, tpw, WN, WK, MT, s);
     case 1: return launch_wgrad_inst<T, HASP2, QD, 2, 2>(a, grid, lds, tpw, WN, WK, MT, s);
     case 2: return launch_wgrad_inst<T, HASP2, QD, 3, 4>(a, grid, lds, tpw, WN, WK, MT, s);
@@ -448,28 +444,11 @@ int launch_wgrad_pick(const c3d_pw_wgrad_args& a, bool qd, int inst, dim3 grid, 
 template <typename T>
 int launch_wgrad(const c3d_pw_wgrad_args& a, hipStream_t stream) {
   typedef MmaT<T> MM;
-  const int NT = (a.Np + 15) >> 4, KT = (a.Kp + 15) >> 4;
   const int taps = a.taps > 1 ? a.taps : 1;
   const bool qd = a.row_mode == C3D_ROWS_DENSE && taps == 1;
-  // wave grid: WN*WK = 8 with ceil(NT/WN) <= 4 and ceil(KT/WK) <= 4
-  int WN = 0, WK = 0, tn_need = 0, tk_need = 0;
-  const int cand[4][2] = {{8, 1}, {4, 2}, {2, 4}, {1, 8}};
-  int best = 1 << 30;
-  for (int c = 0; c < 4; ++c) {
-    const int tn = (NT + cand[c][0] - 1) / cand[c][0], tk = (KT + cand[c][1] - 1) / cand[c][1];
-    if (tn > 4 || tk > 4) continue;
-    // the instantiated grid that will run (zero-padded) is what costs: MFMAs dominate, then fragment loads
-    int ti = 4, tj = 4;
-    for (int i = 0; i < 5; ++i)
-      if (WG_INSTS[i].tn >= tn && WG_INSTS[i].tk >= tk) { ti = WG_INSTS[i].tn; tj = WG_INSTS[i].tk; break; }
-    const int cost = ti * tj * 4 + ti + tj;
-    if (cost < best) { best = cost; WN = cand[c][0]; WK = cand[c][1]; tn_need = tn; tk_need = tk; }
-  }
-  if (WN == 0) return C3D_E_UNSUPPORTED;
-  int inst = 4;
-  for (int i = 0; i < 5; ++i)
-    if (WG_INSTS[i].tn >= tn_need && WG_INSTS[i].tk >= tk_need) { inst = i; break; }
-  const int TNi = WG_INSTS[inst].tn, TKi = WG_INSTS[inst].tk;
+  const PwWaveGrid wg = pw_wave_grid((a.Np + 15) >> 4, (a.Kp + 15) >> 4);
+  if (wg.WN == 0) return C3D_E_UNSUPPORTED;
+  const int WN = wg.WN, WK = wg.WK, inst = wg.inst, TNi = PW_WG_INSTS[inst].tn, TKi = PW_WG_INSTS[inst].tk;
   // rows per tile: as tall as 256 staging threads per operand allow (WG_RPT rows x 8 channels each)
   const int maxG = (a.Np > a.Kp ? a.Np : a.Kp) >> 3;
   int MT = (256 / maxG) * WG_RPT / 32 * 32;
@@ -483,29 +462,11 @@ int launch_wgrad(const c3d_pw_wgrad_args& a, hipStream_t stream) {
     if (lds <= 160 * 1024) break;
   }
   if (MT < 32) return C3D_E_UNSUPPORTED;
-  const int64_t tiles = (a.M + MT - 1) / MT;
-  int64_t blocks = (tiles + 3) / 4;  // >= 4 tiles per workgroup when there is enough work
-  static const int cap_env = c3d_env("C3D_WG_BLOCKS") ? atoi(c3d_env("C3D_WG_BLOCKS")) : 0;  // tuning knob
-  int64_t cap = device_cus() < WGRAD_MAX_PARTS ? device_cus() : WGRAD_MAX_PARTS;
-  if (cap_env > 0 && cap_env <= WGRAD_MAX_PARTS) cap = cap_env;
-  else if (c3d_side_launch) {
-    // beside the data-gradient chain (stage driver's side stream): a cap on the workgroups (history below; 7/8 of the CUs now).  This single-round
-    // kernel at full width holds every CU for its whole duration (launch_hints.h); measured on MI355X, B=32 bf16,
-    // 60-step runs: 256 / 208 / 192 / 176 / 160 / 128 workgroups -> 32.52 / 32.08 / 31.84 / 32.11 / 32.48 / 32.87 ms
-    static const int side_env = c3d_env("C3D_PWWG_SIDE_WGS") ? atoi(c3d_env("C3D_PWWG_SIDE_WGS")) : 0;
-    // round 5 (after the data-gradient kernels' waits became exact, same-call sweeps through the instrumented build): 128 / 144 /
-    // 160 / 176 / 192 / 256 workgroups -> 23.01 / 22.99 / 22.86 / 23.53 / 23.18 / 23.34 ms per step: 5/8 of the CUs.
-    // ...and once c3d_block_out_bwd was folded into the conv_a data gradient (the elementwise pass that used to fill the CUs a
-    // narrow weight gradient left): 96 / 128 / 160 / 192 / 208 / 224 / 240 / 256 -> 23.46 / 22.81 / 22.70 / 22.53 / 22.34 / 22.29 /
-    // 22.33 / 22.34 ms (SCD and CC: 224 best by 0.5 % too): 7/8 of the CUs
-    const int64_t side_cap = side_env > 0 ? side_env : (int64_t)device_cus() * 7 / 8;
-    if (side_cap < cap) cap = side_cap;
-  }
+  int64_t cap = pw_wgrad_cap(WGRAD_MAX_PARTS);
   if (taps > 1 && cap > WGRAD_MAX_PARTS / taps) cap = WGRAD_MAX_PARTS / taps;   // the workspace holds MAX_PARTS slabs
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  const int tpw = (int)((tiles + blocks - 1) / blocks);
-  blocks = (tiles + tpw - 1) / tpw;
+  const PwWalk walk = pw_walk((a.M + MT - 1) / MT, cap, 4);   // >= 4 tiles per workgroup when there is enough work
+  const int64_t blocks = walk.blocks;
+  const int tpw = walk.tiles_per_wg;
   const dim3 grid((unsigned)blocks, taps);
   const int rc = (a.p_coef || a.p_fin.sums) ? launch_wgrad_pick<T, true>(a, qd, inst, grid, lds, tpw, WN, WK, MT, stream)
                                             : launch_wgrad_pick<T, false>(a, qd, inst, grid, lds, tpw, WN, WK, MT, stream);
@@ -533,7 +494,9 @@ extern "C" int64_t c3d_pw_wgrad_ws_floats(int32_t N, int32_t K) { return (int64_
 
 int c3d_detail_pw_wgrad_wide(const c3d_pw_wgrad_args* args, void* stream);   // pw_wide.hip
 int c3d_detail_pw_wgrad_v2(const c3d_pw_wgrad_args* args, hipStream_t stream);   // pw_wgrad_v2.hip: bf16, dense rows
-int c3d_detail_pw_wgrad_v2_flush(hipStream_t stream);                             // pending partials of a chained launch
+int c3d_detail_pw_wgrad_v2_flush(const float* only_ws);                           // pending partials of a chained launch
+
+thread_local int c3d_side_launch = 0;   // launch_hints.h
 
 extern "C" int c3d_pw_wgrad(const c3d_pw_wgrad_args* args, void* stream) {
   if (!args || !args->p || !args->q || !args->dw || !args->ws) return C3D_E_BADARG;
@@ -550,21 +513,21 @@ extern "C" int c3d_pw_wgrad(const c3d_pw_wgrad_args* args, void* stream) {
   if (a.M >= ((int64_t)1 << 31)) return C3D_E_UNSUPPORTED;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int rc = C3D_E_BADARG;
-  if (a.dtype == C3D_DT_F32) rc = launch_wgrad<float>(a, s);
-  else if (a.dtype == C3D_DT_BF16) {
-    // flat-staged, transposing-read kernel for dense rows (C3D_OPT_PW_WGRAD_V2); what it does not take runs here
-    rc = c3d_option_pw_wgrad_v2 ? c3d_detail_pw_wgrad_v2(args, s) : C3D_E_UNSUPPORTED;
-    if (rc == C3D_E_UNSUPPORTED) {
-      // (a launch of this kernel may reuse the workspace pending partials sit in: they are reduced first)
-      if (a.chain) { const int rcf = c3d_detail_pw_wgrad_v2_flush(s); if (rcf != 0) return rcf; }
-      rc = launch_wgrad<bf16_t>(a, s);
-    }
+  // flat-staged, transposing-read kernel for bf16 dense rows (C3D_OPT_PW_WGRAD_V2); what it does not take runs on the first kernel
+  if (a.dtype == C3D_DT_BF16 && c3d_option_pw_wgrad_v2) rc = c3d_detail_pw_wgrad_v2(args, s);
+  if (a.dtype == C3D_DT_F32 || (a.dtype == C3D_DT_BF16 && (!c3d_option_pw_wgrad_v2 || rc == C3D_E_UNSUPPORTED))) {
+    // The first kernel writes a.ws at once: pending partials of a chained launch that sit there are reduced first, whoever
+    // launches.  (A chained launch reduces them wherever they sit: the partials of a chain are reduced in launch order.)
+    const int rcf = c3d_detail_pw_wgrad_v2_flush(a.chain ? nullptr : a.ws);
+    if (rcf != 0) return rcf;
+    rc = a.dtype == C3D_DT_F32 ? launch_wgrad<float>(a, s) : launch_wgrad<bf16_t>(a, s);
   }
   if (rc == C3D_E_UNSUPPORTED) rc = c3d_detail_pw_wgrad_wide(args, stream);   // shapes that do not fit its LDS plan
   return rc;
 }
 
-extern "C" int c3d_pw_wgrad_flush(void* stream) { return c3d_detail_pw_wgrad_v2_flush(reinterpret_cast<hipStream_t>(stream)); }
+// (the reducer runs on the stream of the launch that left the partials)
+extern "C" int c3d_pw_wgrad_flush(void* stream) { (void)stream; return c3d_detail_pw_wgrad_v2_flush(nullptr); }
 
 #ifdef C3D_PW_CLOCK
 extern "C" int c3d_debug_wgrad_clock(unsigned long long* out, int reset) {   // out[WCLK_WAVES][8]

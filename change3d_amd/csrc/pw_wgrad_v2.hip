@@ -23,12 +23,11 @@
 #include "common.h"
 #include "../../include/change3d_hip.h"
 #include "pw_common.h"
+#include "pw_coop.h"
 #include "launch_hints.h"
 #include "bn_fin.h"
-#include <cstdlib>
 
 int c3d_detail_pw_wgrad_reduce(const float* ws, float* dw, int N, int K, int parts, int sn, int sk, hipStream_t stream);   // pw_wgrad.hip
-int c3d_detail_pw_wgrad_v2_flush(hipStream_t stream);
 
 namespace {
 
@@ -37,7 +36,6 @@ constexpr int W2_THREADS = 512;
 // channels at 64 rows), 2 for the narrower side
 constexpr int w2_rounds(int t) { return t >= 4 ? 4 : 2; }
 constexpr int W2_MAX_PARTS = 512;  // = WGRAD_MAX_PARTS of pw_wgrad.hip (c3d_pw_wgrad_ws_floats)
-constexpr uint32_t W2_OOB = 0x80000000u;
 
 struct W2Plan {
   int MT, tiles_per_wg, WN, WK;
@@ -58,29 +56,6 @@ struct W2Red {
   int N, K, parts, sn, sk;
 };
 
-typedef short w2_s16x4_t __attribute__((ext_vector_type(4)));
-typedef short w2_s16x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) w2_s16x4_t* w2_lds_s16x4_ptr_t;
-typedef uint32_t w2_u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t w2_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, p ? (int)bytes : 0, 0x00020000);
-}
-__device__ __forceinline__ uint4 w2_load(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  const w2_u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ void w2_cvt(const uint4& v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ void w2_ld8(const float* p, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
 
 // q = g * (f * sc + sh);  f = q * sigmoid(q), eight channels.  The same IEEE operations as sigmoid_t<bf16_t> (common.h: v_exp_f32
 // of q x -log2(e), + 1, v_rcp_f32) -- bit-identical results -- with the five multiplies / adds issued as packed-f32 instructions
@@ -126,9 +101,9 @@ __global__ __launch_bounds__(W2_THREADS) void pw_wgrad_v2_kernel(const c3d_pw_wg
   if (t1 > tiles) t1 = tiles;
   // buffer resources bounded by THIS workgroup's last row: the ragged end of the last tile reads zeros
   const uint32_t row_hi = (uint32_t)(t1 * MT < M32 ? t1 * MT : M32);
-  const __amdgpu_buffer_rsrc_t rP = w2_rsrc(a.p, row_hi * (uint32_t)Np * 2u);
-  const __amdgpu_buffer_rsrc_t rP2 = w2_rsrc(HASP2 ? a.p2 : nullptr, row_hi * (uint32_t)Np * 2u);
-  const __amdgpu_buffer_rsrc_t rQ = w2_rsrc(a.q, row_hi * (uint32_t)Kp * 2u);
+  const __amdgpu_buffer_rsrc_t rP = co_rsrc(a.p, row_hi * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rP2 = co_rsrc(HASP2 ? a.p2 : nullptr, row_hi * (uint32_t)Np * 2u);
+  const __amdgpu_buffer_rsrc_t rQ = co_rsrc(a.q, row_hi * (uint32_t)Kp * 2u);
 
   // ---- item maps: item i = tid + 512 r of a tile <-> (row = i / G, vector = i % G); its bytes sit at tile base + 16 i
   constexpr int RP = w2_rounds(TN), RQ = w2_rounds(TK);
@@ -142,7 +117,7 @@ __global__ __launch_bounds__(W2_THREADS) void pw_wgrad_v2_kernel(const c3d_pw_wg
       const int rowp = __float2int_rz(((float)i + 0.5f) * invGp);
       const bool okp = i < MT * Gp;
       p_desc[r] = okp ? (rowp << 5) | (i - rowp * Gp) : 0;
-      p_go[r] = okp ? (uint32_t)i * 16u : W2_OOB;
+      p_go[r] = okp ? (uint32_t)i * 16u : CO_OOB;
     }
 #pragma unroll
     for (int r = 0; r < RQ; ++r) {
@@ -150,7 +125,7 @@ __global__ __launch_bounds__(W2_THREADS) void pw_wgrad_v2_kernel(const c3d_pw_wg
       const int rowq = __float2int_rz(((float)i + 0.5f) * invGq);
       const bool okq = i < MT * Gq;
       q_desc[r] = okq ? (rowq << 5) | (i - rowq * Gq) : 0;
-      q_go[r] = okq ? (uint32_t)i * 16u : W2_OOB;
+      q_go[r] = okq ? (uint32_t)i * 16u : CO_OOB;
     }
   }
   uint4 rawp[RP], rawq[RQ];
@@ -160,10 +135,10 @@ __global__ __launch_bounds__(W2_THREADS) void pw_wgrad_v2_kernel(const c3d_pw_wg
   {                                                                                      \
     const uint32_t bp_ = (uint32_t)(TILE) * tbp, bq_ = (uint32_t)(TILE) * tbq;           \
     _Pragma("unroll") for (int r = 0; r < RP; ++r) {                                     \
-      rawp[r] = w2_load(rP, p_go[r] + bp_);                                              \
-      if (HASP2) rawp2[HASP2 ? r : 0] = w2_load(rP2, p_go[r] + bp_);                     \
+      rawp[r] = co_load(rP, p_go[r] + bp_);                                              \
+      if (HASP2) rawp2[HASP2 ? r : 0] = co_load(rP2, p_go[r] + bp_);                     \
     }                                                                                    \
-    _Pragma("unroll") for (int r = 0; r < RQ; ++r) rawq[r] = w2_load(rQ, q_go[r] + bq_);   \
+    _Pragma("unroll") for (int r = 0; r < RQ; ++r) rawq[r] = co_load(rQ, q_go[r] + bq_);   \
   }
 
   // the first tile's rows are requested before anything else: the zero fill and the parameter round trips run under them
@@ -282,12 +257,12 @@ __global__ __launch_bounds__(W2_THREADS) void pw_wgrad_v2_kernel(const c3d_pw_wg
     _Pragma("unroll") for (int r = 0; r < RP; ++r) {                                                                \
       if (r == RP - 1 && !p_last) continue;   /* (wave-uniform: none of this wave's lanes has an item in the last round) */ \
       const int row = p_desc[r] >> 5, v = p_desc[r] & 31;                                                           \
-      bf16_t* dst = p_go[r] != W2_OOB ? (CP) + row * ldp + v * 8 : dump;                                            \
+      bf16_t* dst = p_go[r] != CO_OOB ? (CP) + row * ldp + v * 8 : dump;                                            \
       if constexpr (HASP2) {                                                                                        \
         float f[8], f2[8], cA[8], cB[8], cC[8];                                                                     \
-        w2_cvt(rawp[r], f);                                                                                         \
-        w2_cvt(rawp2[HASP2 ? r : 0], f2);                                                                           \
-        w2_ld8(Pp + v * 8, cA); w2_ld8(Pp + Np + v * 8, cB); w2_ld8(Pp + 2 * Np + v * 8, cC);                       \
+        co_cvt(rawp[r], f);                                                                                         \
+        co_cvt(rawp2[HASP2 ? r : 0], f2);                                                                           \
+        co_ld8(Pp + v * 8, cA); co_ld8(Pp + Np + v * 8, cB); co_ld8(Pp + 2 * Np + v * 8, cC);                       \
         /* a row past the tensor's end is zero x A + B: zeroed by a bit mask (as `real ? fma : 0` the compiler made it a branch) */ \
         const uint32_t keep = rowg0_ + row < M32 ? 0xffffffffu : 0u;                                                \
         _Pragma("unroll") for (int j = 0; j < 8; j += 2) {   /* (packed f32: the same two fused multiply-adds per channel) */ \
@@ -299,24 +274,24 @@ __global__ __launch_bounds__(W2_THREADS) void pw_wgrad_v2_kernel(const c3d_pw_wg
       } else {                                                                                                      \
         *reinterpret_cast<uint4*>(dst) = rawp[r];   /* no prologue: the raw bf16 vector IS the operand */            \
       }                                                                                                             \
-      rawp[r] = w2_load(rP, p_go[r] + bpn_);   /* (past this workgroup's last row: zeros, no memory access) */       \
-      if (HASP2) rawp2[HASP2 ? r : 0] = w2_load(rP2, p_go[r] + bpn_);                                               \
+      rawp[r] = co_load(rP, p_go[r] + bpn_);   /* (past this workgroup's last row: zeros, no memory access) */       \
+      if (HASP2) rawp2[HASP2 ? r : 0] = co_load(rP2, p_go[r] + bpn_);                                               \
     }                                                                                                               \
     _Pragma("unroll") for (int r = 0; r < RQ; ++r) {                                                                \
       if (r == RQ - 1 && !q_last) continue;                                                                         \
       const int row = q_desc[r] >> 5, v = q_desc[r] & 31;                                                           \
-      bf16_t* dst = q_go[r] != W2_OOB ? (CQ) + row * ldq + v * 8 : dump;                                            \
+      bf16_t* dst = q_go[r] != CO_OOB ? (CQ) + row * ldq + v * 8 : dump;                                            \
       if constexpr (QSW) {                                                                                          \
         float f[8], sc[8], sh[8], g[8];                                                                             \
-        w2_cvt(rawq[r], f);                                                                                         \
-        w2_ld8(Qs + v * 8, sc); w2_ld8(Qs + Kp + v * 8, sh);                                                        \
-        w2_ld8(GsC_ + ((gate_on && rowg0_ + row >= bound_) ? Kp : 0) + v * 8, g);   /* (no gate: a row of ones) */    \
+        co_cvt(rawq[r], f);                                                                                         \
+        co_ld8(Qs + v * 8, sc); co_ld8(Qs + Kp + v * 8, sh);                                                        \
+        co_ld8(GsC_ + ((gate_on && rowg0_ + row >= bound_) ? Kp : 0) + v * 8, g);   /* (no gate: a row of ones) */    \
         w2_swish8(f, sc, sh, g);                                                                                    \
         Vec8<bf16_t>::store(dst, f);                                                                                \
       } else {                                                                                                      \
         *reinterpret_cast<uint4*>(dst) = rawq[r];                                                                   \
       }                                                                                                             \
-      rawq[r] = w2_load(rQ, q_go[r] + bqn_);                                                                        \
+      rawq[r] = co_load(rQ, q_go[r] + bqn_);                                                                        \
     }                                                                                                               \
   }
   // ---- multiply one tile: rows are the contraction index
@@ -325,13 +300,13 @@ __global__ __launch_bounds__(W2_THREADS) void pw_wgrad_v2_kernel(const c3d_pw_wg
     const bf16_t* pb_ = (BP) + (KSI) * 32 * ldp + pl;                                                               \
     const bf16_t* qb_ = (BQ) + (KSI) * 32 * ldq + ql;                                                               \
     _Pragma("unroll") for (int i = 0; i < TN; ++i) {                                                                \
-      const w2_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w2_lds_s16x4_ptr_t)(pb_ + i * pstep));        \
-      const w2_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w2_lds_s16x4_ptr_t)(pb_ + 16 * ldp + i * pstep)); \
+      const co_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(pb_ + i * pstep));        \
+      const co_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(pb_ + 16 * ldp + i * pstep)); \
       pa[SLOT][i] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7));           \
     }                                                                                                               \
     _Pragma("unroll") for (int j = 0; j < TK; ++j) {                                                                \
-      const w2_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w2_lds_s16x4_ptr_t)(qb_ + j * qstep));        \
-      const w2_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w2_lds_s16x4_ptr_t)(qb_ + 16 * ldq + j * qstep)); \
+      const co_s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(qb_ + j * qstep));        \
+      const co_s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((co_lds_s16x4_ptr_t)(qb_ + 16 * ldq + j * qstep)); \
       qb[SLOT][j] = __builtin_bit_cast(uint4, __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7));           \
     }                                                                                                               \
   }
@@ -434,12 +409,9 @@ int w2_launch_inst(const c3d_pw_wgrad_args& a, const W2Plan& L, const W2Red& red
                     : w2_launch_il<HASP2, QSW, TN, TK, false>(a, L, red, grid, lds, stream);
 }
 
-struct W2Inst { int tn, tk; };
-constexpr W2Inst W2_INSTS[] = {{1, 1}, {2, 2}, {3, 4}, {4, 3}, {4, 4}};
-
 template <bool HASP2, bool QSW>
 int w2_launch_pick(const c3d_pw_wgrad_args& a, int inst, const W2Plan& L, const W2Red& red, dim3 grid, size_t lds, hipStream_t s) {
-  switch (inst) {
+  switch (inst) {   // PW_WG_INSTS (pw_common.h)
     case 0: return w2_launch_inst<HASP2, QSW, 1, 1>(a, L, red, grid, lds, s);
     case 1: return w2_launch_inst<HASP2, QSW, 2, 2>(a, L, red, grid, lds, s);
     case 2: return w2_launch_inst<HASP2, QSW, 3, 4>(a, L, red, grid, lds, s);
@@ -454,16 +426,20 @@ thread_local W2Pending w2_pending = {{nullptr, nullptr, 0, 0, 0, 0, 0}, nullptr}
 
 }  // namespace
 
-// Reducer launch for the pending partials (c3d_pw_wgrad_flush, and whenever the next launch cannot take them over).
-__attribute__((visibility("hidden"))) int c3d_detail_pw_wgrad_v2_flush(hipStream_t stream) {
-  if (!w2_pending.red.ws) return 0;
+// Reducer launch for the pending partials, on the stream of the launch that wrote them (c3d_pw_wgrad_flush, and whenever
+// the next launch cannot take them over).  only_ws != NULL: only if they sit in that workspace.
+__attribute__((visibility("hidden"))) int c3d_detail_pw_wgrad_v2_flush(const float* only_ws) {
+  if (!w2_pending.red.ws || (only_ws && w2_pending.red.ws != only_ws)) return 0;
   const W2Red r = w2_pending.red;
   w2_pending.red.ws = nullptr;
-  (void)stream;   // the partials' own stream orders the reducer behind the launch that wrote them
   return c3d_detail_pw_wgrad_reduce(r.ws, r.dw, r.N, r.K, r.parts, r.sn, r.sk, w2_pending.stream);
 }
 
-void c3d_detail_pw_wgrad_v2_drop() { w2_pending.red.ws = nullptr; }
+// (the stage driver, returning early with an error: what it left pending in its own workspace is not reduced later into
+// gradients of a pass that failed)
+__attribute__((visibility("hidden"))) void c3d_detail_pw_wgrad_v2_forget(const float* ws) {
+  if (w2_pending.red.ws == ws) w2_pending.red.ws = nullptr;
+}
 
 // Returns C3D_E_UNSUPPORTED for what it does not take (the caller then runs the first kernel).
 __attribute__((visibility("hidden"))) int c3d_detail_pw_wgrad_v2(const c3d_pw_wgrad_args* args, hipStream_t stream) {
@@ -473,28 +449,10 @@ __attribute__((visibility("hidden"))) int c3d_detail_pw_wgrad_v2(const c3d_pw_wg
   const bool hasp2 = a.p_coef || a.p_fin.sums;
   const bool qsw = a.q_mode == C3D_PRO_BN_SE_SWISH;
   if (qsw && !hasp2) return C3D_E_UNSUPPORTED;   // (no layer has it)
-  // 32-bit byte offsets into bounds-checked resources
-  // (one tile past the end is addressed, and "nowhere" = 2^31 + a tile base must not wrap into the tensor)
-  if ((a.M + 512) * (int64_t)(a.Np > a.Kp ? a.Np : a.Kp) * 2 >= ((int64_t)1 << 31)) return C3D_E_UNSUPPORTED;
-  const int NT = (a.Np + 15) >> 4, KT = (a.Kp + 15) >> 4;
-  // wave grid WN x WK = 8 and the instantiated per-wave tile grid, as in pw_wgrad.hip
-  int WN = 0, WK = 0, tn_need = 0, tk_need = 0;
-  const int cand[4][2] = {{8, 1}, {4, 2}, {2, 4}, {1, 8}};
-  int best = 1 << 30;
-  for (int c = 0; c < 4; ++c) {
-    const int tn = (NT + cand[c][0] - 1) / cand[c][0], tk = (KT + cand[c][1] - 1) / cand[c][1];
-    if (tn > 4 || tk > 4) continue;
-    int ti = 4, tj = 4;
-    for (int i = 0; i < 5; ++i)
-      if (W2_INSTS[i].tn >= tn && W2_INSTS[i].tk >= tk) { ti = W2_INSTS[i].tn; tj = W2_INSTS[i].tk; break; }
-    const int cost = ti * tj * 4 + ti + tj;
-    if (cost < best) { best = cost; WN = cand[c][0]; WK = cand[c][1]; tn_need = tn; tk_need = tk; }
-  }
-  if (WN == 0) return C3D_E_UNSUPPORTED;
-  int inst = 4;
-  for (int i = 0; i < 5; ++i)
-    if (W2_INSTS[i].tn >= tn_need && W2_INSTS[i].tk >= tk_need) { inst = i; break; }
-  const int TNi = W2_INSTS[inst].tn, TKi = W2_INSTS[inst].tk;
+  if (!pw_fits_u32(a.M + 512, a.Kp, a.Np, 2)) return C3D_E_UNSUPPORTED;
+  const PwWaveGrid wg = pw_wave_grid((a.Np + 15) >> 4, (a.Kp + 15) >> 4);
+  if (wg.WN == 0) return C3D_E_UNSUPPORTED;
+  const int WN = wg.WN, WK = wg.WK, inst = wg.inst, TNi = PW_WG_INSTS[inst].tn, TKi = PW_WG_INSTS[inst].tk;
   if (inst == 4 && hasp2) return C3D_E_UNSUPPORTED;   // 4 x 4 tiles per wave beside the two-tensor prefetch: scratch (no layer has it)
   W2Plan L;
   L.WN = WN; L.WK = WK;
@@ -502,18 +460,8 @@ __attribute__((visibility("hidden"))) int c3d_detail_pw_wgrad_v2(const c3d_pw_wg
   L.ldq = TKi * WK * 16; if (((L.ldq >> 4) & 1) == 0) L.ldq += 16;
   const int Gp = a.Np >> 3, Gq = a.Kp >> 3;
   const bool gate = qsw && a.q_gate;
-  int64_t cap = device_cus() < W2_MAX_PARTS ? device_cus() : W2_MAX_PARTS;
-  static const int cap_env = c3d_env("C3D_WG_BLOCKS") ? atoi(c3d_env("C3D_WG_BLOCKS")) : 0;   // tuning knobs of pw_wgrad.hip
-  static const int side_env = c3d_env("C3D_PWWG_SIDE_WGS") ? atoi(c3d_env("C3D_PWWG_SIDE_WGS")) : 0;
-  static const int mt_env = c3d_env("C3D_WG2_MT") ? atoi(c3d_env("C3D_WG2_MT")) : 0;
-  if (cap_env > 0 && cap_env <= W2_MAX_PARTS) cap = cap_env;
-  else if (c3d_side_launch) {   // beside the data-gradient chain: 7/8 of the CUs (launch_hints.h)
-#ifndef W2_SIDE_EIGHTHS
-#define W2_SIDE_EIGHTHS 7
-#endif
-    const int64_t side_cap = side_env > 0 ? side_env : (int64_t)device_cus() * W2_SIDE_EIGHTHS / 8;
-    if (side_cap < cap) cap = side_cap;
-  }
+  const int64_t cap = pw_wgrad_cap(W2_MAX_PARTS);
+  static const int mt_env = c3d_knob("C3D_WG2_MT", 0);   // tuning knob
   // rows per tile: the tallest of 256 / 128 / 64 that fits the item budget, LDS and the two-samples-per-tile rule, and still
   // leaves every workgroup a walk of a few tiles
   constexpr int W2_NS_MAX = 16;
@@ -521,16 +469,9 @@ __attribute__((visibility("hidden"))) int c3d_detail_pw_wgrad_v2(const c3d_pw_wg
   size_t lds = 0, par_bytes = 0;
   for (int mt = 256; mt >= 64; mt >>= 1) {
     if (mt_env && mt > mt_env) continue;
-    // the workgroup grid this tile height gives, and the samples one workgroup's rows can then span
-    {
-      const int64_t tiles_ = (a.M + mt - 1) / mt;
-      int64_t blocks_ = (tiles_ + 1) / 2;
-      if (blocks_ > cap) blocks_ = cap;
-      if (blocks_ < 1) blocks_ = 1;
-      const int64_t rows_wg = (tiles_ + blocks_ - 1) / blocks_ * mt;
-      ns = gate ? (int)((rows_wg + a.rows_per_sample - 2) / a.rows_per_sample + 1) : 1;
-      if (ns > W2_NS_MAX) continue;
-    }
+    // the samples one workgroup's rows can span on the grid this tile height gives
+    ns = gate ? (int)(((int64_t)pw_walk((a.M + mt - 1) / mt, cap, 2).tiles_per_wg * mt + a.rows_per_sample - 2) / a.rows_per_sample + 1) : 1;
+    if (ns > W2_NS_MAX) continue;
     par_bytes = (size_t)(3 * a.Np + (2 + ns) * a.Kp) * sizeof(float) + W2_THREADS * 16;   // + the dump region
     if ((mt * Gp + W2_THREADS - 1) / W2_THREADS > w2_rounds(TNi) || (mt * Gq + W2_THREADS - 1) / W2_THREADS > w2_rounds(TKi)) continue;
     if (gate && a.rows_per_sample < mt) continue;
@@ -547,20 +488,16 @@ __attribute__((visibility("hidden"))) int c3d_detail_pw_wgrad_v2(const c3d_pw_wg
   L.par_off = 2 * L.buf_bytes;
   L.ns = ns;
   L.dump_off = L.par_off + (3 * a.Np + (2 + ns) * a.Kp) * (int)sizeof(float);
-  const int64_t tiles = (a.M + MT - 1) / MT;
-  int64_t blocks = (tiles + 1) / 2;   // >= 2 tiles per workgroup when there is enough work
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  const int tpw = (int)((tiles + blocks - 1) / blocks);
-  blocks = (tiles + tpw - 1) / tpw;
-  L.tiles_per_wg = tpw;
+  const PwWalk walk = pw_walk((a.M + MT - 1) / MT, cap, 2);   // >= 2 tiles per workgroup when there is enough work
+  const int64_t blocks = walk.blocks;
+  L.tiles_per_wg = walk.tiles_per_wg;
   const dim3 grid((unsigned)blocks);
   // pending partials of the previous chained launch: this launch's prologue reduces them -- if they are on this stream, in
   // another workspace, and small enough for one register pass (256 partials); anything else gets its own reducer launch now
   W2Red red = {nullptr, nullptr, 0, 0, 0, 0, 0};
   if (w2_pending.red.ws) {
     if (w2_pending.stream == stream && w2_pending.red.ws != a.ws && w2_pending.red.parts <= 256) red = w2_pending.red;
-    else { const int rcf = c3d_detail_pw_wgrad_v2_flush(w2_pending.stream); if (rcf != 0) return rcf; }
+    else { const int rcf = c3d_detail_pw_wgrad_v2_flush(nullptr); if (rcf != 0) return rcf; }
     w2_pending.red.ws = nullptr;
   }
   int rc;

@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "common.h"
-#include "launch_hints.h"
+#include "pw_common.h"
 #include <cstdio>
 #include <cstring>
 #include <cxxabi.h>
@@ -131,13 +131,13 @@ int make_plan(const c3d_stage_desc* d, Plan& P) {
     G.Cin = k.cin; G.Ci = k.cinner; G.Co = k.cout;
     G.Cinp = cpad(k.cin); G.Cip = cpad(k.cinner); G.Cop = cpad(k.cout);
     G.se = k.se_width > 0; G.Cr = k.se_width; G.sc_conv = k.has_sc_conv != 0; G.sc_bn = k.has_sc_bn != 0;
-    // The narrow pointwise kernels (channel counts up to 224) address rows with 32-bit byte offsets into bounds-checked buffer
-    // resources (csrc/pw_gemm.hip): a tensor of 2 GiB or more would be refused by the first launch that meets it, in the MIDDLE
-    // of a stage pass.  Refuse the stage here instead -- c3d_stage_ws_bytes is the caller's first contact with a geometry.
+    // A tensor the narrow pointwise kernels (channel counts up to 224) cannot address (pw_fits_u32) would be refused by the
+    // first launch that meets it, in the MIDDLE of a stage pass.  Refuse the stage here instead -- c3d_stage_ws_bytes is the
+    // caller's first contact with a geometry.
     // (bf16, 256 x 256, T = 3: B <= 96 per GPU; f32: half of that.  The wide (res5) kernels have no such limit.)
     {
       const int cmax = std::max(std::max(G.Cinp, G.Cip), G.Cop);
-      if (cmax <= 224 && (int64_t)std::max(G.M, G.Mo) * cmax * (int64_t)e >= ((int64_t)1 << 31)) return C3D_E_UNSUPPORTED;
+      if (cmax <= 224 && !pw_fits_u32(std::max(G.M, G.Mo), cmax, cmax, (int)e)) return C3D_E_UNSUPPORTED;
     }
     H = G.Ho; W = G.Wo;
   }
@@ -197,8 +197,8 @@ int make_plan(const c3d_stage_desc* d, Plan& P) {
     if (fuse_wgrad(d, G.Cop, G.Cip, C3D_WG_SWISH)) wsf_fused = std::max(wsf_fused, c3d_pw_gemm_wg_ws_floats(G.Co, G.Ci));
     if (fuse_wgrad(d, G.Cip, G.Cinp, C3D_WG_ROWS)) wsf_fused = std::max(wsf_fused, c3d_pw_gemm_wg_ws_floats(G.Ci, G.Cin));
     // (the cooperative conv_a data + weight gradient, csrc/pw_cdgrad.hip: reserved whatever C3D_OPT_PW_CDG says right now)
-    if (d->dtype == C3D_DT_BF16 && c3d_detail_pw_cdg_a_supported(G.Cip, G.Cinp, G.M)) wsf_fused = std::max(wsf_fused, c3d_pw_gemm_wg_ws_floats(G.Ci, G.Cin));
-    if (d->dtype == C3D_DT_BF16 && c3d_detail_pw_cdg_c_supported(G.Cop, G.Cip, G.Mo, (int64_t)d->T * G.Ho * G.Wo))
+    if (d->dtype == C3D_DT_BF16 && c3d_detail_pw_cdg_a_shape(G.Cip, G.Cinp, G.M)) wsf_fused = std::max(wsf_fused, c3d_pw_gemm_wg_ws_floats(G.Ci, G.Cin));
+    if (d->dtype == C3D_DT_BF16 && c3d_detail_pw_cdg_c_shape(G.Cop, G.Cip, G.Mo, (int64_t)d->T * G.Ho * G.Wo))
       wsf_fused = std::max(wsf_fused, c3d_pw_gemm_wg_ws_floats(G.Co, G.Ci));
     mx_g = std::max(mx_g, (size_t)G.Mo * G.Cop * e);
     mx_t1 = std::max(mx_t1, (size_t)G.Mo * G.Cip * e);
@@ -579,7 +579,9 @@ extern "C" int c3d_side_join(void* stream) { return side_join(reinterpret_cast<h
 // ---- profiled launches -------------------------------------------------------------------------------------
 namespace {
 
-int pw_launch(const c3d_pw_args& a, hipStream_t st) {
+// profile row of a pointwise GEMM launch, whichever entry point `fn` takes
+template <typename F>
+int pw_prof(const c3d_pw_args& a, hipStream_t st, F&& fn) {
   const double bytes = (double)a.M * ((double)a.Kp * (a.x2 ? 2 : 1) + (double)a.Np * (a.e1 ? 2 : 1) + (a.pro_out ? a.Kp : 0) +
                                      ((a.wg_mode == C3D_WG_ROWS || a.wg_mode == C3D_WG_MASKSUM) ? a.Np : 0) + (a.add_sums ? a.Np : 0)) * (double)es(a.dtype);
   char nm[64];
@@ -588,7 +590,11 @@ int pw_launch(const c3d_pw_args& a, hipStream_t st) {
                   a.epi_mode, a.row_mode, a.wg_mode == C3D_WG_MASKSUM ? " +bob" : a.wg_mode ? (a.add_sums ? " +dW +bob" : " +dW") : "");
   else
     std::snprintf(nm, sizeof(nm), "c3d_pw_gemm");
-  return prof_call(nm, bytes, st, [&] { return c3d_pw_gemm(&a, st); });
+  return prof_call(nm, bytes, st, fn);
+}
+
+int pw_launch(const c3d_pw_args& a, hipStream_t st) {
+  return pw_prof(a, st, [&] { return c3d_pw_gemm(&a, st); });
 }
 
 int wg_launch(const c3d_pw_wgrad_args& a, hipStream_t st) {
@@ -763,7 +769,26 @@ extern "C" int c3d_stage_bwd(const c3d_stage_desc* d, const void* x, const void*
   int cdg_n = 0;   // cooperative data + weight gradient launches of this call (workspace slot 1 + cdg_n)
   struct RedJob { const float* ws; float* dw; int K, N, parts, sk, sn; };
   std::vector<RedJob> red_jobs;   // their partials: reduced on the side stream behind one fork at the end of the pass
-  c3d_detail_pw_wgrad_v2_drop();   // (nothing may be pending from a call that returned early)
+  // A cooperative data + weight gradient (csrc/pw_cdgrad.hip; the caller has asked its _accepts).  With the side stream on, the
+  // kernel leaves its weight-gradient partials in a slot of their own and ALL reducers of the pass are launched behind one
+  // fork at its end.  (Per launch -- on the side stream, six rotating buffers -- every fork was a barrier packet on the main
+  // queue: 11 us in front of every conv_c launch with the side queue otherwise idle, profiles/r06_trace_gaps.txt; on the main
+  // stream each reducer is 5 us of the data-gradient chain.)  Side stream off: slot 0, the reducer right behind the kernel.
+  auto coop_launch = [&](c3d_pw_args& a, int (*launch)(const c3d_pw_args*, int*, void*)) {
+    const bool defer = side_enabled();
+    int parts = 0;
+    if (defer) a.wg_ws = wgws_fused + (size_t)(1 + cdg_n) * (P.wgrad_ws_fused_slot / 4);
+    RC(pw_prof(a, st, [&] { return launch(&a, defer ? &parts : nullptr, st); }));
+    if (defer) { ++cdg_n; red_jobs.push_back({a.wg_ws, a.wg_dw, a.K, a.N, parts, a.w_sk, a.w_sn}); }
+    return 0;
+  };
+  // chained weight-gradient partials this call leaves pending are this call's to settle: the flush at the end of the pass,
+  // or -- returning early with an error -- forgotten (somebody else's pending partials are not touched: c3d_pw_wgrad settles them)
+  struct PendingGuard {
+    float* const* ws;
+    bool armed = true;
+    ~PendingGuard() { if (armed) { c3d_detail_pw_wgrad_v2_forget(ws[0]); c3d_detail_pw_wgrad_v2_forget(ws[1]); } }
+  } pending_guard{wgws_ab};
   const bool wimg = use_pw_img(d);   // transposed weight images written by this step's c3d_stage_fwd (training mode)
   auto imgp = [&](size_t off) -> const void* { return wimg && off != SIZE_MAX ? at(ws, off) : nullptr; };
   const void* cur_dy = dy;
@@ -815,37 +840,28 @@ extern "C" int c3d_stage_bwd(const c3d_stage_desc* d, const void* x, const void*
     if (!consb) RC(coef(dsums_c, (double)G.Mo, k.bn_c, mr_c, G.Co, G.Cop, coef_c));
     // ---- conv_c data gradient, Swish / SE backward in the epilogue; weight gradient on the side stream (it needs
     //      coef_c, not the data gradient: it is forked BEFORE the data-gradient launch)
-    const bool coop_wc = (c3d_option_pw_cdg & 2) && dt == C3D_DT_BF16 && !(d->flags & C3D_STAGE_SEPARATE_WGRAD) && imgp(F.img_ct) != nullptr &&
-                         c3d_detail_pw_cdg_c_supported(G.Cop, G.Cip, G.Mo, rps);
+    //      -- or fused into the data-gradient launch: the cooperative kernel (csrc/pw_cdgrad.hip) if it accepts the call as it
+    //      will be launched, else the wave-private kernel's variant where that holds the layer
+    PwCall pc(g, k.w_c, t1, G.Mo, G.Co, G.Ci, 1, G.Ci, dt);
+    pc.a.wg_mode = C3D_WG_SWISH; pc.a.wg_dw = k.dw_c; pc.a.wg_ws = wgws_fused;
+    pc.a.x2 = c; pc.a.pro_mode = C3D_PRO_AFFINE2; pc.a.pro_p = coef_c;
+    if (consb) pc.a.fin = fin_coef_consume(dsums_c, k.bn_c, (double)G.Mo, mr_c, true);
+    pc.a.epi_mode = C3D_EPI_SWISH_SE_BWD; pc.a.e1 = b; pc.a.epi_p = ss_b; pc.a.epi_gate = gate; pc.a.epi_q = mr_b;
+    pc.a.stats = nc3; pc.a.rows_per_sample = rps; pc.a.w_img = imgp(F.img_ct);
+    const bool coop_wc = (c3d_option_pw_cdg & 2) && !(d->flags & C3D_STAGE_SEPARATE_WGRAD) && c3d_detail_pw_cdg_c_accepts(&pc.a);
     const bool fuse_wc = coop_wc || ((g_fuse_wgrad & 2) && fuse_wgrad(d, G.Cop, G.Cip, C3D_WG_SWISH) && G.Cop <= 48);
-    if (!fuse_wc)
-    RC(side_run(st, [&](hipStream_t s2) {
-      WgCall w(g, b, k.dw_c, wgws_ab[wg_n++ & 1], G.Mo, G.Ci, G.Co, G.Ci, 1, dt);
-      w.a.chain = g_wgrad_chain;
-      w.a.p2 = c; w.a.p_coef = coef_c; w.a.q_mode = C3D_PRO_BN_SE_SWISH; w.a.q_ss = ss_b; w.a.q_gate = gate;
-      w.a.rows_per_sample = rps;
-      if (consb) w.a.p_fin = fin_coef_consume(dsums_c, k.bn_c, (double)G.Mo, mr_c, false);
-      return wg_launch(w.a, s2);
-    }));
-    {
-      PwCall p(g, k.w_c, t1, G.Mo, G.Co, G.Ci, 1, G.Ci, dt);
-      if (fuse_wc) { p.a.wg_mode = C3D_WG_SWISH; p.a.wg_dw = k.dw_c; p.a.wg_ws = wgws_fused; }
-      p.a.x2 = c; p.a.pro_mode = C3D_PRO_AFFINE2; p.a.pro_p = coef_c;
-      if (consb) p.a.fin = fin_coef_consume(dsums_c, k.bn_c, (double)G.Mo, mr_c, true);
-      p.a.epi_mode = C3D_EPI_SWISH_SE_BWD; p.a.e1 = b; p.a.epi_p = ss_b; p.a.epi_gate = gate; p.a.epi_q = mr_b;
-      p.a.stats = nc3; p.a.rows_per_sample = rps; p.a.w_img = imgp(F.img_ct);
-      if (coop_wc && side_enabled()) {   // (the partials' reducer: deferred, see conv_a below)
-        float* const wsk = wgws_fused + (size_t)(1 + cdg_n) * (P.wgrad_ws_fused_slot / 4);
-        p.a.wg_ws = wsk;
-        c3d_cdg_defer_reduce = 1; c3d_cdg_parts = 0;
-        const int rcl = pw_launch(p.a, st);
-        c3d_cdg_defer_reduce = 0;
-        RC(rcl);
-        if (c3d_cdg_parts > 0) { ++cdg_n; red_jobs.push_back({wsk, p.a.wg_dw, p.a.K, p.a.N, c3d_cdg_parts, p.a.w_sk, p.a.w_sn}); }
-      } else {
-        RC(pw_launch(p.a, st));
-      }
+    if (!fuse_wc) {
+      pc.a.wg_mode = C3D_WG_NONE; pc.a.wg_dw = nullptr; pc.a.wg_ws = nullptr;
+      RC(side_run(st, [&](hipStream_t s2) {
+        WgCall w(g, b, k.dw_c, wgws_ab[wg_n++ & 1], G.Mo, G.Ci, G.Co, G.Ci, 1, dt);
+        w.a.chain = g_wgrad_chain;
+        w.a.p2 = c; w.a.p_coef = coef_c; w.a.q_mode = C3D_PRO_BN_SE_SWISH; w.a.q_ss = ss_b; w.a.q_gate = gate;
+        w.a.rows_per_sample = rps;
+        if (consb) w.a.p_fin = fin_coef_consume(dsums_c, k.bn_c, (double)G.Mo, mr_c, false);
+        return wg_launch(w.a, s2);
+      }));
     }
+    RC(coop_wc ? coop_launch(pc.a, c3d_detail_pw_cdg_c) : pw_launch(pc.a, st));
     // BatchNorm_b / SE backward coefficients.  Blocks without SE (stride 1 always): the fused depthwise backward kernel
     // rebuilds A | B | C from the per-sample sums in its prologue -- no coefficient launch on the critical path
     const bool fold_b = fin_consumer(d) && !G.se && G.s == 1;
@@ -898,19 +914,9 @@ extern "C" int c3d_stage_bwd(const c3d_stage_desc* d, const void* x, const void*
     //      coefficients, not the data gradient)
     // ... or fused into the data-gradient launch: the wave-private kernel's variant (K, N <= 112) or the cooperative kernel
     // (csrc/pw_cdgrad.hip: any of the three stage widths, dense shortcut gradient, packed weight image)
-    const bool coop_wa = (c3d_option_pw_cdg & 1) && dt == C3D_DT_BF16 && !(d->flags & C3D_STAGE_SEPARATE_WGRAD) && res_mode == 0 &&
-                         imgp(F.img_at) != nullptr && c3d_detail_pw_cdg_a_supported(G.Cip, G.Cinp, G.M);
-    const bool fuse_wa = coop_wa || ((g_fuse_wgrad & 1) && fuse_wgrad(d, G.Cip, G.Cinp, C3D_WG_ROWS));
+    // The arguments are filled for the fused form first, and the cooperative kernel is asked about exactly those.
     bool mask_next = false, sums_next = false;
-    if (!fuse_wa)
-    RC(side_run(st, [&](hipStream_t s2) {
-      WgCall w(t2, xin, k.dw_a, wgws_ab[wg_n++ & 1], G.M, G.Cin, G.Ci, G.Cin, 1, dt);
-      w.a.chain = g_wgrad_chain;
-      w.a.p2 = a; w.a.p_coef = coef_a;
-      if (consb) w.a.p_fin = fin_coef_consume(dsums_a, k.bn_a, (double)G.M, mr_a, false);
-      return wg_launch(w.a, s2);
-    }));
-    {
+    auto conv_a_call = [&](bool fuse_wa) {
       PwCall p(t2, k.w_a, dx, G.M, G.Ci, G.Cin, 1, G.Cin, dt);
       if (fuse_wa) { p.a.wg_mode = C3D_WG_ROWS; p.a.wg_x3 = xin; p.a.wg_dw = k.dw_a; p.a.wg_ws = wgws_fused; }
       // xin is the previous block's output y: its ReLU mask goes onto dx here -- dx IS that block's g then (the dx slots
@@ -931,22 +937,22 @@ extern "C" int c3d_stage_bwd(const c3d_stage_desc* d, const void* x, const void*
       if (consb) p.a.fin = fin_coef_consume(dsums_a, k.bn_a, (double)G.M, mr_a, true);
       p.a.epi_mode = C3D_EPI_ADD; p.a.e1 = res; p.a.res_mode = res_mode; p.a.H = G.H; p.a.W = G.W;
       p.a.w_img = imgp(F.img_at);
-      if (coop_wa && side_enabled()) {
-        // The cooperative kernel leaves its weight-gradient partials in a buffer of its own; ALL reducers of the pass are
-        // launched behind one fork at its end.  (Per launch -- on the side stream, six rotating buffers -- every fork was a
-        // barrier packet on the main queue: 11 us in front of every conv_c launch with the side queue otherwise idle,
-        // profiles/r06_trace_gaps.txt; on the main stream each reducer is 5 us of the data-gradient chain.)
-        float* const wsk = wgws_fused + (size_t)(1 + cdg_n) * (P.wgrad_ws_fused_slot / 4);
-        p.a.wg_ws = wsk;
-        c3d_cdg_defer_reduce = 1; c3d_cdg_parts = 0;
-        const int rcl = pw_launch(p.a, st);
-        c3d_cdg_defer_reduce = 0;
-        RC(rcl);
-        if (c3d_cdg_parts > 0) { ++cdg_n; red_jobs.push_back({wsk, p.a.wg_dw, p.a.K, p.a.N, c3d_cdg_parts, p.a.w_sk, p.a.w_sn}); }
-      } else {
-        RC(pw_launch(p.a, st));
-      }
+      return p;
+    };
+    PwCall pa = conv_a_call(true);
+    const bool coop_wa = (c3d_option_pw_cdg & 1) && !(d->flags & C3D_STAGE_SEPARATE_WGRAD) && c3d_detail_pw_cdg_a_accepts(&pa.a);
+    const bool fuse_wa = coop_wa || ((g_fuse_wgrad & 1) && fuse_wgrad(d, G.Cip, G.Cinp, C3D_WG_ROWS));
+    if (!fuse_wa) {
+      pa = conv_a_call(false);
+      RC(side_run(st, [&](hipStream_t s2) {
+        WgCall w(t2, xin, k.dw_a, wgws_ab[wg_n++ & 1], G.M, G.Cin, G.Ci, G.Cin, 1, dt);
+        w.a.chain = g_wgrad_chain;
+        w.a.p2 = a; w.a.p_coef = coef_a;
+        if (consb) w.a.p_fin = fin_coef_consume(dsums_a, k.bn_a, (double)G.M, mr_a, false);
+        return wg_launch(w.a, s2);
+      }));
     }
+    RC(coop_wa ? coop_launch(pa.a, c3d_detail_pw_cdg_a) : pw_launch(pa.a, st));
     // the side stream may lag by ring-1 blocks: block i-1 reuses the ring slot of block i-1+ring
     lag.push_back(side_mark());
     if ((int)lag.size() >= bwd_ring()) { RC(side_join(st, lag.front())); lag.pop_front(); }
@@ -960,6 +966,7 @@ extern "C" int c3d_stage_bwd(const c3d_stage_desc* d, const void* x, const void*
       for (const RedJob& j : red_jobs) RC(c3d_detail_pw_wgrad_reduce(j.ws, j.dw, j.K, j.N, j.parts, j.sk, j.sn, s2));
       return wg_n ? c3d_pw_wgrad_flush(s2) : 0;
     }));
+  pending_guard.armed = false;
   return 0;
 }
 

@@ -225,7 +225,8 @@ typedef struct c3d_pw_wgrad_args {
 int64_t c3d_pw_wgrad_ws_floats(int32_t N, int32_t K);
 int c3d_pw_wgrad(const c3d_pw_wgrad_args* args, void* stream);
 /* Adds the pending partials of this thread's last chained c3d_pw_wgrad launch (if any) into its dw, on `stream` (the stream of
- * that launch).  The stage driver calls it at the end of c3d_stage_bwd; a no-op when nothing is pending.                      */
+ * that launch).  The stage driver calls it at the end of c3d_stage_bwd; a no-op when nothing is pending.  c3d_pw_wgrad itself
+ * adds them first whenever a launch, chained or not, is about to write the `ws` they sit in.                                 */
 int c3d_pw_wgrad_flush(void* stream);
 
 /* ------------------------------------------------------------------------------------
@@ -554,7 +555,7 @@ int c3d_stage_fwd(const c3d_stage_desc* d, const void* x, void* ws_fwd, void* y,
 /* dy: gradient of y (same layout); dx: gradient of x (written).  x / y / ws_fwd as given to c3d_stage_fwd.
  * The weight gradients that are not fused into their data-gradient launch (c3d_pw_wgrad) are launched on the library's side stream, each forked ahead
  * of the data-gradient kernel that reads the same operands, with their grids capped (7/8 of the CUs for the pointwise
- * kernel: csrc/launch_hints.h, csrc/pw_wgrad.hip) so that the data-gradient chain finds free CUs; ws_bwd holds a ring of
+ * kernel: csrc/pw_common.h pw_wgrad_cap) so that the data-gradient chain finds free CUs; ws_bwd holds a ring of
  * three blocks' temporaries (one slot more for dx, which is also the next block's g: c3d_pw_args.add_sums), so the side
  * stream may lag the chain by two blocks.                                                                        */
 int c3d_stage_bwd(const c3d_stage_desc* d, const void* x, const void* y, const void* dy, void* ws_fwd, void* ws_bwd,

@@ -572,6 +572,42 @@ def test_pw_wgrad_chained_reduction_is_bit_identical():
     ops.pw_wgrad_flush()   # nothing pending: a no-op
 
 
+# Pending partials are owned by the launch that left them: an UNCHAINED launch that writes the workspace they sit in -- here the
+# buffer ops._ws hands out on this stream, which the strided shortcut gradient (first kernel) fills at once -- finds them
+# reduced first.  Both dw must equal, BIT FOR BIT, what the two launches give unchained one after the other.
+def test_pw_wgrad_unchained_launch_reduces_pending_partials_in_its_workspace():
+    _need_gpu()
+    from change3d_amd import ops
+    dtype = torch.bfloat16
+    B, rows = 6, 1024
+    M = B * rows
+    Ci, Co = 216, 96
+    Cip, Cop = ops.cpad(Ci), ops.cpad(Co)
+    dev = lambda t: t.to(DEV, dtype).contiguous()
+    t2, a_, x = dev(padc(rnd((M, Ci), 70), Cip)), dev(padc(rnd((M, Ci), 71), Cip)), dev(padc(rnd((M, Co), 75), Cop))
+    coef_a = torch.cat([padc(rnd((Ci,), 76), Cip), padc(rnd((Ci,), 77, 0.1), Cip), padc(rnd((Ci,), 78, 0.1), Cip)]).to(DEV)
+    Hs = 32
+    xs = dev(rnd((B, Hs, Hs, 48), 85))
+    gs = dev(rnd((B * (Hs // 2) * (Hs // 2), Cop), 86))
+    dt = ops.dt_code(dtype)
+
+    def run(shared):
+        dws = [torch.full((Ci, Co), 0.25, device=DEV), torch.full((Co, 48), 0.25, device=DEV)]
+        ws = ops._ws(t2.device, int(ops.L.lib().c3d_pw_wgrad_ws_floats(Ci, Cip))) if shared else None
+        ops.pw_wgrad(t2, x, dws[0], M=M, K=Co, N=Ci, dw_sn=Co, dw_sk=1, dtype=dt, p2=a_, p_coef=coef_a, chain_ws=ws)
+        ops.pw_wgrad(gs, xs, dws[1], M=gs.shape[0], K=48, N=Co, dw_sn=48, dw_sk=1, dtype=dt, row_mode=ops.ROWS_STRIDE2, H=Hs, W=Hs)
+        if shared:
+            assert ops._ws(t2.device, 1).data_ptr() == ws.data_ptr(), "the second launch did not write the first one's workspace"
+            ops.pw_wgrad_flush()
+        torch.cuda.synchronize()
+        return [d.cpu() for d in dws]
+
+    plain, shared = run(False), run(True)
+    for i, (u, v) in enumerate(zip(plain, shared)):
+        assert torch.isfinite(v).all() and (v - 0.25).abs().max().item() > 0, f"launch {i}: nothing was accumulated"
+        assert torch.equal(u, v), f"launch {i}: differs from the unchained launches by {(u - v).abs().max().item():.3e}"
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_pw_wgrad_row_modes(dtype):
     _need_gpu()
