@@ -2,9 +2,8 @@
 #pragma once
 #include "common.h"
 #include "../../include/change3d_hip.h"   // c3d_bn_fin
+#include "launch_hints.h"   // c3d_option_dw_t4
 #include <type_traits>
-
-extern int c3d_option_dw_t4;   // C3D_OPT_DW_T4 (launch_hints.h)
 
 namespace {
 

@@ -1,5 +1,5 @@
 // Shared pieces of the pointwise-convolution kernels: the matrix-core wrappers, and the host-side vocabulary of their launch
-// plans (pw_gemm*.hip, pw_cfwd.hip, pw_cdgrad.hip, pw_wgrad.hip, pw_wgrad_v2.hip, make_plan of stage_driver.hip).
+// plans (pw_gemm*.hip, pw_cfwd.hip, pw_cdgrad.hip, pw_wgrad.hip, pw_wgrad_v2.hip, make_plan of stage_plan.h).
 #pragma once
 #include "common.h"
 #include "launch_hints.h"

@@ -39,7 +39,7 @@ __attribute__((visibility("hidden"))) int c3d_detail_pw_gemm_wg(const c3d_pw_arg
   return C3D_E_UNSUPPORTED;
 }
 
-// Host-side plan check for the stage driver (csrc/stage_driver.hip fuse_wgrad): the same gates and the same LDS plan as the
+// Host-side plan check for the stage driver (csrc/stage_plan.h fuse_wgrad): the same gates and the same LDS plan as the
 // launch path above, so that a shape whose f64 accumulator image does not fit beside the weights and the wave regions (e.g.
 // Kp = 112 with Np >= 80) keeps its c3d_pw_wgrad launch instead of failing c3d_stage_bwd with C3D_E_UNSUPPORTED.
 namespace {

@@ -852,6 +852,53 @@ def test_stage_api_refuses_an_oversize_geometry_up_front():
         assert L.lib().c3d_stage_ws_bytes(C.byref(d), *[C.byref(v) for v in out]) == -2   # C3D_E_UNSUPPORTED
 
 
+def test_stage_saved_regions_are_aligned_disjoint_and_inside_the_forward_workspace():
+    """`c3d_stage_saved` reports the regions of the forward workspace plan (no GPU needed: planning only).  A stage with res3's
+    widths -- first block stride 2 with shortcut convolution + BatchNorm, SqueezeExcitation on every other block: every region
+    it reports is non-empty, 256-byte aligned, inside `ws_fwd_bytes`, and no two regions of the stage overlap; the regions a
+    block does not have by construction (`sc` without a shortcut convolution, `mr_sc` / `ss_sc` without a shortcut BatchNorm,
+    `gate` without SE) are C3D_E_BADARG."""
+    import ctypes as C
+    from change3d_amd import _lib as L
+    cfg = [(24, 108, 48, 2, 8, 1, 1), (48, 108, 48, 1, 0, 0, 0), (48, 108, 48, 1, 8, 0, 0), (48, 108, 48, 1, 0, 0, 0)]
+    blk = (L.BlockDesc * len(cfg))()
+    for bd, c in zip(blk, cfg):
+        bd.cin, bd.cinner, bd.cout, bd.stride, bd.se_width, bd.has_sc_conv, bd.has_sc_bn = c
+    d = L.StageDesc()
+    d.n_blocks, d.B, d.T, d.H, d.W, d.training = len(cfg), 2, 3, 64, 64, 1
+    d.blocks = C.cast(blk, C.POINTER(L.BlockDesc))
+    names = ("a", "b", "c", "sc", "mr_a", "mr_b", "mr_c", "mr_sc", "ss_a", "ss_b", "ss_c", "ss_sc", "gate")
+    for dtype in (1, 0):                                          # C3D_DT_BF16, C3D_DT_F32
+        d.dtype = dtype
+        sizes = [C.c_int64() for _ in range(4)]
+        assert L.lib().c3d_stage_ws_bytes(C.byref(d), *[C.byref(v) for v in sizes]) == 0
+        ws_fwd = sizes[0].value
+        regions = []
+        for i, c in enumerate(cfg):
+            absent = set()
+            if not c[5]:
+                absent.add("sc")
+            if not c[6]:
+                absent |= {"mr_sc", "ss_sc"}
+            if not c[4]:
+                absent.add("gate")
+            for name in names:
+                off, n = C.c_int64(-1), C.c_int64(-1)
+                rc = L.lib().c3d_stage_saved(C.byref(d), i, name.encode(), C.byref(off), C.byref(n))
+                if name in absent:
+                    assert rc == -1, (i, name, rc)                # C3D_E_BADARG
+                    continue
+                assert rc == 0, (i, name, rc)
+                assert n.value > 0 and off.value % 256 == 0 and off.value + n.value <= ws_fwd, (i, name, off.value, n.value, ws_fwd)
+                regions.append((off.value, n.value, i, name))
+        assert len(regions) == 13 + 9 + 10 + 9
+        regions.sort()
+        for (o0, n0, *who0), (o1, _, *who1) in zip(regions, regions[1:]):
+            assert o0 + n0 <= o1, (who0, who1)
+        elem = 2 if dtype == 1 else 4
+        assert regions[0][:2] == (0, 2 * 3 * 64 * 64 * 112 * elem)   # block 0's conv_a output: B T H W x 108 padded to 112
+
+
 def test_pw_gemm_checks_the_folded_block_output_backward_arguments_without_a_launch():
     """`c3d_pw_args.add_sums` / C3D_WG_MASKSUM (c3d_block_out_bwd of the previous block in the conv_a data gradient's epilogue,
     reference model/x3d.py:229-236): the sums are over the MASKED output, so they are an argument error without the mask, and the
