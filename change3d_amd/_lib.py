@@ -80,6 +80,21 @@ class StageDesc(C.Structure):
                 ("blocks", C.POINTER(BlockDesc))]
 
 
+CAP_BEAM_MAX, CAP_BEAM_LAYERS = 8, 8      # C3D_CAP_BEAM_MAX, C3D_CAP_BEAM_LAYERS
+
+
+class CapBeamLayer(C.Structure):
+    _fields_ = [(n, vp) for n in ("sa_in_w", "sa_in_b", "sa_out_w", "sa_out_b", "n1_g", "n1_b", "ca_q_w", "ca_q_b", "ca_out_w",
+                                  "ca_out_b", "n2_g", "n2_b", "kv")]
+
+
+class CapBeamArgs(C.Structure):
+    _fields_ = [(n, i32) for n in ("B", "S", "D", "H", "n_layer", "V", "beam", "max_len", "start_id", "end_id", "dtype")] + \
+               [("ln_eps", f32), ("emb", vp), ("pe", vp), ("wdc_w", vp), ("wdc_b", vp), ("layers", CapBeamLayer * CAP_BEAM_LAYERS),
+                ("ws", vp), ("comp_seq", vp), ("comp_len", vp), ("comp_score", vp), ("meta", vp), ("trace", vp), ("forced", vp),
+                ("logits_out", vp)]
+
+
 # name -> (restype, argtypes); every function declared in include/change3d_hip.h
 SIGNATURES = {
     "c3d_abi_version": (i32, []),
@@ -150,6 +165,8 @@ SIGNATURES = {
     "c3d_cap_ce_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, vp]),
     "c3d_cap_ce_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, vp]),
     "c3d_clamp_": (i32, [vp, i64, f32, vp]),
+    "c3d_cap_beam_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i64, C.POINTER(i64), C.POINTER(i64)]),
+    "c3d_cap_beam_search": (i32, [C.POINTER(CapBeamArgs), vp]),
     "c3d_stage_ws_bytes": (i32, [C.POINTER(StageDesc), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
     "c3d_stage_fwd": (i32, [C.POINTER(StageDesc), vp, vp, vp, vp]),
     "c3d_stage_bwd": (i32, [C.POINTER(StageDesc), vp, vp, vp, vp, vp, vp, vp]),

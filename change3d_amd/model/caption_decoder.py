@@ -456,6 +456,75 @@ class CaptionDecoder(nn.Module):
         return complete_seqs[best], complete_seqs, complete_scores
 
 
+    @torch.no_grad()
+    def beam_search_batch(self, encoder_out, start_id, end_id, beam_size, max_len=52, return_trace=False):
+        """Caption B image pairs in one device-resident search (csrc/caption_beam.hip: one workgroup per pair, incremental
+        decoding over a key/value cache, top-k and beam bookkeeping on the device, one host synchronisation at the end).
+        encoder_out (S, B, D).  Returns a list of B tuples (best_seq or None, complete_seqs, complete_seqs_scores) with the
+        types and conventions of `beam_search`; equal candidate scores are ordered by the lower flat index
+        hypothesis * vocab + word.  `return_trace`: also a list of B traces, one entry per decoded step:
+        (live hypotheses before the step, [(parent, word, score) per selected candidate in rank order]).
+        A shape the kernel's plan refuses (ops.cap_beam_plan) goes pair by pair through `beam_search` (no trace then)."""
+        was_training = self.training
+        self.eval()
+        try:
+            return self._beam_search_batch(encoder_out, start_id, end_id, beam_size, max_len, return_trace)
+        finally:
+            self.train(was_training)
+
+    def _beam_search_batch(self, encoder_out, start_id, end_id, beam_size, max_len, return_trace, forced=None, want_logits=False):
+        ops.require_gpu(encoder_out, "caption decoder memory")
+        S, B, D = encoder_out.shape
+        k, V, dev, act = beam_size, self.vocab_size, encoder_out.device, self.act_dtype
+        dt = ops.dt_code(act)
+        plan = ops.cap_beam_plan(S, D, self.n_head, len(self.transformer.layers), V, k, max_len, dt, B)
+        if plan is None:
+            if return_trace or forced is not None or want_logits:
+                raise NotImplementedError("the batched beam search does not take this shape: no trace / forced decoding")
+            return [self._beam_search(encoder_out[:, b:b + 1].contiguous(), start_id, end_id, k, max_len) for b in range(B)]
+        kv = project_memory(self.transformer, encoder_out)                    # per layer [S*B][2D], shared by a pair's beams
+        ws = torch.empty(max(plan[0], 16), dtype=torch.uint8, device=dev)
+        sq, steps = max_len + 1, max_len - 1
+        # one int32 buffer for everything the host reads back: sequences | lengths | scores (f32 bits) | meta | trace
+        n_seq, n_len, n_meta = B * k * sq, B * k, B * 4
+        n_tr = B * steps * (1 + 3 * k) if return_trace else 0
+        out = torch.zeros(n_seq + 2 * n_len + n_meta + n_tr, dtype=torch.int32, device=dev)
+        o_len, o_sc, o_meta, o_tr = n_seq, n_seq + n_len, n_seq + 2 * n_len, n_seq + 2 * n_len + n_meta
+        logits = torch.zeros((B, steps, k, V), dtype=torch.float32, device=dev) if want_logits else None
+        if forced is not None:
+            forced = forced.to(device=dev, dtype=torch.int32).contiguous()
+            assert forced.shape == (B, steps, k, 2), forced.shape
+        ops.cap_beam_search(self, kv, B, S, start_id, end_id, k, max_len, dt, ws, out[:o_len], out[o_len:o_sc],
+                            out[o_sc:o_meta].view(torch.float32), out[o_meta:o_tr], trace=out[o_tr:] if return_trace else None,
+                            forced=forced, logits_out=logits)
+        host = out.cpu()                                                      # the one synchronisation
+        seqs = host[:o_len].view(B, k, sq).tolist()
+        lens = host[o_len:o_sc].view(B, k).tolist()
+        scores = host[o_sc:o_meta].view(torch.float32).view(B, k).tolist()
+        meta = host[o_meta:o_tr].view(B, 4).tolist()
+        results = []
+        for b in range(B):
+            n, best = meta[b][0], meta[b][1]
+            cs = [seqs[b][i][:lens[b][i]] for i in range(n)]
+            results.append((cs[best] if best >= 0 else None, cs, scores[b][:n]))
+        self.last_search_steps = [m[2] for m in meta]
+        if want_logits:
+            return results, logits
+        if not return_trace:
+            return results
+        tr = host[o_tr:].view(B, steps, 1 + 3 * k)
+        tr_sc = tr[:, :, 1:].reshape(B, steps, k, 3)[..., 2].contiguous().view(torch.float32).tolist()
+        tr = tr.tolist()
+        traces = []
+        for b in range(B):
+            t = []
+            for s in range(meta[b][2]):
+                live = tr[b][s][0]
+                t.append((live, [(tr[b][s][1 + 3 * r], tr[b][s][2 + 3 * r], tr_sc[b][s][r]) for r in range(live)]))
+            traces.append(t)
+        return results, traces
+
+
 class _PackedCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits_sf, caps, declen, ignore_index, V):

@@ -802,6 +802,39 @@ def clamp_(g, limit):
     _launch("c3d_clamp_", g.numel() * 8, L.lib().c3d_clamp_, _p(g), g.numel(), float(limit), _stream())
 
 
+def cap_beam_plan(S, D, H, n_layer, V, beam, max_len, dtype, B=1):
+    """c3d_cap_beam_plan: (workspace bytes, dynamic-LDS bytes) of a batched beam search, or None for a shape the kernel does
+    not take (C3D_E_UNSUPPORTED).  Host only: callable without a GPU."""
+    ws, lds = C.c_int64(0), C.c_int64(0)
+    rc = L.lib().c3d_cap_beam_plan(S, D, H, n_layer, V, beam, max_len, dtype, B, C.byref(ws), C.byref(lds))
+    if rc == -2:
+        return None
+    L.check(rc, "c3d_cap_beam_plan")
+    return ws.value, lds.value
+
+
+def cap_beam_search(dec, kv, B, S, start_id, end_id, beam, max_len, dtype, ws, comp_seq, comp_len, comp_score, meta, trace=None,
+                    forced=None, logits_out=None):
+    """c3d_cap_beam_search over B pairs: `dec` a CaptionDecoder (its parameters are read in place), `kv` the per-layer
+    projected memory [S*B][2D] of model.caption_decoder.project_memory.  One launch, no synchronisation."""
+    a = L.CapBeamArgs()
+    D = dec.vocab_embedding.weight.shape[1]
+    a.B, a.S, a.D, a.H, a.n_layer, a.V, a.beam, a.max_len = B, S, D, dec.n_head, len(dec.transformer.layers), dec.vocab_size, beam, max_len
+    a.start_id, a.end_id, a.dtype = int(start_id), int(end_id), dtype
+    a.ln_eps = float(dec.transformer.layers[0].norm1.eps)
+    a.emb, a.pe = _p(dec.vocab_embedding.weight), _p(dec.position_encoding.pe)
+    a.wdc_w, a.wdc_b = _p(dec.wdc.weight), _p(dec.wdc.bias)
+    for i, (layer, kv2) in enumerate(zip(dec.transformer.layers, kv)):
+        sa, ca, l = layer.self_attn, layer.multihead_attn2, a.layers[i]
+        l.sa_in_w, l.sa_in_b, l.sa_out_w, l.sa_out_b = _p(sa.in_proj_weight), _p(sa.in_proj_bias), _p(sa.out_proj.weight), _p(sa.out_proj.bias)
+        l.n1_g, l.n1_b, l.n2_g, l.n2_b = _p(layer.norm1.weight), _p(layer.norm1.bias), _p(layer.norm2.weight), _p(layer.norm2.bias)
+        l.ca_q_w, l.ca_q_b = _p(ca.in_proj_weight), _p(ca.in_proj_bias)           # rows [:D] of the packed projection
+        l.ca_out_w, l.ca_out_b, l.kv = _p(ca.out_proj.weight), _p(ca.out_proj.bias), _p(kv2)
+    a.ws, a.comp_seq, a.comp_len, a.comp_score, a.meta = _p(ws), _p(comp_seq), _p(comp_len), _p(comp_score), _p(meta)
+    a.trace, a.forced, a.logits_out = _p(trace), _p(forced), _p(logits_out)
+    _launch("c3d_cap_beam_search", ws.numel() * ws.element_size(), L.lib().c3d_cap_beam_search, C.byref(a), _stream())
+
+
 def linear_fwd(x, weight, bias, y, M, K, N, dtype):
     """y[M][Np] = x[M][Kp] @ weight[N][K]^T + bias (nn.Linear / in_proj slices)."""
     pw_gemm(x, weight, y, M=M, K=K, N=N, w_sn=weight.stride(0), w_sk=1, dtype=dtype, bias=bias)

@@ -59,14 +59,38 @@ def train_step(args, model, enc_opt, dec_opt, imgs_a, imgs_b, caps, caplens):
     return loss.detach(), stats
 
 
+def encode_memory(model, pre, post, chunk=8):
+    """Encoder memory (H/16 * W/16, B, 192) of B pairs, the encoder run on at most `chunk` pairs at a time: the search batch
+    may be larger than what the eval-mode encoder takes (f32 at 256 x 256: the stage planner stops at B = 48, and
+    c3d_stage_fwd_folded answered C3D_E_UNSUPPORTED at 16 pairs or more when this was written; 8 is what was measured)."""
+    mems = []
+    for i in range(0, pre.shape[0], chunk):
+        feat = model.update_cc(pre[i:i + chunk], post[i:i + chunk])             # (b, 192, H/16, W/16)
+        B, C, H, W = feat.shape
+        mems.append(feat.permute(2, 3, 0, 1).reshape(H * W, B, C))              # rearrange 'b c h w -> (h w) b c'
+    return mems[0] if len(mems) == 1 else torch.cat(mems, dim=1)
+
+
 @torch.no_grad()
-def evaluate(args, model, pairs, start_id, end_id, pad_id=0):
+def evaluate(args, model, pairs, start_id, end_id, pad_id=0, eval_batch=None):
     """reference scripts/train_CC.py:170-399 without the file I/O and the text metrics: eval mode (BatchNorm folded
     into the encoder weights), one pair at a time as the reference's batch_size=1 loader does, beam search of width
     `args.beam_size`; returns the hypotheses (special tokens stripped, :345) -- `None` entries are pairs for which no
-    beam emitted <end> (the reference records no caption for them, :326-328)."""
+    beam emitted <end> (the reference records no caption for them, :326-328).
+    `eval_batch` (default `args.eval_batch`, 1): N > 1 runs the encoder on N pairs at once and captions them in one
+    device-resident search (`CaptionDecoder.beam_search_batch`); 1 is the per-pair loop below, unchanged."""
     model.eval()
     hyps = []
+    n = int(eval_batch if eval_batch is not None else getattr(args, "eval_batch", 1))
+    if n > 1:
+        pairs = list(pairs)
+        for i in range(0, len(pairs), n):
+            pre = torch.cat([p[0] for p in pairs[i:i + n]])
+            post = torch.cat([p[1] for p in pairs[i:i + n]])
+            memory = encode_memory(model, pre, post)
+            for best, _, _ in model.decoder.beam_search_batch(memory, start_id, end_id, args.beam_size):
+                hyps.append(None if best is None else [w for w in best if w not in (start_id, end_id, pad_id)])
+        return hyps
     for pre, post in pairs:
         feat = model.update_cc(pre, post)                                       # (1, 192, H/16, W/16)
         B, C, H, W = feat.shape
@@ -96,6 +120,8 @@ def main():
     p.add_argument("--max_steps", type=int, default=100)
     p.add_argument("--beam_size", type=int, default=1, help="reference default (scripts/train_CC.py:600)")
     p.add_argument("--eval_pairs", type=int, default=0, help="caption this many synthetic pairs after training")
+    p.add_argument("--eval_batch", type=int, default=1,
+                   help="pairs captioned per device-resident batched beam search; 1: the reference's one-pair-at-a-time loop")
     p.add_argument("--act_dtype", choices=["bf16", "f32"], default="bf16")
     args = p.parse_args()
     if "CC" not in args.dataset:

@@ -713,6 +713,58 @@ int c3d_cap_ce_bwd(const void* logits, const int64_t* caps, const int64_t* decle
  * limit <= 0 or NaN is C3D_E_BADARG.                                                                               */
 int c3d_clamp_(float* g, int64_t n, float limit, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Batched beam search of the captioning evaluation (reference scripts/train_CC.py:214-330, the loop inside `evaluate()`,
+ * with the decoder arithmetic of model/caption_decoder.py:316-423 / :526-613 in evaluation mode): one workgroup per image
+ * pair runs the whole search -- incremental decoding over a key/value cache, log-softmax, top-k and all beam bookkeeping on
+ * the device, no host synchronisation, no wait on another workgroup.  Semantics of the reference loop, kept: at step 1 only
+ * hypothesis 0 is expanded; a hypothesis leaves the beam when it emits end_id and the beam shrinks; the loop ends when the
+ * beam is empty or after step max_len - 1; completed hypotheses are recorded in rank order within a step; the winner is the
+ * FIRST maximum of the completed scores (-1: no hypothesis completed, no caption); scores accumulate in f32.  Equal
+ * candidate scores are ordered by the lower flat index hypothesis * V + word (torch.topk documents no order).
+ * ------------------------------------------------------------------------------------ */
+#define C3D_CAP_BEAM_MAX 8      /* hypotheses per pair */
+#define C3D_CAP_BEAM_LAYERS 8   /* decoder layers */
+typedef struct c3d_cap_beam_layer {
+  const float *sa_in_w, *sa_in_b;   /* self_attn.in_proj_weight [3D][D], in_proj_bias [3D] */
+  const float *sa_out_w, *sa_out_b; /* self_attn.out_proj [D][D], [D] */
+  const float *n1_g, *n1_b;         /* norm1 */
+  const float *ca_q_w, *ca_q_b;     /* multihead_attn2.in_proj_weight[:D] [D][D], in_proj_bias[:D] */
+  const float *ca_out_w, *ca_out_b; /* multihead_attn2.out_proj */
+  const float *n2_g, *n2_b;         /* norm2 */
+  const void* kv;                   /* projected memory of ALL pairs, rows (s*B + b) of [K | V] = 2D elements of `dtype`:
+                                     * indexed by pair, shared by the pair's hypotheses */
+} c3d_cap_beam_layer;
+typedef struct c3d_cap_beam_args {
+  int32_t B, S, D, H, n_layer, V, beam, max_len, start_id, end_id, dtype;
+  float ln_eps;
+  const float *emb, *pe;            /* vocab_embedding.weight [V][D]; position table [>= max_len][D] */
+  const float *wdc_w, *wdc_b;       /* vocabulary projection [V][D], [V] */
+  c3d_cap_beam_layer layers[C3D_CAP_BEAM_LAYERS];
+  void* ws;                         /* c3d_cap_beam_plan's ws_bytes: the self-attention key/value cache */
+  /* results, per pair: completed hypotheses in the order they completed */
+  int32_t* comp_seq;                /* [B][beam][max_len + 1], start token first; the caller zeroes it */
+  int32_t* comp_len;                /* [B][beam] */
+  float* comp_score;                /* [B][beam] */
+  int32_t* meta;                    /* [B][4]: completed count, winner index or -1, steps decoded, live count at the end */
+  /* optional (NULL: off).  trace [B][max_len-1][1 + 3*beam] int32, zeroed by the caller: per step the live count before the
+   * step, then per selected candidate in rank order (parent, word, score as f32 bits).
+   * Test surface: forced [B][max_len-1][beam][2] int32 = (parent, word) taken INSTEAD of the top-k (teacher forcing; scores
+   * are still the candidates'); logits_out f32 [B][max_len-1][beam][V]: the vocabulary logits of every expanded hypothesis. */
+  int32_t* trace;
+  const int32_t* forced;
+  float* logits_out;
+} c3d_cap_beam_args;
+/* The limits, host only (no runtime call): 0 and the workspace / dynamic-LDS bytes of a search over B pairs, or
+ * C3D_E_UNSUPPORTED (nothing may be launched): beam <= 8, n_layer <= 8, D a multiple of 8 and <= 256, head width D/H <= 32,
+ * max_len <= 64, and an LDS plan (hidden rows, k x V f32 logits, one probability row of max(S, max_len) per wave) within
+ * 160 KB -- at D = 192, V = 501: S <= 3000 for every beam.                                                         */
+int c3d_cap_beam_plan(int32_t S, int32_t D, int32_t H, int32_t n_layer, int32_t V, int32_t beam, int32_t max_len,
+                      int32_t dtype, int64_t B, int64_t* ws_bytes, int64_t* lds_bytes);
+/* Replaces the per-pair host loop of reference scripts/train_CC.py:248-330 (one decoder pass over the whole 52-token window
+ * per step, torch topk, host bookkeeping).  One launch on `stream`; C3D_E_UNSUPPORTED exactly where the plan says so. */
+int c3d_cap_beam_search(const c3d_cap_beam_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
