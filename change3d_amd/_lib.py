@@ -126,6 +126,9 @@ SIGNATURES = {
     "c3d_enhance_apply": (i32, [vp, vp, vp, i32, i32, i64, i32, i32, i32, vp]),
     "c3d_enhance_bwd_mask": (i32, [vp, vp, vp, i32, i32, i64, i32, i32, i32, vp]),
     "c3d_enhance_bwd_apply": (i32, [vp, vp, vp, vp, i32, i32, i64, i32, i32, i32, i32, vp]),
+    "c3d_stem_enhance_fwd": (i32, [vp, vp, vp, vp, i32, i32, i64, i32, i32, i32, i32, i32, vp]),
+    "c3d_stem_enhance_mid": (i32, [vp, vp, vp, vp, i32, i32, i64, i32, i32, i32, vp]),
+    "c3d_stem_enhance_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, i32, i32, i32, i32, vp]),
     "c3d_frame_scatter": (i32, [vp, vp, i32, i32, i64, i32, i32, i32, i32, vp]),
     "c3d_stem_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "c3d_stem_bwd_dv": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -250,6 +250,192 @@ __global__ void enhance_bwd_apply_kernel(const T* __restrict__ dout, const T* __
   }
 }
 
+// ---- stem output + enhance without the stem's y ----------------------------------------------------------------
+// The stem has no shortcut, so y = relu(bn(u)) is a pure function of u and the 2 x Cp scale|shift vector: the three
+// kernels below recompute it on load (rounded to T exactly as block_out_fwd_kernel stores it) instead of reading a
+// materialised y, and the backward one also forms dy = enhance-backward(dout) on load instead of reading a stored dy.
+// Threads keep a fixed channel vector (blockDim and hwv are multiples of G), as block_out_* do.
+template <typename T>
+__device__ __forceinline__ void stem_y(const float (&uv)[8], const float (&a)[8], const float (&b)[8], float (&y)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) y[j] = round_as<T>(fmaxf(fmaf(uv[j], a[j], b[j]), 0.f));
+}
+
+__device__ __forceinline__ void load_rows8(const float* __restrict__ p, float (&f)[8]) {
+  const float4 x = *reinterpret_cast<const float4*>(p), y = *reinterpret_cast<const float4*>(p + 4);
+  f[0] = x.x; f[1] = x.y; f[2] = x.z; f[3] = x.w; f[4] = y.x; f[5] = y.y; f[6] = y.z; f[7] = y.w;
+}
+
+// forward, every frame but t_mid: out[:, t] = y[:, t];  d = |y[:, t_pre] - y[:, t_post]|   (d dense [B*HW][Cp])
+template <typename T>
+__global__ __launch_bounds__(256) void stem_enhance_fwd_kernel(const T* __restrict__ u, const float* __restrict__ ss,
+                                                               T* __restrict__ out, T* __restrict__ d, int64_t nvec,
+                                                               int64_t hwv, int G, int Tn, int t_pre, int t_post,
+                                                               int t_mid) {
+  const int v = threadIdx.x % G;
+  float a[8], b[8];
+  load_rows8(ss + v * 8, a);
+  load_rows8(ss + G * 8 + v * 8, b);
+  typedef typename Vec8<T>::raw_t raw_t;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    const int64_t bb = i / hwv, r = i - bb * hwv;
+    const int64_t base = bb * Tn * hwv + r;
+    const raw_t rp = Vec8<T>::load_raw(u + (base + t_pre * hwv) * 8);
+    const raw_t rq = Vec8<T>::load_raw(u + (base + t_post * hwv) * 8);
+    float f[8], p[8], q[8];
+    Vec8<T>::cvt_raw(rp, f);
+    stem_y<T>(f, a, b, p);
+    Vec8<T>::store(out + (base + t_pre * hwv) * 8, p);
+    Vec8<T>::cvt_raw(rq, f);
+    stem_y<T>(f, a, b, q);
+    Vec8<T>::store(out + (base + t_post * hwv) * 8, q);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = fabsf(p[j] - q[j]);
+    Vec8<T>::store(d + i * 8, p);
+    for (int t = 0; t < Tn; ++t) {   // the perception frames other than t_mid (none for T = 3)
+      if (t == t_pre || t == t_post || t == t_mid) continue;
+      Vec8<T>::load(u + (base + t * hwv) * 8, f);
+      stem_y<T>(f, a, b, q);
+      Vec8<T>::store(out + (base + t * hwv) * 8, q);
+    }
+  }
+}
+
+// forward, frame t_mid: out[:, t_mid] = y[:, t_mid] + relu(e)      (e dense [B*HW][Cp]; the add in f32 on the rounded y)
+template <typename T>
+__global__ __launch_bounds__(256) void stem_enhance_mid_kernel(const T* __restrict__ u, const float* __restrict__ ss,
+                                                               const T* __restrict__ e, T* __restrict__ out,
+                                                               int64_t nvec, int64_t hwv, int G, int Tn, int t_mid) {
+  const int v = threadIdx.x % G;
+  float a[8], b[8];
+  load_rows8(ss + v * 8, a);
+  load_rows8(ss + G * 8 + v * 8, b);
+  typedef typename Vec8<T>::raw_t raw_t;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    const int64_t bb = i / hwv, r = i - bb * hwv;
+    const int64_t row = (bb * Tn + t_mid) * hwv + r;
+    const raw_t ru = Vec8<T>::load_raw(u + row * 8);
+    const raw_t re = Vec8<T>::load_raw(e + i * 8);
+    float f[8], y[8], ev[8];
+    Vec8<T>::cvt_raw(ru, f);
+    Vec8<T>::cvt_raw(re, ev);
+    stem_y<T>(f, a, b, y);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] += fmaxf(ev[j], 0.f);
+    Vec8<T>::store(out + row * 8, y);
+  }
+}
+
+// backward: block_out_bwd_kernel<T, false> without a shortcut, with its dy and y operands produced on load:
+//   y  = relu(bn(u)) rounded to T;   dy = dout, and on frames t_pre / t_post dout +- sign(y_pre - y_post) * dd in f32
+//   rounded to T (the value enhance_bwd_apply_kernel stored);   g = dy * (y > 0);   dsums += (sum g, sum g*uhat).
+// Same grid, grid-stride order, BOB_U batching, f32 per-thread partials and f64 reduction as that kernel: a thread adds
+// the same terms in the same order.  The row -> (sample, frame, offset) split is carried along the walk (one division
+// per thread, not one per row).
+template <typename T>
+__global__ __launch_bounds__(256) void stem_enhance_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ c,
+                                                               const float* __restrict__ ss, const T* __restrict__ dd,
+                                                               T* __restrict__ g, const float* __restrict__ mr_c,
+                                                               double* __restrict__ dsums_c, int64_t nvec, int64_t hwv,
+                                                               int G, int C, int Tn, int t_pre, int t_post) {
+  extern __shared__ float red[];  // [blockDim][24]
+  const int v = threadIdx.x % G;
+  const int Cp = G * 8;
+  float s1[8], s2[8];
+  float mc[8], rc[8], a[8], b[8];
+  load_rows8(mr_c + v * 8, mc);
+  load_rows8(mr_c + Cp + v * 8, rc);
+  load_rows8(ss + v * 8, a);
+  load_rows8(ss + Cp + v * 8, b);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t other = (int64_t)(t_post - t_pre) * hwv;   // row distance from a t_pre row to its t_post partner
+  constexpr int BOB_U = 4;
+  typedef typename Vec8<T>::raw_t raw_t;
+  // cursor of the next row this thread visits: sample cb, frame ct, offset cr inside the frame
+  int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t cb, cr;
+  int ct;
+  {
+    const int64_t bt = ci / hwv;
+    cr = ci - bt * hwv;
+    cb = bt / Tn;
+    ct = (int)(bt - cb * Tn);
+  }
+  for (int64_t i0 = ci; i0 < nvec; i0 += BOB_U * stride) {
+    raw_t rd[BOB_U], rc_[BOB_U], ro[BOB_U], rdd[BOB_U];
+    int side[BOB_U];   // 0: untouched frame, +1: t_pre row, -1: t_post row
+#pragma unroll
+    for (int u = 0; u < BOB_U; ++u) {
+      const int64_t i = i0 + u * stride;
+      side[u] = 0;
+      if (i < nvec) {
+        rd[u] = Vec8<T>::load_raw(dout + i * 8);
+        rc_[u] = Vec8<T>::load_raw(c + i * 8);
+        side[u] = (ct == t_pre) ? 1 : ((ct == t_post) ? -1 : 0);
+        if (side[u]) {
+          ro[u] = Vec8<T>::load_raw(c + (i + side[u] * other) * 8);
+          rdd[u] = Vec8<T>::load_raw(dd + (cb * hwv + cr) * 8);
+        }
+        cr += stride;
+        while (cr >= hwv) {
+          cr -= hwv;
+          if (++ct == Tn) { ct = 0; ++cb; }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < BOB_U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i < nvec) {
+        float d[8], yv[8], cv[8];
+        Vec8<T>::cvt_raw(rd[u], d);
+        Vec8<T>::cvt_raw(rc_[u], cv);
+        stem_y<T>(cv, a, b, yv);
+        if (side[u]) {
+          float ov[8], yo[8], dv[8];
+          Vec8<T>::cvt_raw(ro[u], ov);
+          Vec8<T>::cvt_raw(rdd[u], dv);
+          stem_y<T>(ov, a, b, yo);
+          const float sgn_self = (side[u] > 0) ? 1.f : -1.f;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float df = (side[u] > 0) ? (yv[j] - yo[j]) : (yo[j] - yv[j]);   // y_pre - y_post
+            const float sg = (df > 0.f) ? 1.f : ((df < 0.f) ? -1.f : 0.f);
+            d[j] = round_as<T>(d[j] + sgn_self * sg * dv[j]);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float gg = (yv[j] > 0.f) ? d[j] : 0.f;
+          d[j] = gg;
+          s1[j] += gg; s2[j] += gg * ((cv[j] - mc[j]) * rc[j]);
+        }
+        Vec8<T>::store(g + i * 8, d);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    red[threadIdx.x * 24 + j] = s1[j]; red[threadIdx.x * 24 + 8 + j] = s2[j]; red[threadIdx.x * 24 + 16 + j] = 0.f;
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < G * 24; idx += blockDim.x) {
+    const int vv = idx / 24, k = idx % 24;
+    double acc = 0;
+    for (int t = vv; t < (int)blockDim.x; t += G) acc += red[t * 24 + k];
+    const int ch = vv * 8 + (k & 7);
+    const int which = k >> 3;
+    if (ch < C) {
+      if (which == 0) atomicAdd(dsums_c + ch, acc);
+      else if (which == 1) atomicAdd(dsums_c + C + ch, acc);
+    }
+  }
+}
+
 // Generic helpers ------------------------------------------------------------------------------
 // dst[b, t, p, :] (frame of an NDHWC tensor) += / = src dense [B*HW][Cp]
 template <typename T>
@@ -422,6 +608,76 @@ extern "C" int c3d_enhance_bwd_apply(const void* dout, const void* y, const void
               (enhance_bwd_apply_kernel<bf16_t><<<ew_grid(nvec, 256), 256, 0, s>>>(
                   (const bf16_t*)dout, (const bf16_t*)y, (const bf16_t*)dd, (bf16_t*)dy, nvec, hwv, T, t_pre,
                   t_post)));
+  C3D_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- stem output + enhance (no materialised y / dy): see the kernels above --------------------------------------
+namespace {
+inline bool stem_enhance_geom_ok(int32_t B, int32_t T, int64_t HW, int32_t Cp, int32_t t_pre, int32_t t_post, int32_t t_mid) {
+  if (B <= 0 || T < 3 || HW <= 0 || Cp <= 0 || (Cp & 7) || Cp > 256) return false;
+  if (t_pre < 0 || t_pre >= T || t_post < 0 || t_post >= T || t_mid < 0 || t_mid >= T) return false;
+  return t_pre != t_post && t_mid != t_pre && t_mid != t_post;
+}
+}  // namespace
+
+extern "C" int c3d_stem_enhance_fwd(const void* u, const float* ss, void* out, void* d, int32_t B, int32_t T, int64_t HW,
+                                    int32_t Cp, int32_t t_pre, int32_t t_post, int32_t t_mid, int32_t dtype, void* stream) {
+  if (!u || !ss || !out || !d || !stem_enhance_geom_ok(B, T, HW, Cp, t_pre, t_post, t_mid)) return C3D_E_BADARG;
+  if ((uintptr_t)ss & 15) return C3D_E_BADARG;   // scale | shift rows are read as 16-byte vectors
+  const int G = Cp / 8, blk = ew_block(G);
+  const int64_t hwv = HW * G, nvec = (int64_t)B * hwv;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EW_DISPATCH(dtype,
+              (stem_enhance_fwd_kernel<float><<<ew_grid(nvec, blk), blk, 0, s>>>(
+                  (const float*)u, ss, (float*)out, (float*)d, nvec, hwv, G, T, t_pre, t_post, t_mid)),
+              (stem_enhance_fwd_kernel<bf16_t><<<ew_grid(nvec, blk), blk, 0, s>>>(
+                  (const bf16_t*)u, ss, (bf16_t*)out, (bf16_t*)d, nvec, hwv, G, T, t_pre, t_post, t_mid)));
+  C3D_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int c3d_stem_enhance_mid(const void* u, const float* ss, const void* e, void* out, int32_t B, int32_t T,
+                                    int64_t HW, int32_t Cp, int32_t t_mid, int32_t dtype, void* stream) {
+  if (!u || !ss || !e || !out || B <= 0 || T <= 0 || HW <= 0 || Cp <= 0 || (Cp & 7) || Cp > 256 || t_mid < 0 || t_mid >= T)
+    return C3D_E_BADARG;
+  if ((uintptr_t)ss & 15) return C3D_E_BADARG;
+  const int G = Cp / 8, blk = ew_block(G);
+  const int64_t hwv = HW * G, nvec = (int64_t)B * hwv;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EW_DISPATCH(dtype,
+              (stem_enhance_mid_kernel<float><<<ew_grid(nvec, blk), blk, 0, s>>>(
+                  (const float*)u, ss, (const float*)e, (float*)out, nvec, hwv, G, T, t_mid)),
+              (stem_enhance_mid_kernel<bf16_t><<<ew_grid(nvec, blk), blk, 0, s>>>(
+                  (const bf16_t*)u, ss, (const bf16_t*)e, (bf16_t*)out, nvec, hwv, G, T, t_mid)));
+  C3D_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int c3d_stem_enhance_bwd(const void* dout, const void* u, const float* ss, const void* dd, const float* mr,
+                                    void* g, double* dsums, int32_t B, int32_t T, int64_t HW, int32_t C, int32_t Cp,
+                                    int32_t t_pre, int32_t t_post, int32_t dtype, void* stream) {
+  if (!dout || !u || !ss || !dd || !mr || !g || !dsums || C <= 0 || C > Cp) return C3D_E_BADARG;
+  if (B <= 0 || T < 2 || HW <= 0 || (Cp & 7) || Cp > 256 || t_pre < 0 || t_pre >= T || t_post < 0 || t_post >= T ||
+      t_pre == t_post)
+    return C3D_E_BADARG;
+  if (((uintptr_t)ss & 15) || ((uintptr_t)mr & 15)) return C3D_E_BADARG;
+  const int G = Cp / 8, blk = ew_block(G);
+  const int64_t hwv = HW * G, nvec = (int64_t)B * T * hwv;
+  // block_out_bwd's grid (its cap and its tuning knob): the walk, and with it every thread's sum, is that kernel's
+  int grid = ew_grid(nvec, blk);
+  static const int env_cap = c3d_env("C3D_BOB_GRID") ? atoi(c3d_env("C3D_BOB_GRID")) : 0;
+  const int cap = env_cap > 0 ? env_cap : 384;
+  if (grid > cap) grid = cap;
+  const size_t lds = (size_t)blk * 24 * sizeof(float);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  EW_DISPATCH(dtype,
+              (stem_enhance_bwd_kernel<float><<<grid, blk, lds, s>>>((const float*)dout, (const float*)u, ss,
+                                                                      (const float*)dd, (float*)g, mr, dsums, nvec, hwv, G,
+                                                                      C, T, t_pre, t_post)),
+              (stem_enhance_bwd_kernel<bf16_t><<<grid, blk, lds, s>>>((const bf16_t*)dout, (const bf16_t*)u, ss,
+                                                                       (const bf16_t*)dd, (bf16_t*)g, mr, dsums, nvec, hwv,
+                                                                       G, C, T, t_pre, t_post)));
   C3D_CHECK_LAUNCH();
   return 0;
 }

@@ -14,7 +14,7 @@ from .. import ops
 from ..ops import cpad
 from .change_decoder import ChangeDecoder
 from .utils import weight_init
-from .x3d import _ClipStemFn, create_x3d, to_logical, to_ndhwc
+from .x3d import _ClipStemFn, _stem_backward_convs, _stem_forward_convs, create_x3d, to_logical, to_ndhwc
 
 
 class _EnhanceFn(torch.autograd.Function):
@@ -58,6 +58,64 @@ class _EnhanceFn(torch.autograd.Function):
         dx = torch.empty_like(xc)
         ops.enhance_bwd_apply(doc, xc, dd, dx, B, T, H * W, cpad(C), 0, t_post, dt)
         return to_logical(dx), None, None
+
+
+class _ClipStemEnhanceFn(torch.autograd.Function):
+    """`enhance(stem(clip), fc[0])` as ONE function (`_ClipStemFn` followed by `_EnhanceFn`, same values bit for bit)
+    that never stores the stem's y = relu(bn(u)) nor the gradient dy between the two: the stem has no shortcut, so the
+    enhance kernels recompute y from u and the scale/shift vector on load (`c3d_stem_enhance_fwd/_mid`), and one
+    backward kernel forms dy from dout on load and produces g = dy * (y > 0) with the BatchNorm-backward sums
+    (`c3d_stem_enhance_bwd`).  The 24 x 24 GEMMs between them are the launches `_EnhanceFn` makes."""
+
+    @staticmethod
+    def forward(ctx, pre, post, frames, anchor, stem, weight, t_post):
+        ops.require_gpu(pre, "encoder input")
+        B, Ci, H, W = pre.shape
+        K = frames.shape[2]
+        if Ci != 3 or tuple(frames.shape) != (1, 3, K, H, W) or tuple(post.shape) != tuple(pre.shape):
+            raise NotImplementedError("clip assembly expects (B,3,H,W) images and (1,3,K,H,W) perception frames")
+        T = K + 2
+        clip = torch.empty((B, 3, T, H, W), dtype=torch.float32, device=pre.device)
+        ops.build_clip(pre.detach().contiguous().float(), post.detach().contiguous().float(),
+                       frames.detach().contiguous().float(), clip, B, K, H, W)
+        act, dt = stem.act_dtype, ops.dt_code(stem.act_dtype)
+        u, ss, mr = _stem_forward_convs(clip, stem)
+        C = u.shape[-1]
+        t_mid, M2 = T // 2, B * H * W
+        out = torch.empty_like(u)
+        d = torch.empty((M2, cpad(C)), dtype=act, device=u.device)
+        ops.stem_enhance_fwd(u, ss, out, d, B, T, H * W, cpad(C), 0, t_post, t_mid, dt)
+        e = torch.empty_like(d)
+        ops.pw_gemm(d, weight, e, M=M2, K=C, N=C, w_sn=C, w_sk=1, dtype=dt)
+        ops.stem_enhance_mid(u, ss, e, out, B, T, H * W, cpad(C), t_mid, dt)
+        ctx.stem, ctx.frames, ctx.K, ctx.x_needs_grad = stem, frames, K, False
+        ctx.need_frames = ctx.needs_input_grad[2]
+        ctx.saved = (clip, u, ss, mr, d, e, weight)
+        ctx.meta = (t_post, t_mid)
+        return to_logical(out)
+
+    @staticmethod
+    def backward(ctx, dout):
+        clip, u, ss, mr, d, e, weight = ctx.saved
+        t_post, t_mid = ctx.meta
+        B, T, H, W, C = u.shape
+        act, dt = u.dtype, ops.dt_code(u.dtype)
+        doc = to_ndhwc(dout).to(act)
+        M2 = B * H * W
+        de = torch.empty_like(d)
+        ops.enhance_bwd_mask(doc, e, de, B, T, H * W, cpad(C), t_mid, dt)
+        dd = torch.empty_like(d)
+        ops.pw_gemm(de, weight, dd, M=M2, K=C, N=C, w_sn=1, w_sk=C, dtype=dt)
+        gw = ops.grad_of(weight)
+        ops.side_run(lambda: ops.pw_wgrad(de, d, gw, M=M2, K=C, N=C, dw_sn=C, dw_sk=1, dtype=dt), de, d)
+        g = torch.empty_like(u)
+        dsums = torch.zeros(2 * C, dtype=torch.float64, device=u.device)
+        ops.stem_enhance_bwd(doc, u, ss, dd, mr, g, dsums, B, T, H * W, C, 0, t_post, dt)
+        gp = None
+        if ctx.need_frames:
+            gp = torch.zeros(ctx.frames.shape, dtype=torch.float32, device=dout.device)
+        _stem_backward_convs(ctx, clip, u, mr, g, dsums, (gp, 1, ctx.K) if gp is not None else None)
+        return None, None, gp, None, None, None, None
 
 
 def _ndhwc_storage(t):
@@ -150,8 +208,9 @@ class Encoder(nn.Module):
     def enhance(self, x: torch.Tensor, fc: nn.Module) -> torch.Tensor:
         return _EnhanceFn.apply(x, fc[0].weight, self.args.num_perception_frame + 1)
 
-    def base_forward(self, x: torch.Tensor, output_final: bool = False, _stem_out=None):
-        """`_stem_out`: blocks[0] already applied (the fused clip + stem path of `forward`)."""
+    def base_forward(self, x: torch.Tensor, output_final: bool = False, _stem_out=None, _stem_enhanced=False):
+        """`_stem_out`: blocks[0] already applied (the fused clip + stem path of `forward`); `_stem_enhanced`: and
+        `enhance(., fc[0])` as well (`_ClipStemEnhanceFn`)."""
         if output_final:
             for i in range(5):
                 x = _stem_out if (i == 0 and _stem_out is not None) else self.x3d.blocks[i](x)
@@ -159,17 +218,27 @@ class Encoder(nn.Module):
         out = []
         for i in range(4):
             x = _stem_out if (i == 0 and _stem_out is not None) else self.x3d.blocks[i](x)
-            x = self.enhance(x, self.fc[i])
+            if not (i == 0 and _stem_out is not None and _stem_enhanced):
+                x = self.enhance(x, self.fc[i])
             x, frames = tap_frames(x, 1, self.args.num_perception_frame)
             out.append(frames)
         return out
 
+    def _clip_stem_ok(self, x: torch.Tensor, y: torch.Tensor) -> bool:
+        """Whether clip assembly and blocks[0] can run as one function (`_ClipStemFn` / `_ClipStemEnhanceFn`)."""
+        return (x.is_cuda and not x.requires_grad and not y.requires_grad and x.dim() == 4 and x.shape[1] == 3
+                and (x.shape[2] * x.shape[3]) % 4 == 0 and tuple(x.shape[2:]) == tuple(self.perception_frames.shape[3:]))
+
     def forward(self, x: torch.Tensor, y: torch.Tensor, output_final: bool = False):
         stem = self.x3d.blocks[0]
-        if (x.is_cuda and not x.requires_grad and not y.requires_grad and x.dim() == 4 and x.shape[1] == 3
-                and (x.shape[2] * x.shape[3]) % 4 == 0 and tuple(x.shape[2:]) == tuple(self.perception_frames.shape[3:])):
+        if self._clip_stem_ok(x, y):
             # torch.cat([x, perception_frames.expand(B), y], dim=2) + blocks[0] as one function: HIP clip assembly,
             # batch-summed perception-frame gradient written by the stem's own backward kernel
+            if ops.STEM_ENHANCE and not output_final:
+                # ... and enhance(., fc[0]) too, without the stem's y = relu(bn(u)) ever stored
+                s0 = _ClipStemEnhanceFn.apply(x, y, self.perception_frames, stem.norm.weight, stem, self.fc[0][0].weight,
+                                              self.args.num_perception_frame + 1)
+                return self.base_forward(None, output_final, _stem_out=s0, _stem_enhanced=True)
             s0 = _ClipStemFn.apply(x, y, self.perception_frames, stem.norm.weight, stem)
             return self.base_forward(None, output_final, _stem_out=s0)
         expand = self.perception_frames.expand(x.shape[0], -1, -1, -1, -1)

@@ -66,7 +66,8 @@ def _f32(n, dev):
 
 
 # ---------------------------------------------------------------------------------- stem
-def _stem_forward(ctx, xin, stem):
+def _stem_forward_convs(xin, stem):
+    """The stem up to its BatchNorm statistics: u = conv_xy(conv_t(x)) and the scale|shift, mean|rstd vectors."""
     B, Ci, T, H, W = xin.shape
     dev, dt = xin.device, ops.dt_code(stem.act_dtype)
     training = stem.training
@@ -77,6 +78,14 @@ def _stem_forward(ctx, xin, stem):
     ops.stem_fwd(xin, conv_s.weight, conv_t.weight, u, sums, B, T, H, W, dt)
     ss, mr = _f32(2 * cpad(C), dev), _f32(2 * cpad(C), dev)
     ops.bn_finalize(sums, B * T * H * W, stem.norm, C, ss, mr, training)
+    return u, ss, mr
+
+
+def _stem_forward(ctx, xin, stem):
+    B, Ci, T, H, W = xin.shape
+    dt = ops.dt_code(stem.act_dtype)
+    C = stem.conv.conv_t.weight.shape[0]
+    u, ss, mr = _stem_forward_convs(xin, stem)
     y = torch.empty_like(u)
     ops.block_out_fwd(u, ss, None, None, ops.SC_NONE, y, B * T * H * W, cpad(C), dt)
     ctx.stem, ctx.saved = stem, (xin, u, y, mr)
@@ -97,6 +106,17 @@ def _stem_backward(ctx, dy, frames_grad=None):
     g = torch.empty_like(u)
     dsums = torch.zeros(2 * C, dtype=torch.float64, device=dev)
     ops.block_out_bwd(dyc, y, u, None, g, mr, None, dsums, None, M, C, dt)
+    return _stem_backward_convs(ctx, xin, u, mr, g, dsums, frames_grad)
+
+
+def _stem_backward_convs(ctx, xin, u, mr, g, dsums, frames_grad=None):
+    """The stem's backward below its BatchNorm + ReLU: `g` = dy * (y > 0) and its BatchNorm-backward sums `dsums`."""
+    stem = ctx.stem
+    B, _, T, H, W = xin.shape
+    dev, dt = xin.device, ops.dt_code(stem.act_dtype)
+    conv_s, conv_t = stem.conv.conv_t, stem.conv.conv_xy
+    C = conv_s.weight.shape[0]
+    M = B * T * H * W
     coef = _f32(3 * cpad(C), dev)
     ops.bn_bwd_coef(dsums, M, stem.norm, mr, C, coef)
     dv = torch.empty_like(u)

@@ -459,6 +459,31 @@ def enhance_bwd_apply(dout, y, dd, dy, B, T, HW, Cp, t_pre, t_post, dtype):
                                           _stream())
 
 
+# C3D_STEM_ENHANCE=0: level 0 of the encoder runs block_out_fwd + _EnhanceFn (a stored y and dy) instead of the
+# stem_enhance_* kernels below (model/trainer.py::_ClipStemEnhanceFn); same results either way
+STEM_ENHANCE = os.environ.get("C3D_STEM_ENHANCE", "1") != "0"
+
+
+def stem_enhance_fwd(u, ss, out, d, B, T, HW, Cp, t_pre, t_post, t_mid, dtype):
+    """out[:, t] = relu(bn(u))[:, t] for t != t_mid and d = |y[:, t_pre] - y[:, t_post]| (billed: T-1 frames read,
+    T-1 frames + d written)."""
+    _launch("c3d_stem_enhance_fwd", B * HW * Cp * (2 * T - 1) * _es(dtype), L.lib().c3d_stem_enhance_fwd, _p(u), _p(ss), _p(out), _p(d),
+            B, T, HW, Cp, t_pre, t_post, t_mid, dtype, _stream())
+
+
+def stem_enhance_mid(u, ss, e, out, B, T, HW, Cp, t_mid, dtype):
+    """out[:, t_mid] = relu(bn(u))[:, t_mid] + relu(e)."""
+    _launch("c3d_stem_enhance_mid", B * HW * Cp * 3 * _es(dtype), L.lib().c3d_stem_enhance_mid, _p(u), _p(ss), _p(e), _p(out),
+            B, T, HW, Cp, t_mid, dtype, _stream())
+
+
+def stem_enhance_bwd(dout, u, ss, dd, mr, g, dsums, B, T, HW, C_, t_pre, t_post, dtype):
+    """g, dsums of block_out_bwd(enhance_bwd_apply(dout, y, dd), y, u) with y recomputed from (u, ss) (billed: dout, u
+    read and g written once, dd once; the partner-frame rows of u are read a second time)."""
+    _launch("c3d_stem_enhance_bwd", B * HW * cpad(C_) * (3 * T + 1) * _es(dtype), L.lib().c3d_stem_enhance_bwd, _p(dout), _p(u), _p(ss),
+            _p(dd), _p(mr), _p(g), _p(dsums), B, T, HW, C_, cpad(C_), t_pre, t_post, dtype, _stream())
+
+
 def frame_scatter(src, dst, B, T, HW, Cp, t_dst, accumulate, dtype):
     """dst[:, t_dst] (+)= src for channels-last src [B][HW][Cp], dst [B][T][HW][Cp]."""
     _launch("c3d_frame_scatter", B * HW * Cp * (3 if accumulate else 2) * _es(dtype), L.lib().c3d_frame_scatter, _p(src), _p(dst), B, T, HW, Cp,

@@ -328,6 +328,20 @@ int c3d_enhance_bwd_mask(const void* dout, const void* e, void* de, int32_t B, i
 int c3d_enhance_bwd_apply(const void* dout, const void* y, const void* dd, void* dy, int32_t B, int32_t T,
                           int64_t HW, int32_t Cp, int32_t t_pre, int32_t t_post, int32_t dtype,
                           void* stream);
+/* Stem output + enhance without a materialised y = relu(bn(u)) (the stem has no shortcut: y is recomputed on load from
+ * u and ss = scale[Cp] | shift[Cp], rounded to the storage type exactly as c3d_block_out_fwd stores it).
+ *   c3d_stem_enhance_fwd : out[:, t] = y[:, t] for every t != t_mid;  d = |y[:, t_pre] - y[:, t_post]|  (dense [B*HW][Cp])
+ *   c3d_stem_enhance_mid : out[:, t_mid] = y[:, t_mid] + relu(e)                 (after c3d_pw_gemm(d -> e))
+ *   c3d_stem_enhance_bwd : c3d_block_out_bwd (no shortcut) on dy = c3d_enhance_bwd_apply(dout, y, dd), neither y nor dy
+ *                          stored: g = dy * (y > 0), dsums[2][C] += (sum g, sum g * (u - mean) * rstd); mr = mean | rstd.
+ * Results are bit-identical to the c3d_block_out_fwd / c3d_frame_absdiff / c3d_enhance_* / c3d_block_out_bwd sequence. */
+int c3d_stem_enhance_fwd(const void* u, const float* ss, void* out, void* d, int32_t B, int32_t T, int64_t HW,
+                         int32_t Cp, int32_t t_pre, int32_t t_post, int32_t t_mid, int32_t dtype, void* stream);
+int c3d_stem_enhance_mid(const void* u, const float* ss, const void* e, void* out, int32_t B, int32_t T, int64_t HW,
+                         int32_t Cp, int32_t t_mid, int32_t dtype, void* stream);
+int c3d_stem_enhance_bwd(const void* dout, const void* u, const float* ss, const void* dd, const float* mr, void* g,
+                         double* dsums, int32_t B, int32_t T, int64_t HW, int32_t C, int32_t Cp, int32_t t_pre,
+                         int32_t t_post, int32_t dtype, void* stream);
 int c3d_frame_scatter(const void* src, void* dst, int32_t B, int32_t T, int64_t HW, int32_t Cp,
                       int32_t t_dst, int32_t accumulate, int32_t dtype, void* stream);
 
