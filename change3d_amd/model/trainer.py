@@ -14,7 +14,30 @@ from .. import ops
 from ..ops import cpad
 from .change_decoder import ChangeDecoder
 from .utils import weight_init
-from .x3d import _ClipStemFn, _stem_backward_convs, _stem_forward_convs, create_x3d, to_logical, to_ndhwc
+from .x3d import (_assemble_clip, _ClipStemFn, _frames_grad, _stem_backward_convs, _stem_forward_convs, create_x3d,
+                  to_logical, to_ndhwc)
+
+
+def _enhance_conv(d, weight, C, dt):
+    """The 1x1 conv of enhance, forward: e = d @ weight^T (its ReLU is applied by the consumer of e)."""
+    e = torch.empty_like(d)
+    ops.pw_gemm(d, weight, e, M=d.shape[0], K=C, N=C, w_sn=C, w_sk=1, dtype=dt)
+    return e
+
+
+def _enhance_conv_backward(doc, d, e, weight):
+    """... and backward, from the gradient `doc` [B,T,H,W,C] of enhance's output: de = doc[:, T//2] * (e > 0), the
+    weight gradient on the side stream, and the returned dd = de @ weight."""
+    B, T, H, W, C = doc.shape
+    dt = ops.dt_code(doc.dtype)
+    M2 = B * H * W
+    de = torch.empty_like(d)
+    ops.enhance_bwd_mask(doc, e, de, B, T, H * W, cpad(C), T // 2, dt)
+    dd = torch.empty_like(d)
+    ops.pw_gemm(de, weight, dd, M=M2, K=C, N=C, w_sn=1, w_sk=C, dtype=dt)
+    gw = ops.grad_of(weight)
+    ops.side_run(lambda: ops.pw_wgrad(de, d, gw, M=M2, K=C, N=C, dw_sn=C, dw_sk=1, dtype=dt), de, d)
+    return dd
 
 
 class _EnhanceFn(torch.autograd.Function):
@@ -33,30 +56,21 @@ class _EnhanceFn(torch.autograd.Function):
         M2 = B * H * W
         d = torch.empty((M2, cpad(C)), dtype=act, device=dev)
         ops.frame_absdiff(xc, d, B, T, H * W, cpad(C), 0, t_post, dt)
-        e = torch.empty_like(d)
-        ops.pw_gemm(d, weight, e, M=M2, K=C, N=C, w_sn=C, w_sk=1, dtype=dt)
+        e = _enhance_conv(d, weight, C, dt)
         out = torch.empty_like(xc)
         ops.enhance_apply(xc, e, out, B, T, H * W, cpad(C), t_mid, dt)
         ctx.saved = (xc, d, e, weight)
-        ctx.meta = (B, C, T, H, W, t_post, t_mid)
+        ctx.t_post = t_post
         return to_logical(out)
 
     @staticmethod
     def backward(ctx, dout):
         xc, d, e, weight = ctx.saved
-        B, C, T, H, W, t_post, t_mid = ctx.meta
-        act = xc.dtype
-        dt = ops.dt_code(act)
-        doc = to_ndhwc(dout).to(act)
-        M2 = B * H * W
-        de = torch.empty_like(d)
-        ops.enhance_bwd_mask(doc, e, de, B, T, H * W, cpad(C), t_mid, dt)
-        dd = torch.empty_like(d)
-        ops.pw_gemm(de, weight, dd, M=M2, K=C, N=C, w_sn=1, w_sk=C, dtype=dt)
-        gw = ops.grad_of(weight)
-        ops.side_run(lambda: ops.pw_wgrad(de, d, gw, M=M2, K=C, N=C, dw_sn=C, dw_sk=1, dtype=dt), de, d)
+        B, T, H, W, C = xc.shape
+        doc = to_ndhwc(dout).to(xc.dtype)
+        dd = _enhance_conv_backward(doc, d, e, weight)
         dx = torch.empty_like(xc)
-        ops.enhance_bwd_apply(doc, xc, dd, dx, B, T, H * W, cpad(C), 0, t_post, dt)
+        ops.enhance_bwd_apply(doc, xc, dd, dx, B, T, H * W, cpad(C), 0, ctx.t_post, ops.dt_code(xc.dtype))
         return to_logical(dx), None, None
 
 
@@ -69,52 +83,30 @@ class _ClipStemEnhanceFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pre, post, frames, anchor, stem, weight, t_post):
-        ops.require_gpu(pre, "encoder input")
-        B, Ci, H, W = pre.shape
-        K = frames.shape[2]
-        if Ci != 3 or tuple(frames.shape) != (1, 3, K, H, W) or tuple(post.shape) != tuple(pre.shape):
-            raise NotImplementedError("clip assembly expects (B,3,H,W) images and (1,3,K,H,W) perception frames")
-        T = K + 2
-        clip = torch.empty((B, 3, T, H, W), dtype=torch.float32, device=pre.device)
-        ops.build_clip(pre.detach().contiguous().float(), post.detach().contiguous().float(),
-                       frames.detach().contiguous().float(), clip, B, K, H, W)
-        act, dt = stem.act_dtype, ops.dt_code(stem.act_dtype)
+        clip = _assemble_clip(ctx, pre, post, frames)
+        dt = ops.dt_code(stem.act_dtype)
         u, ss, mr = _stem_forward_convs(clip, stem)
-        C = u.shape[-1]
-        t_mid, M2 = T // 2, B * H * W
+        B, T, H, W, C = u.shape
         out = torch.empty_like(u)
-        d = torch.empty((M2, cpad(C)), dtype=act, device=u.device)
-        ops.stem_enhance_fwd(u, ss, out, d, B, T, H * W, cpad(C), 0, t_post, t_mid, dt)
-        e = torch.empty_like(d)
-        ops.pw_gemm(d, weight, e, M=M2, K=C, N=C, w_sn=C, w_sk=1, dtype=dt)
-        ops.stem_enhance_mid(u, ss, e, out, B, T, H * W, cpad(C), t_mid, dt)
-        ctx.stem, ctx.frames, ctx.K, ctx.x_needs_grad = stem, frames, K, False
-        ctx.need_frames = ctx.needs_input_grad[2]
+        d = torch.empty((B * H * W, cpad(C)), dtype=stem.act_dtype, device=u.device)
+        ops.stem_enhance_fwd(u, ss, out, d, B, T, H * W, cpad(C), 0, t_post, T // 2, dt)
+        e = _enhance_conv(d, weight, C, dt)
+        ops.stem_enhance_mid(u, ss, e, out, B, T, H * W, cpad(C), T // 2, dt)
+        ctx.stem, ctx.t_post = stem, t_post
         ctx.saved = (clip, u, ss, mr, d, e, weight)
-        ctx.meta = (t_post, t_mid)
         return to_logical(out)
 
     @staticmethod
     def backward(ctx, dout):
         clip, u, ss, mr, d, e, weight = ctx.saved
-        t_post, t_mid = ctx.meta
         B, T, H, W, C = u.shape
-        act, dt = u.dtype, ops.dt_code(u.dtype)
-        doc = to_ndhwc(dout).to(act)
-        M2 = B * H * W
-        de = torch.empty_like(d)
-        ops.enhance_bwd_mask(doc, e, de, B, T, H * W, cpad(C), t_mid, dt)
-        dd = torch.empty_like(d)
-        ops.pw_gemm(de, weight, dd, M=M2, K=C, N=C, w_sn=1, w_sk=C, dtype=dt)
-        gw = ops.grad_of(weight)
-        ops.side_run(lambda: ops.pw_wgrad(de, d, gw, M=M2, K=C, N=C, dw_sn=C, dw_sk=1, dtype=dt), de, d)
+        doc = to_ndhwc(dout).to(u.dtype)
+        dd = _enhance_conv_backward(doc, d, e, weight)
         g = torch.empty_like(u)
         dsums = torch.zeros(2 * C, dtype=torch.float64, device=u.device)
-        ops.stem_enhance_bwd(doc, u, ss, dd, mr, g, dsums, B, T, H * W, C, 0, t_post, dt)
-        gp = None
-        if ctx.need_frames:
-            gp = torch.zeros(ctx.frames.shape, dtype=torch.float32, device=dout.device)
-        _stem_backward_convs(ctx, clip, u, mr, g, dsums, (gp, 1, ctx.K) if gp is not None else None)
+        ops.stem_enhance_bwd(doc, u, ss, dd, mr, g, dsums, B, T, H * W, C, 0, ctx.t_post, ops.dt_code(u.dtype))
+        gp, frames_grad = _frames_grad(ctx, dout.device)
+        _stem_backward_convs(ctx, clip, u, mr, g, dsums, frames_grad)
         return None, None, gp, None, None, None, None
 
 
@@ -208,21 +200,22 @@ class Encoder(nn.Module):
     def enhance(self, x: torch.Tensor, fc: nn.Module) -> torch.Tensor:
         return _EnhanceFn.apply(x, fc[0].weight, self.args.num_perception_frame + 1)
 
-    def base_forward(self, x: torch.Tensor, output_final: bool = False, _stem_out=None, _stem_enhanced=False):
-        """`_stem_out`: blocks[0] already applied (the fused clip + stem path of `forward`); `_stem_enhanced`: and
-        `enhance(., fc[0])` as well (`_ClipStemEnhanceFn`)."""
-        if output_final:
-            for i in range(5):
-                x = _stem_out if (i == 0 and _stem_out is not None) else self.x3d.blocks[i](x)
-            return x[:, :, self.args.num_perception_frame]
+    def base_forward(self, x: torch.Tensor, output_final: bool = False, *, _level0=None):
+        """`_level0` = (value, enhanced): level 0 as the fused clip + stem path of `forward` computed it -- blocks[0]
+        applied to the clip, and whether `enhance(., fc[0])` is in it as well (`_ClipStemEnhanceFn`)."""
+        x, enhanced = _level0 if _level0 is not None else (self.x3d.blocks[0](x), False)
+        assert not (output_final and enhanced)
         out = []
-        for i in range(4):
-            x = _stem_out if (i == 0 and _stem_out is not None) else self.x3d.blocks[i](x)
-            if not (i == 0 and _stem_out is not None and _stem_enhanced):
+        for i in range(5 if output_final else 4):
+            if i > 0:
+                x, enhanced = self.x3d.blocks[i](x), False
+            if output_final:   # X3D blocks 0..4 only: no enhancement, no taps
+                continue
+            if not enhanced:
                 x = self.enhance(x, self.fc[i])
             x, frames = tap_frames(x, 1, self.args.num_perception_frame)
             out.append(frames)
-        return out
+        return x[:, :, self.args.num_perception_frame] if output_final else out
 
     def _clip_stem_ok(self, x: torch.Tensor, y: torch.Tensor) -> bool:
         """Whether clip assembly and blocks[0] can run as one function (`_ClipStemFn` / `_ClipStemEnhanceFn`)."""
@@ -238,9 +231,9 @@ class Encoder(nn.Module):
                 # ... and enhance(., fc[0]) too, without the stem's y = relu(bn(u)) ever stored
                 s0 = _ClipStemEnhanceFn.apply(x, y, self.perception_frames, stem.norm.weight, stem, self.fc[0][0].weight,
                                               self.args.num_perception_frame + 1)
-                return self.base_forward(None, output_final, _stem_out=s0, _stem_enhanced=True)
+                return self.base_forward(None, output_final, _level0=(s0, True))
             s0 = _ClipStemFn.apply(x, y, self.perception_frames, stem.norm.weight, stem)
-            return self.base_forward(None, output_final, _stem_out=s0)
+            return self.base_forward(None, output_final, _level0=(s0, False))
         expand = self.perception_frames.expand(x.shape[0], -1, -1, -1, -1)
         frames = torch.cat([x.unsqueeze(2), expand, y.unsqueeze(2)], dim=2)
         return self.base_forward(frames, output_final)

@@ -134,6 +134,31 @@ def _stem_backward_convs(ctx, xin, u, mr, g, dsums, frames_grad=None):
     return dx
 
 
+def _assemble_clip(ctx, pre, post, frames):
+    """cat([pre, frames.expand(B), post], dim=2) by a HIP copy kernel, for the functions whose inputs are (pre, post,
+    frames, ...); leaves on `ctx` what `_frames_grad` and `_stem_backward_convs` read."""
+    ops.require_gpu(pre, "encoder input")
+    B, Ci, H, W = pre.shape
+    K = frames.shape[2]
+    if Ci != 3 or tuple(frames.shape) != (1, 3, K, H, W) or tuple(post.shape) != tuple(pre.shape):
+        raise NotImplementedError("clip assembly expects (B,3,H,W) images and (1,3,K,H,W) perception frames")
+    clip = torch.empty((B, 3, K + 2, H, W), dtype=torch.float32, device=pre.device)
+    ops.build_clip(pre.detach().contiguous().float(), post.detach().contiguous().float(),
+                   frames.detach().contiguous().float(), clip, B, K, H, W)
+    ctx.frames, ctx.K, ctx.x_needs_grad = frames, K, False
+    ctx.need_frames = ctx.needs_input_grad[2]
+    return clip
+
+
+def _frames_grad(ctx, dev):
+    """(gp, frames_grad): the zeroed gradient buffer of the perception frames (None when they need no gradient) and the
+    `frames_grad` argument that makes the stem's backward accumulate into it."""
+    if not ctx.need_frames:
+        return None, None
+    gp = torch.zeros(ctx.frames.shape, dtype=torch.float32, device=dev)
+    return gp, (gp, 1, ctx.K)
+
+
 class _StemFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, anchor, stem):
@@ -156,24 +181,12 @@ class _ClipStemFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pre, post, frames, anchor, stem):
-        ops.require_gpu(pre, "encoder input")
-        B, Ci, H, W = pre.shape
-        K = frames.shape[2]
-        if Ci != 3 or tuple(frames.shape) != (1, 3, K, H, W) or tuple(post.shape) != tuple(pre.shape):
-            raise NotImplementedError("clip assembly expects (B,3,H,W) images and (1,3,K,H,W) perception frames")
-        clip = torch.empty((B, 3, K + 2, H, W), dtype=torch.float32, device=pre.device)
-        ops.build_clip(pre.detach().contiguous().float(), post.detach().contiguous().float(),
-                       frames.detach().contiguous().float(), clip, B, K, H, W)
-        ctx.frames, ctx.K, ctx.x_needs_grad = frames, K, False
-        ctx.need_frames = ctx.needs_input_grad[2]
-        return _stem_forward(ctx, clip, stem)
+        return _stem_forward(ctx, _assemble_clip(ctx, pre, post, frames), stem)
 
     @staticmethod
     def backward(ctx, dy):
-        gp = None
-        if ctx.need_frames:
-            gp = torch.zeros(ctx.frames.shape, dtype=torch.float32, device=dy.device)
-        _stem_backward(ctx, dy, (gp, 1, ctx.K) if gp is not None else None)
+        gp, frames_grad = _frames_grad(ctx, dy.device)
+        _stem_backward(ctx, dy, frames_grad)
         return None, None, gp, None, None
 
 
@@ -533,23 +546,15 @@ def stage_saved_activations(y):
     if fn is None or not hasattr(fn, "stage"):
         raise ValueError("not the output of a residual stage evaluated with grad enabled")
     out = []
-    if hasattr(fn, "saved_ws"):   # C++ stage driver: views into the forward workspace
-        bind, ws, act = fn.stage.binding(), fn.saved_ws, fn.stage.act_dtype
-        for i, blk in enumerate(fn.stage.res_blocks):
-            rec = dict(C_a=blk.cinner, C_b=blk.cinner, C_c=blk.cout, C_sc=blk.cout)
-            for name, cp in (("a", cpad(blk.cinner)), ("b", cpad(blk.cinner)), ("c", cpad(blk.cout)), ("sc", cpad(blk.cout))):
-                if name == "sc" and blk.branch1_norm is None:
-                    continue
-                off, n = bind.saved(i, name)
-                rec[name] = ws[off:off + n].view(act).view(-1, cp)
-                off, n = bind.saved(i, "mr_" + name)
-                rec["mr_" + name] = ws[off:off + n].view(torch.float32)
-            out.append(rec)
-        return out
-    for blk, sv in zip(fn.stage.res_blocks, fn.saved):
-        rec = dict(a=sv["a"], b=sv["b"], c=sv["c"], mr_a=sv["mr_a"], mr_b=sv["mr_b"], mr_c=sv["mr_c"],
-                   C_a=blk.cinner, C_b=blk.cinner, C_c=blk.cout)
-        if sv["mr_1"] is not None:
-            rec.update(sc=sv["sc"], mr_sc=sv["mr_1"], C_sc=blk.cout)
+    bind, ws, act = fn.stage.binding(), fn.saved_ws, fn.stage.act_dtype   # views into the forward workspace
+    for i, blk in enumerate(fn.stage.res_blocks):
+        rec = dict(C_a=blk.cinner, C_b=blk.cinner, C_c=blk.cout, C_sc=blk.cout)
+        for name, cp in (("a", cpad(blk.cinner)), ("b", cpad(blk.cinner)), ("c", cpad(blk.cout)), ("sc", cpad(blk.cout))):
+            if name == "sc" and blk.branch1_norm is None:
+                continue
+            off, n = bind.saved(i, name)
+            rec[name] = ws[off:off + n].view(act).view(-1, cp)
+            off, n = bind.saved(i, "mr_" + name)
+            rec["mr_" + name] = ws[off:off + n].view(torch.float32)
         out.append(rec)
     return out
