@@ -182,6 +182,7 @@ SIGNATURES = {
     "c3d_stage_fwd_folded": (i32, [C.POINTER(StageDesc), vp, vp, vp, vp, vp]),
     "c3d_stage_saved": (i32, [C.POINTER(StageDesc), i32, C.c_char_p, C.POINTER(i64), C.POINTER(i64)]),
     "c3d_last_kernel": (C.c_char_p, []),
+    "c3d_launch_count": (i64, []),
 }
 
 _lib = None

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(SE_THREADS) void bn_se_finalize_kernel(
   // channel slice [c_lo, c_hi) of everything that is written (running statistics, scale/shift, gate)
   const int cs = (Cp + (int)gridDim.x - 1) / (int)gridDim.x;
   const int c_lo = (int)blockIdx.x * cs, c_hi = c_lo + cs < Cp ? c_lo + cs : Cp;
-  if (tid == 0 && blockIdx.x == 0 && training && nbt) *nbt += 1;
+  if (tid == 0 && blockIdx.x == 0 && training == 1 && nbt) *nbt += 1;   // (training == 2 is the folded EVAL forward)
   // 4 lanes per channel split the batch loop (latency, not bandwidth, is what this kernel costs, so
   // every serial loop is spread over adjacent lanes)
   for (int idx = tid; idx < Cp * 4; idx += blockDim.x) {

@@ -138,6 +138,7 @@ inline int c3d_knob(const char* name, int dflt) {
 // a dispatcher that answers C3D_E_UNSUPPORTED falls through to another kernel without telling its caller, so a test asks
 // afterwards (c3d_last_kernel) to know what it compared.
 inline thread_local const void* c3d_last_launch = nullptr;
+inline thread_local int64_t c3d_launches = 0;   // launches of this thread through c3d_launch_lds (c3d_launch_count)
 
 template <auto Kernel, class... Args>
 int c3d_launch_lds(const dim3 grid, const dim3 block, const size_t lds, hipStream_t stream, const Args&... args) {
@@ -145,6 +146,7 @@ int c3d_launch_lds(const dim3 grid, const dim3 block, const size_t lds, hipStrea
       hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (raised != hipSuccess) return (int)raised;
   c3d_last_launch = reinterpret_cast<const void*>(Kernel);
+  ++c3d_launches;
   Kernel<<<grid, block, lds, stream>>>(args...);
   return (int)hipGetLastError();
 }

@@ -58,6 +58,8 @@ extern "C" int c3d_set_option(int32_t option, int32_t value) {
   return rc;
 }
 
+extern "C" int64_t c3d_launch_count(void) { return c3d_launches; }
+
 // The runtime knows the mangled device name of every registered kernel by its host handle; demangled, that is
 // "void (anonymous namespace)::dw_fwd_v2_kernel<unsigned short, 3, true, true>(unsigned short const*, ...)" (bf16_t is unsigned
 // short): return type, namespace and parameter list are cut, the template arguments stay.

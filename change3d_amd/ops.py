@@ -148,6 +148,12 @@ def last_kernel():
     return L.lib().c3d_last_kernel().decode()
 
 
+def launch_count():
+    """Kernels this thread has launched through that launcher so far (c3d_launch_count): the difference around a call is 2
+    where c3d_pw_gemm answered it with a separate c3d_bn_se_finalize launch in front of the GEMM."""
+    return int(L.lib().c3d_launch_count())
+
+
 def side_run(fn, *tensors):
     """Run `fn` (kernel launches) on the side stream after everything issued so far on the current
     stream.  Only inside an autograd backward pass (that is where the join callback can be queued: one

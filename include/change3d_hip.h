@@ -669,6 +669,10 @@ int c3d_stage_saved(const c3d_stage_desc* d, int32_t blk, const char* name, int6
  * apply, and this is how a test knows which one it measured.  The string belongs to the calling thread and is valid until
  * its next call.                                                                                                     */
 const char* c3d_last_kernel(void);
+/* how many kernels the calling thread has launched through that launcher so far.  c3d_pw_gemm may answer one call with two
+ * of them (a workgroup's rows span more samples than its in-kernel SE gate holds: c3d_bn_se_finalize, then the GEMM), and
+ * the name above is the GEMM's either way; the difference of this count around a call tells the two apart.  Host-only. */
+int64_t c3d_launch_count(void);
 
 /* ------------------------------------------------------------------------------------
  * Caption decoder of the change-captioning path (reference model/caption_decoder.py:526-613 CaptionDecoder, :316-423

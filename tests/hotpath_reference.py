@@ -2,7 +2,8 @@
 cooperative pointwise forward GEMMs, the pointwise data gradients and the weight-gradient operand forms): plain torch on
 the CPU, nothing imported from the package, the oracle or the reference tree.  tests/test_hotpath_reference_cpu.py pins
 every function here against torch.autograd through F.conv3d / F.batch_norm in float64; tests/test_hotpath_bf16_gpu.py
-compares the kernels with them.
+compares the kernels with them, tests/test_bn_se_gpu.py the BatchNorm / SqueezeExcitation finalize and coefficient kernels
+(se_case / se_bn_bwd at the end of this file).
 
 Conventions.  Activations are the bf16-quantised values the device gets, as float64, in the repository's channels-last
 layouts ([T,H,W,C] per sample for the depthwise functions, [rows, C] for the pointwise ones) WITHOUT padding channels;
@@ -327,3 +328,106 @@ def conv_c_dgrad(g, c, coef, w, b_rows, scale, shift, gate_row=None, eps=2.0 ** 
 def wgrad(P, Q):
     """c3d_pw_wgrad: dW [N][K] = P^T Q over the rows, with its magnitude sum."""
     return P.t() @ Q, P.abs().t() @ Q.abs()
+
+
+# ------------------------------------------------------------------------------------------------ BatchNorm_b / SE backward
+# The middle of a residual block, from its definition: pb = bn_b(b) (batch statistics over all B * R rows), z = the mean of pb
+# over a sample's rows, hid = relu(W1 z + b1), gate = sigmoid(W2 hid + b2), q = gate pb, Swish(q) goes on to conv_c.  With d
+# the gradient at the Swish output, conv_c's data-gradient epilogue leaves dq = d swish'(q), t1 = dq gate and, per (sample,
+# channel), nc3 = (sum dq pb [the gradient at the gate], sum t1, sum t1 bhat), bhat = (b - mean) rstd; the depthwise forward
+# left ncf = (sum b, sum b^2).  c3d_se_bn_bwd_coef (csrc/bn_se.hip) turns those O(B C) numbers into the SE parameter gradients
+# and into db = A t1 + B[n] + C b, the gradient at b, applied on operand load by the depthwise backward.
+def se_case(B, R, C, Cr, seed, se=True, eps=1e-5):
+    """A small block middle in float64: b [B][R][C] (conv_b output), d (gradient at the Swish output), gamma, beta and the four
+    SE tensors (se = (w1 [Cr][C], b1, w2 [C][Cr], b2); parameters are f32-representable, as the device gets them), and -- from
+    the definition above, nothing taken from the kernels -- ncf [B][C][2], nc3 [B][C][3], mean, rstd, scale, shift, gate [B][C],
+    hid [B][Cr] and t1 [B][R][C].  se=False: a block without SqueezeExcitation (gate 1; se, gate and hid are None)."""
+    g = torch.Generator().manual_seed(seed)
+
+    def rn(shape, scale=1.0):
+        return (torch.randn(shape, generator=g, dtype=torch.float32) * scale).double()
+
+    def f32(t):
+        return t.float().double()
+
+    b = rn((B, R, C)) * (rn((C,)).abs() + 0.5) + rn((C,), 0.5) + rn((B, 1, C), 0.3)     # per-sample means differ: the gate does too
+    d = rn((B, R, C))
+    gamma, beta = f32(rn((C,)).abs() + 0.5), rn((C,), 0.3)
+    mean = b.mean((0, 1))
+    var = ((b - mean) ** 2).mean((0, 1))
+    rstd = 1.0 / torch.sqrt(var + eps)
+    scale = gamma * rstd
+    shift = beta - mean * scale
+    pb = (b - mean) * rstd * gamma + beta
+    out = dict(B=B, R=R, C=C, Cr=Cr, eps=eps, b=b, d=d, gamma=gamma, beta=beta, mean=mean, rstd=rstd, scale=scale, shift=shift,
+               ncf=torch.stack([b.sum(1), (b * b).sum(1)], 2), se=None, gate=None, hid=None)
+    gate_rows = torch.ones_like(pb)
+    if se:
+        w1, b1 = rn((Cr, C), 2.0 / C ** 0.5), rn((Cr,), 0.3)
+        w2, b2 = rn((C, Cr), 1.0 / Cr ** 0.5), rn((C,), 0.3)
+        hid = torch.relu(pb.mean(1) @ w1.t() + b1)
+        gate = torch.sigmoid(hid @ w2.t() + b2)
+        out.update(se=(w1, b1, w2, b2), gate=gate, hid=hid)
+        gate_rows = gate[:, None, :].expand_as(pb)
+    dq = d * swish_grad(gate_rows * pb)
+    t1 = dq * gate_rows
+    bhat = (b - mean) * rstd
+    out.update(t1=t1, nc3=torch.stack([(dq * pb).sum(1), t1.sum(1), (t1 * bhat).sum(1)], 2))
+    return out
+
+
+def se_bn_bwd(nc3, ncf, R, gamma, mean, rstd, scale, shift, se=None, gate=None, hid=None):
+    """SE backward + BatchNorm_b backward coefficients from the per-sample sums, every argument as the kernel gets it (float64 of
+    its f32 inputs): nc3 [B][C][3], ncf [B][C][2], R rows per sample, se = (w1, b1, w2, b2) or None, gate [B][C], hid [B][Cr].
+        du = nc3_0 gate (1 - gate)                 gradient at the gate's pre-activation
+        dh = (hid > 0) du W2                       hid is the SUPPLIED one: no mask can flip between device and reference
+        dz = dh W1                                 gradient at z, spread evenly over the sample's R rows of pb
+        dW2 = du^T hid, db2 = sum_n du, dW1 = dh^T z, db1 = sum_n dh,  z = scale ncf_0 / R + shift
+        s1 = sum_n (nc3_1 + dz), s2 = sum_n (nc3_2 + dz / R * rstd (ncf_0 - R mean))       = (d beta, d gamma)
+        A = gamma rstd, C = -A rstd s2 / (B R), B[n] = A dz[n] / R - A s1 / (B R) - C mean
+    Returns a dict name -> (value, mag, err) for coefA [C], coefB [B][C], coefC [C], dgamma, dbeta, dw1 [Cr][C], db1, dw2 [C][Cr],
+    db2 (the SE gradients only with se): mag is the magnitude sum of the LAST sum in front of the value (what an eps per rounding
+    of that sum multiplies), err the absolute error its inputs bring along when the chain in front is done in f32 the way
+    csrc/bn_se.hip does it -- err(du) 4 u |du| (one conversion, 1 - gate, two products), err(z) 2 u (|scale m| + |shift|), err(dh)
+    through the ceil(C / 8)-step chains and their three-level tree, err(dz) through the Cr-step chain -- carried into coefB, s1, s2
+    the way conv_c_dgrad carries `err`.  Without se, coefB is the same for every sample."""
+    u = 1.001 * 2.0 ** -24        # (1.001: the second-order terms of chains of up to ~100 roundings)
+    B, C = nc3.shape[0], nc3.shape[1]
+    count = float(B) * R
+    zero = torch.zeros(B, C, dtype=nc3.dtype)
+    dz, dz_err = zero, zero
+    out = {}
+    if se is not None:
+        w1, _, w2, _ = se
+        Cr = w1.shape[0]
+        du = nc3[:, :, 0] * gate * (1 - gate)
+        du_err = 4 * u * du.abs()
+        m = ncf[:, :, 0] / R
+        z = scale * m + shift
+        z_mag = (scale * m).abs() + shift.abs()
+        z_err = 2 * u * z_mag
+        mask = (hid > 0).to(nc3.dtype)
+        dh = (du @ w2) * mask
+        dh_mag = (du.abs() @ w2.abs()) * mask
+        dh_err = ((C + 7) // 8 + 3) * u * dh_mag + (du_err @ w2.abs()) * mask
+        dz = dh @ w1
+        dz_mag = dh.abs() @ w1.abs()
+        dz_err = Cr * u * dz_mag + dh_err @ w1.abs()
+        out["dw2"] = (du.t() @ hid, du.abs().t() @ hid.abs(), du_err.t() @ hid.abs())
+        out["db2"] = (du.sum(0), du.abs().sum(0), du_err.sum(0))
+        out["dw1"] = (dh.t() @ z, dh.abs().t() @ z.abs(), dh_err.t() @ z.abs() + dh.abs().t() @ z_err)
+        out["db1"] = (dh.sum(0), dh.abs().sum(0), dh_err.sum(0))
+    sb = rstd * (ncf[:, :, 0] / R - mean)            # (sum of bhat over the sample's rows) / R
+    s1 = (nc3[:, :, 1] + dz).sum(0)
+    s1_mag, s1_err = (nc3[:, :, 1].abs() + dz.abs()).sum(0), dz_err.sum(0)
+    s2 = (nc3[:, :, 2] + dz * sb).sum(0)
+    s2_mag, s2_err = (nc3[:, :, 2].abs() + (dz * sb).abs()).sum(0), (dz_err * sb.abs()).sum(0)
+    A = gamma * rstd
+    k = A * rstd / count
+    Cc, Cc_mag, Cc_err = -k * s2, k.abs() * s2_mag, k.abs() * s2_err
+    Bn = A * dz / R - A * s1 / count - Cc * mean
+    Bn_mag = (A * dz / R).abs() + (A / count).abs() * s1_mag + Cc_mag * mean.abs()
+    Bn_err = A.abs() / R * dz_err + (A / count).abs() * s1_err + Cc_err * mean.abs()
+    out.update(coefA=(A, A.abs(), torch.zeros_like(A)), coefB=(Bn, Bn_mag, Bn_err), coefC=(Cc, Cc_mag, Cc_err),
+               dgamma=(s2, s2_mag, s2_err), dbeta=(s1, s1_mag, s1_err))
+    return out

@@ -188,3 +188,47 @@ def test_affine2_operand_is_batchnorm_backward():
     same(p, x.grad, "BatchNorm backward")
     assert (slack == 0).all()
     same(R.swish_grad(xd), torch.autograd.grad(F.silu(x).sum(), x)[0], "swish'")
+
+
+@pytest.mark.parametrize("se", [True, False])
+@pytest.mark.parametrize("B,rows,C,Cr", [(3, 16, 54, 8), (5, 48, 108, 8), (2, 16, 216, 16), (33, 16, 24, 8)])
+def test_se_and_batchnorm_b_backward_equal_autograd(B, rows, C, Cr, se):
+    """se_case / se_bn_bwd against autograd through the explicit block middle: bn_b (batch statistics) -> mean pool -> FC1 -> ReLU
+    -> FC2 -> sigmoid -> gate -> Swish.  db = A t1 + B[n] + C b is the gradient at b; the six parameter gradients are autograd's."""
+    k = R.se_case(B, rows, C, Cr, seed=60 + B, se=se)
+    b = k["b"].clone().requires_grad_(True)
+    gamma, beta = k["gamma"].clone().requires_grad_(True), k["beta"].clone().requires_grad_(True)
+    pb = F.batch_norm(b.view(B * rows, C), None, None, gamma, beta, training=True, eps=k["eps"]).view(B, rows, C)
+    params = [gamma, beta]
+    if se:
+        w1, b1, w2, b2 = (t.clone().requires_grad_(True) for t in k["se"])
+        params += [w1, b1, w2, b2]
+        hid = torch.relu(pb.mean(1) @ w1.t() + b1)
+        gate = torch.sigmoid(hid @ w2.t() + b2)
+        same(k["hid"], hid.detach(), "hid")
+        same(k["gate"], gate.detach(), "gate")
+        g2, h2, _ = R.se_gate(k["ncf"][:, :, 0], float(rows), k["scale"], k["shift"], *k["se"])
+        same(g2, gate.detach(), "se_gate from the per-sample sums")
+        same(h2, hid.detach(), "hid from the per-sample sums")
+        assert (k["hid"] > 0).any() and (k["hid"] == 0).any()        # both sides of the ReLU mask are exercised
+        y = F.silu(pb * gate[:, None, :])
+    else:
+        assert k["se"] is None and k["gate"] is None and k["hid"] is None
+        y = F.silu(pb)
+    y.backward(k["d"])
+    bn = R.bn_from_sums(k["ncf"][:, :, 0].sum(0), k["ncf"][:, :, 1].sum(0), float(B * rows), k["gamma"], k["beta"], k["eps"])
+    for name in ("scale", "shift", "mean", "rstd"):
+        same(bn[name], k[name], name)
+    r = R.se_bn_bwd(k["nc3"], k["ncf"], float(rows), k["gamma"], k["mean"], k["rstd"], k["scale"], k["shift"], k["se"], k["gate"], k["hid"])
+    db = r["coefA"][0] * k["t1"] + r["coefB"][0][:, None, :] + r["coefC"][0] * k["b"]
+    same(db, b.grad, "db = A t1 + B[n] + C b")
+    names = ["dgamma", "dbeta"] + (["dw1", "db1", "dw2", "db2"] if se else [])
+    assert set(r) == set(names) | {"coefA", "coefB", "coefC"}
+    for name, p in zip(names, params):
+        same(r[name][0], p.grad, name)
+    for name, (val, mag, err) in r.items():
+        assert val.shape == mag.shape == err.shape, name
+        assert (mag >= val.abs() * (1 - 1e-12)).all() and (err >= 0).all(), name
+        assert bool((err > 0).any()) == (se and name != "coefA"), name        # only the SE chain is f32 in front of these
+    if not se:
+        assert torch.equal(r["coefB"][0], r["coefB"][0][:1].expand(B, C))      # one B for every sample
