@@ -39,38 +39,9 @@ __device__ unsigned long long c3d_fb_clk[FCLK_WAVES][10];
 
 namespace {
 
-// C3D_FB_ROWS (build-time experiment, tools/experiments/): tile rows = waves per workgroup.  8 = the shipped geometry (8 x 8
-// pixels, 512 threads, one workgroup per CU); 4 = 4 x 8 pixels, 256 threads, two workgroups per CU out of phase.
-#ifndef C3D_FB_ROWS
-#define C3D_FB_ROWS 8
-#endif
-constexpr int FB_TH = C3D_FB_ROWS, FB_TW = 8, FB_DH = FB_TH + 2, FB_DW = FB_TW + 2, FB_NTHR = FB_TH * FB_TW * 8;
-#if C3D_FB_ROWS == 8
-#define FB_KATTR __launch_bounds__(FB_NTHR)
-#else
-#define FB_KATTR __launch_bounds__(FB_NTHR) __attribute__((amdgpu_waves_per_eu(2, 2)))   // 256 registers per wave: two workgroups per CU
-#endif
+// tile = 8 x 8 pixels (one row per wave), 512 threads, one workgroup per CU; staged with a one-pixel halo
+constexpr int FB_TH = 8, FB_TW = 8, FB_DH = FB_TH + 2, FB_DW = FB_TW + 2, FB_NTHR = FB_TH * FB_TW * 8;
 
-template <typename T> struct Raw8;
-template <> struct Raw8<bf16_t> {
-  typedef uint4 type;
-  static __device__ __forceinline__ type load(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
-  static __device__ __forceinline__ void cvt(const type& v, float (&f)[8]) {
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-  }
-};
-template <> struct Raw8<float> {
-  struct type { float4 a, b; };
-  static __device__ __forceinline__ type load(const float* p) {
-    type t; t.a = *reinterpret_cast<const float4*>(p); t.b = *reinterpret_cast<const float4*>(p + 4); return t;
-  }
-  static __device__ __forceinline__ void cvt(const type& v, float (&f)[8]) {
-    f[0] = v.a.x; f[1] = v.a.y; f[2] = v.a.z; f[3] = v.a.w; f[4] = v.b.x; f[5] = v.b.y; f[6] = v.b.z; f[7] = v.b.w;
-  }
-};
 // 4-channel half vectors: what a thread owns of a pixel
 template <typename T> struct Raw4;
 template <> struct Raw4<bf16_t> {
@@ -96,12 +67,6 @@ template <> struct Raw4<float> {
 __device__ __forceinline__ void lds4(const float* p, float (&f)[4]) {
   const float4 a = *reinterpret_cast<const float4*>(p);
   f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
-}
-
-__device__ __forceinline__ void lds8(const float* p, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
 }
 
 // empty asm that "modifies" the accumulators: their FMAs cannot be sunk below it, later LDS reads not hoisted above
@@ -268,8 +233,186 @@ __device__ __forceinline__ void fb_flush(void* scratch, const float (&S1)[4], co
   }
 }
 
+// ---- the pieces both kernels are made of, each written once.  File-scope macros over the kernels' arguments and locals (T, TT,
+// NI, SL, tid, g, wl, cf, ...), not forced-inline functions like fb_taps_s1 / fb_flush: each piece was tried as a function on
+// its own, and each one -- down to the zeroing of the sums -- changed the register allocation or the instruction count of
+// every kernel that used it (profiles/dw_refactor.txt has the figures).  As macros all 18 kernels are the code they were.
+
+// thread = [pixel][channel half][channel vector]: the 8 lanes of a pixel own its 32 channels, so the `a` rows they load and
+// the `t2` rows they store are 64 contiguous bytes per pixel (half-vector loads of one channel half per wave -- h = tid >> 8
+// until late round 4 -- were 8-byte pieces 16 B apart: twice the cache-line segments per instruction, and the stride-2
+// classes four times).  LDS: a 16-lane read group covers 4 pixels x 4 vectors of ONE half each -- the two half planes are
+// a multiple of 16 float4 apart, so the bank quad is the (pixel, vector) alone: conflict-free as before.
+// Then the workgroup: a tile is 8S x 8S input pixels.
+#define FB_DECODE(S)                                                                                                \
+  const int h = (tid >> 2) & 1;                           /* channel half of the vector */                          \
+  const int cv = tid & (DW_CV - 1);                                                                                 \
+  const int pix = tid >> 3;                                                                                         \
+  const int px = pix & (FB_TW - 1), py = pix >> 3;                                                                  \
+  DW_WG_DECODE((g.W + FB_TW * (S) - 1) / (FB_TW * (S)), (g.H + FB_TH * (S) - 1) / (FB_TH * (S)))                    \
+  const int cb8 = c0 + cv * 8;                            /* the 8-channel vector this thread stages */             \
+  const int cb4 = cb8 + h * 4;                            /* the 4 channels this thread owns */                     \
+  const bool c_ok = cb8 < g.Cp;                           /* (Cp is a multiple of 8: both halves exist or neither) */
+
+// wl <- the chunk's weights, cf <- its seven parameter rows.  With fin.sums the first three rows are the BatchNorm_b backward
+// coefficients of a block without SqueezeExcitation, rebuilt from the per-sample sums of the conv_c data gradient's epilogue
+// (csrc/bn_fin.h: no c3d_se_bn_bwd_coef launch in front of this kernel); the first workgroup of each channel chunk
+// accumulates d gamma / d beta
+#define FB_STAGE_PARAMS                                                                                             \
+  DW_STAGE_WEIGHTS(FB_NTHR)                                                                                         \
+  if (fin.sums) {                                                                                                   \
+    if (tid < 128) {                                                                                                \
+      float cA, cB, cC;                                                                                             \
+      c3dfin::bn_b_bwd_coef_nc(fin, g.C, g.Cp, c0 + (tid >> 2), tid & 3, co.group == 0, cA, cB, cC);                \
+      if ((tid & 3) == 0) { cf[tid >> 2] = cA; cf[32 + (tid >> 2)] = cB; cf[64 + (tid >> 2)] = cC; }                \
+    }                                                                                                               \
+  }                                                                                                                 \
+  for (int i = tid + (fin.sums ? 3 * 32 : 0); i < 7 * 32; i += FB_NTHR) {                                           \
+    const int k = i >> 5, c = c0 + (i & 31);                                                                        \
+    float v = 0.f;                                                                                                  \
+    if (c < g.Cp) {                                                                                                 \
+      v = k == 0 ? coefA[c] : k == 1 ? coefB[(size_t)b * g.Cp + c] : k == 2 ? coefC[c] : k == 3 ? ss_a[c]           \
+        : k == 4 ? ss_a[g.Cp + c] : k == 5 ? mr_a[c] : mr_a[g.Cp + c];                                              \
+    }                                                                                                               \
+    cf[i] = v;                                                                                                      \
+  }
+
+// BN_a-backward sums (sum t2, sum t2*ahat): f32 per thread over its walk (tiles_per_wg x T terms), f64 from the
+// cross-thread reduction on (the sums of the two terms nearly cancel on some channels: d gamma needs the digits);
+// dwa: weight-gradient partial sums of this thread's 4 channels, as register pairs (v_pk_fma_f32)
+#define FB_ZERO_SUMS                                                                                                \
+  float S1[4], S2[4];                                                                                               \
+  _Pragma("unroll") for (int j = 0; j < 4; ++j) { S1[j] = 0.f; S2[j] = 0.f; }                                       \
+  f32x2_t dwa[27][2];                                                                                               \
+  _Pragma("unroll") for (int k = 0; k < 27; ++k) { dwa[k][0] = f32x2_t{0.f, 0.f}; dwa[k][1] = f32x2_t{0.f, 0.f}; }
+
+// staging descriptors of this thread's vectors i = tid + 512 sl of a tile of NI, computed once: element offset relative to the
+// tile's db origin, (row, column) in the tile (0x7fff7fff: no source -> zero)
+#define FB_SLOTS                                                                                                    \
+  int rel[SL], yx[SL];                                                                                              \
+  _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                                               \
+    const int i_ = tid + sl * FB_NTHR;                                                                              \
+    const int p_ = i_ / DW_CV;                                                                                      \
+    const int ix_ = p_ % FB_DW, q_ = p_ / FB_DW;                                                                    \
+    const int iy_ = q_ % FB_DH, t_ = q_ / FB_DH;                                                                    \
+    const bool use_ = i_ < NI && c_ok && t_ < g.T;                                                                  \
+    rel[sl] = ((t_ * g.Ho + iy_) * g.Wo + ix_) * g.Cp + cb8;                                                        \
+    yx[sl] = use_ ? (iy_ | (ix_ << 16)) : 0x7fff7fff;                                                               \
+  }
+
+// db = A*t1 + B[n] + C*b of one 8-channel vector (raw rows V1, V2, read only when SRC; zero otherwise) as its two f32 half
+// vectors LO, HI.  The ring kernel converts in place: LO / HI are where V1 / V2 lie.
+#define FB_COEF                                                                                                     \
+  float cA[8], cB[8], cC[8];                                                                                        \
+  lds8(cf + 0 * 32 + cv * 8, cA);                                                                                   \
+  lds8(cf + 1 * 32 + cv * 8, cB);                                                                                   \
+  lds8(cf + 2 * 32 + cv * 8, cC);
+#define FB_DB8(SRC, V1, V2, LO, HI)                                                                                 \
+  {                                                                                                                 \
+    float f[8];                                                                                                     \
+    if (SRC) {                                                                                                      \
+      float f2[8];                                                                                                  \
+      Raw8<T>::cvt(V1, f);                                                                                          \
+      Raw8<T>::cvt(V2, f2);                                                                                         \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) f[j] = fmaf(cA[j], f[j], fmaf(cC[j], f2[j], cB[j]));            \
+    } else {                                                                                                        \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) f[j] = 0.f;                                                     \
+    }                                                                                                               \
+    LO = make_float4(f[0], f[1], f[2], f[3]);                                                                       \
+    HI = make_float4(f[4], f[5], f[6], f[7]);                                                                       \
+  }
+
+// one pixel of a thread: a_in = relu(bn_a(a)) for the weight gradient and the mask (zero for a pixel or frame that does not
+// exist), and the cleared data-gradient accumulators.  FETCH: what brings arc[t] in, where it is not there yet
+#define FB_AIN(FETCH)                                                                                               \
+  _Pragma("unroll") for (int t = 0; t < TT; ++t) {                                                                  \
+    if (p_ok && t < g.T) {                                                                                          \
+      FETCH                                                                                                         \
+      float av[4];                                                                                                  \
+      R4::cvt(arc[t], av);                                                                                          \
+      ain[t][0] = f32x2_t{fmaxf(fmaf(av[0], sa[0], sb[0]), 0.f), fmaxf(fmaf(av[1], sa[1], sb[1]), 0.f)};            \
+      ain[t][1] = f32x2_t{fmaxf(fmaf(av[2], sa[2], sb[2]), 0.f), fmaxf(fmaf(av[3], sa[3], sb[3]), 0.f)};            \
+    } else {                                                                                                        \
+      ain[t][0] = f32x2_t{0.f, 0.f}; ain[t][1] = f32x2_t{0.f, 0.f};                                                 \
+    }                                                                                                               \
+    acc[t][0] = f32x2_t{0.f, 0.f}; acc[t][1] = f32x2_t{0.f, 0.f};                                                   \
+  }
+
+// ---- 27 taps, stride 1, three frames: one LDS read feeds the data gradient (x weight) and the weight gradient (x a_in).
+// `tp`: the lowest-address tap (ky = kx = 2) as base, every other tap is a non-negative immediate offset of the ds_read.
+// Software pipeline over the nine (ky, kx) steps: the LDS reads of step s+1 are issued before the FMAs of step s (with two
+// waves per SIMD the ~130-clock LDS latency of a step was exposed nine times per tile); two fragment slots.
+#define FB_LOAD(S, SLOT)                                                                                          \
+  {                                                                                                               \
+    constexpr int ky_ = (S) / 3, kx_ = (S) % 3;                                                                   \
+    _Pragma("unroll") for (int kt = 0; kt < 3; ++kt)                                                             \
+      wq[SLOT][kt] = *reinterpret_cast<const float4*>(wl + (kt * 9 + (S)) * 32 + cv * 8 + h * 4);                \
+    _Pragma("unroll") for (int to = 0; to < TT; ++to)                                                            \
+      hq[SLOT][to] = tp[((to * FB_DH + (2 - ky_)) * FB_DW + (2 - kx_)) * DW_CV];                                 \
+  }
+#define FB_STEP(S, SLOT, HOOK)                                                                                    \
+  {                                                                                                               \
+    _Pragma("unroll") for (int to = 0; to < TT; ++to) {                                                          \
+      const f32x2_t v0 = {hq[SLOT][to].x, hq[SLOT][to].y}, v1 = {hq[SLOT][to].z, hq[SLOT][to].w};                 \
+      _Pragma("unroll") for (int kt = 0; kt < 3; ++kt) {                                                         \
+        const int ti = to + kt - 1;   /* in[ti] <-> out[to] through temporal tap kt */                            \
+        if (ti >= 0 && ti < TT) {                                                                                 \
+          const f32x2_t w0 = {wq[SLOT][kt].x, wq[SLOT][kt].y}, w1 = {wq[SLOT][kt].z, wq[SLOT][kt].w};             \
+          acc[ti][0] = __builtin_elementwise_fma(v0, w0, acc[ti][0]);                                             \
+          acc[ti][1] = __builtin_elementwise_fma(v1, w1, acc[ti][1]);                                             \
+          dwa[kt * 9 + (S)][0] = __builtin_elementwise_fma(v0, ain[ti][0], dwa[kt * 9 + (S)][0]);                 \
+          dwa[kt * 9 + (S)][1] = __builtin_elementwise_fma(v1, ain[ti][1], dwa[kt * 9 + (S)][1]);                 \
+        }                                                                                                         \
+      }                                                                                                           \
+    }                                                                                                             \
+    /* pin the schedule: the data-gradient accumulators are only consumed under `p_ok` in the epilogue and the   \
+       weight-gradient sums at the end of the walk, so the compiler sinks their FMAs and keeps the LDS reads of  \
+       ALL nine steps live until then (216 registers, spills) */                                                  \
+    pin_acc<TT>(acc);                                                                                             \
+    pin_dw(dwa[(S)], dwa[9 + (S)], dwa[18 + (S)]);                                                                \
+    HOOK(S)                                                                                                       \
+  }
+// the walk; HOOK(step) follows every step: nothing in the register-prefetch kernel, a request of the ring kernel (SPREAD)
+#define FB_WALK9(HOOK)                                                                                              \
+  {                                                                                                                 \
+    float4 wq[2][3], hq[2][TT];                                                                                     \
+    FB_LOAD(0, 0)                                                                                                   \
+    FB_LOAD(1, 1) FB_STEP(0, 0, HOOK)                                                                               \
+    FB_LOAD(2, 0) FB_STEP(1, 1, HOOK)                                                                               \
+    FB_LOAD(3, 1) FB_STEP(2, 0, HOOK)                                                                               \
+    FB_LOAD(4, 0) FB_STEP(3, 1, HOOK)                                                                               \
+    FB_LOAD(5, 1) FB_STEP(4, 0, HOOK)                                                                               \
+    FB_LOAD(6, 0) FB_STEP(5, 1, HOOK)                                                                               \
+    FB_LOAD(7, 1) FB_STEP(6, 0, HOOK)                                                                               \
+    FB_LOAD(8, 0) FB_STEP(7, 1, HOOK)                                                                               \
+    FB_STEP(8, 0, HOOK)                                                                                             \
+  }
+#define FB_NO_HOOK(STEP)
+
+// ---- mask, store t2, BN_a-backward sums of this thread's pixel of parity class (CY, CX) in the tile at (y0, x0); `orel` is
+// the lane's offset in the tile, `ofr` the frame stride.  Stride 1 (and so the ring kernel) has class (0, 0) only
+#define FB_EPI(CY, CX)                                                                                            \
+  if (p_ok) {                                                                                                     \
+    float ma[4], ra[4];                                                                                           \
+    lds4(cf + 5 * 32 + cv * 8 + h * 4, ma);                                                                       \
+    lds4(cf + 6 * 32 + cv * 8 + h * 4, ra);                                                                       \
+    T* ob = t2 + ((((int64_t)b * g.T) * g.H + y0 + (CY)) * g.W + x0 + (CX)) * g.Cp;                               \
+    _Pragma("unroll") for (int t = 0; t < TT; ++t) {                                                             \
+      if (t < g.T) {                                                                                              \
+        float av[4], o[4];                                                                                        \
+        R4::cvt(arc[t], av);                                                                                      \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                          \
+          const float d = round_as<T>(ain[t][j >> 1][j & 1] > 0.f ? acc[t][j >> 1][j & 1] : 0.f);                 \
+          o[j] = d;                                                                                               \
+          S1[j] += d; S2[j] += d * ((av[j] - ma[j]) * ra[j]);                                                     \
+        }                                                                                                         \
+        R4::store(ob + (orel + t * ofr), o);                                                                      \
+      }                                                                                                           \
+    }                                                                                                             \
+  }
+
 template <typename T, int TT, int S>
-__global__ FB_KATTR void dw_bwd_fused_kernel(
+__global__ __launch_bounds__(FB_NTHR) void dw_bwd_fused_kernel(
     const T* __restrict__ t1, const T* __restrict__ bb, const float* __restrict__ coefA,
     const float* __restrict__ coefB, const float* __restrict__ coefC, const float* __restrict__ w,
     const T* __restrict__ a, const float* __restrict__ ss_a, const float* __restrict__ mr_a, T* __restrict__ t2,
@@ -285,75 +428,14 @@ __global__ FB_KATTR void dw_bwd_fused_kernel(
 
   const int tid = threadIdx.x;
   FCLK_DECL
-  // thread = [pixel][channel half][channel vector]: the 8 lanes of a pixel own its 32 channels, so the `a` rows they load and
-  // the `t2` rows they store are 64 contiguous bytes per pixel (half-vector loads of one channel half per wave -- h = tid >> 8
-  // until late round 4 -- were 8-byte pieces 16 B apart: twice the cache-line segments per instruction, and the stride-2
-  // classes four times).  LDS: a 16-lane read group covers 4 pixels x 4 vectors of ONE half each -- the two half planes are
-  // a multiple of 16 float4 apart, so the bank quad is the (pixel, vector) alone: conflict-free as before.
-  const int h = (tid >> 2) & 1;                           // channel half of the vector
-  const int cv = tid & (DW_CV - 1);
-  const int pix = tid >> 3;
-  const int px = pix & (FB_TW - 1), py = pix >> 3;
+  FB_DECODE(S)
+  FB_STAGE_PARAMS
+  FB_ZERO_SUMS
 
-  const int tiles_x = (g.W + FB_TW * S - 1) / (FB_TW * S), tiles_y = (g.H + FB_TH * S - 1) / (FB_TH * S);   // tile: 8S x 8S input pixels
-  const int ntiles = tiles_x * tiles_y;
-  const int gx = (ntiles + tiles_per_wg - 1) / tiles_per_wg;
-  const ChunkOrder co = chunk_order((g.Cp + DW_CV * 8 - 1) / (DW_CV * 8), gx * g.B);
-  if (co.group < 0) return;
-  const int b = co.group / gx, tg = co.group % gx;
-  const int c0 = co.chunk * DW_CV * 8;
-  const int cb8 = c0 + cv * 8;                            // the 8-channel vector this thread stages
-  const int cb4 = cb8 + h * 4;                            // the 4 channels this thread owns
-  const bool c_ok = cb8 < g.Cp;                           // (Cp is a multiple of 8: both halves exist or neither)
-
-  for (int i = tid; i < 27 * 32; i += FB_NTHR) {
-    const int tap = i >> 5, c = c0 + (i & 31);
-    wl[i] = (c < g.C) ? w[(size_t)c * 27 + tap] : 0.f;
-  }
-  if (fin.sums) {
-    // BatchNorm_b backward coefficients of a block without SqueezeExcitation, rebuilt from the per-sample sums of the
-    // conv_c data gradient's epilogue (csrc/bn_fin.h: no c3d_se_bn_bwd_coef launch in front of this kernel); the first
-    // workgroup of each channel chunk accumulates d gamma / d beta
-    if (tid < 128) {
-      float cA, cB, cC;
-      c3dfin::bn_b_bwd_coef_nc(fin, g.C, g.Cp, c0 + (tid >> 2), tid & 3, co.group == 0, cA, cB, cC);
-      if ((tid & 3) == 0) { cf[tid >> 2] = cA; cf[32 + (tid >> 2)] = cB; cf[64 + (tid >> 2)] = cC; }
-    }
-  }
-  for (int i = tid + (fin.sums ? 3 * 32 : 0); i < 7 * 32; i += FB_NTHR) {
-    const int k = i >> 5, c = c0 + (i & 31);
-    float v = 0.f;
-    if (c < g.Cp) {
-      v = k == 0 ? coefA[c] : k == 1 ? coefB[(size_t)b * g.Cp + c] : k == 2 ? coefC[c] : k == 3 ? ss_a[c]
-        : k == 4 ? ss_a[g.Cp + c] : k == 5 ? mr_a[c] : mr_a[g.Cp + c];
-    }
-    cf[i] = v;
-  }
-
-  // BN_a-backward sums (sum t2, sum t2*ahat): f32 per thread over its walk (tiles_per_wg x T terms), f64 from the
-  // cross-thread reduction on (the sums of the two terms nearly cancel on some channels: d gamma needs the digits)
-  float S1[4], S2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { S1[j] = 0.f; S2[j] = 0.f; }
-  f32x2_t dwa[27][2];   // weight-gradient partial sums of this thread's 4 channels, as register pairs (v_pk_fma_f32)
-#pragma unroll
-  for (int k = 0; k < 27; ++k) { dwa[k][0] = f32x2_t{0.f, 0.f}; dwa[k][1] = f32x2_t{0.f, 0.f}; }
-
-  // per-slot staging descriptors, computed once (offset relative to the tile origin; (row, column) in the tile)
   typename R8::type r1[SL], r2[SL];
   typename R4::type ar[TT];
   unsigned vmask = 0;
-  int rel[SL], yx[SL];
-#pragma unroll
-  for (int sl = 0; sl < SL; ++sl) {
-    const int i_ = tid + sl * FB_NTHR;
-    const int p_ = i_ / DW_CV;
-    const int ix_ = p_ % FB_DW, q_ = p_ / FB_DW;
-    const int iy_ = q_ % FB_DH, t_ = q_ / FB_DH;
-    const bool use_ = i_ < NI && c_ok && t_ < g.T;
-    rel[sl] = ((t_ * g.Ho + iy_) * g.Wo + ix_) * g.Cp + cb8;
-    yx[sl] = use_ ? (iy_ | (ix_ << 16)) : 0x7fff7fff;
-  }
+  FB_SLOTS
   const int orel = (S * py * g.W + S * px) * g.Cp + cb4, ofr = g.H * g.W * g.Cp;   // lane offset in a tile (class (0,0) pixel), frame stride
   // raw (t1, b) rows of the db tile of tile TL -> r1 / r2
 #define FB_ISSUE_RAW(TL)                                                                          \
@@ -399,33 +481,15 @@ __global__ FB_KATTR void dw_bwd_fused_kernel(
     float4* tb = tile + (size_t)((tl - tl0) & 1) * 2 * NI;
     // ---- stage db = A*t1 + B[n] + C*b (zero outside the image) as two f32 half-vector planes
     {
-      float cA[8], cB[8], cC[8];
-      lds8(cf + 0 * 32 + cv * 8, cA);
-      lds8(cf + 1 * 32 + cv * 8, cB);
-      lds8(cf + 2 * 32 + cv * 8, cC);
+      FB_COEF
 #pragma unroll
       for (int sl = 0; sl < SL; ++sl) {
         const int i = tid + sl * FB_NTHR;
-        if (i < NI) {
-          float f[8];
-          if ((vmask >> sl) & 1u) {
-            float f2[8];
-            R8::cvt(r1[sl], f);
-            R8::cvt(r2[sl], f2);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = fmaf(cA[j], f[j], fmaf(cC[j], f2[j], cB[j]));
-          } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = 0.f;
-          }
-          tb[i] = make_float4(f[0], f[1], f[2], f[3]);            // i = p * DW_CV + cv
-          tb[NI + i] = make_float4(f[4], f[5], f[6], f[7]);
-        }
+        if (i < NI) FB_DB8((vmask >> sl) & 1u, r1[sl], r2[sl], tb[i], tb[NI + i])   // i = p * DW_CV + cv
       }
     }
     FCLK(1)
-    // ---- one pixel of this thread (class (CY, CX) of its quad; stride 1: the only one): a_in = relu(bn_a(a)) for the
-    // weight gradient and the mask
+    // ---- one pixel of this thread (class (CY, CX) of its quad; stride 1: the only one)
     typename R4::type arc[TT];
     f32x2_t ain[TT][2];
     f32x2_t acc[TT][2];
@@ -436,38 +500,7 @@ __global__ FB_KATTR void dw_bwd_fused_kernel(
 #define FB_PRE(CY, CX)                                                                                            \
   {                                                                                                               \
     p_ok = c_ok && y0 + S * py + (CY) < g.H && x0 + S * px + (CX) < g.W;                                          \
-    _Pragma("unroll") for (int t = 0; t < TT; ++t) {                                                             \
-      if (p_ok && t < g.T) {                                                                                      \
-        arc[t] = ar[t];                                                                                           \
-        float av[4];                                                                                              \
-        R4::cvt(arc[t], av);                                                                                      \
-        ain[t][0] = f32x2_t{fmaxf(fmaf(av[0], sa[0], sb[0]), 0.f), fmaxf(fmaf(av[1], sa[1], sb[1]), 0.f)};        \
-        ain[t][1] = f32x2_t{fmaxf(fmaf(av[2], sa[2], sb[2]), 0.f), fmaxf(fmaf(av[3], sa[3], sb[3]), 0.f)};        \
-      } else {                                                                                                    \
-        ain[t][0] = f32x2_t{0.f, 0.f}; ain[t][1] = f32x2_t{0.f, 0.f};                                             \
-      }                                                                                                           \
-      acc[t][0] = f32x2_t{0.f, 0.f}; acc[t][1] = f32x2_t{0.f, 0.f};                                               \
-    }                                                                                                             \
-  }
-    // ---- mask, store t2, BN_a-backward sums
-#define FB_EPI(CY, CX)                                                                                            \
-  if (p_ok) {                                                                                                     \
-    float ma[4], ra[4];                                                                                           \
-    lds4(cf + 5 * 32 + cv * 8 + h * 4, ma);                                                                       \
-    lds4(cf + 6 * 32 + cv * 8 + h * 4, ra);                                                                       \
-    T* ob = t2 + ((((int64_t)b * g.T) * g.H + y0 + (CY)) * g.W + x0 + (CX)) * g.Cp;                               \
-    _Pragma("unroll") for (int t = 0; t < TT; ++t) {                                                             \
-      if (t < g.T) {                                                                                              \
-        float av[4], o[4];                                                                                        \
-        R4::cvt(arc[t], av);                                                                                      \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                          \
-          const float d = round_as<T>(ain[t][j >> 1][j & 1] > 0.f ? acc[t][j >> 1][j & 1] : 0.f);                 \
-          o[j] = d;                                                                                               \
-          S1[j] += d; S2[j] += d * ((av[j] - ma[j]) * ra[j]);                                                     \
-        }                                                                                                         \
-        R4::store(ob + (orel + t * ofr), o);                                                                      \
-      }                                                                                                           \
-    }                                                                                                             \
+    FB_AIN(arc[t] = ar[t];)                                                                                       \
   }
     FB_PRE(0, 0)
     if constexpr (S == 2) {
@@ -515,63 +548,17 @@ __global__ FB_KATTR void dw_bwd_fused_kernel(
     __syncthreads();
     FCLK(3)
 
-    // ---- 27 taps: one LDS read feeds the data gradient (x weight) and the weight gradient (x a_in)
-    // lowest-address tap (ky = kx = 2) as base: every other tap is a non-negative immediate offset of the ds_read
     const float4* tp = tb + (size_t)h * NI + (py * FB_DW + px) * DW_CV + cv;
-    // software pipeline over the nine (ky, kx) steps: the LDS reads of step s+1 are issued before the FMAs of step s
-    // (with two waves per SIMD the ~130-clock LDS latency of a step was exposed nine times per tile)
-    float4 wq[2][3], hq[2][TT];
-#define FB_LOAD(S, SLOT)                                                                                          \
-  {                                                                                                               \
-    constexpr int ky_ = (S) / 3, kx_ = (S) % 3;                                                                   \
-    _Pragma("unroll") for (int kt = 0; kt < 3; ++kt)                                                             \
-      wq[SLOT][kt] = *reinterpret_cast<const float4*>(wl + (kt * 9 + (S)) * 32 + cv * 8 + h * 4);                \
-    _Pragma("unroll") for (int to = 0; to < TT; ++to)                                                            \
-      hq[SLOT][to] = tp[((to * FB_DH + (2 - ky_)) * FB_DW + (2 - kx_)) * DW_CV];                                 \
-  }
-#define FB_STEP(S, SLOT)                                                                                          \
-  {                                                                                                               \
-    _Pragma("unroll") for (int to = 0; to < TT; ++to) {                                                          \
-      const f32x2_t v0 = {hq[SLOT][to].x, hq[SLOT][to].y}, v1 = {hq[SLOT][to].z, hq[SLOT][to].w};                 \
-      _Pragma("unroll") for (int kt = 0; kt < 3; ++kt) {                                                         \
-        const int ti = to + kt - 1;   /* in[ti] <-> out[to] through temporal tap kt */                            \
-        if (ti >= 0 && ti < TT) {                                                                                 \
-          const f32x2_t w0 = {wq[SLOT][kt].x, wq[SLOT][kt].y}, w1 = {wq[SLOT][kt].z, wq[SLOT][kt].w};             \
-          acc[ti][0] = __builtin_elementwise_fma(v0, w0, acc[ti][0]);                                             \
-          acc[ti][1] = __builtin_elementwise_fma(v1, w1, acc[ti][1]);                                             \
-          dwa[kt * 9 + (S)][0] = __builtin_elementwise_fma(v0, ain[ti][0], dwa[kt * 9 + (S)][0]);                 \
-          dwa[kt * 9 + (S)][1] = __builtin_elementwise_fma(v1, ain[ti][1], dwa[kt * 9 + (S)][1]);                 \
-        }                                                                                                         \
-      }                                                                                                           \
-    }                                                                                                             \
-    /* pin the schedule: the data-gradient accumulators are only consumed under `p_ok` below and the weight-     \
-       gradient sums at the end of the walk, so the compiler sinks their FMAs and keeps the LDS reads of ALL     \
-       nine steps live until then (216 registers, spills) */                                                      \
-    pin_acc<TT>(acc);                                                                                             \
-    pin_dw(dwa[(S)], dwa[9 + (S)], dwa[18 + (S)]);                                                                \
-  }
     if constexpr (TT <= 3) {
-      FB_LOAD(0, 0)
-      FB_LOAD(1, 1) FB_STEP(0, 0)
-      FB_LOAD(2, 0) FB_STEP(1, 1)
-      FB_LOAD(3, 1) FB_STEP(2, 0)
-      FB_LOAD(4, 0) FB_STEP(3, 1)
-      FB_LOAD(5, 1) FB_STEP(4, 0)
-      FB_LOAD(6, 0) FB_STEP(5, 1)
-      FB_LOAD(7, 1) FB_STEP(6, 0)
-      FB_LOAD(8, 0) FB_STEP(7, 1)
-      FB_STEP(8, 0)
+      FB_WALK9(FB_NO_HOOK)
     } else {
       fb_taps_s1<TT>(tp, wl + cv * 8 + h * 4, acc, dwa, ain);   // five frames (SCD)
     }
-#undef FB_LOAD
-#undef FB_STEP
     FCLK(4)
     FB_EPI(0, 0)
     FCLK(5)
   }
 #undef FB_PRE
-#undef FB_EPI
 #undef FB_ISSUE
 #undef FB_ISSUE_RAW
 #undef FB_ISSUE_A
@@ -668,63 +655,12 @@ __global__ __launch_bounds__(FB_NTHR) void dw_bwd_ring_kernel(
   FCLK_DECL
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = (tid >> 2) & 1;                           // thread = [pixel][channel half][channel vector], as above
-  const int cv = tid & (DW_CV - 1);
-  const int pix = tid >> 3;
-  const int px = pix & (FB_TW - 1), py = pix >> 3;        // py == wave
+  FB_DECODE(1)                                             // (py == wave)
+  FB_STAGE_PARAMS
+  FB_ZERO_SUMS
 
-  const int tiles_x = (g.W + FB_TW - 1) / FB_TW, tiles_y = (g.H + FB_TH - 1) / FB_TH;
-  const int ntiles = tiles_x * tiles_y;
-  const int gx = (ntiles + tiles_per_wg - 1) / tiles_per_wg;
-  const ChunkOrder co = chunk_order((g.Cp + DW_CV * 8 - 1) / (DW_CV * 8), gx * g.B);
-  if (co.group < 0) return;
-  const int b = co.group / gx, tg = co.group % gx;
-  const int c0 = co.chunk * DW_CV * 8;
-  const int cb8 = c0 + cv * 8;
-  const int cb4 = cb8 + h * 4;
-  const bool c_ok = cb8 < g.Cp;
-
-  for (int i = tid; i < 27 * 32; i += FB_NTHR) {
-    const int tap = i >> 5, c = c0 + (i & 31);
-    wl[i] = (c < g.C) ? w[(size_t)c * 27 + tap] : 0.f;
-  }
-  if (fin.sums) {
-    if (tid < 128) {
-      float cA, cB, cC;
-      c3dfin::bn_b_bwd_coef_nc(fin, g.C, g.Cp, c0 + (tid >> 2), tid & 3, co.group == 0, cA, cB, cC);
-      if ((tid & 3) == 0) { cf[tid >> 2] = cA; cf[32 + (tid >> 2)] = cB; cf[64 + (tid >> 2)] = cC; }
-    }
-  }
-  for (int i = tid + (fin.sums ? 3 * 32 : 0); i < 7 * 32; i += FB_NTHR) {
-    const int k = i >> 5, c = c0 + (i & 31);
-    float v = 0.f;
-    if (c < g.Cp) {
-      v = k == 0 ? coefA[c] : k == 1 ? coefB[(size_t)b * g.Cp + c] : k == 2 ? coefC[c] : k == 3 ? ss_a[c]
-        : k == 4 ? ss_a[g.Cp + c] : k == 5 ? mr_a[c] : mr_a[g.Cp + c];
-    }
-    cf[i] = v;
-  }
-
-  float S1[4], S2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { S1[j] = 0.f; S2[j] = 0.f; }
-  f32x2_t dwa[27][2];
-#pragma unroll
-  for (int k = 0; k < 27; ++k) { dwa[k][0] = f32x2_t{0.f, 0.f}; dwa[k][1] = f32x2_t{0.f, 0.f}; }
-
-  // staging descriptors of this thread's vectors i = tid + 512 sl = 64 (wave + 8 sl) + lane: element offset relative to the
-  // tile's db origin, (row, column) in the tile (0x7fff7fff: no source -> zero)
-  int rel[SL], yx[SL];
-#pragma unroll
-  for (int sl = 0; sl < SL; ++sl) {
-    const int i_ = tid + sl * FB_NTHR;
-    const int p_ = i_ / DW_CV;
-    const int ix_ = p_ % FB_DW, q_ = p_ / FB_DW;
-    const int iy_ = q_ % FB_DH, t_ = q_ / FB_DH;
-    const bool use_ = i_ < NI && c_ok && t_ < g.T;
-    rel[sl] = ((t_ * g.Ho + iy_) * g.Wo + ix_) * g.Cp + cb8;
-    yx[sl] = use_ ? (iy_ | (ix_ << 16)) : 0x7fff7fff;
-  }
+  // this thread's vectors are i = tid + 512 sl = 64 (wave + 8 sl) + lane
+  FB_SLOTS
   const int rel_safe = (g.Wo + 1) * g.Cp + c0;            // the tile's first interior pixel, frame 0, first vector of the chunk
   // `a` pieces of this wave (A_LDS): lane -> (frame, pixel of the wave's tile row, vector)
   int arel[NA > 0 ? NA : 1];
@@ -799,26 +735,14 @@ __global__ __launch_bounds__(FB_NTHR) void dw_bwd_ring_kernel(
     const int tx_ = (TL) % tiles_x, ty_ = (TL) / tiles_x;                                         \
     const int dy0_ = ty_ * FB_TH - 1, dx0_ = tx_ * FB_TW - 1;                                     \
     uint4* p0_ = reinterpret_cast<uint4*>(ring + (size_t)(SIDX) * P::SLOT_BYTES);                 \
-    float cA[8], cB[8], cC[8];                                                                    \
-    lds8(cf + 0 * 32 + cv * 8, cA);                                                               \
-    lds8(cf + 1 * 32 + cv * 8, cB);                                                               \
-    lds8(cf + 2 * 32 + cv * 8, cC);                                                               \
+    FB_COEF                                                                                       \
     _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                           \
       if (wave + 8 * sl < NP) {                                                                   \
         const int i = tid + sl * FB_NTHR;                                                         \
         const unsigned gy_ = (unsigned)(dy0_ + (yx[sl] & 0xffff));                                \
         const unsigned gx_ = (unsigned)(dx0_ + (yx[sl] >> 16));                                   \
-        float f[8];                                                                               \
-        if (gy_ < (unsigned)g.Ho && gx_ < (unsigned)g.Wo) {                                       \
-          float f2[8];                                                                            \
-          Raw8<T>::cvt(p0_[i], f);                                                                \
-          Raw8<T>::cvt(p0_[NPL + i], f2);                                                         \
-          _Pragma("unroll") for (int j = 0; j < 8; ++j) f[j] = fmaf(cA[j], f[j], fmaf(cC[j], f2[j], cB[j])); \
-        } else {                                                                                  \
-          _Pragma("unroll") for (int j = 0; j < 8; ++j) f[j] = 0.f;                               \
-        }                                                                                         \
-        reinterpret_cast<float4*>(p0_)[i] = make_float4(f[0], f[1], f[2], f[3]);                  \
-        reinterpret_cast<float4*>(p0_)[NPL + i] = make_float4(f[4], f[5], f[6], f[7]);            \
+        FB_DB8(gy_ < (unsigned)g.Ho && gx_ < (unsigned)g.Wo, p0_[i], p0_[NPL + i],                \
+               reinterpret_cast<float4*>(p0_)[i], reinterpret_cast<float4*>(p0_)[NPL + i])        \
       }                                                                                           \
     }                                                                                             \
   }
@@ -871,62 +795,14 @@ __global__ __launch_bounds__(FB_NTHR) void dw_bwd_ring_kernel(
     if constexpr (!SPREAD) RB_ISSUE_ALL
     if (tl + 1 < tl1) RB_ISSUE_A(tl + 1)
     FCLK(2)
-#pragma unroll
-    for (int t = 0; t < TT; ++t) {
-      if (p_ok && t < g.T) {
-        float av[4];
-        R4::cvt(arc[t], av);
-        ain[t][0] = f32x2_t{fmaxf(fmaf(av[0], sa[0], sb[0]), 0.f), fmaxf(fmaf(av[1], sa[1], sb[1]), 0.f)};
-        ain[t][1] = f32x2_t{fmaxf(fmaf(av[2], sa[2], sb[2]), 0.f), fmaxf(fmaf(av[3], sa[3], sb[3]), 0.f)};
-      } else {
-        ain[t][0] = f32x2_t{0.f, 0.f}; ain[t][1] = f32x2_t{0.f, 0.f};
-      }
-      acc[t][0] = f32x2_t{0.f, 0.f}; acc[t][1] = f32x2_t{0.f, 0.f};
-    }
+    FB_AIN()
     FCLK(1)
-    // ---- 27 taps (the register-prefetch kernel's walk: two fragment slots, LDS reads of step s+1 before the FMAs of step s)
+    // ---- 27 taps (the register-prefetch kernel's walk)
     const float4* tp = tb + (size_t)h * NPL + (py * FB_DW + px) * DW_CV + cv;
     if constexpr (TT <= 3) {
-      float4 wq[2][3], hq[2][TT];
-#define FB_LOAD(S, SLOT)                                                                                          \
-  {                                                                                                               \
-    constexpr int ky_ = (S) / 3, kx_ = (S) % 3;                                                                   \
-    _Pragma("unroll") for (int kt = 0; kt < 3; ++kt)                                                             \
-      wq[SLOT][kt] = *reinterpret_cast<const float4*>(wl + (kt * 9 + (S)) * 32 + cv * 8 + h * 4);                \
-    _Pragma("unroll") for (int to = 0; to < TT; ++to)                                                            \
-      hq[SLOT][to] = tp[((to * FB_DH + (2 - ky_)) * FB_DW + (2 - kx_)) * DW_CV];                                 \
-  }
-#define FB_STEP(S, SLOT)                                                                                          \
-  {                                                                                                               \
-    _Pragma("unroll") for (int to = 0; to < TT; ++to) {                                                          \
-      const f32x2_t v0 = {hq[SLOT][to].x, hq[SLOT][to].y}, v1 = {hq[SLOT][to].z, hq[SLOT][to].w};                 \
-      _Pragma("unroll") for (int kt = 0; kt < 3; ++kt) {                                                         \
-        const int ti = to + kt - 1;                                                                               \
-        if (ti >= 0 && ti < TT) {                                                                                 \
-          const f32x2_t w0 = {wq[SLOT][kt].x, wq[SLOT][kt].y}, w1 = {wq[SLOT][kt].z, wq[SLOT][kt].w};             \
-          acc[ti][0] = __builtin_elementwise_fma(v0, w0, acc[ti][0]);                                             \
-          acc[ti][1] = __builtin_elementwise_fma(v1, w1, acc[ti][1]);                                             \
-          dwa[kt * 9 + (S)][0] = __builtin_elementwise_fma(v0, ain[ti][0], dwa[kt * 9 + (S)][0]);                 \
-          dwa[kt * 9 + (S)][1] = __builtin_elementwise_fma(v1, ain[ti][1], dwa[kt * 9 + (S)][1]);                 \
-        }                                                                                                         \
-      }                                                                                                           \
-    }                                                                                                             \
-    pin_acc<TT>(acc);                                                                                             \
-    pin_dw(dwa[(S)], dwa[9 + (S)], dwa[18 + (S)]);                                                                \
-    if constexpr (SPREAD) { RB_ISSUE_Q(S) if constexpr ((S) == 8) { RB_ISSUE_Q(9) } }                             \
-  }
-      FB_LOAD(0, 0)
-      FB_LOAD(1, 1) FB_STEP(0, 0)
-      FB_LOAD(2, 0) FB_STEP(1, 1)
-      FB_LOAD(3, 1) FB_STEP(2, 0)
-      FB_LOAD(4, 0) FB_STEP(3, 1)
-      FB_LOAD(5, 1) FB_STEP(4, 0)
-      FB_LOAD(6, 0) FB_STEP(5, 1)
-      FB_LOAD(7, 1) FB_STEP(6, 0)
-      FB_LOAD(8, 0) FB_STEP(7, 1)
-      FB_STEP(8, 0)
-#undef FB_LOAD
-#undef FB_STEP
+#define RB_HOOK(STEP) if constexpr (SPREAD) { RB_ISSUE_Q(STEP) if constexpr ((STEP) == 8) { RB_ISSUE_Q(9) } }
+      FB_WALK9(RB_HOOK)
+#undef RB_HOOK
     } else {
       fb_taps_s1<TT>(tp, wl + cv * 8 + h * 4, acc, dwa, ain);   // five frames (SCD): plain walk, plane stride NPL in `tp`
       if constexpr (SPREAD) RB_ISSUE_ALL
@@ -939,26 +815,7 @@ __global__ __launch_bounds__(FB_NTHR) void dw_bwd_ring_kernel(
     }
     FCLK(6)
     // ---- mask, store t2, BN_a-backward sums
-    if (p_ok) {
-      float ma[4], ra[4];
-      lds4(cf + 5 * 32 + cv * 8 + h * 4, ma);
-      lds4(cf + 6 * 32 + cv * 8 + h * 4, ra);
-      T* ob = t2 + ((((int64_t)b * g.T) * g.H + y0) * g.W + x0) * g.Cp;
-#pragma unroll
-      for (int t = 0; t < TT; ++t) {
-        if (t < g.T) {
-          float av[4], o[4];
-          R4::cvt(arc[t], av);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float d = round_as<T>(ain[t][j >> 1][j & 1] > 0.f ? acc[t][j >> 1][j & 1] : 0.f);
-            o[j] = d;
-            S1[j] += d; S2[j] += d * ((av[j] - ma[j]) * ra[j]);
-          }
-          R4::store(ob + (orel + t * ofr), o);
-        }
-      }
-    }
+    FB_EPI(0, 0)
     FCLK(5)
     if (tl + 1 < tl1) RB_CONVERT(tl + 1, slot1)
     FCLK(8)
@@ -975,19 +832,26 @@ __global__ __launch_bounds__(FB_NTHR) void dw_bwd_ring_kernel(
   FCLK_FLUSH
 }
 
+// tiles of a map: 8S x 8S input pixels each
+inline int fb_ntiles(const DwGeom& g, const int S) {
+  return ((g.W + FB_TW * S - 1) / (FB_TW * S)) * ((g.H + FB_TH * S - 1) / (FB_TH * S));
+}
+// the one launch of both kernels: a DwBwdCall as their (typed) argument list
+template <auto Kernel, typename T>
+int fb_launch(const DwBwdCall& c, const DwWalk& wk, const size_t lds) {
+  return c3d_launch_lds<Kernel>(dim3(wk.grid), dim3(FB_NTHR), lds, c.stream, reinterpret_cast<const T*>(c.t1),
+                                reinterpret_cast<const T*>(c.b), c.cA, c.cB, c.cC, c.w, reinterpret_cast<const T*>(c.a), c.ss_a,
+                                c.mr_a, reinterpret_cast<T*>(c.t2), c.dsums, c.dw, c.g, wk.tpw, c.fin);
+}
+
 template <int TT, bool SPREAD>
 int launch_ring_t(const DwBwdCall& c) {
   typedef RingPlan<TT> P;
   static_assert(P::LDS_BYTES <= 160 * 1024, "ring does not fit");
   static_assert((size_t)P::R * P::SLOT_BYTES >= (size_t)27 * (FB_NTHR + 48) * sizeof(float), "dump region");
   static_assert((P::AHEAD - 1) * (2 * P::SL + P::NA) <= 12, "fb_wait_vm covers counts up to 12");
-  const DwGeom& g = c.g;
-  const int ntiles = ((g.W + FB_TW - 1) / FB_TW) * ((g.H + FB_TH - 1) / FB_TH);
-  const DwWalk wk = dw_walk(g, ntiles, c3d_knob("C3D_DWBF_MAX", 64), 4, 85L * device_cus() / 100, "C3D_DWBF_TPW");
-  return c3d_launch_lds<dw_bwd_ring_kernel<TT, SPREAD>>(
-      dim3(wk.grid), dim3(FB_NTHR), P::LDS_BYTES, c.stream, reinterpret_cast<const bf16_t*>(c.t1),
-      reinterpret_cast<const bf16_t*>(c.b), c.cA, c.cB, c.cC, c.w, reinterpret_cast<const bf16_t*>(c.a), c.ss_a, c.mr_a,
-      reinterpret_cast<bf16_t*>(c.t2), c.dsums, c.dw, g, wk.tpw, c.fin);
+  const DwWalk wk = dw_walk(c.g, fb_ntiles(c.g, 1), c3d_knob("C3D_DWBF_MAX", 64), 4, 85L * device_cus() / 100, "C3D_DWBF_TPW");
+  return fb_launch<dw_bwd_ring_kernel<TT, SPREAD>, bf16_t>(c, wk, P::LDS_BYTES);
 }
 
 template <typename T, int TT, int S>
@@ -996,8 +860,6 @@ int launch_fused_t(const DwBwdCall& c) {
   const size_t lds = (27 * 32 + 7 * 32) * sizeof(float) + (size_t)2 * 2 * NI * sizeof(float4);
   static_assert((size_t)2 * 2 * NI * sizeof(float4) >= (size_t)27 * (FB_NTHR + 48) * sizeof(float), "dump region");
   if (lds > 160 * 1024) return C3D_E_UNSUPPORTED;
-  const DwGeom& g = c.g;
-  const int ntiles = ((g.W + FB_TW * S - 1) / (FB_TW * S)) * ((g.H + FB_TH * S - 1) / (FB_TH * S));
   // one 512-thread workgroup is resident per CU: a walk amortises the weight-gradient flush (~3 us) and pipelines the
   // loads; short enough for ~2 rounds of workgroups (C3D_DWBF_TPW: tuning knob)
   // measured on MI355X (B=32 bf16 step, side stream on): 4 / 8 / 16 / 32 / 64 tiles -> 32.9 / 31.3 / 30.6 / 30.4 / 31.2 ms
@@ -1005,13 +867,10 @@ int launch_fused_t(const DwBwdCall& c) {
   // -> the longest walk that still gives (almost) every CU a workgroup: 16 / 32 / 32 tiles for the 32x32 / 64x64 / 128x128 stages
   // (round 5, re-swept at 23.2 ms per step: cap 16 / 32 / 64 / 128 tiles -> 23.42 / 23.18 / 22.95 / 23.15 ms; with the narrower
   // side-stream weight gradient, three interleaved repeats: 22.90 against 23.39 ms for the old pair of defaults)
-  // a stride-2 tile is four pixels per thread; (half-height tiles: twice as many)
-  const int start = c3d_knob("C3D_DWBF_MAX", 64) / (S * S) * (8 / FB_TH);
-  constexpr int WGC = 512 / FB_NTHR;           // workgroups resident per CU
-  const DwWalk wk = dw_walk(g, ntiles, start, 4, 85L * WGC * device_cus() / 100, "C3D_DWBF_TPW");
-  return c3d_launch_lds<dw_bwd_fused_kernel<T, TT, S>>(
-      dim3(wk.grid), dim3(FB_NTHR), lds, c.stream, reinterpret_cast<const T*>(c.t1), reinterpret_cast<const T*>(c.b), c.cA, c.cB,
-      c.cC, c.w, reinterpret_cast<const T*>(c.a), c.ss_a, c.mr_a, reinterpret_cast<T*>(c.t2), c.dsums, c.dw, g, wk.tpw, c.fin);
+  // a stride-2 tile is four pixels per thread
+  const int start = c3d_knob("C3D_DWBF_MAX", 64) / (S * S);
+  const DwWalk wk = dw_walk(c.g, fb_ntiles(c.g, S), start, 4, 85L * device_cus() / 100, "C3D_DWBF_TPW");
+  return fb_launch<dw_bwd_fused_kernel<T, TT, S>, T>(c, wk, lds);
 }
 
 template <typename T>
@@ -1028,7 +887,7 @@ int dispatch_fused(const DwBwdCall& c, const int dtype) {
   // LDS-DMA ring kernels (bit 2: requests spread over the tap walk; bit 3: three-frame maps under 64 x 64 too -- their
   // 16-tile walks pay the two-tile ring fill: res4 of the BCD step 65.9 us with the register prefetch, 68.0 us with the
   // ring; the five-frame register kernel spills, its ring variant wins on every map: SCD 663 -> 681 img/s)
-  if (C3D_FB_ROWS == 8 && g.stride == 1 && (c3d_option_dw_ring & 1) && ((c3d_option_dw_ring & 8) || g.T > 3 || (long)g.H * g.W >= 64 * 64))
+  if (g.stride == 1 && (c3d_option_dw_ring & 1) && ((c3d_option_dw_ring & 8) || g.T > 3 || (long)g.H * g.W >= 64 * 64))
     return with_frames(g.T, [&c](auto n) {
       return (c3d_option_dw_ring & 4) ? launch_ring_t<decltype(n)::value, true>(c) : launch_ring_t<decltype(n)::value, false>(c);
     });

@@ -35,6 +35,53 @@ __device__ __forceinline__ ChunkOrder chunk_order(const int chunks, const int ng
 inline unsigned chunk_order_grid(const int chunks, const long ngroups) {
   return (unsigned)(((ngroups + N_XCD - 1) / N_XCD) * N_XCD * chunks);
 }
+// The workgroup decode of every tile-walking depthwise kernel (kernel arguments `g`, `tiles_per_wg`): tile counts, walk
+// groups per sample `gx`, then co / b (sample) / tg (walk group) / c0 (first channel of the chunk); a padding workgroup
+// returns.  This and the weight staging are macros over the kernels' own arguments and locals: every forced-inline function
+// tried in their place changed the register allocation of all the kernels that used it (profiles/dw_refactor.txt).
+#define DW_WG_DECODE(TILES_X, TILES_Y)                                                            \
+  const int tiles_x = (TILES_X), tiles_y = (TILES_Y);                                             \
+  const int ntiles = tiles_x * tiles_y;                                                           \
+  const int gx = (ntiles + tiles_per_wg - 1) / tiles_per_wg;                                      \
+  const ChunkOrder co = chunk_order((g.Cp + DW_CV * 8 - 1) / (DW_CV * 8), gx * g.B);              \
+  if (co.group < 0) return;                                                                       \
+  const int b = co.group / gx, tg = co.group % gx;                                                \
+  const int c0 = co.chunk * DW_CV * 8;
+
+// weights of the chunk -> LDS as [tap][32 channels] (zero for channels >= C); kernel locals `wl`, `tid`, argument `w`
+#define DW_STAGE_WEIGHTS(NTHR)                                                                    \
+  for (int i = tid; i < 27 * 32; i += (NTHR)) {                                                   \
+    const int tap = i >> 5, c = c0 + (i & 31);                                                    \
+    wl[i] = (c < g.C) ? w[(size_t)c * 27 + tap] : 0.f;                                            \
+  }
+
+// raw (unconverted) 8-element vectors: what a register prefetch holds between issue and use
+template <typename T> struct Raw8;
+template <> struct Raw8<bf16_t> {
+  typedef uint4 type;
+  static __device__ __forceinline__ type load(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
+  static __device__ __forceinline__ void cvt(const type& v, float (&f)[8]) {
+    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
+    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
+    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
+    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
+  }
+};
+template <> struct Raw8<float> {
+  struct type { float4 a, b; };
+  static __device__ __forceinline__ type load(const float* p) {
+    type t; t.a = *reinterpret_cast<const float4*>(p); t.b = *reinterpret_cast<const float4*>(p + 4); return t;
+  }
+  static __device__ __forceinline__ void cvt(const type& v, float (&f)[8]) {
+    f[0] = v.a.x; f[1] = v.a.y; f[2] = v.a.z; f[3] = v.a.w; f[4] = v.b.x; f[5] = v.b.y; f[6] = v.b.z; f[7] = v.b.w;
+  }
+};
+
+__device__ __forceinline__ void lds8(const float* p, float (&f)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p);
+  const float4 b = *reinterpret_cast<const float4*>(p + 4);
+  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+}
 
 // Frame-count instantiation of a clip: three frames (BCD, CC), four (BDA: num_perception_frame = 2), five (SCD).  With
 // C3D_OPT_DW_T4 = 0 a four-frame clip runs on the five-frame instantiation, its fifth frame staged as zeros.

@@ -27,35 +27,6 @@ template <typename T> struct LdsStore;  // tile element type in LDS
 template <> struct LdsStore<float> { typedef float type; };
 template <> struct LdsStore<bf16_t> { typedef bf16_t type; };
 
-// raw (unconverted) 8-element vectors: what a register prefetch holds between issue and use
-template <typename T> struct RawD;
-template <> struct RawD<bf16_t> {
-  typedef uint4 type;
-  static __device__ __forceinline__ type load(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
-  static __device__ __forceinline__ void cvt(const type& v, float (&f)[8]) {
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-  }
-};
-template <> struct RawD<float> {
-  struct type { float4 a, b; };
-  static __device__ __forceinline__ type load(const float* p) {
-    type t; t.a = *reinterpret_cast<const float4*>(p); t.b = *reinterpret_cast<const float4*>(p + 4); return t;
-  }
-  static __device__ __forceinline__ void cvt(const type& v, float (&f)[8]) {
-    f[0] = v.a.x; f[1] = v.a.y; f[2] = v.a.z; f[3] = v.a.w; f[4] = v.b.x; f[5] = v.b.y; f[6] = v.b.z; f[7] = v.b.w;
-  }
-};
-
-
-__device__ __forceinline__ void lds_ld8(const float* p, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-
 // ----------------------------------------------------------------------------------------------
 // Forward.  grid = (tiles_x*tiles_y, channel chunks, B); block = TH*TW*DW_CV threads.
 template <typename T, int S, int TH, int TW, int TT>
@@ -71,22 +42,12 @@ __global__ __launch_bounds__(TH * TW * DW_CV) void dw_fwd_kernel(
   L* tile = reinterpret_cast<L*>(red + (NTHR / 64) * DW_CV * 16);     // [T][IH][IW][32]
 
   const int tid = threadIdx.x;
-  const int tiles_x = (g.Wo + TW - 1) / TW, tiles_y = (g.Ho + TH - 1) / TH;
-  const int ntiles = tiles_x * tiles_y;
-  const int gx_ = (ntiles + tiles_per_wg - 1) / tiles_per_wg;
-  const ChunkOrder co = chunk_order((g.Cp + DW_CV * 8 - 1) / (DW_CV * 8), gx_ * g.B);
-  if (co.group < 0) return;
-  const int chunk = co.chunk, b = co.group / gx_, tg = co.group % gx_;
-  const int c0 = chunk * DW_CV * 8;
+  DW_WG_DECODE((g.Wo + TW - 1) / TW, (g.Ho + TH - 1) / TH)
   const int cv = tid % DW_CV;
   const int cbase = c0 + cv * 8;
   const bool c_ok = cbase < g.Cp;
 
-  // weights -> LDS as [tap][32 channels] (zero for channels >= C)
-  for (int i = tid; i < 27 * 32; i += NTHR) {
-    const int tap = i / 32, c = c0 + (i & 31);
-    wl[i] = (c < g.C) ? w[(size_t)c * 27 + tap] : 0.f;
-  }
+  DW_STAGE_WEIGHTS(NTHR)
   float sc[8], sh[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { sc[j] = c_ok ? ss[cbase + j] : 0.f; sh[j] = c_ok ? ss[g.Cp + cbase + j] : 0.f; }
@@ -110,10 +71,10 @@ __global__ __launch_bounds__(TH * TW * DW_CV) void dw_fwd_kernel(
     const int ix = p % IW;
     const int q = p / IW;
     const int iy = q % IH, t = q / IH;
-    const int gy = iy0 + iy, gx = ix0 + ix;
+    const int yy = iy0 + iy, xx = ix0 + ix;
     float f[8];
-    if (c_ok && gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) {
-      Vec8<T>::load(x + ((((size_t)b * g.T + t) * g.H + gy) * g.W + gx) * g.Cp + cbase, f);
+    if (c_ok && yy >= 0 && yy < g.H && xx >= 0 && xx < g.W) {
+      Vec8<T>::load(x + ((((size_t)b * g.T + t) * g.H + yy) * g.W + xx) * g.Cp + cbase, f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) f[j] = fmaxf(fmaf(f[j], sc[j], sh[j]), 0.f);
     } else {
@@ -219,12 +180,6 @@ __global__ __launch_bounds__(TH * TW * DW_CV) void dw_fwd_kernel(
 // LDS = one workgroup per CU (1.3 TB/s); the 4 x 16 tile is 69 KB = two.  Four frames (BDA): 92 KB against 55 KB, also 4 x 16.
 constexpr int V2_TW = 16, V2_IW = V2_TW + 2;
 
-__device__ __forceinline__ void lds_ld8v2(const float* p, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-
 // LDS plane geometry of the v2 kernels: one plane per (channel vector, half vector) holding a float4
 // per pixel, [t][iy][ix]; the plane stride is padded by one float4 so the 8 planes of a pixel fall on
 // distinct bank groups (conflict-free staging writes), and lanes walk x so stencil reads are dense.
@@ -234,10 +189,108 @@ template <int TT> struct V2Geo {
   static constexpr int PLANE = TT * IH * V2_IW + 1;             // float4 units
   static constexpr int NI = TT * IH * V2_IW * DW_CV;            // staged 8-channel vectors per tile
   static constexpr int SL = (NI + 255) / 256;
+  // staging (DWF_SLOTS / DWF_ISSUE): input tile IH x IW, its origin OY, OX input pixels per tile step (less the halo), and the
+  // descriptor packing rel << (5 + XB) | valid << (4 + XB) | ix << 4 | iy
+  static constexpr int IW = V2_IW, OY = TH, OX = V2_TW, XB = 5, RS = 0;
 };
 
-// PK: every prefetch slot's tile-independent part -- (frame, row, column) of its item in the staged tile and the element
-// offset from the tile origin -- is decoded once into one packed register per slot; the per-tile request is then two adds,
+// ---- what dw_fwd_v2_kernel and dw_fwd_v2s2_kernel share, each written once.  File-scope macros over the kernels' arguments and
+// locals, as in dw_bwd_fused.hip and for its reason: the kernels stay the code they were (profiles/dw_refactor.txt).
+// LDS head and thread index
+#define DWF_HEAD                                                                                                    \
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];                                              \
+  float* wl = reinterpret_cast<float*>(smem);                  /* [27][32] */                                       \
+  float* fss = wl + 27 * 32;                                   /* [2][32] scale | shift of this chunk (fin.sums mode) */ \
+  float4* tile = reinterpret_cast<float4*>(fss + 64);          /* [4 cv][2 halves][PLANE] */                        \
+  const int tid = threadIdx.x, lane = tid & 63;
+// workgroup decode, the two roles of a thread (`wcv`: its wave's channel vector), weights, statistics
+#define DWF_ROLES(NTHR, TILES_X, TILES_Y)                                                                           \
+  DW_WG_DECODE(TILES_X, TILES_Y)                                                                                    \
+  const int scv = tid & 3;              /* staging role: item i = tid + NTHR*slot -> (cv = i & 3, pixel = i >> 2) */ \
+  const int sbase = c0 + scv * 8;                                                                                   \
+  const bool s_ok = sbase < g.Cp;                                                                                   \
+  const int cbase = c0 + wcv * 8;       /* compute role */                                                          \
+  const bool c_ok = cbase < g.Cp;                                                                                   \
+  DW_STAGE_WEIGHTS(NTHR)                                                                                            \
+  float s1[8], s2[8];                                                                                               \
+  _Pragma("unroll") for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+// Prefetch slots of the staging role, geometry G (V2Geo / V2S2Geo).  PK: every slot's tile-independent part -- (frame, row,
+// column) of its item in the staged tile and the element offset from the tile origin (>> G::RS: a multiple of 8 elements where
+// 22 bits would not hold it) -- is decoded once into one packed register per slot
+#define DWF_SLOTS(G, NTHR)                                                                                          \
+  typename RW::type raw[SL];                                                                                        \
+  unsigned vmask = 0;                                                                                               \
+  unsigned dsc[PK ? SL : 1];                                                                                        \
+  if constexpr (PK) {                                                                                               \
+    _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                                             \
+      const int i_ = tid + sl * (NTHR);                                                                             \
+      const int p_ = i_ >> 2;                                                                                       \
+      const int ix_ = p_ % G::IW, q_ = p_ / G::IW;                                                                  \
+      const int iy_ = q_ % G::IH, t_ = q_ / G::IH;                                                                  \
+      const bool ok_ = i_ < NI && s_ok && t_ < g.T;                                                                 \
+      const unsigned rel_ = (unsigned)(((t_ * g.H + iy_) * g.W + ix_) * g.Cp + sbase);                              \
+      dsc[sl] = ok_ ? ((rel_ >> G::RS) << (5 + G::XB)) | (16u << G::XB) | ((unsigned)ix_ << 4) | (unsigned)iy_ : 0u; \
+    }                                                                                                               \
+  }
+// the raw rows of tile TL -> raw / vmask
+#define DWF_ISSUE(G, NTHR, TL)                                                                                      \
+  if constexpr (PK) {                                                                                               \
+    const int tx_ = (TL) % tiles_x, ty_ = (TL) / tiles_x;                                                           \
+    const int by_ = ty_ * G::OY - 1, bx_ = tx_ * G::OX - 1;                                                         \
+    const T* xt_ = x + (ptrdiff_t)(((b * g.T * g.H + by_) * g.W + bx_) * g.Cp);   /* wave-uniform */                \
+    vmask = 0;                                                                                                      \
+    _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                                             \
+      const unsigned d_ = dsc[sl];                                                                                  \
+      const unsigned gy_ = (unsigned)(by_ + (int)(d_ & 15u)), gx_ = (unsigned)(bx_ + (int)((d_ >> 4) & ((1u << G::XB) - 1u))); \
+      if ((d_ & (16u << G::XB)) && gy_ < (unsigned)g.H && gx_ < (unsigned)g.W) {                                    \
+        raw[sl] = RW::load(xt_ + ((d_ >> (5 + G::XB)) << G::RS));                                                   \
+        vmask |= 1u << sl;                                                                                          \
+      }                                                                                                             \
+    }                                                                                                               \
+  } else {                                                                                                          \
+    const int tx_ = (TL) % tiles_x, ty_ = (TL) / tiles_x;                                                           \
+    vmask = 0;                                                                                                      \
+    _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                                             \
+      const int i_ = tid + sl * (NTHR);                                                                             \
+      const int p_ = i_ >> 2;                                                                                       \
+      const int ix_ = p_ % G::IW, q_ = p_ / G::IW;                                                                  \
+      const int iy_ = q_ % G::IH, t_ = q_ / G::IH;                                                                  \
+      const int gy_ = ty_ * G::OY - 1 + iy_, gx_ = tx_ * G::OX - 1 + ix_;                                           \
+      if (i_ < NI && s_ok && t_ < g.T && gy_ >= 0 && gy_ < g.H && gx_ >= 0 && gx_ < g.W) {                         \
+        raw[sl] = RW::load(x + ((((size_t)b * g.T + t_) * g.H + gy_) * g.W + gx_) * g.Cp + sbase);                  \
+        vmask |= 1u << sl;                                                                                          \
+      }                                                                                                             \
+    }                                                                                                               \
+  }
+// BatchNorm scale / shift of the staging role's vector: given, or rebuilt from the producer's completed sums while the first
+// tile's loads are in flight (csrc/bn_fin.h; the workgroup of (sample 0, walk 0) owns the chunk's global outputs)
+#define DWF_SCALE_SHIFT(NTHR)                                                                                       \
+  float sc[8], sh[8];                                                                                               \
+  if (fin.sums) {                                                                                                   \
+    if (tid == 0 && co.chunk == 0 && co.group == 0 && fin.training && fin.nbt) *fin.nbt += 1;                       \
+    c3dfin::bn_consume(fin, g.C, g.Cp, c0, 32, co.group == 0, fss, fss + 32, tid, (NTHR));                          \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) { sc[j] = s_ok ? fss[scv * 8 + j] : 0.f; sh[j] = s_ok ? fss[32 + scv * 8 + j] : 0.f; } \
+  } else {                                                                                                          \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) { sc[j] = s_ok ? ss[sbase + j] : 0.f; sh[j] = s_ok ? ss[g.Cp + sbase + j] : 0.f; } \
+  }
+// per-sample statistics of a walk: NCH channels per lane from CFIRST on, summed over groups of LANES lanes, two f64 atomics
+// per channel
+#define DWF_FLUSH(NCH, LANES, CFIRST)                                                                               \
+  _Pragma("unroll") for (int j = 0; j < (NCH); ++j) {                                                               \
+    float r1 = s1[j], r2 = s2[j];                                                                                   \
+    if constexpr ((LANES) == 64) {                                                                                  \
+      r1 = wave_sum(r1); r2 = wave_sum(r2);                                                                         \
+    } else {   /* the pair interleaved: the same sums, in the instruction order the half-wave flush had */          \
+      _Pragma("unroll") for (int o = (LANES) / 2; o > 0; o >>= 1) { r1 += __shfl_xor(r1, o, 64); r2 += __shfl_xor(r2, o, 64); } \
+    }                                                                                                               \
+    const int c = (CFIRST) + j;                                                                                     \
+    if ((lane & ((LANES) - 1)) == 0 && c < g.C) {                                                                   \
+      atomicAdd(nc + ((size_t)b * g.Cp + c) * 2, (double)r1);                                                       \
+      atomicAdd(nc + ((size_t)b * g.Cp + c) * 2 + 1, (double)r2);                                                   \
+    }                                                                                                               \
+  }
+
+// PK (packed slot descriptors, DWF_SLOTS): the per-tile request is then two adds,
 // two unsigned compares and one 64-bit address instead of two divisions by constants, a frame multiply and three 64-bit
 // multiply-adds per slot (9 slots: ~200 of a tile's ~1 060 VALU instructions in a kernel whose VALU is its busiest unit).
 // The launcher takes it when the offset fits 22 bits and the tensor 2^31 elements.
@@ -252,15 +305,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HV ? 2 : 1,
                                                         const float* __restrict__ w, T* __restrict__ y,
                                                         double* __restrict__ nc, const DwGeom g,
                                                         const int tiles_per_wg, const c3d_bn_fin fin) {
-  typedef RawD<T> RW;
+  typedef Raw8<T> RW;
   typedef V2Geo<TT> G;
   constexpr int NI = G::NI, SL = G::SL, PLANE = G::PLANE, PYR = G::PYR, V2_TH = G::TH, V2_IH = G::IH;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* wl = reinterpret_cast<float*>(smem);                  // [27][32]
-  float* fss = wl + 27 * 32;                                   // [2][32] scale | shift of this chunk (fin.sums mode)
-  float4* tile = reinterpret_cast<float4*>(fss + 64);          // [4 cv][2 halves][PLANE]
-
-  const int tid = threadIdx.x, lane = tid & 63;
+  DWF_HEAD
   const int wcv = __builtin_amdgcn_readfirstlane(tid >> 6);    // this wave's channel vector
   // lane = column x, rows PYR*yp .. PYR*yp + PYR-1.  The columns of ODD row groups are rotated: a ds_read_b128 is served in
   // four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- i.e. half a row group plus
@@ -272,89 +320,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HV ? 2 : 1,
   // ReLU unit on the hand-picked kink-free seeds of the strict f32 tests -- those tests now name and grant such a unit,
   // oracle/kinks.py)
   const int lx = (lane + (yp & 1) * ((16 - (PYR * V2_IW) % 16) & 15)) & 15;
-  const int tiles_x = (g.W + V2_TW - 1) / V2_TW, tiles_y = (g.H + V2_TH - 1) / V2_TH;
-  const int ntiles = tiles_x * tiles_y;
-  const int gx = (ntiles + tiles_per_wg - 1) / tiles_per_wg;
-  const ChunkOrder co = chunk_order((g.Cp + DW_CV * 8 - 1) / (DW_CV * 8), gx * g.B);
-  if (co.group < 0) return;
-  const int chunk = co.chunk, b = co.group / gx, tg = co.group % gx;
-  const int c0 = chunk * DW_CV * 8;
-  // staging role: item i = tid + 256*slot -> (cv = i & 3, pixel = i >> 2)
-  const int scv = tid & 3;
-  const int sbase = c0 + scv * 8;
-  const bool s_ok = sbase < g.Cp;
-  const int cbase = c0 + wcv * 8;       // compute role
-  const bool c_ok = cbase < g.Cp;
-
-  for (int i = tid; i < 27 * 32; i += 256) {
-    const int tap = i / 32, c = c0 + (i & 31);
-    wl[i] = (c < g.C) ? w[(size_t)c * 27 + tap] : 0.f;
-  }
-  float s1[8], s2[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-
-  typename RW::type raw[SL];
-  unsigned vmask = 0;
-  unsigned dsc[PK ? SL : 1];   // rel << 10 | valid << 9 | ix << 4 | iy
-  if constexpr (PK) {
-#pragma unroll
-    for (int sl = 0; sl < SL; ++sl) {
-      const int i_ = tid + sl * 256;
-      const int p_ = i_ >> 2;
-      const int ix_ = p_ % V2_IW, q_ = p_ / V2_IW;
-      const int iy_ = q_ % V2_IH, t_ = q_ / V2_IH;
-      const bool ok_ = i_ < NI && s_ok && t_ < g.T;
-      const unsigned rel_ = (unsigned)(((t_ * g.H + iy_) * g.W + ix_) * g.Cp + sbase);
-      dsc[sl] = ok_ ? (rel_ << 10) | 512u | ((unsigned)ix_ << 4) | (unsigned)iy_ : 0u;
-    }
-  }
-#define V2_ISSUE(TL)                                                                            \
-  if constexpr (PK) {                                                                           \
-    const int tx_ = (TL) % tiles_x, ty_ = (TL) / tiles_x;                                       \
-    const int by_ = ty_ * V2_TH - 1, bx_ = tx_ * V2_TW - 1;                                     \
-    const T* xt_ = x + (ptrdiff_t)(((b * g.T * g.H + by_) * g.W + bx_) * g.Cp);   /* wave-uniform */ \
-    vmask = 0;                                                                                  \
-    _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                         \
-      const unsigned d_ = dsc[sl];                                                              \
-      const unsigned gy_ = (unsigned)(by_ + (int)(d_ & 15u)), gx_ = (unsigned)(bx_ + (int)((d_ >> 4) & 31u)); \
-      if ((d_ & 512u) && gy_ < (unsigned)g.H && gx_ < (unsigned)g.W) {                          \
-        raw[sl] = RW::load(xt_ + (d_ >> 10));                                                   \
-        vmask |= 1u << sl;                                                                      \
-      }                                                                                         \
-    }                                                                                           \
-  } else {                                                                                      \
-    const int tx_ = (TL) % tiles_x, ty_ = (TL) / tiles_x;                                       \
-    vmask = 0;                                                                                  \
-    _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                         \
-      const int i_ = tid + sl * 256;                                                            \
-      const int p_ = i_ >> 2;                                                                   \
-      const int ix_ = p_ % V2_IW, q_ = p_ / V2_IW;                                              \
-      const int iy_ = q_ % V2_IH, t_ = q_ / V2_IH;                                              \
-      const int gy_ = ty_ * V2_TH - 1 + iy_, gx_ = tx_ * V2_TW - 1 + ix_;                       \
-      if (i_ < NI && s_ok && t_ < g.T && gy_ >= 0 && gy_ < g.H && gx_ >= 0 && gx_ < g.W) {     \
-        raw[sl] = RW::load(x + ((((size_t)b * g.T + t_) * g.H + gy_) * g.W + gx_) * g.Cp + sbase); \
-        vmask |= 1u << sl;                                                                      \
-      }                                                                                         \
-    }                                                                                           \
-  }
+  DWF_ROLES(256, (g.W + V2_TW - 1) / V2_TW, (g.H + V2_TH - 1) / V2_TH)
+  DWF_SLOTS(G, 256)
 
   const int tl0 = tg * tiles_per_wg;
   int tl1 = tl0 + tiles_per_wg;
   if (tl1 > ntiles) tl1 = ntiles;
-  if (tl0 < tl1) V2_ISSUE(tl0)
-  // BatchNorm scale / shift of this chunk: given, or rebuilt from the producer's completed sums while the first
-  // tile's loads are in flight (csrc/bn_fin.h; the workgroup of (sample 0, walk 0) owns the chunk's global outputs)
-  float sc[8], sh[8];
-  if (fin.sums) {
-    if (tid == 0 && co.chunk == 0 && co.group == 0 && fin.training && fin.nbt) *fin.nbt += 1;
-    c3dfin::bn_consume(fin, g.C, g.Cp, c0, 32, co.group == 0, fss, fss + 32, tid, 256);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sc[j] = s_ok ? fss[scv * 8 + j] : 0.f; sh[j] = s_ok ? fss[32 + scv * 8 + j] : 0.f; }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sc[j] = s_ok ? ss[sbase + j] : 0.f; sh[j] = s_ok ? ss[g.Cp + sbase + j] : 0.f; }
-  }
+  if (tl0 < tl1) DWF_ISSUE(G, 256, tl0)
+  DWF_SCALE_SHIFT(256)
   for (int tl = tl0; tl < tl1; ++tl) {
     const int tx = tl % tiles_x, ty = tl / tiles_x;
     __syncthreads();
@@ -379,7 +352,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HV ? 2 : 1,
         tile[(scv * 2 + 1) * PLANE + p] = make_float4(f[4], f[5], f[6], f[7]);
       }
     }
-    if (tl + 1 < tl1) V2_ISSUE(tl + 1)
+    if (tl + 1 < tl1) DWF_ISSUE(G, 256, tl + 1)
     __syncthreads();
 
     if constexpr (HV) {
@@ -471,7 +444,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HV ? 2 : 1,
       for (int kx = 0; kx < 3; ++kx) {
         float wk[3][8];  // wave-uniform: broadcast LDS reads
 #pragma unroll
-        for (int kt = 0; kt < 3; ++kt) lds_ld8v2(wl + (kt * 9 + ky * 3 + kx) * 32 + wcv * 8, wk[kt]);
+        for (int kt = 0; kt < 3; ++kt) lds8(wl + (kt * 9 + ky * 3 + kx) * 32 + wcv * 8, wk[kt]);
 #pragma unroll
         for (int ti = 0; ti < TT; ++ti) {
           float in[PYR][8];
@@ -519,30 +492,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HV ? 2 : 1,
     }
       }
   }
-#undef V2_ISSUE
   if (nc == nullptr) return;
   if constexpr (HV) {   // a lane holds four channels: the 32 lanes of each half of the wave are summed
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float r1 = s1[j], r2 = s2[j];
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) { r1 += __shfl_xor(r1, o, 64); r2 += __shfl_xor(r2, o, 64); }
-      const int c = cbase + (lane >> 5) * 4 + j;
-      if ((lane & 31) == 0 && c < g.C) {
-        atomicAdd(nc + ((size_t)b * g.Cp + c) * 2, (double)r1);
-        atomicAdd(nc + ((size_t)b * g.Cp + c) * 2 + 1, (double)r2);
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float r1 = wave_sum(s1[j]), r2 = wave_sum(s2[j]);
-    const int c = cbase + j;
-    if (lane == 0 && c < g.C) {
-      atomicAdd(nc + ((size_t)b * g.Cp + c) * 2, (double)r1);
-      atomicAdd(nc + ((size_t)b * g.Cp + c) * 2 + 1, (double)r2);
-    }
+    DWF_FLUSH(4, 32, cbase + (lane >> 5) * 4)
+  } else {
+    DWF_FLUSH(8, 64, cbase)
   }
 }
 
@@ -609,7 +563,7 @@ template <int TT> struct V2S2Geo {
   static constexpr int PAR = S2_HY * S2_HX;                     // float4 units per (frame, parity) plane
   static constexpr int PLANE = TT * 4 * PAR + 1;                // per (channel vector, half vector)
   static constexpr int NI = TT * S2_IH * S2_IW * DW_CV;         // staged 8-channel vectors per tile
-  static constexpr int SL = (NI + 255) / 256;
+  static constexpr int IH = S2_IH, IW = S2_IW, OY = 2 * S2_TH, OX = 2 * S2_TW, XB = 6, RS = 3;   // (see V2Geo)
 };
 
 // PK: packed slot descriptors, as in dw_fwd_v2_kernel (14 slots here: their per-tile decode was more VALU instructions than
@@ -624,16 +578,11 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void dw_fwd_v2s2_kernel(const T* __
                                                           const float* __restrict__ w, T* __restrict__ y,
                                                           double* __restrict__ nc, const DwGeom g,
                                                           const int tiles_per_wg, const c3d_bn_fin fin) {
-  typedef RawD<T> RW;
+  typedef Raw8<T> RW;
   typedef V2S2Geo<TT> G;
   constexpr int NTHR = W8 ? 512 : 256;
   constexpr int NI = G::NI, SL = (G::NI + NTHR - 1) / NTHR, PLANE = G::PLANE, PAR = G::PAR;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* wl = reinterpret_cast<float*>(smem);                  // [27][32]
-  float* fss = wl + 27 * 32;                                   // [2][32] scale | shift of this chunk (fin.sums mode)
-  float4* tile = reinterpret_cast<float4*>(fss + 64);          // [4 cv][2 halves][PLANE]
-
-  const int tid = threadIdx.x, lane = tid & 63;
+  DWF_HEAD
   const int wave_ = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wcv = wave_ & 3;                                   // this wave's channel vector
   [[maybe_unused]] const int whalf = wave_ >> 2;               // W8: its half of the vector (0 with four waves)
@@ -641,87 +590,14 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void dw_fwd_v2s2_kernel(const T* __
   // ds_read_b128 lane group joins (rows S2_HX = 17 float4 apart) fall on 16 distinct bank quads (see dw_fwd_v2_kernel)
   const int ly = lane >> 4;
   const int lx = (lane + (ly & 1) * ((16 - S2_HX % 16) & 15)) & 15;
-  const int tiles_x = (g.Wo + S2_TW - 1) / S2_TW, tiles_y = (g.Ho + S2_TH - 1) / S2_TH;
-  const int ntiles = tiles_x * tiles_y;
-  const int gx = (ntiles + tiles_per_wg - 1) / tiles_per_wg;
-  const ChunkOrder co = chunk_order((g.Cp + DW_CV * 8 - 1) / (DW_CV * 8), gx * g.B);
-  if (co.group < 0) return;
-  const int chunk = co.chunk, b = co.group / gx, tg = co.group % gx;
-  const int c0 = chunk * DW_CV * 8;
-  const int scv = tid & 3;              // staging role: item i = tid + 256*slot -> (cv = i & 3, pixel = i >> 2)
-  const int sbase = c0 + scv * 8;
-  const bool s_ok = sbase < g.Cp;
-  const int cbase = c0 + wcv * 8;       // compute role
-  const bool c_ok = cbase < g.Cp;
-
-  for (int i = tid; i < 27 * 32; i += NTHR) {
-    const int tap = i / 32, c = c0 + (i & 31);
-    wl[i] = (c < g.C) ? w[(size_t)c * 27 + tap] : 0.f;
-  }
-  float s1[8], s2[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-
-  // per-slot constants of the staging role: offset inside the input tile (global) and inside the parity planes (LDS)
-  typename RW::type raw[SL];
-  unsigned vmask = 0;
-  unsigned dsc[PK ? SL : 1];   // (rel / 8) << 11 | valid << 10 | ix << 4 | iy   (rel is a multiple of 8 elements)
-  if constexpr (PK) {
-#pragma unroll
-    for (int sl = 0; sl < SL; ++sl) {
-      const int i_ = tid + sl * NTHR;
-      const int p_ = i_ >> 2;
-      const int ix_ = p_ % S2_IW, q_ = p_ / S2_IW;
-      const int iy_ = q_ % S2_IH, t_ = q_ / S2_IH;
-      const bool ok_ = i_ < NI && s_ok && t_ < g.T;
-      const unsigned rel_ = (unsigned)(((t_ * g.H + iy_) * g.W + ix_) * g.Cp + sbase);
-      dsc[sl] = ok_ ? ((rel_ >> 3) << 11) | 1024u | ((unsigned)ix_ << 4) | (unsigned)iy_ : 0u;
-    }
-  }
-#define S2_ISSUE(TL)                                                                            \
-  if constexpr (PK) {                                                                           \
-    const int tx_ = (TL) % tiles_x, ty_ = (TL) / tiles_x;                                       \
-    const int by_ = ty_ * (2 * S2_TH) - 1, bx_ = tx_ * (2 * S2_TW) - 1;                         \
-    const T* xt_ = x + (ptrdiff_t)(((b * g.T * g.H + by_) * g.W + bx_) * g.Cp);   /* wave-uniform */ \
-    vmask = 0;                                                                                  \
-    _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                         \
-      const unsigned d_ = dsc[sl];                                                              \
-      const unsigned gy_ = (unsigned)(by_ + (int)(d_ & 15u)), gx_ = (unsigned)(bx_ + (int)((d_ >> 4) & 63u)); \
-      if ((d_ & 1024u) && gy_ < (unsigned)g.H && gx_ < (unsigned)g.W) {                         \
-        raw[sl] = RW::load(xt_ + ((d_ >> 11) << 3));                                            \
-        vmask |= 1u << sl;                                                                      \
-      }                                                                                         \
-    }                                                                                           \
-  } else {                                                                                      \
-    const int tx_ = (TL) % tiles_x, ty_ = (TL) / tiles_x;                                       \
-    vmask = 0;                                                                                  \
-    _Pragma("unroll") for (int sl = 0; sl < SL; ++sl) {                                         \
-      const int i_ = tid + sl * NTHR;                                                           \
-      const int p_ = i_ >> 2;                                                                   \
-      const int ix_ = p_ % S2_IW, q_ = p_ / S2_IW;                                              \
-      const int iy_ = q_ % S2_IH, t_ = q_ / S2_IH;                                              \
-      const int gy_ = ty_ * (2 * S2_TH) - 1 + iy_, gx_ = tx_ * (2 * S2_TW) - 1 + ix_;           \
-      if (i_ < NI && s_ok && t_ < g.T && gy_ >= 0 && gy_ < g.H && gx_ >= 0 && gx_ < g.W) {     \
-        raw[sl] = RW::load(x + ((((size_t)b * g.T + t_) * g.H + gy_) * g.W + gx_) * g.Cp + sbase); \
-        vmask |= 1u << sl;                                                                      \
-      }                                                                                         \
-    }                                                                                           \
-  }
+  DWF_ROLES(NTHR, (g.Wo + S2_TW - 1) / S2_TW, (g.Ho + S2_TH - 1) / S2_TH)
+  DWF_SLOTS(G, NTHR)
 
   const int tl0 = tg * tiles_per_wg;
   int tl1 = tl0 + tiles_per_wg;
   if (tl1 > ntiles) tl1 = ntiles;
-  if (tl0 < tl1) S2_ISSUE(tl0)
-  float sc[8], sh[8];
-  if (fin.sums) {   // BatchNorm_a scale / shift rebuilt from conv_a's completed sums (csrc/bn_fin.h), as in the stride-1 kernel
-    if (tid == 0 && co.chunk == 0 && co.group == 0 && fin.training && fin.nbt) *fin.nbt += 1;
-    c3dfin::bn_consume(fin, g.C, g.Cp, c0, 32, co.group == 0, fss, fss + 32, tid, NTHR);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sc[j] = s_ok ? fss[scv * 8 + j] : 0.f; sh[j] = s_ok ? fss[32 + scv * 8 + j] : 0.f; }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sc[j] = s_ok ? ss[sbase + j] : 0.f; sh[j] = s_ok ? ss[g.Cp + sbase + j] : 0.f; }
-  }
+  if (tl0 < tl1) DWF_ISSUE(G, NTHR, tl0)
+  DWF_SCALE_SHIFT(NTHR)
   for (int tl = tl0; tl < tl1; ++tl) {
     const int tx = tl % tiles_x, ty = tl / tiles_x;
     __syncthreads();
@@ -746,7 +622,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void dw_fwd_v2s2_kernel(const T* __
         tile[(scv * 2 + 1) * PLANE + d] = make_float4(f[4], f[5], f[6], f[7]);
       }
     }
-    if (tl + 1 < tl1) S2_ISSUE(tl + 1)
+    if (tl + 1 < tl1) DWF_ISSUE(G, NTHR, tl + 1)
     __syncthreads();
 
     if constexpr (W8) {
@@ -815,7 +691,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void dw_fwd_v2s2_kernel(const T* __
       for (int kx = 0; kx < 3; ++kx) {
         float wk[3][8];  // wave-uniform: broadcast LDS reads
 #pragma unroll
-        for (int kt = 0; kt < 3; ++kt) lds_ld8v2(wl + (kt * 9 + ky * 3 + kx) * 32 + wcv * 8, wk[kt]);
+        for (int kt = 0; kt < 3; ++kt) lds8(wl + (kt * 9 + ky * 3 + kx) * 32 + wcv * 8, wk[kt]);
         const int off = ((ky & 1) * 2 + (kx & 1)) * PAR + (ky >> 1) * S2_HX + (kx >> 1);   // compile-time immediate
 #pragma unroll
         for (int ti = 0; ti < TT; ++ti) {
@@ -850,17 +726,8 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void dw_fwd_v2s2_kernel(const T* __
     }
       }
   }
-#undef S2_ISSUE
   if (nc == nullptr) return;
-#pragma unroll
-  for (int j = 0; j < (W8 ? 4 : 8); ++j) {
-    const float r1 = wave_sum(s1[j]), r2 = wave_sum(s2[j]);
-    const int c = cbase + (W8 ? whalf * 4 : 0) + j;
-    if (lane == 0 && c < g.C) {
-      atomicAdd(nc + ((size_t)b * g.Cp + c) * 2, (double)r1);
-      atomicAdd(nc + ((size_t)b * g.Cp + c) * 2 + 1, (double)r2);
-    }
-  }
+  DWF_FLUSH(W8 ? 4 : 8, 64, cbase + (W8 ? whalf * 4 : 0))
 }
 
 template <typename T, int TT>

@@ -1223,6 +1223,73 @@ def test_bn_b_finalize_folded_into_conv_c_and_fused_depthwise_backward_is_bit_id
     close(res[1]["dw"], res[0]["dw"], dtype, "dw (f32 atomics)", scale=res[0]["dw"].abs().max().item())
 
 
+@pytest.mark.parametrize("B,C", [(5, 54), (3, 108)])
+def test_bn_b_backward_coefficients_rebuilt_by_every_bf16_depthwise_backward_kernel(B, C):
+    """The folded BatchNorm_b coefficient rebuild (fin.sums) is part of the parameter staging that the register-prefetch and the
+    LDS-DMA ring kernels share; in bf16 only the ring kernel of the default option ran it under a test.  c3d_dw333_bwd_fused_fin
+    under C3D_OPT_DW_RING = 0 (register prefetch), 9 (ring, requests in a burst) and 13 (ring, requests spread): t2, the
+    BatchNorm_a sums, d gamma and d beta are bit-equal across the three kernels and to c3d_se_bn_bwd_coef +
+    c3d_dw333_bwd_fused; the weight gradient (f32 atomics) as in the test above."""
+    _need_gpu()
+    from change3d_amd import ops
+    dtype = torch.bfloat16
+    T, H, W = 3, 16, 24
+    Cp = ops.cpad(C)
+    dt = ops.dt_code(dtype)
+    rps = T * H * W
+    M = B * rps
+    bt = padc(q(rnd((M, C), 300), dtype), Cp).to(DEV, dtype).contiguous()
+    nc = torch.zeros(B, Cp, 2, dtype=torch.float64, device=DEV)
+    bq = bt.float().double().view(B, rps, Cp)
+    nc[:, :, 0], nc[:, :, 1] = bq.sum(1), (bq * bq).sum(1)
+
+    def bn_module():
+        m = torch.nn.BatchNorm3d(C).to(DEV)
+        with torch.no_grad():
+            m.weight.copy_(rnd((C,), 310).abs() + 0.5); m.bias.copy_(rnd((C,), 311, 0.3))
+            m.running_mean.copy_(rnd((C,), 312, 0.2)); m.running_var.copy_(rnd((C,), 313).abs() + 0.5)
+        return m
+
+    ss_b, mr_b = torch.zeros(2 * Cp, device=DEV), torch.zeros(2 * Cp, device=DEV)
+    ops.bn_se_finalize(nc.view(-1), B, rps, bn_module(), None, C, ss_b, mr_b, None, None, True)
+    a = padc(q(rnd((B, T, H, W, C), 320), dtype), Cp).to(DEV, dtype).contiguous()
+    b5 = bt.view(B, T, H, W, Cp)
+    t1 = padc(q(rnd((B, T, H, W, C), 321), dtype), Cp).to(DEV, dtype).contiguous()
+    nc3 = torch.zeros(B, Cp, 3, dtype=torch.float64, device=DEV)
+    nc3[:, :C] = rnd((B, C, 3), 322).double().to(DEV) * 50.0
+    wd = rnd((C, 1, 3, 3, 3), 323, 0.3).to(DEV).contiguous()
+    ssa = torch.cat([padc(rnd((C,), 324).abs() + 0.5, Cp), padc(rnd((C,), 325, 0.3), Cp)]).to(DEV)
+    mra = torch.cat([padc(rnd((C,), 326, 0.5), Cp), padc(rnd((C,), 327).abs() + 0.5, Cp)]).to(DEV)
+    res, names = {}, {}
+    try:
+        for leg in ("unfolded", 0, 9, 13):
+            ops.set_option(ops.OPT_DW_RING, 13 if leg == "unfolded" else leg)
+            m = bn_module()
+            t2 = torch.full_like(a, float("nan"))
+            dsums = torch.zeros(2 * C, dtype=torch.float64, device=DEV)
+            dw = torch.zeros((C, 27), dtype=torch.float32, device=DEV)
+            if leg == "unfolded":
+                cA, cC, cB = torch.zeros(Cp, device=DEV), torch.zeros(Cp, device=DEV), torch.zeros(B * Cp, device=DEV)
+                ops.se_bn_bwd_coef(nc3.view(-1), nc.view(-1), B, rps, m, mr_b, ss_b, None, None, None, C, cA, cC, cB)
+                ops.dw_bwd_fused(t1, b5, cA, cB, cC, wd, a, ssa, mra, t2, dsums, dw, B, T, H, W, C, dt)
+            else:
+                ops.dw_bwd_fused_fin(t1, b5, ops.fin_b_bwd(nc3, B, m, float(M), mr_b), wd, a, ssa, mra, t2, dsums, dw, B, T, H, W, C, dt)
+            names[leg] = ops.last_kernel()
+            torch.cuda.synchronize()
+            res[leg] = dict(t2=t2, dsums=dsums, dgamma=m.weight.grad.clone(), dbeta=m.bias.grad.clone(), dw=dw)
+    finally:
+        ops.set_option(ops.OPT_DW_RING, 13)
+    assert names[0] == "dw_bwd_fused_kernel<unsigned short, 3, 1>", names
+    assert names[9] == "dw_bwd_ring_kernel<3, false>" and names[13] == "dw_bwd_ring_kernel<3, true>", names
+    assert names["unfolded"] == names[13], names
+    ref = res["unfolded"]
+    assert torch.isfinite(ref["t2"].float()).all() and float(ref["dgamma"].abs().max()) > 0
+    for leg in (0, 9, 13):
+        for k in ("t2", "dsums", "dgamma", "dbeta"):
+            assert torch.equal(ref[k], res[leg][k]), f"OPT_DW_RING {leg}: {k} differs"
+        close(res[leg]["dw"], ref["dw"], dtype, f"dw (f32 atomics), OPT_DW_RING {leg}", scale=ref["dw"].abs().max().item())
+
+
 def test_block_out_bwd_refuses_misaligned_parameter_vectors():
     """c3d_block_out_bwd reads the mean | rstd rows as 16-byte vectors (one round trip instead of eight dependent ones, round 5):
     a misaligned `mr_c` is an argument error, not a fault."""
