@@ -1,11 +1,13 @@
 """Pins tests/hotpath_reference.py: at small shapes every float64 restatement, with the bf16 rounding step switched off,
 equals torch.autograd through F.conv3d / F.batch_norm / the same composition in float64 to 1e-10 -- forward and every
 gradient.  The GPU tests compare kernels with these functions; a wrong restatement must not be able to agree with a wrong
-kernel by construction."""
+kernel by construction.  The same for tests/decoder_reference.py (transposed convolution, 3x3 head, stem conv_xy backward)
+against F.conv_transpose2d / F.conv2d / F.conv3d, at two small ragged shapes each."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+import decoder_reference as D
 import hotpath_reference as R
 
 TOL = 1e-10
@@ -232,3 +234,74 @@ def test_se_and_batchnorm_b_backward_equal_autograd(B, rows, C, Cr, se):
         assert bool((err > 0).any()) == (se and name != "coefA"), name        # only the SE chain is f32 in front of these
     if not se:
         assert torch.equal(r["coefB"][0], r["coefB"][0][:1].expand(B, C))      # one B for every sample
+
+
+# ------------------------------------------------------------------------------------------------ tests/decoder_reference.py
+def _mag_ok(val, mag):
+    assert (mag >= val.abs() - 1e-12).all()
+
+
+@pytest.mark.parametrize("C,B,h,wd", [(3, 2, 5, 7), (5, 1, 1, 6)])
+def test_convT_restatements_equal_autograd(C, B, h, wd):
+    x = rnd((B, h, wd, C), 100).requires_grad_(True)
+    w = rnd((C, C, 4, 4), 101, 0.3).requires_grad_(True)
+    bias, skip, dout = rnd((C,), 102), rnd((B, 2 * h, 2 * wd, C), 103), rnd((B, 2 * h, 2 * wd, C), 104)
+    y = F.conv_transpose2d(x.permute(0, 3, 1, 2), w, bias, stride=2, padding=1).permute(0, 2, 3, 1) + skip
+    y.backward(dout)
+    o, m = D.convt4s2_fwd(x.detach(), w.detach(), bias, skip, rounded=False)
+    same(o, y.detach(), "convT forward")
+    _mag_ok(o, m)
+    o2, _ = D.convt4s2_fwd(x.detach(), w.detach(), bias, None, rounded=False)
+    same(o2, y.detach() - skip, "convT forward without skip")
+    d, m = D.convt4s2_dgrad(dout, w.detach(), rounded=False)
+    same(d, x.grad, "convT data gradient")
+    _mag_ok(d, m)
+    g, m = D.convt4s2_wgrad(x.detach(), dout)
+    same(g, w.grad, "convT weight gradient")
+    _mag_ok(g, m)
+    orr, _ = D.convt4s2_fwd(x.detach(), w.detach(), bias, skip)                    # rounded weights: 2^-9 per product
+    assert ((orr - o).abs() <= 2.0 ** -9 * D.convt4s2_fwd(x.detach(), w.detach(), bias, skip, rounded=False)[1]).all() and not torch.equal(orr, o)
+
+
+@pytest.mark.parametrize("NC,sig,B,H,W", [(1, True, 2, 5, 7), (3, False, 1, 4, 9)])
+def test_head_restatements_equal_autograd(NC, sig, B, H, W):
+    C = 4
+    x = rnd((B, H, W, C), 110).requires_grad_(True)
+    w = rnd((NC, C, 3, 3), 111, 0.3).requires_grad_(True)
+    dout = rnd((B, NC, H, W), 112)
+    lg = F.conv2d(x.permute(0, 3, 1, 2), w, padding=1)
+    y = torch.sigmoid(lg) if sig else lg
+    y.backward(dout)
+    o, l, m = D.head3x3_fwd(x.detach(), w.detach(), sig, rounded=False)
+    same(o, y.detach(), "head forward")
+    same(l, lg.detach(), "head logits")
+    _mag_ok(l, m)
+    dx, dxm, dxs, dw, dwm, dws = D.head3x3_bwd(dout, o if sig else None, x.detach(), w.detach(), sig, rounded=False)
+    same(dx, x.grad, "head data gradient")
+    same(dw, w.grad, "head weight gradient")
+    _mag_ok(dx, dxm)
+    _mag_ok(dw, dwm)
+    assert (dxs == 0).all() and (dws == 0).all()
+    dxr, _, dxs, dwr, _, dws = D.head3x3_bwd(dout, o if sig else None, x.detach(), w.detach(), sig)
+    assert ((dxr - dx).abs() <= 2.0 ** -7 * dxm).all() and ((dwr - dw).abs() <= 2.0 ** -8 * dwm).all() and not torch.equal(dxr, dx)
+    assert (dxs >= 0).all() and (dws >= 0).all()
+
+
+@pytest.mark.parametrize("B,T,H,W,t_first,n_frames", [(2, 3, 5, 7, 1, 1), (3, 5, 4, 9, 1, 3)])
+def test_stem_wx_restatement_equals_autograd(B, T, H, W, t_first, n_frames):
+    x = rnd((B, 3, T, H, W), 120).requires_grad_(True)
+    w = rnd((24, 3, 1, 3, 3), 121, 0.3).requires_grad_(True)
+    dv = rnd((B, T, H, W, 24), 122)
+    v = F.conv3d(x, w, padding=(0, 1, 1))
+    v.backward(dv.permute(0, 4, 1, 2, 3))
+    for per_sample in (True, False):
+        out = D.stem_wx(x.detach(), w.detach(), dv, t_first, n_frames, per_sample)
+        dw, dwm, dp, dpm = out["unrounded"]
+        same(dw, w.grad.reshape(24, 27), "stem dW_t")
+        ref = x.grad[:, :, t_first:t_first + n_frames]
+        same(dp, ref if per_sample else ref.sum(0), "stem dP")
+        _mag_ok(dw, dwm)
+        _mag_ok(dp, dpm)
+        dwr, _, dpr, _ = out["rounded"]
+        assert ((dwr - dw).abs() <= 2.0 ** -9 * dwm).all() and ((dpr - dp).abs() <= 2.0 ** -9 * dpm).all() and not torch.equal(dwr, dw)
+    assert D.stem_wx(x.detach(), w.detach(), dv, 0, 0, False)["unrounded"][2] is None

@@ -911,6 +911,162 @@ def test_scd_losses_vs_torch():
     assert torch.isnan(CrossEntropyLoss2d(ignore_index=0)(pd.detach(), z.to(DEV))).item()
 
 
+# ---- the same kernels where their grid-stride loops wrap (csrc/train_ops.hip: bce_dice_reduce_kernel and confusion_kernel run
+# at most 1024 x 256 threads, ce2d_reduce / cossim_reduce 2048 x 256, the backward kernels and adam_kernel 4096 x 256; the cases
+# above stay inside one pass).  u = 2^-24, one f32 rounding; "1 ulp" of a library function is 2 u of its value.
+U32 = 2.0 ** -24
+
+
+def test_bce_dice_and_confusion_where_the_grid_stride_loops_wrap():
+    """n = 3 x 262 144 + 77: every thread of the reduce kernels takes three elements, 77 of them a fourth.  Against float64 of the
+    same f32 inputs.  Loss: a term (t - 1) log(1 - p) - t log p is computed in f32 -- logf 1 ulp, the product and the difference
+    one rounding each: 4 u of |t log p| + |(1 - t) log(1 - p)|, and 1 - p is rounded before the logarithm, u of 1 - p, which moves
+    log(1 - p) by u; the sums are double; the finalize kernel rounds bce, the three dice sums, and adds / divides in f32: 16 u of
+    |bce| + 1 + dice.  Gradient: (p - t) / max((1 - p) p, 1e-12) / n - (2 t / D - N / D^2): eight f32 roundings in each half."""
+    _need_gpu()
+    from change3d_amd import ops
+    n = 262144 * 3 + 77
+    p = torch.sigmoid(rnd((n,), 70, 3.0))
+    p[0], p[1], p[n - 1], p[n - 2] = 1.0, 0.0, 1.0, 0.0         # saturated probabilities exercise the clamps, in the first and the last pass
+    p[5:13] = 0.5                                                # strict '>' 0.5 in the confusion matrix
+    t = (rnd((n,), 71) > 0.8).float()
+    t[0], t[1], t[n - 1], t[n - 2] = 0.0, 1.0, 1.0, 0.0
+    pd, td = p.to(DEV), t.to(DEV)
+    sums4 = torch.zeros(4, dtype=torch.float64, device=DEV)
+    loss = torch.full((1,), float("nan"), device=DEV)
+    ops.bce_dice_fwd(pd, td, sums4, loss)
+    dprob = torch.full((n,), float("nan"), device=DEV)
+    dloss = torch.full((1,), 0.75, device=DEV)
+    ops.bce_dice_bwd(pd, td, sums4, dloss, dprob)
+    cm = torch.zeros(4, dtype=torch.int64, device=DEV)
+    ops.confusion2(pd, td, cm)
+    torch.cuda.synchronize()
+    P, T = p.double(), t.double()
+    lp, l1p = torch.log(P).clamp_min(-100.0), torch.log(1 - P).clamp_min(-100.0)
+    term_mag = (T * lp).abs() + ((1 - T) * l1p).abs()
+    bce = ((T - 1) * l1p - T * lp).mean()
+    inter, sp, st = (P * T).sum(), P.sum(), T.sum()
+    Dn, Nn = sp + st + 1e-5, 2 * inter + 1e-5
+    ref = bce + 1 - Nn / Dn
+    tol = (4 * U32 * term_mag + U32).mean() + 16 * U32 * (bce.abs() + 1 + Nn / Dn)
+    print(f"\nLOSS-WRAP bce_dice loss error/bound {abs(loss.item() - ref.item()) / tol.item():.3f}")
+    assert abs(loss.item() - ref.item()) <= tol.item(), (loss.item(), ref.item(), tol.item())
+    gb = (P - T) / ((1 - P) * P).clamp_min(1e-12) / n
+    gd = 2 * T / Dn - Nn / (Dn * Dn)
+    gref = 0.75 * (gb - gd)
+    gtol = 0.75 * 16 * U32 * (gb.abs() + (2 * T / Dn).abs() + Nn / (Dn * Dn))
+    err = (dprob.cpu().double() - gref).abs()
+    print(f"LOSS-WRAP bce_dice gradient worst error/bound {(err / gtol).max().item():.3f}")
+    assert bool((err <= gtol).all()), (err / gtol).max()
+    pred = (p > 0.5).long()
+    cm_ref = torch.bincount((2 * t.long() + pred), minlength=4)
+    assert torch.equal(cm.cpu(), cm_ref), (cm, cm_ref)
+
+
+def test_scd_losses_where_the_grid_stride_loops_wrap():
+    """B x HW = 3 x 592 x 592 = 1 051 392 pixels, just above the 2 x 524 288 the reduce kernels cover in two passes (and above the
+    1 048 576 of the backward kernels): some threads take a third pixel (a second one in the backward).  NC = 7 on views whose
+    channel AND batch strides differ from a dense tensor's (rows 0 .. H - 1 of channels 1 .. 7 of a [B][8][H + 1][W] tensor).
+    Gradients per element against float64 autograd.  A softmax value p_c carries r = (16 + 2 max_c |x_c - max|) u <= 64 u (the
+    difference is rounded before expf (2 ulp), seven additions, a reciprocal, a product).  Cross entropy: scale (p_c - onehot):
+    scale (r p_c + 4 u |p_c - onehot|).  ChangeSimilarity: dot, |p1|^2, |p2|^2 are 8-term fma sums of such values (2 r + 8 u each),
+    den = sqrt(n1 n2) and cos = dot / den follow (4 r + 19 u), g_c = gcos (p2_c / den - cos p1_c / n1) has (6 r + 30 u) of the
+    magnitude G_c = |gcos| (p2_c / den + |cos| p1_c / n1), a = sum g_c p1_c adds (r + 8 u) of A = sum G_c p1_c, and
+    d_c = p1_c (g_c - a) one more r + 2 u of p1_c (G_c + A)."""
+    _need_gpu()
+    from change3d_amd import ops
+    B, NC, H, W = 3, 7, 592, 592
+    assert 2 * 524288 < B * H * W < 2 * 524288 + 4096
+    full1, full2 = rnd((B, NC + 1, H + 1, W), 310, 2.0).to(DEV), rnd((B, NC + 1, H + 1, W), 311, 2.0).to(DEV)
+    x1, x2 = full1[:, 1:, :H], full2[:, 1:, :H]
+    assert x1.stride(1) != H * W and x1.stride(0) != NC * H * W
+    g = np.random.default_rng(312)
+    chg = torch.from_numpy((g.random((B, H, W)) < 0.3).astype(np.int64))
+    lab = (torch.from_numpy(g.integers(0, NC, size=(B, H, W))).long() * chg).to(DEV)
+    chg = chg.to(DEV)
+    # ---- device
+    sums2, ce = torch.zeros(2, dtype=torch.float64, device=DEV), torch.full((1,), float("nan"), device=DEV)
+    ops.ce2d_fwd(x1, lab, 0, sums2, ce)
+    dl = torch.full((1,), 0.5, device=DEV)
+    dce = torch.full((B, NC, H, W), float("nan"), device=DEV)
+    ops.ce2d_bwd(x1, lab, 0, sums2, dl, dce)
+    sums1, sim = torch.zeros(1, dtype=torch.float64, device=DEV), torch.full((1,), float("nan"), device=DEV)
+    ops.cossim_fwd(x1, x2, chg.reshape(B, -1), sums1, sim)
+    d2 = torch.full((1,), 2.0, device=DEV)
+    dx1, dx2 = torch.full((B, NC, H, W), float("nan"), device=DEV), torch.full((B, NC, H, W), float("nan"), device=DEV)
+    ops.cossim_bwd(x1, x2, chg.reshape(B, -1), d2, dx1, dx2)
+    torch.cuda.synchronize()
+    # ---- float64 autograd, on the device
+    a, b = x1.double().clone().requires_grad_(True), x2.double().clone().requires_grad_(True)
+    ce_ref = F.nll_loss(F.log_softmax(a, 1), lab, ignore_index=0)
+    (0.5 * ce_ref).backward()
+    ce_grad = a.grad.clone()
+    a.grad = None
+    p1 = F.softmax(a, 1).permute(0, 2, 3, 1).reshape(-1, NC)
+    p2 = F.softmax(b, 1).permute(0, 2, 3, 1).reshape(-1, NC)
+    tgt = ((~chg.bool()).double() - chg.double()).reshape(-1)
+    sim_ref = F.cosine_embedding_loss(p1, p2, tgt, margin=0.0)
+    (2.0 * sim_ref).backward()
+    assert abs(ce.item() - ce_ref.item()) < 2e-6 * max(1.0, abs(ce_ref.item()))
+    assert abs(sim.item() - sim_ref.item()) < 2e-6
+    with torch.no_grad():
+        md = max((a.max(1).values - a.min(1).values).max().item(), (b.max(1).values - b.min(1).values).max().item())
+        assert md <= 24.0, md
+        r = 64 * U32
+        count = (lab != 0).sum().double()
+        sm = F.softmax(a, 1)
+        onehot = F.one_hot(lab, NC).permute(0, 3, 1, 2).double()
+        live = (lab != 0).unsqueeze(1).double()
+        tol = 0.5 / count * (r * sm + 4 * U32 * (sm - onehot).abs()) * live
+        err = (dce.double() - ce_grad).abs()
+        assert bool((dce[(lab == 0).unsqueeze(1).expand_as(dce)] == 0).all())
+        worst = (err[tol > 0] / tol[tol > 0]).max().item()
+        print(f"\nLOSS-WRAP ce2d gradient worst error/bound {worst:.3f}")
+        assert bool((err <= tol).all()), worst
+        q1, q2 = F.softmax(a, 1), F.softmax(b, 1)                       # [B][NC][H][W]
+        dot, n1, n2 = (q1 * q2).sum(1, keepdim=True), (q1 * q1).sum(1, keepdim=True) + 1e-12, (q2 * q2).sum(1, keepdim=True) + 1e-12
+        den = torch.sqrt(n1 * n2)
+        cs = dot / den
+        gcos = 2.0 / (B * H * W)
+        for name, dev, grad, pa, pb, na in (("d x1", dx1, a.grad, q1, q2, n1), ("d x2", dx2, b.grad, q2, q1, n2)):
+            G = gcos * (pb / den + cs.abs() * pa / na)
+            A = (G * pa).sum(1, keepdim=True)
+            eg = (6 * r + 30 * U32) * G
+            ea = (eg * pa).sum(1, keepdim=True) + (r + 8 * U32) * A
+            tol = pa * (eg + ea) + (r + 2 * U32) * pa * (G + A)
+            err = (dev.double() - grad).abs()
+            worst = (err / tol).max().item()
+            print(f"LOSS-WRAP cossim gradient {name} worst error/bound {worst:.3f}")
+            assert bool((err <= tol).all()), (name, worst)
+
+
+def test_adam_where_the_grid_stride_loop_wraps_with_host_and_device_hyper_parameters():
+    """n = 2 x 1 048 576 + 333: adam_kernel runs 4096 x 256 threads, every one takes two elements and 333 a third.  Three steps,
+    once with lr / bias corrections as host arguments and once through hparams_dev (the leg the captured step uses): the two runs
+    are bit-identical, and both meet the tolerance test_bce_dice_and_adam uses against torch.optim.Adam."""
+    _need_gpu()
+    from change3d_amd import ops
+    n = 1048576 * 2 + 333
+    w0, g0 = rnd((n,), 64), rnd((n,), 65)
+    wr = torch.nn.Parameter(w0.clone())
+    opt = torch.optim.Adam([wr], 2e-4, (0.9, 0.99), eps=1e-8, weight_decay=1e-4)
+    state = [(w0.to(DEV), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)) for _ in range(2)]
+    for step in range(1, 4):
+        wr.grad = g0 * step
+        opt.step()
+        bc1, bc2 = 1 - 0.9 ** step, 1 - 0.99 ** step
+        gd = (g0 * step).to(DEV)
+        (wa, ma, va), (wb, mb, vb) = state
+        ops.adam_step(wa, gd, ma, va, n, None, 2e-4, bc1, bc2 ** 0.5, 0.9, 0.99, 1e-8, 1e-4)
+        hp = torch.tensor([2e-4, bc1, bc2 ** 0.5], dtype=torch.float32, device=DEV)
+        ops.adam_step(wb, gd, mb, vb, n, hp, 0.0, 1.0, 1.0, 0.9, 0.99, 1e-8, 1e-4)       # the host values must be ignored
+    torch.cuda.synchronize()
+    for ta, tb in zip(*state):
+        assert torch.equal(ta, tb)
+    for wd in (state[0][0], state[1][0]):
+        assert torch.allclose(wd.cpu(), wr.detach(), rtol=1e-6, atol=1e-7), (wd.cpu() - wr.detach()).abs().max()
+
+
 # --------------------------------------------------------------- consumer-side BatchNorm finalisation
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("C,T,stride,shape", [(54, 3, 1, (2, 16, 24)), (216, 3, 1, (3, 16, 16)), (108, 5, 1, (2, 16, 24)),
