@@ -1,0 +1,188 @@
+"""Whole-scene change maps: a trained model, a pair of co-registered images of any size, a change map back.
+
+The encoder's perception frames fix the model's input at `in_height x in_width`, so a scene is cut into overlapping tiles
+of that size, every tile runs through the folded-BatchNorm eval forward, and the per-tile outputs are blended back with a
+window.  The reference stops at `val()` over pre-cut crops (reference scripts/train_BCD.py:92-154, scripts/train_SCD.py:
+104-178); nothing there tiles a scene.  Here the scene is uploaded once as uint8 `[Hs, Ws, 6]` and stays in HBM:
+`c3d_scene_gather` cuts and normalises `batch` tiles per launch, `Trainer.update_bcd / update_scd` predicts them, and
+`c3d_scene_stitch` writes each strip of scene rows as soon as the tile rows that cover it exist, from a ring of
+`k = ceil(t / s)` tile rows.
+
+Geometry, per axis, for tile `t` and stride `s` (`1 <= s <= t`, `t - s` even): margin `m = (t - s) / 2`,
+`n = ceil(extent / s)` tiles, tile `i` starts at `i*s - m`.  Every scene pixel then lies in the central `s`-wide region of
+some tile.  Coordinates outside the scene fold back as `np.pad(mode="reflect")` does, for any overhang.
+
+BDA scenes are not wired up: its two heads are the same two output kinds (an argmax map and a thresholded map).
+"""
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .data.transforms import BCDTransforms
+
+AxisPlan = namedtuple("AxisPlan", "extent tile stride margin n k starts")
+WINDOWS = ("hann", "flat")
+
+
+def axis_plan(extent, tile, stride):
+    """Tiling of one axis: margin, tile count, ring depth and the (possibly negative) start of every tile."""
+    extent, tile, stride = int(extent), int(tile), int(stride)
+    if extent < 1 or tile < 1:
+        raise ValueError(f"extent and tile must be positive, got {extent} and {tile}")
+    if stride < 1 or stride > tile:
+        raise ValueError(f"stride must satisfy 1 <= stride <= tile = {tile}, got {stride}")
+    if (tile - stride) % 2:
+        raise ValueError(f"tile - stride must be even (the margin is (tile - stride) / 2), got {tile} - {stride}")
+    margin, n = (tile - stride) // 2, -(-extent // stride)
+    return AxisPlan(extent, tile, stride, margin, n, -(-tile // stride), np.arange(n, dtype=np.int64) * stride - margin)
+
+
+def reflect_index(coord, extent):
+    """numpy `reflect` for any overhang: period 2 * (extent - 1), the edge pixel is not repeated; extent 1 maps to 0."""
+    c = np.asarray(coord, dtype=np.int64)
+    if extent == 1:
+        return np.zeros_like(c)
+    period = 2 * (extent - 1)
+    c = np.mod(c, period)
+    return np.where(c >= extent, period - c, c)
+
+
+def window_vector(name, tile):
+    """One axis of the separable blending window, computed in float64 and rounded to f32 once: `flat` = ones, `hann` =
+    sin^2(pi * (i + 0.5) / tile), which is strictly positive."""
+    if name == "flat":
+        return np.ones(tile, dtype=np.float32)
+    if name == "hann":
+        return (np.sin(np.pi * (np.arange(tile, dtype=np.float64) + 0.5) / tile) ** 2).astype(np.float32)
+    raise ValueError(f"window must be one of {WINDOWS}, got {name!r}")
+
+
+def strip_rows(plan, row):
+    """Scene rows [y0, y1) that are final once tile row `row` exists: [row*s - m, (row+1)*s - m) clipped to the scene; the
+    last tile row also closes the scene.  Empty (y1 <= y0) while the margin still reaches above the scene."""
+    y0 = max(row * plan.stride - plan.margin, 0)
+    y1 = plan.extent if row == plan.n - 1 else min((row + 1) * plan.stride - plan.margin, plan.extent)
+    return y0, max(y1, y0)
+
+
+def upload_windows(window, th, tw, device):
+    return torch.from_numpy(window_vector(window, th)).to(device), torch.from_numpy(window_vector(window, tw)).to(device)
+
+
+class SceneStitcher:
+    """The ring of `k` tile rows of one output head and its strips: `put` copies predictions of consecutive tiles of one
+    tile row into the ring, `stitch(row)` writes the rows that row completed."""
+
+    def __init__(self, py, px, channels, window, device, blend=False, cls=True, windows=None):
+        """`windows` = (wy, wx) device vectors that are already uploaded (SceneInferencer keeps one pair per device)."""
+        self.py, self.px, self.C = py, px, int(channels)
+        nbytes = py.k * px.n * self.C * py.tile * px.tile * 4
+        if nbytes >= 2 ** 31:
+            raise L.Change3DHipError(f"the stitch ring needs {nbytes} bytes ({py.k} tile rows x {px.n} tiles x {self.C} channels): "
+                                     f"it must stay under 2 GiB; use a larger stride or split the scene into column bands")
+        self.ring = torch.empty((py.k, px.n, self.C, py.tile, px.tile), dtype=torch.float32, device=device)
+        self.wy, self.wx = windows if windows is not None else upload_windows(window, py.tile, px.tile, device)
+        self.blend = torch.empty((self.C, py.extent, px.extent), dtype=torch.float32, device=device) if blend else None
+        self.cls = torch.empty((py.extent, px.extent), dtype=torch.uint8, device=device) if cls else None
+
+    def put(self, row, col, values):
+        self.ring[row % self.py.k, col:col + values.shape[0]].copy_(values.reshape(values.shape[0], self.C, self.py.tile, self.px.tile))
+
+    def stitch(self, row, gate=None):
+        ops.scene_stitch(self.ring, self.wy, self.wx, self.blend, self.cls, self.py.extent, self.px.extent, self.C, self.py.tile,
+                         self.px.tile, self.py.stride, self.px.stride, row, gate=gate)
+
+
+class SceneInferencer:
+    """`SceneInferencer(model, task).predict(scene_u8)`: `task` is "bcd" or "scd", `stride` defaults to half the tile (an
+    int, or a (y, x) pair), `window` is "hann" or "flat", `batch` tiles go through the model per forward.
+
+    BCD returns `(prob f32 [Hs, Ws], mask u8 [Hs, Ws])` with mask = blended prob > 0.5.  SCD returns `(pre_cls, post_cls,
+    change)` u8 maps: the class maps are the argmax of the blended logits multiplied by the change mask, the reference's
+    validation post-processing (reference scripts/train_SCD.py:148-154).  All results stay on the device."""
+
+    def __init__(self, model, task, stride=None, window="hann", batch=32, mean=BCDTransforms.DEFAULT_MEAN,
+                 std=BCDTransforms.DEFAULT_STD):
+        if task not in ("bcd", "scd"):
+            raise ValueError(f"task must be 'bcd' or 'scd', got {task!r}")
+        if window not in WINDOWS:
+            raise ValueError(f"window must be one of {WINDOWS}, got {window!r}")
+        if int(batch) < 1:
+            raise ValueError("batch must be at least 1")
+        self.model, self.task, self.window, self.batch = model.eval(), task, window, int(batch)
+        self.th, self.tw = int(model.args.in_height), int(model.args.in_width)
+        sy, sx = (stride, stride) if not isinstance(stride, (tuple, list)) else stride
+        self.sy, self.sx = int(self.th // 2 if sy is None else sy), int(self.tw // 2 if sx is None else sx)
+        axis_plan(self.th, self.th, self.sy), axis_plan(self.tw, self.tw, self.sx)      # refuse a bad stride here
+        self.num_class = int(model.args.num_class)
+        self.mean, self.std = [float(v) for v in mean], [float(v) for v in std]
+        self._consts, self._origins = {}, {}             # device tables: uploaded once, not per scene
+
+    def _constants(self, dev):
+        """(mean, std, wy, wx) on `dev`: uploads from pageable memory block the host, so they happen once per device."""
+        if dev not in self._consts:
+            self._consts[dev] = (torch.tensor(self.mean, device=dev), torch.tensor(self.std, device=dev),
+                                 *upload_windows(self.window, self.th, self.tw, dev))
+        return self._consts[dev]
+
+    def _origin_table(self, py, px, dev):
+        """i32 [n, 2] of (y, x) tile starts in row-major tile order; one upload per scene size and device."""
+        key = (py.extent, px.extent, dev)
+        if key not in self._origins:
+            origins = np.stack([np.repeat(py.starts, px.n), np.tile(px.starts, py.n)], axis=1).astype(np.int32)
+            self._origins[key] = torch.from_numpy(origins).to(dev)
+        return self._origins[key]
+
+    def _device(self):
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise L.Change3DHipError(f"the model is on {dev}: whole-scene inference runs only as HIP kernels on an MI355X "
+                                     f"(no CPU fallback)")
+        return dev
+
+    @torch.no_grad()
+    def predict(self, scene_u8):
+        dev = self._device()
+        scene = torch.as_tensor(scene_u8)
+        if scene.dtype != torch.uint8 or scene.dim() != 3 or scene.shape[-1] != 6:
+            raise ValueError("scene must be uint8 [Hs, Ws, 6] (pre RGB | post RGB)")
+        L.lib()
+        scene = scene.to(dev).contiguous()                                            # the one upload
+        Hs, Ws = int(scene.shape[0]), int(scene.shape[1])
+        py, px = axis_plan(Hs, self.th, self.sy), axis_plan(Ws, self.tw, self.sx)
+        n = py.n * px.n
+        origins = self._origin_table(py, px, dev)
+        mean, std, wy, wx = self._constants(dev)
+        if self.task == "bcd":
+            heads = [SceneStitcher(py, px, 1, self.window, dev, blend=True, windows=(wy, wx))]
+        else:
+            heads = [SceneStitcher(py, px, C, self.window, dev, windows=(wy, wx)) for C in (self.num_class, self.num_class, 1)]
+        nb = min(self.batch, n)
+        pre = torch.empty((nb, 3, self.th, self.tw), dtype=torch.float32, device=dev)
+        post = torch.empty_like(pre)
+        for j0 in range(0, n, nb):
+            b = min(nb, n - j0)
+            ops.scene_gather(scene, origins[j0:j0 + b], mean, std, pre, post, Hs, Ws, b, self.th, self.tw)
+            out = self.model.update_bcd(pre[:b], post[:b]) if self.task == "bcd" else self.model.update_scd(pre[:b], post[:b])
+            outs = [out] if self.task == "bcd" else list(out)
+            j = j0
+            while j < j0 + b:                           # the batch, one tile row at a time: a strip goes out once its row is whole
+                row, col = divmod(j, px.n)
+                cnt = min(px.n - col, j0 + b - j)
+                for head, o in zip(heads, outs):
+                    head.put(row, col, o[j - j0:j - j0 + cnt].float())
+                if col + cnt == px.n:
+                    if self.task == "bcd":
+                        heads[0].stitch(row)
+                    else:
+                        heads[2].stitch(row)
+                        heads[0].stitch(row, gate=heads[2].cls)
+                        heads[1].stitch(row, gate=heads[2].cls)
+                j += cnt
+        torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
+        if self.task == "bcd":
+            return heads[0].blend[0], heads[0].cls
+        return heads[0].cls, heads[1].cls, heads[2].cls

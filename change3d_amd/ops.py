@@ -773,6 +773,23 @@ def augment_gather(store, label_store, table, mean6, std6, pre, post, label_a, l
             _p(mean6), _p(std6), _p(pre), _p(post), _p(label_a), _p(label_b), _p(scratch), task, N, Hs, Ws, B, H, W, _stream())
 
 
+def scene_gather(scene, origins, mean6, std6, pre, post, Hs, Ws, n, th, tw):
+    """c3d_scene_gather: `n` tiles of th x tw from the resident uint8 scene [Hs, Ws, 6]; `origins` is a DEVICE int32 [n, 2]
+    of (y, x), reflected where a tile overhangs."""
+    _launch("c3d_scene_gather", n * th * tw * (6 + 24), L.lib().c3d_scene_gather, _p(scene), _p(origins), _p(mean6), _p(std6),
+            _p(pre), _p(post), Hs, Ws, n, th, tw, _stream())
+
+
+def scene_stitch(ring, wy, wx, blend, cls, Hs, Ws, C, th, tw, sy, sx, row, gate=None):
+    """c3d_scene_stitch: the scene rows final after tile row `row` from the ring f32 [ky, ncols, C, th, tw] into `blend`
+    (f32 [C, Hs, Ws] or None) and `cls` (u8 [Hs, Ws] or None: mask for C == 1, argmax for C > 1, times the u8 map `gate`)."""
+    ky, kx = -(-th // max(sy, 1)), -(-tw // max(sx, 1))
+    rows = min(sy + (th - sy) // 2, Hs)
+    nbytes = rows * Ws * C * (ky * kx * 4 + (4 if blend is not None else 0)) + (rows * Ws if cls is not None else 0)
+    _launch("c3d_scene_stitch", nbytes, L.lib().c3d_scene_stitch, _p(ring), _p(wy), _p(wx), _p(blend), _p(cls), _p(gate), Hs, Ws,
+            C, th, tw, sy, sx, row, _stream())
+
+
 def build_clip(pre, post, frames, clip, B, K, H, W):
     _launch("c3d_build_clip", clip.numel() * 8, L.lib().c3d_build_clip, _p(pre), _p(post), _p(frames), _p(clip), B, K, H, W,
             _stream())

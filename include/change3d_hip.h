@@ -504,6 +504,37 @@ int c3d_augment_gather(const uint8_t* store, const uint8_t* label_store, const i
                        const float* std6, float* pre, float* post, void* label_a, void* label_b, float* scratch,
                        int32_t task, int32_t N, int32_t Hs, int32_t Ws, int32_t B, int32_t H, int32_t W, void* stream);
 
+/* Whole-scene inference (change3d_amd/infer.py; the reference only validates on pre-cut crops): tile a uint8 scene pair that
+ * stays in HBM, and put the per-tile predictions back together.  Per axis, for tile t and stride s (1 <= s <= t, t - s even;
+ * C3D_E_BADARG otherwise): margin m = (t - s) / 2, n = ceil(extent / s) tiles, tile i starts at i*s - m, and k = ceil(t / s)
+ * tile rows cover any scene row.  Coordinates outside the scene fold back as numpy's `reflect` does for ANY overhang
+ * (period 2*(extent-1), extent 1 -> 0): a scene smaller than a tile or than the margin is legal.
+ *   scene    u8 [Hs][Ws][6] (pre RGB | post RGB, the layout of c3d_bcd_preprocess) at an even address; any Ws; 64-bit offsets
+ *   origins  i32 [n][2] DEVICE = (y, x) of each tile's first pixel, negative or overhanging as the geometry asks; every
+ *            source coordinate is clamped after folding, so no table content can address memory outside the scene
+ *   mean6, std6  f32 [6] DEVICE vectors, as for c3d_bcd_preprocess
+ * Outputs: pre, post f32 [n][3][th][tw] = ((u8/255) - mean)/std, bit-identical to c3d_bcd_preprocess for a tile inside the
+ * scene.  One launch.                                                                                                  */
+int c3d_scene_gather(const uint8_t* scene, const int32_t* origins, const float* mean6, const float* std6, float* pre,
+                     float* post, int32_t Hs, int32_t Ws, int32_t n, int32_t th, int32_t tw, void* stream);
+/* The scene rows that became final with tile row `row`: [row*sy - my, (row+1)*sy - my) clipped to the scene, and for the last
+ * tile row everything up to Hs (nothing follows it).  A margin of a stride or more can leave that range empty: 0 is returned
+ * and nothing is launched.
+ *   ring     f32 [ky][ncols][C][th][tw]: tile row r lives in slot r % ky; rows row-ky+1 .. row must be there.  ky * ncols * C *
+ *            th * tw * 4 bytes must stay under 2 GiB (C3D_E_UNSUPPORTED); th, tw <= 4096
+ *   wy, wx   f32 [th], [tw] DEVICE window vectors, every entry > 0; the weight of tile pixel (y, x) is wy[y] * wx[x]
+ * Per pixel and channel: sum(w * p) / sum(w) over the covering tiles that exist (tile rows 0 .. row, every column), f32, in
+ * a fixed order -- tile row ascending, then tile column ascending, one fused multiply-add per tap -- by one thread: no atomics,
+ * two runs agree bit for bit.
+ *   blend    f32 [C][Hs][Ws] or NULL
+ *   cls      u8 [Hs][Ws] or NULL: C == 1: blend > 0.5 (the reference's binarisation); C > 1: argmax over channels, the lowest
+ *            index on a tie (torch.argmax).  At least one of blend / cls is given.
+ *   gate     u8 [Hs][Ws] or NULL: cls is multiplied by it where both are written -- the change mask over the two SCD class maps
+ *            (reference scripts/train_SCD.py:148-154); its rows of this strip must have been stitched before on `stream`  */
+int c3d_scene_stitch(const float* ring, const float* wy, const float* wx, float* blend, uint8_t* cls, const uint8_t* gate,
+                     int32_t Hs, int32_t Ws, int32_t C, int32_t th, int32_t tw, int32_t sy, int32_t sx, int32_t row,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
  * stage (reference model/x3d.py:331-412 = ResStage of ResBlocks, driven by `self.x3d.blocks[i](x)` at
