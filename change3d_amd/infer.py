@@ -12,7 +12,14 @@ Geometry, per axis, for tile `t` and stride `s` (`1 <= s <= t`, `t - s` even): m
 `n = ceil(extent / s)` tiles, tile `i` starts at `i*s - m`.  Every scene pixel then lies in the central `s`-wide region of
 some tile.  Coordinates outside the scene fold back as `np.pad(mode="reflect")` does, for any overhang.
 
-BDA scenes are not wired up: its two heads are the same two output kinds (an argmax map and a thresholded map).
+BDA (xBD) is the third scene task: `update_bda`'s localisation head is stitched like the BCD probability (blend, mask =
+blend > 0.5) and its damage head like an SCD class map (blended logits, argmax gated by the localisation mask).
+
+`predict(scene, objects=True)` appends the objects of the map (`SceneObjects`): `c3d_scene_objects` labels the connected
+components of the mask on the device, drops those below `min_area`, numbers the rest in raster order and fills one table
+row per object -- area, box, mean probability, and the majority class of the class map inside it, which for BDA is the xBD
+convention of one damage class per building.  It is enqueued behind the last strip: still one upload and one host
+synchronisation per scene, nothing is read back.
 """
 from collections import namedtuple
 
@@ -24,6 +31,10 @@ from . import ops
 from .data.transforms import BCDTransforms
 
 AxisPlan = namedtuple("AxisPlan", "extent tile stride margin n k starts")
+# labels i32 [Hs, Ws]; table i32 [max_objects, 8] = (area, x0, y0, x1, y1, cls, first, score_q); counts i32 [2] = (found, rows
+# written); object_cls u8 [Hs, Ws]; hist i32 [max_objects, num_class] or None (BCD has no class map)
+SceneObjects = namedtuple("SceneObjects", "labels table counts object_cls hist")
+TASKS = ("bcd", "scd", "bda")
 WINDOWS = ("hann", "flat")
 
 
@@ -97,17 +108,23 @@ class SceneStitcher:
 
 
 class SceneInferencer:
-    """`SceneInferencer(model, task).predict(scene_u8)`: `task` is "bcd" or "scd", `stride` defaults to half the tile (an
+    """`SceneInferencer(model, task).predict(scene_u8)`: `task` is "bcd", "scd" or "bda", `stride` defaults to half the tile (an
     int, or a (y, x) pair), `window` is "hann" or "flat", `batch` tiles go through the model per forward.
 
     BCD returns `(prob f32 [Hs, Ws], mask u8 [Hs, Ws])` with mask = blended prob > 0.5.  SCD returns `(pre_cls, post_cls,
     change)` u8 maps: the class maps are the argmax of the blended logits multiplied by the change mask, the reference's
-    validation post-processing (reference scripts/train_SCD.py:148-154).  All results stay on the device."""
+    validation post-processing (reference scripts/train_SCD.py:148-154).  BDA returns `(loc_prob f32 [Hs, Ws], loc_mask u8,
+    damage_map u8, cls_logits f32 [num_class, Hs, Ws])` with damage_map = argmax of the blended logits times loc_mask.
+    `objects=True` appends a `SceneObjects`: the objects of the mask (BCD, score = prob), of the change mask voted over
+    `post_cls` (SCD), or the buildings of `loc_mask` voted over `damage_map` (BDA, score = loc_prob); classes from 1 vote.
+    All results stay on the device."""
 
     def __init__(self, model, task, stride=None, window="hann", batch=32, mean=BCDTransforms.DEFAULT_MEAN,
                  std=BCDTransforms.DEFAULT_STD):
-        if task not in ("bcd", "scd"):
-            raise ValueError(f"task must be 'bcd' or 'scd', got {task!r}")
+        if task not in TASKS:
+            raise ValueError(f"task must be one of {TASKS}, got {task!r}")
+        if task == "bda" and not (hasattr(model, "decoder_loc") and hasattr(model, "decoder_cls")):
+            raise ValueError("task 'bda' needs a model with the localisation and damage heads (num_perception_frame = 2)")
         if window not in WINDOWS:
             raise ValueError(f"window must be one of {WINDOWS}, got {window!r}")
         if int(batch) < 1:
@@ -144,8 +161,10 @@ class SceneInferencer:
         return dev
 
     @torch.no_grad()
-    def predict(self, scene_u8):
+    def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536):
         dev = self._device()
+        if connectivity not in (4, 8) or int(max_objects) < 1:
+            raise ValueError(f"connectivity must be 4 or 8 and max_objects positive, got {connectivity} and {max_objects}")
         scene = torch.as_tensor(scene_u8)
         if scene.dtype != torch.uint8 or scene.dim() != 3 or scene.shape[-1] != 6:
             raise ValueError("scene must be uint8 [Hs, Ws, 6] (pre RGB | post RGB)")
@@ -158,6 +177,8 @@ class SceneInferencer:
         mean, std, wy, wx = self._constants(dev)
         if self.task == "bcd":
             heads = [SceneStitcher(py, px, 1, self.window, dev, blend=True, windows=(wy, wx))]
+        elif self.task == "bda":                        # update_bda's order: damage logits, localisation probability
+            heads = [SceneStitcher(py, px, C, self.window, dev, blend=True, windows=(wy, wx)) for C in (self.num_class, 1)]
         else:
             heads = [SceneStitcher(py, px, C, self.window, dev, windows=(wy, wx)) for C in (self.num_class, self.num_class, 1)]
         nb = min(self.batch, n)
@@ -166,7 +187,7 @@ class SceneInferencer:
         for j0 in range(0, n, nb):
             b = min(nb, n - j0)
             ops.scene_gather(scene, origins[j0:j0 + b], mean, std, pre, post, Hs, Ws, b, self.th, self.tw)
-            out = self.model.update_bcd(pre[:b], post[:b]) if self.task == "bcd" else self.model.update_scd(pre[:b], post[:b])
+            out = getattr(self.model, "update_" + self.task)(pre[:b], post[:b])
             outs = [out] if self.task == "bcd" else list(out)
             j = j0
             while j < j0 + b:                           # the batch, one tile row at a time: a strip goes out once its row is whole
@@ -177,12 +198,26 @@ class SceneInferencer:
                 if col + cnt == px.n:
                     if self.task == "bcd":
                         heads[0].stitch(row)
+                    elif self.task == "bda":
+                        heads[1].stitch(row)
+                        heads[0].stitch(row, gate=heads[1].cls)
                     else:
                         heads[2].stitch(row)
                         heads[0].stitch(row, gate=heads[2].cls)
                         heads[1].stitch(row, gate=heads[2].cls)
                 j += cnt
-        torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
         if self.task == "bcd":
-            return heads[0].blend[0], heads[0].cls
-        return heads[0].cls, heads[1].cls, heads[2].cls
+            result = (heads[0].blend[0], heads[0].cls)
+            found = dict(mask=heads[0].cls, score=heads[0].blend[0])
+        elif self.task == "bda":
+            result = (heads[1].blend[0], heads[1].cls, heads[0].cls, heads[0].blend)
+            found = dict(mask=heads[1].cls, cls_map=heads[0].cls, score=heads[1].blend[0], n_cls=self.num_class)
+        else:
+            result = (heads[0].cls, heads[1].cls, heads[2].cls)
+            found = dict(mask=heads[2].cls, cls_map=heads[1].cls, n_cls=self.num_class)
+        if objects:
+            labels, table, hist, object_cls, counts = ops.scene_objects(first_class=1, connectivity=connectivity, min_area=min_area,
+                                                                        max_objects=max_objects, **found)
+            result += (SceneObjects(labels, table, counts, object_cls, hist),)
+        torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
+        return result

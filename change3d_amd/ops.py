@@ -790,6 +790,41 @@ def scene_stitch(ring, wy, wx, blend, cls, Hs, Ws, C, th, tw, sy, sx, row, gate=
             C, th, tw, sy, sx, row, _stream())
 
 
+def scene_label_tile():
+    """(th, tw) of the LDS tile of c3d_scene_objects' local phase; host only."""
+    th, tw = C.c_int32(0), C.c_int32(0)
+    L.check(L.lib().c3d_scene_label_tile(C.byref(th), C.byref(tw)), "c3d_scene_label_tile")
+    return th.value, tw.value
+
+
+def scene_objects(mask, cls_map=None, score=None, connectivity=8, min_area=1, n_cls=1, first_class=1, max_objects=65536,
+                  want_hist=True, want_object_cls=True):
+    """c3d_scene_objects on the u8 map `mask` [Hs, Ws] (nonzero = foreground): `(labels i32 [Hs, Ws], table i32 [max_objects,
+    8], hist i32-holding-u32 [max_objects, n_cls] or None, object_cls u8 [Hs, Ws] or None, counts i32 [2])`, all on the
+    device; nothing is read back.  `hist` exists only with a class map."""
+    assert mask.dtype == torch.uint8 and mask.dim() == 2 and mask.is_contiguous() and mask.is_cuda
+    Hs, Ws = int(mask.shape[0]), int(mask.shape[1])
+    if cls_map is not None:
+        assert cls_map.dtype == torch.uint8 and cls_map.shape == mask.shape and cls_map.is_contiguous()
+    if score is not None:
+        assert score.dtype == torch.float32 and score.shape == mask.shape and score.is_contiguous()
+    nbytes = L.lib().c3d_scene_label_ws_bytes(Hs, Ws, int(n_cls) if cls_map is not None else 1)
+    if nbytes < 0 or int(max_objects) < 1:
+        raise L.Change3DHipError(f"c3d_scene_objects refuses a {Hs} x {Ws} scene with n_cls = {n_cls}, max_objects = "
+                                 f"{max_objects} (code {nbytes if nbytes < 0 else -1})")
+    dev = mask.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    labels = torch.empty((Hs, Ws), dtype=torch.int32, device=dev)
+    table = torch.empty((int(max_objects), 8), dtype=torch.int32, device=dev)
+    hist = torch.empty((int(max_objects), int(n_cls)), dtype=torch.int32, device=dev) if want_hist and cls_map is not None else None
+    object_cls = torch.empty((Hs, Ws), dtype=torch.uint8, device=dev) if want_object_cls else None
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _launch("c3d_scene_objects", Hs * Ws * 40, L.lib().c3d_scene_objects, _p(mask), _p(cls_map), _p(score), Hs, Ws,
+            int(connectivity), int(min_area), int(n_cls), int(first_class), int(max_objects), _p(labels), _p(table), _p(hist),
+            _p(object_cls), _p(counts), _p(ws), _stream())
+    return labels, table, hist, object_cls, counts
+
+
 def build_clip(pre, post, frames, clip, B, K, H, W):
     _launch("c3d_build_clip", clip.numel() * 8, L.lib().c3d_build_clip, _p(pre), _p(post), _p(frames), _p(clip), B, K, H, W,
             _stream())

@@ -1,13 +1,21 @@
 """Change maps of whole scenes: `python -m change3d_amd.scripts.predict_scene --task BCD --weights best_model.pth
 --pre A.png --post B.png`, or `--file_root DIR --split test` for the reference's directory layout
-(`<root>/<split>/{t1,t2,label}` for BCD, `{t1,t2,label1,label2,change}` for SCD; change3d_amd/data/dataset.py).
+(`<root>/<split>/{t1,t2,label}` for BCD, `{t1,t2,label1,label2,change}` for SCD, xBD's `{t1,t2,label1,label2}` for
+`--task BDA`; change3d_amd/data/dataset.py).
 
 The reference has no such step: its scripts stop at `val()` over pre-cut crops of the training size (reference
 scripts/train_BCD.py:92-154, scripts/train_SCD.py:104-178).  A pair of any size is decoded with PIL, uploaded once as
 uint8 and tiled, predicted and stitched on the GPU (change3d_amd/infer.py).  The mask (0 / 255) or the two class maps and
 the change mask are written as PNG; where labels exist the scene's predictions go to the on-device confusion matrix (BCD)
 or joint histogram (SCD) of the training mirrors and the reference's score line is printed
-(scripts/train_BCD.py:364-370, scripts/train_SCD.py:172-176).
+(scripts/train_BCD.py:364-370, scripts/train_SCD.py:172-176).  BDA writes `loc/<name>.png` (0 / 255) and
+`damage/<name>.png`, and with labels prints the columns of `train_BDA.py`'s `val` from the device counts of
+`c3d_bda_confusion`.
+
+`--objects` adds `objects/<name>.csv`, one line per connected object of the mask (SCD: of the change mask, `cls` voted over
+the post class map, no score) with at least `--min_area` pixels (`id,area,x0,y0,x1,y1,cls,score`), found on the device by
+`c3d_scene_objects`; BDA also writes
+`damage_objects/<name>.png`, the majority damage class of every building painted over its footprint, and scores it.
 """
 import os
 import sys
@@ -22,18 +30,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from change3d_amd.data.dataset import BCDDataset, SCDDataset, read_label, read_rgb  # noqa: E402
+from change3d_amd.data.dataset import BCDDataset, BDADataset, SCDDataset, read_label, read_rgb  # noqa: E402
 from change3d_amd.infer import SceneInferencer  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
-from change3d_amd.model.utils import SCDHistogram  # noqa: E402
+from change3d_amd.model.utils import BDAEvaluator, Evaluator, SCDHistogram, bda_scores  # noqa: E402
 from change3d_amd.utils.metric_tool import ConfuseMatrixMeter  # noqa: E402
 
 
+def num_classes(args):
+    """--num_class, or the task's default: 7 SCD classes (SECOND), 5 BDA damage classes (xBD); BCD has one output."""
+    if args.task == "BCD":
+        return 1
+    return args.num_class if args.num_class is not None else {"SCD": 7, "BDA": 5}[args.task]
+
+
 def build_model(args, device):
-    scd = args.task == "SCD"
-    margs = SimpleNamespace(pretrained=args.pretrained, num_perception_frame=3 if scd else 1, in_height=args.in_height,
-                            in_width=args.in_width, dataset="SECOND" if scd else "LEVIR-CD",
-                            num_class=args.num_class if scd else 1,
+    frames, dataset = {"BCD": (1, "LEVIR-CD"), "SCD": (3, "SECOND"), "BDA": (2, "xBD")}[args.task]
+    margs = SimpleNamespace(pretrained=args.pretrained, num_perception_frame=frames, in_height=args.in_height,
+                            in_width=args.in_width, dataset=dataset,
+                            num_class=num_classes(args),
                             act_dtype=torch.bfloat16 if args.act_dtype == "bf16" else torch.float32)
     model = Trainer(margs)
     state = torch.load(args.weights, map_location="cpu")
@@ -44,7 +59,7 @@ def build_model(args, device):
 def scenes(args):
     """(name, image uint8 [H, W, 6], label uint8 or None) per scene."""
     if args.file_root:
-        ds = (SCDDataset if args.task == "SCD" else BCDDataset)(args.file_root, args.split)
+        ds = {"BCD": BCDDataset, "SCD": SCDDataset, "BDA": BDADataset}[args.task](args.file_root, args.split)
         for i, name in enumerate(ds.file_list):
             img, label = ds.raw(i)
             yield os.path.splitext(name)[0], img, label
@@ -52,7 +67,9 @@ def scenes(args):
     pre, post = read_rgb(args.pre), read_rgb(args.post)
     if pre.shape != post.shape:
         raise ValueError(f"{args.pre} is {pre.shape[:2]} but {args.post} is {post.shape[:2]}")
-    files = [args.label] if args.task == "BCD" else [args.label1, args.label2, args.change]
+    if args.task == "BDA":                                # cv2's channel order, as BDADataset reads the training pairs
+        pre, post = pre[:, :, ::-1], post[:, :, ::-1]
+    files = {"BCD": [args.label], "SCD": [args.label1, args.label2, args.change], "BDA": [args.label1, args.label2]}[args.task]
     label = None
     if all(files):
         labels = [read_label(f) for f in files]
@@ -65,27 +82,81 @@ def save_png(path, array):
     Image.fromarray(array).save(path)
 
 
+def save_objects(path, objects):
+    """One CSV line per table row; the one read-back of the table.  Returns (found, written)."""
+    found, rows = (int(v) for v in objects.counts.cpu())
+    table = objects.table[:rows].cpu().numpy()
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("id,area,x0,y0,x1,y1,cls,score\n")
+        for k, (area, x0, y0, x1, y1, cls, _, score_q) in enumerate(table.tolist()):
+            f.write(f"{k + 1},{area},{x0},{y0},{x1},{y1},{cls},{score_q / 65535:.4f}\n")
+    if found > rows:
+        print(f"{path}: {found} objects found, the table holds the first {rows} (max_objects)")
+    return found, rows
+
+
+def print_bda_scores(evaluator, object_hist, num_class):
+    """The log columns of train_BDA.py's val; then the damage scores of the per-building majority map, where asked for."""
+    loc_f1, harmonic, oaf1, damage_f1 = evaluator.scores()
+    print(f"\nTest:\tloc_f1_score = {loc_f1:.4f}\tharmonic_mean_f1 = {harmonic:.4f}\toaf1 = {oaf1:.4f}\t"
+          f"damage_f1_score = [{', '.join(f'{v:.4f}' for v in damage_f1)}]")
+    if object_hist is None:
+        return loc_f1, harmonic, oaf1, damage_f1
+    per_object = Evaluator(num_class)                      # confusion_matrix[gt, pred]; c3d_hist2d counted [pred, gt]
+    per_object.confusion_matrix = object_hist.matrix().T.astype(np.longlong)
+    f1 = per_object.Damage_F1_socore()
+    print(f"Objects:\tharmonic_mean_f1 = {len(f1) / np.sum(1.0 / f1):.4f}\tdamage_f1_score = [{', '.join(f'{v:.4f}' for v in f1)}]")
+    return loc_f1, harmonic, oaf1, damage_f1
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    num_class = num_classes(args)
     if not args.file_root and not (args.pre and args.post):
         raise SystemExit("give --pre and --post, or --file_root")
     device = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(device)
     model = build_model(args, device)
     inf = SceneInferencer(model, args.task.lower(), stride=args.stride, window=args.window, batch=args.batch_size)
-    meter = ConfuseMatrixMeter(n_class=2) if args.task == "BCD" else SCDHistogram(args.num_class, device)
+    meter = {"BCD": lambda: ConfuseMatrixMeter(n_class=2), "SCD": lambda: SCDHistogram(num_class, device),
+             "BDA": lambda: BDAEvaluator(num_class, device)}[args.task]()
+    object_hist = SCDHistogram(num_class, device) if args.task == "BDA" and args.objects else None
     scored = 0
     for name, img, label in scenes(args):
-        out = inf.predict(torch.from_numpy(np.ascontiguousarray(img)))
+        scene = torch.from_numpy(np.ascontiguousarray(img))
+        if args.objects:
+            out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity)
+        else:
+            out = inf.predict(scene)
         if args.task == "BCD":
             mask = out[1]
             save_png(os.path.join(args.out_dir, name + ".png"), mask.cpu().numpy() * 255)
+            if args.objects:
+                save_objects(os.path.join(args.out_dir, "objects", name + ".csv"), out[-1])
             if label is not None:        # ceil(u8 / 255), the label side of c3d_bcd_preprocess
                 meter.update_cm_device(mask.float(), (torch.from_numpy(np.ascontiguousarray(label)).to(device) > 0).float())
                 scored += 1
+        elif args.task == "BDA":
+            loc_prob, loc_mask, damage_map, cls_logits = out[:4]
+            save_png(os.path.join(args.out_dir, "loc", name + ".png"), loc_mask.cpu().numpy() * 255)
+            save_png(os.path.join(args.out_dir, "damage", name + ".png"), damage_map.cpu().numpy())
+            if args.objects:
+                save_png(os.path.join(args.out_dir, "damage_objects", name + ".png"), out[-1].object_cls.cpu().numpy())
+                save_objects(os.path.join(args.out_dir, "objects", name + ".csv"), out[-1])
+            if label is not None:        # scripts/train_BDA.py: label[:, 0].float() and the product of the two channels
+                lab = torch.from_numpy(np.ascontiguousarray(label)).to(device)
+                label_loc, label_cls = lab[..., 0].float(), lab[..., 0].long() * lab[..., 1].long()
+                meter.add_batch(cls_logits[None], loc_prob[None, None], label_loc[None], label_cls[None])
+                if args.objects:         # the per-building majority map against the damage labels, where there is one
+                    inside = label_cls > 0
+                    object_hist.update(out[-1].object_cls[inside], label_cls[inside])
+                scored += 1
         else:
-            for sub, m in zip(("pred1", "pred2", "change"), out):
+            for sub, m in zip(("pred1", "pred2", "change"), out[:3]):
                 save_png(os.path.join(args.out_dir, sub, name + ".png"), m.cpu().numpy() * (255 if sub == "change" else 1))
+            if args.objects:             # the objects of the change mask; cls: the majority class of pred2 inside
+                save_objects(os.path.join(args.out_dir, "objects", name + ".csv"), out[-1])
             if label is not None:        # reference scripts/train_SCD.py:216-217: the class labels count inside the change only
                 lab = torch.from_numpy(np.ascontiguousarray(label)).to(device).long()
                 meter.update(out[0], lab[..., 0] * lab[..., 2])
@@ -94,6 +165,8 @@ def main(argv=None):
         print(f"{name}: {img.shape[0]} x {img.shape[1]} -> {args.out_dir}")
     if not scored:
         return None
+    if args.task == "BDA":
+        return print_bda_scores(meter, object_hist, num_class)
     if args.task == "BCD":
         s = meter.get_scores()
         print(f"\nTest:\t Kappa (te) = {s['Kappa']:.4f}\t IoU (te) = {s['IoU']:.4f}\tF1 (te) = {s['F1']:.4f}\t "
@@ -106,12 +179,13 @@ def main(argv=None):
 
 def build_parser():
     p = ArgumentParser()
-    p.add_argument("--task", choices=["BCD", "SCD"], default="BCD")
+    p.add_argument("--task", choices=["BCD", "SCD", "BDA"], default="BCD")
     p.add_argument("--weights", required=True, help="best_model.pth (a state dict) or checkpoint.pth.tar of the training scripts")
     p.add_argument("--pre", default="")
     p.add_argument("--post", default="")
     p.add_argument("--label", default="", help="BCD change mask of the --pre / --post pair, scored when given")
-    p.add_argument("--label1", default="", help="SCD: pre class map; scored when --label1, --label2 and --change are given")
+    p.add_argument("--label1", default="", help="SCD: pre class map; scored when --label1, --label2 and --change are given.  BDA: "
+                   "localisation (--label1) and damage class (--label2)")
     p.add_argument("--label2", default="")
     p.add_argument("--change", default="")
     p.add_argument("--file_root", default="", help="data set root in the reference's layout, instead of --pre / --post")
@@ -123,7 +197,10 @@ def build_parser():
     p.add_argument("--act_dtype", choices=["f32", "bf16"], default="bf16")
     p.add_argument("--in_height", type=int, default=256)
     p.add_argument("--in_width", type=int, default=256)
-    p.add_argument("--num_class", type=int, default=7, help="SCD classes")
+    p.add_argument("--num_class", type=int, default=None, help="SCD classes (default 7) or BDA damage classes (default 5)")
+    p.add_argument("--objects", action="store_true", help="also the connected objects of the mask (SCD: of the change mask), as objects/<name>.csv")
+    p.add_argument("--min_area", type=int, default=1, help="--objects: drop objects with fewer pixels")
+    p.add_argument("--connectivity", type=int, choices=[4, 8], default=8)
     p.add_argument("--pretrained", default="./pretrained/X3D_L.pyth")
     p.add_argument("--gpu_id", default=0, type=int)
     return p

@@ -535,6 +535,39 @@ int c3d_scene_stitch(const float* ring, const float* wy, const float* wx, float*
                      int32_t Hs, int32_t Ws, int32_t C, int32_t th, int32_t tw, int32_t sy, int32_t sx, int32_t row,
                      void* stream);
 
+/* Objects of a scene map (csrc/scene_objects.hip): connected components of a u8 mask that stays in HBM, a minimum-area filter,
+ * raster numbering and one table row per object.  Integer arithmetic and integer atomics only: every output is exact and two
+ * runs agree bit for bit.  Nine launches and at most three memsets on `stream`, nothing is read back by the host; the
+ * workspace is zeroed inside the call.  Inputs (device):
+ *   mask      u8 [Hs][Ws], nonzero = foreground;  Hs * Ws < 2^31 (C3D_E_UNSUPPORTED beyond)
+ *   cls_map   u8 [Hs][Ws] or NULL: the votes; a value >= n_cls is counted nowhere; 1 <= n_cls <= 16 as in c3d_bda_confusion
+ *   score     f32 [Hs][Ws] or NULL
+ *   connectivity 4 or 8;  min_area <= 1 keeps every component;  max_objects >= 1 rows of `table` (and of `hist`)
+ * Outputs:
+ *   labels    i32 [Hs][Ws]: 0 = background or a pixel of a removed component (fewer than min_area pixels); the kept ones are
+ *             numbered 1 .. N in raster order of their first pixel (the smallest y*Ws + x), as scipy.ndimage.label numbers
+ *   table     i32 [max_objects][8], row id-1 = (area, x0, y0, x1, y1, cls, first, score_q); rows past the last object are 0
+ *               x0..y1  inclusive bounding box;  first = linear index of the first pixel
+ *               cls     the class in [first_class, n_cls) with the most pixels of cls_map inside the object, the lowest index
+ *                       on a tie; 0 when nobody votes or cls_map is NULL
+ *               score_q (S + area/2) / area in integers, S = u64 sum over the object of
+ *                       q = __float2uint_rn(fminf(fmaxf(p, 0), 1) * 65535.0f)  (NaN counts as 0); 0 when score is NULL
+ *   hist      u32 [max_objects][n_cls] or NULL: the votes per object; untouched when cls_map is NULL
+ *   object_cls u8 [Hs][Ws] or NULL: table[label-1].cls painted over the object, 0 elsewhere
+ *   counts    i32 [2] = (N found, rows written = min(N, max_objects)).  Objects past max_objects keep their ids in `labels`,
+ *             get object_cls 0 and are written nowhere else.  counts[0] = -1: a union-find walk reached its cap of Hs*Ws
+ *             steps (parents only decrease, so this cannot happen; the cap keeps a corrupted workspace from spinning)
+ *   ws        c3d_scene_label_ws_bytes(Hs, Ws, n_cls) bytes (n_cls = 1 without a class map), 256-byte aligned
+ * Refused before anything is enqueued: connectivity other than 4 / 8, n_cls outside [1, 16] with a class map, max_objects <
+ * 1, first_class < 0, a NULL mask / labels / table / counts / ws (C3D_E_BADARG); Hs * Ws >= 2^31 (C3D_E_UNSUPPORTED).  */
+int64_t c3d_scene_label_ws_bytes(int32_t Hs, int32_t Ws, int32_t n_cls);      /* < 0: C3D_E_* */
+/* extent of the LDS tile of the local labelling phase: scene sizes around its multiples are the ones to test */
+int c3d_scene_label_tile(int32_t* th, int32_t* tw);
+int c3d_scene_objects(const uint8_t* mask, const uint8_t* cls_map, const float* score, int32_t Hs, int32_t Ws,
+                      int32_t connectivity, int32_t min_area, int32_t n_cls, int32_t first_class, int32_t max_objects,
+                      int32_t* labels, int32_t* table, uint32_t* hist, uint8_t* object_cls, int32_t* counts, void* ws,
+                      void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
  * stage (reference model/x3d.py:331-412 = ResStage of ResBlocks, driven by `self.x3d.blocks[i](x)` at
