@@ -95,6 +95,16 @@ class CapBeamArgs(C.Structure):
                 ("logits_out", vp)]
 
 
+CAP_METRICS_MAX_REFS, CAP_METRICS_MAX_NOCHANGE, CAP_TOTALS = 7, 8, 17   # C3D_CAP_METRICS_MAX_REFS, .._MAX_NOCHANGE, C3D_CAP_TOTALS
+CAP_ST_TABLE_FULL, CAP_ST_BAD_SELECTION, CAP_ST_BAD_SENTENCE = 1, 2, 4  # bits of totals[16]
+
+
+class CapMetricsArgs(C.Structure):
+    _fields_ = [(n, i32) for n in ("N", "R", "L", "M", "n_nochange", "reserved")] + [("table_capacity", i64)] + \
+               [(n, vp) for n in ("hyp", "hyp_len", "refs", "ref_len", "sel", "nochange", "nochange_len", "ws", "stats", "lcs",
+                                  "flags", "rouge", "cider", "totals")]
+
+
 # name -> (restype, argtypes); every function declared in include/change3d_hip.h
 SIGNATURES = {
     "c3d_abi_version": (i32, []),
@@ -175,6 +185,9 @@ SIGNATURES = {
     "c3d_clamp_": (i32, [vp, i64, f32, vp]),
     "c3d_cap_beam_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i64, C.POINTER(i64), C.POINTER(i64)]),
     "c3d_cap_beam_search": (i32, [C.POINTER(CapBeamArgs), vp]),
+    "c3d_cap_strip": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, vp]),
+    "c3d_cap_metrics_plan": (i32, [i32, i32, i32, i64, C.POINTER(i64), C.POINTER(i64)]),
+    "c3d_cap_metrics": (i32, [C.POINTER(CapMetricsArgs), vp]),
     "c3d_stage_ws_bytes": (i32, [C.POINTER(StageDesc), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
     "c3d_stage_fwd": (i32, [C.POINTER(StageDesc), vp, vp, vp, vp]),
     "c3d_stage_bwd": (i32, [C.POINTER(StageDesc), vp, vp, vp, vp, vp, vp, vp]),

@@ -918,6 +918,65 @@ def cap_beam_search(dec, kv, B, S, start_id, end_id, beam, max_len, dtype, ws, c
     _launch("c3d_cap_beam_search", ws.numel() * ws.element_size(), L.lib().c3d_cap_beam_search, C.byref(a), _stream())
 
 
+def cap_strip(raw, start_id, end_id, pad_id):
+    """c3d_cap_strip: `raw` int32 [rows, L_in] on the device -> (tokens int32 [rows, 64], lengths int32 [rows]) without the three
+    special ids, order kept (reference scripts/train_CC.py:336-343).  One launch, nothing read back."""
+    assert raw.dtype == torch.int32 and raw.dim() == 2 and raw.is_contiguous()
+    require_gpu(raw, "cap_strip input")
+    rows, L_in = int(raw.shape[0]), int(raw.shape[1])
+    out = torch.empty((rows, 64), dtype=torch.int32, device=raw.device)
+    out_len = torch.empty(rows, dtype=torch.int32, device=raw.device)
+    _launch("c3d_cap_strip", raw.numel() * 8, L.lib().c3d_cap_strip, _p(raw), rows, L_in, int(start_id), int(end_id), int(pad_id),
+            _p(out), _p(out_len), _stream())
+    return out, out_len
+
+
+def cap_metrics_plan(N, R, Lr, ref_tokens=0, table_capacity=0):
+    """c3d_cap_metrics_plan: (workspace bytes, table capacity), or None for a shape the kernels do not take
+    (C3D_E_UNSUPPORTED).  Host only: callable without a GPU."""
+    ws, cap = C.c_int64(0), C.c_int64(int(table_capacity))
+    rc = L.lib().c3d_cap_metrics_plan(int(N), int(R), int(Lr), int(ref_tokens), C.byref(ws), C.byref(cap))
+    if rc == -2:
+        return None
+    L.check(rc, "c3d_cap_metrics_plan")
+    return ws.value, cap.value
+
+
+def cap_metrics(hyp, hyp_len, refs, ref_len, sel=None, nochange=None, nochange_len=None, ref_tokens=0, table_capacity=0, ws=None):
+    """c3d_cap_metrics on a corpus that lives on the device: hyp int32 [N, L], hyp_len int32 [N], refs int32 [N, R, L], ref_len
+    int32 [N, R], optional sel int32 [M] and no-change rows int32 [K, L] / [K].  Returns a dict of device tensors -- stats i32
+    [M, 10], lcs i32 [M, R], flags i32 [M], rouge / cider f64 [M], totals i64 [17], ws u8 (status and table), capacity --
+    nothing is read back here: totals[16] is the status the caller must look at (include/change3d_hip.h).  `ws`: a u8 buffer of
+    at least the plan's bytes to use instead of a fresh one (tests put a guard behind the table)."""
+    for t in (hyp, hyp_len, refs, ref_len) + tuple(x for x in (sel, nochange, nochange_len) if x is not None):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+        require_gpu(t, "cap_metrics input")
+    N, Lr = int(hyp.shape[0]), int(hyp.shape[1])
+    R = int(refs.shape[1])
+    assert refs.shape == (N, R, Lr) and hyp_len.shape == (N,) and ref_len.shape == (N, R)
+    M = N if sel is None else int(sel.numel())
+    K = 0 if nochange is None else int(nochange.shape[0])
+    assert K == 0 or (nochange.shape == (K, Lr) and nochange_len.shape == (K,))
+    plan = cap_metrics_plan(N, R, Lr, ref_tokens, table_capacity)
+    if plan is None or M < 1 or K > L.CAP_METRICS_MAX_NOCHANGE:
+        raise L.Change3DHipError(f"c3d_cap_metrics refuses N = {N}, R = {R}, L = {Lr}, M = {M}, {K} no-change rows")
+    nbytes, cap = plan
+    dev = hyp.device
+    assert ws is None or (ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_contiguous() and ws.data_ptr() % 256 == 0)
+    out = {"ws": torch.empty(nbytes, dtype=torch.uint8, device=dev) if ws is None else ws, "capacity": cap,
+           "stats": torch.empty((M, 10), dtype=torch.int32, device=dev), "lcs": torch.empty((M, R), dtype=torch.int32, device=dev),
+           "flags": torch.empty(M, dtype=torch.int32, device=dev), "rouge": torch.empty(M, dtype=torch.float64, device=dev),
+           "cider": torch.empty(M, dtype=torch.float64, device=dev),
+           "totals": torch.empty(L.CAP_TOTALS, dtype=torch.int64, device=dev)}
+    a = L.CapMetricsArgs()
+    a.N, a.R, a.L, a.M, a.n_nochange, a.table_capacity = N, R, Lr, M, K, cap
+    a.hyp, a.hyp_len, a.refs, a.ref_len, a.sel = _p(hyp), _p(hyp_len), _p(refs), _p(ref_len), _p(sel)
+    a.nochange, a.nochange_len, a.ws = _p(nochange) if K else None, _p(nochange_len) if K else None, _p(out["ws"])
+    a.stats, a.lcs, a.flags, a.rouge, a.cider, a.totals = (_p(out[k]) for k in ("stats", "lcs", "flags", "rouge", "cider", "totals"))
+    _launch("c3d_cap_metrics", nbytes + (N * (R + 1) * Lr) * 4, L.lib().c3d_cap_metrics, C.byref(a), _stream())
+    return out
+
+
 def linear_fwd(x, weight, bias, y, M, K, N, dtype):
     """y[M][Np] = x[M][Kp] @ weight[N][K]^T + bias (nn.Linear / in_proj slices)."""
     pw_gemm(x, weight, y, M=M, K=K, N=N, w_sn=weight.stride(0), w_sk=1, dtype=dtype, bias=bias)

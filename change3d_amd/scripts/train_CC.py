@@ -3,9 +3,9 @@
 scripts/train_CC.py:75-168 `train`, :420-520 `main`): same step (encoder(output_final=True) -> 'b c h w -> (h w) b c'
 -> CaptionDecoder -> packed cross-entropy -> zero_grad x2 -> backward -> clip_gradient -> encoder / decoder Adam steps
 with StepLR(900, gamma=1)), same hyper-parameters (Adam lr 1e-4, weight_decay 1e-5, grad_clip 5, dropout 0.1, 8 heads,
-3 layers, embed_dim 192), and the beam-search captioning of `evaluate()` (:170-330; `--eval_pairs N`).  File datasets,
-the word map and the caption metrics (BLEU / METEOR / ROUGE / CIDEr: host-side text scoring, `eval_func/`) are outside
-SURVEY.md section 8: `--dataset SYNTH-CC` draws LEVIR-CC-shaped synthetic pairs + token sequences.
+3 layers, embed_dim 192), and the beam-search captioning of `evaluate()` (:170-330; `--eval_pairs N`).  File datasets
+and the word map are outside SURVEY.md section 8: `--dataset SYNTH-CC` draws LEVIR-CC-shaped synthetic pairs + token
+sequences.  `validate()` scores the captions on the device (BLEU-1..4, ROUGE-L, CIDEr of `eval_func/`; no METEOR).
 
     python -m change3d_amd.scripts.train_CC --batch_size 16 --max_steps 20 --act_dtype bf16
 """
@@ -21,6 +21,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from change3d_amd import synthetic as synth  # noqa: E402
+from change3d_amd.caption_metrics import CaptionScorer  # noqa: E402
 from change3d_amd.hostopt import freeze_gc  # noqa: E402
 from change3d_amd.model.caption_decoder import packed_cross_entropy  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
@@ -100,6 +101,42 @@ def evaluate(args, model, pairs, start_id, end_id, pad_id=0, eval_batch=None):
     return hyps
 
 
+def _print_scores(scores):
+    """the lines of the reference's eval_caption_score (model/utils.py:523-527), METEOR left out"""
+    print("Bleu [{}, {}, {}, {}]".format(*(scores[f"Bleu_{k}"] for k in range(1, 5))))
+    print("ROUGE_L {}".format(scores["ROUGE_L"]))
+    print("CIDEr {}".format(scores["CIDEr"]))
+
+
+def validate(args, model, pairs, allcaps, word_ids, nochange_rows=(), eval_batch=None, return_hyps=False):
+    """reference scripts/train_CC.py:170-399 = `evaluate` + the scores: `allcaps` int [n, R, L] are the raw reference rows of the
+    loader (one row of R captions per pair), `word_ids` = (start_id, end_id, pad_id), `nochange_rows` the no-change sentences
+    as token rows (:348-350; none: every pair is a change pair).  Captions a pair, strips the special tokens (:336-343), scores
+    the no-change subset, the change subset and all pairs on the device (change3d_amd/caption_metrics.py; no METEOR), prints
+    the reference's lines and returns the overall dict, the value the reference picks its best checkpoint by (`Bleu_4`, :517)."""
+    start_id, end_id, pad_id = word_ids
+    hyps = evaluate(args, model, pairs, start_id, end_id, pad_id, eval_batch)
+    special = {start_id, end_id, pad_id}
+    refs = [[[w for w in c if w not in special] for c in caps] for caps in allcaps.tolist()]
+    scorer = CaptionScorer(next(model.parameters()).device)
+    scorer.add(hyps, refs)
+    idx_n, idx_c, acc_n, acc_c = scorer.split(nochange_rows)
+    print("len(nochange_references):", len(idx_n))
+    print("len(change_references):", len(idx_c))
+    if idx_n:
+        print("nochange_metric:")
+        _print_scores(scorer.score(idx_n))
+        print("nochange_acc:", acc_n)
+    if idx_c:
+        print("change_metric:")
+        _print_scores(scorer.score(idx_c))
+        print("change_acc:", acc_c)
+    print(".......................................................")
+    metrics = scorer.score()
+    _print_scores(metrics)
+    return (metrics, hyps) if return_hyps else metrics
+
+
 def main():
     p = ArgumentParser()
     p.add_argument("--dataset", default="SYNTH-CC")
@@ -119,7 +156,7 @@ def main():
     p.add_argument("--vocab_size", type=int, default=501, help="len(WORDMAP) of the reference; synthetic here")
     p.add_argument("--max_steps", type=int, default=100)
     p.add_argument("--beam_size", type=int, default=1, help="reference default (scripts/train_CC.py:600)")
-    p.add_argument("--eval_pairs", type=int, default=0, help="caption this many synthetic pairs after training")
+    p.add_argument("--eval_pairs", type=int, default=0, help="caption and score this many synthetic pairs after training")
     p.add_argument("--eval_batch", type=int, default=1,
                    help="pairs captioned per device-resident batched beam search; 1: the reference's one-pair-at-a-time loop")
     p.add_argument("--act_dtype", choices=["bf16", "f32"], default="bf16")
@@ -153,7 +190,10 @@ def main():
         start_id, end_id = args.vocab_size - 2, args.vocab_size - 1            # synthetic word map: <start>, <end> last
         torch.cuda.synchronize()
         t0 = time.time()
-        hyps = evaluate(args, model, [(ep[i:i + 1], eq[i:i + 1]) for i in range(n)], start_id, end_id)
+        # synthetic references: 5 captions per pair, raw rows as the loader yields them (<start> ... <end> <pad>)
+        allcaps = synth.synth_captions(n * 5, seed=1, vocab_size=args.vocab_size)[0].view(n, 5, -1)
+        _, hyps = validate(args, model, [(ep[i:i + 1], eq[i:i + 1]) for i in range(n)], allcaps, (start_id, end_id, 0),
+                           return_hyps=True)
         torch.cuda.synchronize()
         done = [h for h in hyps if h is not None]
         print(f"evaluate: {n} pairs, beam {args.beam_size}, {len(done)} captions, mean length "

@@ -847,6 +847,55 @@ int c3d_cap_beam_plan(int32_t S, int32_t D, int32_t H, int32_t n_layer, int32_t 
  * per step, torch topk, host bookkeeping).  One launch on `stream`; C3D_E_UNSUPPORTED exactly where the plan says so. */
 int c3d_cap_beam_search(const c3d_cap_beam_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Caption metrics of the captioning validation (csrc/caption_metrics.hip): the BLEU-1..4 statistics, ROUGE-L and CIDEr of
+ * reference eval_func/bleu/bleu_scorer.py:60-83, rouge/rouge.py:23-128, cider/cider_scorer.py:93-182 and the change /
+ * no-change bookkeeping of scripts/train_CC.py:347-376, on token ids.  Integers are exact; ROUGE-L and CIDEr are float64 with
+ * the reference's operations (sums in ascending first-occurrence position).  METEOR is not computed.
+ * Sentences are compact rows of L <= 64 int32 tokens in [0, 65534] with their lengths; at most 7 references per image and 8
+ * no-change sentences (C3D_E_UNSUPPORTED beyond).
+ * ------------------------------------------------------------------------------------ */
+#define C3D_CAP_METRICS_MAX_REFS 7
+#define C3D_CAP_METRICS_MAX_NOCHANGE 8
+#define C3D_CAP_TOTALS 17
+/* out [rows][64] / out_len [rows] = the tokens of raw [rows][L_in] that are none of start_id / end_id / pad_id, in order (the
+ * list comprehension of reference scripts/train_CC.py:336-343), the rest of the row -1.  A row that keeps more than 64 tokens
+ * keeps its first 64 and reports its true length, which c3d_cap_metrics refuses as a bad sentence.  One launch.          */
+int c3d_cap_strip(const int32_t* raw, int64_t rows, int32_t L_in, int32_t start_id, int32_t end_id, int32_t pad_id,
+                  int32_t* out, int32_t* out_len, void* stream);
+typedef struct c3d_cap_metrics_args {
+  int32_t N, R, L, M;               /* images of the corpus, references per image, row stride (<= 64), selected images */
+  int32_t n_nochange, reserved;     /* rows of `nochange` (0: no bookkeeping) */
+  int64_t table_capacity;           /* slots of the document-frequency table, a power of two (c3d_cap_metrics_plan) */
+  const int32_t *hyp, *hyp_len;     /* [N][L], [N]; a hypothesis may be empty */
+  const int32_t *refs, *ref_len;    /* [N][R][L], [N][R]; a reference may not be empty */
+  const int32_t* sel;               /* [M] image indices or NULL (M = N, every image in order).  The document frequency is
+                                     * counted over the selected images only: one upload serves every subset */
+  const int32_t *nochange, *nochange_len;   /* [n_nochange][L], [n_nochange] or NULL */
+  void* ws;                         /* ws_bytes of the plan, 256-byte aligned; zeroed inside the call.  After the call:
+                                     * u32 status at 0, u64 keys [capacity] at 256, u32 counts [capacity] behind them -- an
+                                     * n-gram's key is four 16-bit fields of token + 1, first token lowest, 0 = no token;
+                                     * slot order varies from run to run, counts do not (test / debug access) */
+  /* per selected image, in selection order */
+  int32_t* stats;                   /* [M][10] testlen, closest reference length (a tie goes to the shorter), guess[4], correct[4] */
+  int32_t* lcs;                     /* [M][R] LCS length of the hypothesis and each reference */
+  int32_t* flags;                   /* [M] bit 0: reference 1 (reference 0 when R == 1) is a no-change sentence; bit 1: the
+                                     * hypothesis is one */
+  double *rouge, *cider;            /* [M] */
+  int64_t* totals;                  /* [C3D_CAP_TOTALS]: 0..9 the column sums of stats; 10 images with flag bit 0; 11 those of
+                                     * them with bit 1; 12 images without bit 0; 13 those of them without bit 1; 14 / 15 the sums
+                                     * of rouge / cider (float64 bits, fixed-order tree); 16 status, 0 = fine, else bits: 1 the
+                                     * table is full (a probe reached its cap of `table_capacity` steps; cider is 0 then), 2 a
+                                     * selection index outside [0, N) (the image scores 0), 4 a sentence with a length outside
+                                     * [0, L], a token outside [0, 65534] or an empty reference (scored as empty) */
+} c3d_cap_metrics_args;
+/* Host only.  table_capacity is in/out: <= 0 asks for the default, the next power of two >= 2 * 4 * ref_tokens (ref_tokens =
+ * the sum of the reference lengths; <= 0: N * R * L) -- at most half full with every n-gram distinct; a positive value must be
+ * a power of two and is kept (C3D_E_BADARG otherwise).  ws_bytes = 256 + 12 * table_capacity.                          */
+int c3d_cap_metrics_plan(int32_t N, int32_t R, int32_t L, int64_t ref_tokens, int64_t* ws_bytes, int64_t* table_capacity);
+/* One memset and three launches on `stream` (statistics and table, CIDEr, reduction); nothing is read back by the host. */
+int c3d_cap_metrics(const c3d_cap_metrics_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
