@@ -99,6 +99,9 @@ CAP_METRICS_MAX_REFS, CAP_METRICS_MAX_NOCHANGE, CAP_TOTALS = 7, 8, 17   # C3D_CA
 CAP_ST_TABLE_FULL, CAP_ST_BAD_SELECTION, CAP_ST_BAD_SENTENCE = 1, 2, 4  # bits of totals[16]
 
 
+MATCH_ST_TABLE_FULL, MATCH_ST_TRUNCATED, MATCH_ST_BAD_COUNTS = 1, 2, 4     # C3D_MATCH_ST_*: bits of counts[4] / totals[4]
+
+
 class CapMetricsArgs(C.Structure):
     _fields_ = [(n, i32) for n in ("N", "R", "L", "M", "n_nochange", "reserved")] + [("table_capacity", i64)] + \
                [(n, vp) for n in ("hyp", "hyp_len", "refs", "ref_len", "sel", "nochange", "nochange_len", "ws", "stats", "lcs",
@@ -172,6 +175,8 @@ SIGNATURES = {
     "c3d_scene_label_ws_bytes": (i64, [i32, i32, i32]),
     "c3d_scene_label_tile": (i32, [vp, vp]),
     "c3d_scene_objects": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "c3d_objects_match_ws_bytes": (i64, [i32, i32, C.POINTER(i64)]),
+    "c3d_objects_match": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "c3d_cap_embed_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_embed_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_dropout": (i32, [vp, vp, i64, i32, f32, C.c_uint64, i32, vp]),

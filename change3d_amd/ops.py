@@ -825,6 +825,47 @@ def scene_objects(mask, cls_map=None, score=None, connectivity=8, min_area=1, n_
     return labels, table, hist, object_cls, counts
 
 
+def objects_match_plan(Hs, Ws, table_capacity=0):
+    """c3d_objects_match_ws_bytes: (workspace bytes, table capacity); `table_capacity` 0 asks for the one that cannot overflow."""
+    cap = C.c_int64(int(table_capacity))
+    nbytes = L.lib().c3d_objects_match_ws_bytes(int(Hs), int(Ws), C.byref(cap))
+    if nbytes < 0:
+        raise L.Change3DHipError(f"c3d_objects_match refuses a {Hs} x {Ws} scene with a table of {table_capacity} slots (code {nbytes})")
+    return int(nbytes), int(cap.value)
+
+
+def objects_match(labels_p, table_p, counts_p, labels_g, table_g, counts_g, n_cls=1, iou_thr=0.5, table_capacity=0, totals=None,
+                  total_iou=None, ws=None):
+    """c3d_objects_match on the `labels`, `table` and `counts` of two `scene_objects` calls over the same scene, prediction first:
+    `(match_p i32 [max_p, 4], match_g i32 [max_g, 4], conf i64 [n_cls, n_cls], counts i64 [6], sum_iou f64 [1])`, all on the
+    device; nothing is read back.  `totals` i64 [5 + n_cls * n_cls] and `total_iou` f64 [1], zeroed once by the caller, are
+    added into."""
+    for t in (labels_p, table_p, counts_p, labels_g, table_g, counts_g):
+        require_gpu(t, "objects_match input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert labels_p.dim() == 2 and labels_g.shape == labels_p.shape and table_p.shape[1] == 8 and table_g.shape[1] == 8
+    Hs, Ws = int(labels_p.shape[0]), int(labels_p.shape[1])
+    max_p, max_g, n_cls = int(table_p.shape[0]), int(table_g.shape[0]), int(n_cls)
+    nbytes, cap = objects_match_plan(Hs, Ws, table_capacity)
+    dev = labels_p.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.numel() >= nbytes
+    if totals is not None:
+        assert totals.dtype == torch.int64 and totals.numel() == 5 + n_cls * n_cls and totals.is_contiguous()
+    if total_iou is not None:
+        assert total_iou.dtype == torch.float64 and total_iou.numel() == 1
+    match_p = torch.empty((max_p, 4), dtype=torch.int32, device=dev)
+    match_g = torch.empty((max_g, 4), dtype=torch.int32, device=dev)
+    conf = torch.empty((max(n_cls, 1), max(n_cls, 1)), dtype=torch.int64, device=dev)   # n_cls < 1 is refused by the call
+    counts = torch.empty(6, dtype=torch.int64, device=dev)
+    sum_iou = torch.empty(1, dtype=torch.float64, device=dev)
+    _launch("c3d_objects_match", Hs * Ws * 8 + cap * 24, L.lib().c3d_objects_match, _p(labels_p), _p(table_p), _p(counts_p),
+            _p(labels_g), _p(table_g), _p(counts_g), Hs, Ws, max_p, max_g, n_cls, float(iou_thr), cap, _p(match_p), _p(match_g),
+            _p(conf), _p(counts), _p(sum_iou), _p(totals), _p(total_iou), _p(ws), _stream())
+    return match_p, match_g, conf, counts, sum_iou
+
+
 def build_clip(pre, post, frames, clip, B, K, H, W):
     _launch("c3d_build_clip", clip.numel() * 8, L.lib().c3d_build_clip, _p(pre), _p(post), _p(frames), _p(clip), B, K, H, W,
             _stream())

@@ -16,10 +16,17 @@ or joint histogram (SCD) of the training mirrors and the reference's score line 
 the post class map, no score) with at least `--min_area` pixels (`id,area,x0,y0,x1,y1,cls,score`), found on the device by
 `c3d_scene_objects`; BDA also writes
 `damage_objects/<name>.png`, the majority damage class of every building painted over its footprint, and scores it.
+
+`--objects` with labels also scores the objects themselves (change3d_amd/object_metrics.py, `c3d_objects_match`): the
+predicted objects against the objects of the label mask (BCD), of the change label voted over label2 (SCD) or the buildings
+of `label_loc > 0` voted over `label_loc * label_cls` (BDA).  A pair matches iff its IoU is strictly above `--iou_thr`.  One
+more line follows the score line, `objects: tp fp fn precision recall f1 sq rq pq` (BDA: and the object F1 per damage
+class), and `objects/<name>.match.csv` lists `id,gt_id,inter,union,covered` per predicted object and, under a `# gt` line,
+`id,pred_id,inter,union,covered` per ground-truth object.
 """
 import os
 import sys
-from argparse import ArgumentParser
+from argparse import ArgumentParser, ArgumentTypeError
 from types import SimpleNamespace
 
 import numpy as np
@@ -33,6 +40,7 @@ if ROOT not in sys.path:
 from change3d_amd.data.dataset import BCDDataset, BDADataset, SCDDataset, read_label, read_rgb  # noqa: E402
 from change3d_amd.infer import SceneInferencer  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
+from change3d_amd.object_metrics import ObjectEvaluator  # noqa: E402
 from change3d_amd.model.utils import BDAEvaluator, Evaluator, SCDHistogram, bda_scores  # noqa: E402
 from change3d_amd.utils.metric_tool import ConfuseMatrixMeter  # noqa: E402
 
@@ -96,6 +104,29 @@ def save_objects(path, objects):
     return found, rows
 
 
+def save_matches(path, objects, gt_counts, match_p, match_g):
+    """objects/<name>.match.csv: the rows of the predicted objects, then those of the ground-truth objects under `# gt`."""
+    rows_p, rows_g = int(objects.counts[1]), int(gt_counts[1])
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("id,gt_id,inter,union,covered\n")
+        for k, (partner, inter, union, covered) in enumerate(match_p[:rows_p].cpu().tolist()):
+            f.write(f"{k + 1},{partner},{inter},{union},{covered}\n")
+        f.write("# gt\nid,pred_id,inter,union,covered\n")
+        for k, (partner, inter, union, covered) in enumerate(match_g[:rows_g].cpu().tolist()):
+            f.write(f"{k + 1},{partner},{inter},{union},{covered}\n")
+
+
+def print_object_scores(evaluator, per_class=False):
+    s = evaluator.scores()
+    line = (f"objects: tp = {s['tp']} fp = {s['fp']} fn = {s['fn']} precision = {s['precision']:.4f} recall = {s['recall']:.4f} "
+            f"f1 = {s['f1']:.4f} sq = {s['sq']:.4f} rq = {s['rq']:.4f} pq = {s['pq']:.4f}")
+    if per_class:
+        line += f" class_f1 = [{', '.join(f'{v:.4f}' for v in s['class_f1'])}]"
+    print(line)
+    return s
+
+
 def print_bda_scores(evaluator, object_hist, num_class):
     """The log columns of train_BDA.py's val; then the damage scores of the per-building majority map, where asked for."""
     loc_f1, harmonic, oaf1, damage_f1 = evaluator.scores()
@@ -110,6 +141,13 @@ def print_bda_scores(evaluator, object_hist, num_class):
     return loc_f1, harmonic, oaf1, damage_f1
 
 
+def iou_threshold(text):
+    v = float(text)
+    if not 0.5 <= v < 1.0:
+        raise ArgumentTypeError(f"--iou_thr must lie in [0.5, 1), got {text}")
+    return v
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     num_class = num_classes(args)
@@ -122,7 +160,16 @@ def main(argv=None):
     meter = {"BCD": lambda: ConfuseMatrixMeter(n_class=2), "SCD": lambda: SCDHistogram(num_class, device),
              "BDA": lambda: BDAEvaluator(num_class, device)}[args.task]()
     object_hist = SCDHistogram(num_class, device) if args.task == "BDA" and args.objects else None
+    object_eval = None                                    # made by the first labelled scene of a run with --objects
     scored = 0
+
+    def score_objects(name, objects, gt_mask, gt_cls=None):
+        nonlocal object_eval
+        if object_eval is None:
+            object_eval = ObjectEvaluator(n_cls=num_class, iou_thr=args.iou_thr, connectivity=args.connectivity, device=device)
+        match_p, match_g = object_eval.update(objects, gt_mask.to(torch.uint8), None if gt_cls is None else gt_cls.to(torch.uint8))
+        save_matches(os.path.join(args.out_dir, "objects", name + ".match.csv"), objects, object_eval.last_gt_counts, match_p, match_g)
+
     for name, img, label in scenes(args):
         scene = torch.from_numpy(np.ascontiguousarray(img))
         if args.objects:
@@ -135,7 +182,10 @@ def main(argv=None):
             if args.objects:
                 save_objects(os.path.join(args.out_dir, "objects", name + ".csv"), out[-1])
             if label is not None:        # ceil(u8 / 255), the label side of c3d_bcd_preprocess
-                meter.update_cm_device(mask.float(), (torch.from_numpy(np.ascontiguousarray(label)).to(device) > 0).float())
+                lab = torch.from_numpy(np.ascontiguousarray(label)).to(device)
+                meter.update_cm_device(mask.float(), (lab > 0).float())
+                if args.objects:
+                    score_objects(name, out[-1], lab > 0)
                 scored += 1
         elif args.task == "BDA":
             loc_prob, loc_mask, damage_map, cls_logits = out[:4]
@@ -151,6 +201,7 @@ def main(argv=None):
                 if args.objects:         # the per-building majority map against the damage labels, where there is one
                     inside = label_cls > 0
                     object_hist.update(out[-1].object_cls[inside], label_cls[inside])
+                    score_objects(name, out[-1], lab[..., 0] > 0, label_cls)
                 scored += 1
         else:
             for sub, m in zip(("pred1", "pred2", "change"), out[:3]):
@@ -161,20 +212,24 @@ def main(argv=None):
                 lab = torch.from_numpy(np.ascontiguousarray(label)).to(device).long()
                 meter.update(out[0], lab[..., 0] * lab[..., 2])
                 meter.update(out[1], lab[..., 1] * lab[..., 2])
+                if args.objects:         # the objects of the change label; cls: the majority class of label2 inside
+                    score_objects(name, out[-1], lab[..., 2] > 0, lab[..., 1])
                 scored += 1
         print(f"{name}: {img.shape[0]} x {img.shape[1]} -> {args.out_dir}")
     if not scored:
         return None
     if args.task == "BDA":
-        return print_bda_scores(meter, object_hist, num_class)
-    if args.task == "BCD":
-        s = meter.get_scores()
-        print(f"\nTest:\t Kappa (te) = {s['Kappa']:.4f}\t IoU (te) = {s['IoU']:.4f}\tF1 (te) = {s['F1']:.4f}\t "
-              f"R (te) = {s['recall']:.4f}\tP (te) = {s['precision']:.4f}")
-        return s
-    Fscd, iou, sek = meter.scores()
-    print(f"Fscd: {Fscd * 100:.2f} IoU: {iou * 100:.2f} Sek: {sek * 100:.2f}")
-    return Fscd, iou, sek
+        result = print_bda_scores(meter, object_hist, num_class)
+    elif args.task == "BCD":
+        result = meter.get_scores()
+        print(f"\nTest:\t Kappa (te) = {result['Kappa']:.4f}\t IoU (te) = {result['IoU']:.4f}\tF1 (te) = {result['F1']:.4f}\t "
+              f"R (te) = {result['recall']:.4f}\tP (te) = {result['precision']:.4f}")
+    else:
+        result = meter.scores()
+        print(f"Fscd: {result[0] * 100:.2f} IoU: {result[1] * 100:.2f} Sek: {result[2] * 100:.2f}")
+    if object_eval is not None:
+        print_object_scores(object_eval, per_class=args.task == "BDA")
+    return result
 
 
 def build_parser():
@@ -201,6 +256,8 @@ def build_parser():
     p.add_argument("--objects", action="store_true", help="also the connected objects of the mask (SCD: of the change mask), as objects/<name>.csv")
     p.add_argument("--min_area", type=int, default=1, help="--objects: drop objects with fewer pixels")
     p.add_argument("--connectivity", type=int, choices=[4, 8], default=8)
+    p.add_argument("--iou_thr", type=iou_threshold, default=0.5, help="--objects with labels: a predicted and a labelled object match iff "
+                   "their IoU is strictly above this; in [0.5, 1)")
     p.add_argument("--pretrained", default="./pretrained/X3D_L.pyth")
     p.add_argument("--gpu_id", default=0, type=int)
     return p

@@ -568,6 +568,55 @@ int c3d_scene_objects(const uint8_t* mask, const uint8_t* cls_map, const float* 
                       int32_t* labels, int32_t* table, uint32_t* hist, uint8_t* object_cls, int32_t* counts, void* ws,
                       void* stream);
 
+/* Objects of a prediction matched to the objects of a ground truth (csrc/objects_match.hip): the join of two c3d_scene_objects
+ * results over the same Hs x Ws.  Every pixel with p = labels_p > 0 and g = labels_g > 0 adds 1 to the count of the exact
+ * 64-bit key (p << 32) | g in an open-addressing table in `ws`; the pair (p, g, inter) matches iff
+ * (double)inter > iou_thr * (double)union with union = area_p + area_g - inter, strictly, which for iou_thr >= 0.5 makes a
+ * match unique on both sides.  One memset (the workspace) and four launches on `stream`; nothing is read back by the host, the
+ * object counts are read from counts_p / counts_g on the device.  Integer arithmetic and integer atomics except sum_iou, which
+ * one workgroup adds in a fixed order (ascending predicted id, 256 interleaved partial sums, then a fixed tree): two runs agree
+ * bit for bit.  Inputs (device):
+ *   labels_p, table_p, counts_p   labels i32 [Hs][Ws], table i32 [max_p][8] and counts i32 [2] of c3d_scene_objects on the
+ *   labels_g, table_g, counts_g   prediction, and the same with max_g rows on the ground truth;  Hs * Ws < 2^31
+ *   max_p, max_g   rows of table_p / table_g and of match_p / match_g (the max_objects of the two calls), >= 1.  The objects of
+ *                  a side are its ids 1 .. rows, rows = counts[1] kept inside [0, max]; a label id above `rows` is treated as
+ *                  background: its pixels are counted nowhere
+ *   n_cls          1 <= n_cls <= 16: side of `conf`.  A table row's cls outside [0, n_cls) counts as class 0
+ *   iou_thr        in [0.5, 1)
+ *   table_capacity slots of the pair table: a power of two <= 2^32, as returned by c3d_objects_match_ws_bytes.  The capacity
+ *                  that cannot overflow is the next power of two >= 2 * Hs * Ws (every pair owns at least one pixel, the table
+ *                  is at most half full); a smaller one is legal and may set C3D_MATCH_ST_TABLE_FULL
+ * Outputs:
+ *   match_p   i32 [max_p][4], row id-1 = (partner id or 0, inter, union, covered); inter and union are 0 without a partner;
+ *   match_g   i32 [max_g][4]  covered = pixels of the object inside ANY object of the other side.  Rows past the last object
+ *             are 0, written by the call
+ *   conf      i64 [n_cls][n_cls], row = ground-truth class, column = predicted class (table[..].cls): a matched pair counts at
+ *             [cls_g][cls_p], a missed ground-truth object at [cls_g][0], a false alarm at [0][cls_p]; its sum is TP + FP + FN
+ *   counts    i64 [6] = (pairs, TP, FP, FN, status, 0); FP = rows_p - TP, FN = rows_g - TP
+ *   sum_iou   f64 [1] = sum over the matches of (double)inter / (double)union
+ *   totals    i64 [5 + n_cls*n_cls] or NULL, total_iou f64 [1] or NULL: (TP, FP, FN, pairs) and conf are ADDED into
+ *             totals[0..3] and totals[5..], status is OR-ed into totals[4], sum_iou is added to total_iou[0]; by one thread at
+ *             the end of the last launch, so calls on one stream accumulate in stream order.  The caller zeroes them once
+ *   ws        c3d_objects_match_ws_bytes(Hs, Ws, &table_capacity) = 256 + 12 * table_capacity bytes, 256-byte aligned
+ * status bits (the call always ends, and writes nothing out of range):
+ *   C3D_MATCH_ST_TABLE_FULL  an insert probed min(table_capacity, 4096) slots without finding its key or a free slot: its
+ *                            pixels are missing.  That is also the worst case of an overflowing table: 4096 loads per dropped run
+ *   C3D_MATCH_ST_TRUNCATED   counts_*[0] > counts_*[1] (objects past max_objects) or counts_*[1] > max_*: pixels of the ids
+ *                            without a table row were counted nowhere
+ *   C3D_MATCH_ST_BAD_COUNTS  counts_*[0] < 0 on either input (c3d_scene_objects reported an error)
+ * Refused before anything is enqueued: a NULL pointer other than totals / total_iou / stream, Hs or Ws <= 0, n_cls outside
+ * [1, 16], max_p < 1 or max_g < 1, iou_thr outside [0.5, 1) or NaN, a capacity that is no power of two in [1, 2^32]
+ * (C3D_E_BADARG); Hs * Ws >= 2^31 (C3D_E_UNSUPPORTED).  c3d_objects_match_ws_bytes: *table_capacity in: 0 = the capacity that
+ * cannot overflow for this scene, else a power of two, which is kept; out: the capacity used.  < 0: C3D_E_*.               */
+#define C3D_MATCH_ST_TABLE_FULL 1
+#define C3D_MATCH_ST_TRUNCATED 2
+#define C3D_MATCH_ST_BAD_COUNTS 4
+int64_t c3d_objects_match_ws_bytes(int32_t Hs, int32_t Ws, int64_t* table_capacity);
+int c3d_objects_match(const int32_t* labels_p, const int32_t* table_p, const int32_t* counts_p, const int32_t* labels_g,
+                      const int32_t* table_g, const int32_t* counts_g, int32_t Hs, int32_t Ws, int32_t max_p, int32_t max_g,
+                      int32_t n_cls, double iou_thr, int64_t table_capacity, int32_t* match_p, int32_t* match_g, int64_t* conf,
+                      int64_t* counts, double* sum_iou, int64_t* totals, double* total_iou, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
  * stage (reference model/x3d.py:331-412 = ResStage of ResBlocks, driven by `self.x3d.blocks[i](x)` at
