@@ -20,6 +20,10 @@ components of the mask on the device, drops those below `min_area`, numbers the 
 row per object -- area, box, mean probability, and the majority class of the class map inside it, which for BDA is the xBD
 convention of one damage class per building.  It is enqueued behind the last strip: still one upload and one host
 synchronisation per scene, nothing is read back.
+
+`predict(scene, objects=True, outlines=True)` appends the polygons of those objects (`SceneOutlines`) after them:
+`c3d_scene_outlines` traces the label map into closed rings on the device, one outline per object and one ring per hole, as
+a ring table and a vertex list; it is enqueued behind the labelling, before the same one synchronisation.
 """
 from collections import namedtuple
 
@@ -34,6 +38,10 @@ AxisPlan = namedtuple("AxisPlan", "extent tile stride margin n k starts")
 # labels i32 [Hs, Ws]; table i32 [max_objects, 8] = (area, x0, y0, x1, y1, cls, first, score_q); counts i32 [2] = (found, rows
 # written); object_cls u8 [Hs, Ws]; hist i32 [max_objects, num_class] or None (BCD has no class map)
 SceneObjects = namedtuple("SceneObjects", "labels table counts object_cls hist")
+# rings i32 [max_rings, 8] = (id, start, n_vertices, area, perimeter, x, y, 0) in the order of their starting edge; vertices i32
+# [max_vertices, 2] = (vx, vy) lattice points, ring after ring; counts i32 [5] = (rings found, rows written, vertices found,
+# vertices written, status: _lib.OUTLINE_ST_*)
+SceneOutlines = namedtuple("SceneOutlines", "rings vertices counts")
 TASKS = ("bcd", "scd", "bda")
 WINDOWS = ("hann", "flat")
 
@@ -117,6 +125,10 @@ class SceneInferencer:
     damage_map u8, cls_logits f32 [num_class, Hs, Ws])` with damage_map = argmax of the blended logits times loc_mask.
     `objects=True` appends a `SceneObjects`: the objects of the mask (BCD, score = prob), of the change mask voted over
     `post_cls` (SCD), or the buildings of `loc_mask` voted over `damage_map` (BDA, score = loc_prob); classes from 1 vote.
+    `outlines=True` (with `objects=True`) appends a `SceneOutlines` after it: the polygon rings of those objects.  `max_rings`
+    and `max_vertices` default to `ops.scene_outlines_defaults`: 4 rings per row of the object table and 16 vertices per ring,
+    cut to Hs * Ws and 4 * Hs * Ws.  The worst case, a 4-connected checkerboard, has Hs * Ws / 2 rings and 2 * Hs * Ws
+    vertices; a scene past the limits sets `OUTLINE_ST_TRUNCATED` in `counts[4]` and keeps a prefix of its rings.
     All results stay on the device."""
 
     def __init__(self, model, task, stride=None, window="hann", batch=32, mean=BCDTransforms.DEFAULT_MEAN,
@@ -161,7 +173,12 @@ class SceneInferencer:
         return dev
 
     @torch.no_grad()
-    def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536):
+    def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
+                max_vertices=None):
+        if outlines and not objects:
+            raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
+        if any(v is not None and int(v) < 1 for v in (max_rings, max_vertices)):
+            raise ValueError(f"max_rings and max_vertices must be positive, got {max_rings} and {max_vertices}")
         dev = self._device()
         if connectivity not in (4, 8) or int(max_objects) < 1:
             raise ValueError(f"connectivity must be 4 or 8 and max_objects positive, got {connectivity} and {max_objects}")
@@ -219,5 +236,8 @@ class SceneInferencer:
             labels, table, hist, object_cls, counts = ops.scene_objects(first_class=1, connectivity=connectivity, min_area=min_area,
                                                                         max_objects=max_objects, **found)
             result += (SceneObjects(labels, table, counts, object_cls, hist),)
+            if outlines:
+                result += (SceneOutlines(*ops.scene_outlines(labels, counts, connectivity=connectivity, max_objects=max_objects,
+                                                             max_rings=max_rings, max_vertices=max_vertices)),)
         torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
         return result

@@ -866,6 +866,47 @@ def objects_match(labels_p, table_p, counts_p, labels_g, table_g, counts_g, n_cl
     return match_p, match_g, conf, counts, sum_iou
 
 
+def scene_outlines_defaults(Hs, Ws, max_objects=65536):
+    """(max_rings, max_vertices) where the caller names none: 4 ring rows per table row of `scene_objects` (an outline and
+    three holes each, on average) and 16 vertices per ring row, both cut to what a scene of this size can hold at all.  The
+    worst case is far above either: a 4-connected checkerboard has Hs * Ws / 2 rings and 2 * Hs * Ws vertices, and a label
+    map of single pixels with distinct ids has Hs * Ws rings and 4 * Hs * Ws vertices.  A scene that exceeds the defaults
+    sets `OUTLINE_ST_TRUNCATED` and loses the rings past the limits, never anything else."""
+    N = int(Hs) * int(Ws)
+    max_rings = max(1, min(4 * int(max_objects), N))
+    return max_rings, max(1, min(16 * max_rings, 4 * N))
+
+
+def scene_outlines(labels, counts, connectivity=8, max_objects=65536, max_rings=None, max_vertices=None, ws=None):
+    """c3d_scene_outlines on the `labels` i32 [Hs, Ws] and `counts` i32 [2] of `scene_objects` (same `connectivity` and
+    `max_objects`): `(rings i32 [max_rings, 8] = (id, start, n_vertices, area, perimeter, x, y, 0), vertices i32 [max_vertices,
+    2] = (vx, vy), counts i32 [5] = (rings found, rows written, vertices found, vertices written, status))`, all on the
+    device; nothing is read back.  Vertex rows past counts[3] are not initialised.  Defaults: `scene_outlines_defaults`."""
+    for t in (labels, counts):
+        require_gpu(t, "scene_outlines input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert labels.dim() == 2 and counts.numel() == 2
+    Hs, Ws = int(labels.shape[0]), int(labels.shape[1])
+    d_rings, d_vertices = scene_outlines_defaults(Hs, Ws, max_objects)
+    max_rings = d_rings if max_rings is None else int(max_rings)
+    max_vertices = d_vertices if max_vertices is None else int(max_vertices)
+    nbytes = L.lib().c3d_scene_outlines_ws_bytes(Hs, Ws)
+    if nbytes < 0 or int(max_objects) < 1 or max_rings < 1 or max_vertices < 1 or connectivity not in (4, 8):
+        raise L.Change3DHipError(f"c3d_scene_outlines refuses a {Hs} x {Ws} scene with connectivity = {connectivity}, max_objects = "
+                                 f"{max_objects}, max_rings = {max_rings}, max_vertices = {max_vertices} (code "
+                                 f"{nbytes if nbytes < 0 else -1})")
+    dev = labels.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    rings = torch.empty((max_rings, 8), dtype=torch.int32, device=dev)
+    vertices = torch.empty((max_vertices, 2), dtype=torch.int32, device=dev)
+    out = torch.empty(5, dtype=torch.int32, device=dev)
+    _launch("c3d_scene_outlines", Hs * Ws * 64, L.lib().c3d_scene_outlines, _p(labels), _p(counts), Hs, Ws, int(connectivity),
+            int(max_objects), max_rings, max_vertices, _p(rings), _p(vertices), _p(out), _p(ws), _stream())
+    return rings, vertices, out
+
+
 def build_clip(pre, post, frames, clip, B, K, H, W):
     _launch("c3d_build_clip", clip.numel() * 8, L.lib().c3d_build_clip, _p(pre), _p(post), _p(frames), _p(clip), B, K, H, W,
             _stream())

@@ -17,6 +17,11 @@ the post class map, no score) with at least `--min_area` pixels (`id,area,x0,y0,
 `c3d_scene_objects`; BDA also writes
 `damage_objects/<name>.png`, the majority damage class of every building painted over its footprint, and scores it.
 
+`--objects --polygons` adds `objects/<name>.geojson`: a `FeatureCollection` in pixel coordinates with one `Polygon` per object,
+traced on the device by `c3d_scene_outlines` -- `[outline, hole, ...]`, every ring closed by repeating its first vertex, holes
+in ring order -- with the CSV's `id, area, cls, score` and the outline's `perimeter` as properties.  An object whose rings did
+not fit `--max_rings` / `--max_vertices` is left out and the run ends with an error that says so.
+
 `--objects` with labels also scores the objects themselves (change3d_amd/object_metrics.py, `c3d_objects_match`): the
 predicted objects against the objects of the label mask (BCD), of the change label voted over label2 (SCD) or the buildings
 of `label_loc > 0` voted over `label_loc * label_cls` (BDA).  A pair matches iff its IoU is strictly above `--iou_thr`.  One
@@ -24,6 +29,7 @@ more line follows the score line, `objects: tp fp fn precision recall f1 sq rq p
 class), and `objects/<name>.match.csv` lists `id,gt_id,inter,union,covered` per predicted object and, under a `# gt` line,
 `id,pred_id,inter,union,covered` per ground-truth object.
 """
+import json
 import os
 import sys
 from argparse import ArgumentParser, ArgumentTypeError
@@ -104,6 +110,46 @@ def save_objects(path, objects):
     return found, rows
 
 
+def polygons_geojson(table, rings, vertices):
+    """(FeatureCollection dict, ids left out) from host arrays: `table` [rows, 8] of the objects, `rings` [ring rows, 8] and
+    `vertices` [vertices written, 2] of their outlines.  An object is complete iff it has one ring of positive area, every
+    ring of it has its vertices (start >= 0) and the signed areas add up to the table's area -- a hole ring cut off by
+    max_rings leaves the sum too large.  Incomplete objects are left out."""
+    table, rings, vertices = np.asarray(table), np.asarray(rings), np.asarray(vertices)
+    by_id = {}
+    for row in rings.tolist():
+        by_id.setdefault(row[0], []).append(row)
+    features, skipped = [], []
+    for k, (area, _, _, _, _, cls, _, score_q) in enumerate(table.tolist()):
+        own = by_id.get(k + 1, [])
+        outline = [r for r in own if r[3] > 0]
+        if len(outline) != 1 or any(r[1] < 0 or r[1] + r[2] > len(vertices) for r in own) or sum(r[3] for r in own) != area:
+            skipped.append(k + 1)
+            continue
+        coords = []
+        for r in outline + [r for r in own if r[3] <= 0]:  # the outline, then the holes in ring order
+            ring = vertices[r[1]:r[1] + r[2]].tolist()
+            coords.append(ring + ring[:1])
+        features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords},
+                         "properties": {"id": k + 1, "area": area, "cls": cls, "score": round(score_q / 65535, 4),
+                                        "perimeter": outline[0][4]}})
+    return {"type": "FeatureCollection", "features": features}, skipped
+
+
+def save_polygons(path, objects, outlines):
+    """objects/<name>.geojson; the one read-back of the rings.  Returns the ids that were left out."""
+    ring_rows, written = int(outlines.counts[1]), int(outlines.counts[3])
+    rows = int(objects.counts[1])
+    doc, skipped = polygons_geojson(objects.table[:rows].cpu().numpy(), outlines.rings[:ring_rows].cpu().numpy(),
+                                    outlines.vertices[:written].cpu().numpy())
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(doc, f)
+    if skipped:
+        print(f"{path}: {len(skipped)} of {rows} objects left out, their rings were cut off (status {int(outlines.counts[4])})")
+    return skipped
+
+
 def save_matches(path, objects, gt_counts, match_p, match_g):
     """objects/<name>.match.csv: the rows of the predicted objects, then those of the ground-truth objects under `# gt`."""
     rows_p, rows_g = int(objects.counts[1]), int(gt_counts[1])
@@ -148,8 +194,16 @@ def iou_threshold(text):
     return v
 
 
+def parse_args(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.polygons and not args.objects:
+        parser.error("--polygons outlines the objects of the map: it needs --objects")
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     num_class = num_classes(args)
     if not args.file_root and not (args.pre and args.post):
         raise SystemExit("give --pre and --post, or --file_root")
@@ -162,6 +216,7 @@ def main(argv=None):
     object_hist = SCDHistogram(num_class, device) if args.task == "BDA" and args.objects else None
     object_eval = None                                    # made by the first labelled scene of a run with --objects
     scored = 0
+    cut_off = 0                                           # objects whose polygon was left out of a .geojson
 
     def score_objects(name, objects, gt_mask, gt_cls=None):
         nonlocal object_eval
@@ -172,7 +227,12 @@ def main(argv=None):
 
     for name, img, label in scenes(args):
         scene = torch.from_numpy(np.ascontiguousarray(img))
-        if args.objects:
+        if args.polygons:                 # the outlines come last; every `out[-1]` below is the objects
+            out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, outlines=True,
+                              max_rings=args.max_rings, max_vertices=args.max_vertices)
+            cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1]))
+            out = out[:-1]
+        elif args.objects:
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity)
         else:
             out = inf.predict(scene)
@@ -216,6 +276,8 @@ def main(argv=None):
                     score_objects(name, out[-1], lab[..., 2] > 0, lab[..., 1])
                 scored += 1
         print(f"{name}: {img.shape[0]} x {img.shape[1]} -> {args.out_dir}")
+    if cut_off:
+        raise SystemExit(f"{cut_off} objects have no polygon: their rings did not fit; raise --max_rings / --max_vertices")
     if not scored:
         return None
     if args.task == "BDA":
@@ -256,6 +318,9 @@ def build_parser():
     p.add_argument("--objects", action="store_true", help="also the connected objects of the mask (SCD: of the change mask), as objects/<name>.csv")
     p.add_argument("--min_area", type=int, default=1, help="--objects: drop objects with fewer pixels")
     p.add_argument("--connectivity", type=int, choices=[4, 8], default=8)
+    p.add_argument("--polygons", action="store_true", help="--objects: also their outlines, as objects/<name>.geojson")
+    p.add_argument("--max_rings", type=int, default=None, help="--polygons: rows of the ring table (default: 4 per object row)")
+    p.add_argument("--max_vertices", type=int, default=None, help="--polygons: rows of the vertex list (default: 16 per ring row)")
     p.add_argument("--iou_thr", type=iou_threshold, default=0.5, help="--objects with labels: a predicted and a labelled object match iff "
                    "their IoU is strictly above this; in [0.5, 1)")
     p.add_argument("--pretrained", default="./pretrained/X3D_L.pyth")

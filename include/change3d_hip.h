@@ -617,6 +617,62 @@ int c3d_objects_match(const int32_t* labels_p, const int32_t* table_p, const int
                       int32_t n_cls, double iou_thr, int64_t table_capacity, int32_t* match_p, int32_t* match_g, int64_t* conf,
                       int64_t* counts, double* sum_iou, int64_t* totals, double* total_iou, void* ws, void* stream);
 
+/* Outlines of the objects of a scene map (csrc/scene_outlines.hip): the label map of c3d_scene_objects traced into closed
+ * rectilinear polygon rings, one ring of positive area per object and one of negative area per hole, while it stays in HBM.
+ * Integer arithmetic and integer atomics only: every output is exact and two runs agree bit for bit.  One memset and
+ * 10 + ceil(log2(4 Hs Ws)) launches on `stream`, nothing is read back by the host, no workgroup waits for another; the call
+ * zeroes what it needs of the workspace.  The definition:
+ *   geometry    pixel (y, x) is the unit square [x, x+1] x [y, y+1]; vertices are lattice points (vx, vy), 0 <= vx <= Ws,
+ *               0 <= vy <= Hs
+ *   edges       a boundary edge of object `id` is a side of a pixel labelled id whose neighbour across that side has another
+ *               label or lies outside the scene.  Pixels with a label <= 0 or above rows = clamp(counts_obj[1], 0,
+ *               max_objects) own no edges
+ *   direction   sides are numbered 0 top, 1 right, 2 bottom, 3 left and directed with the object on the right of travel in
+ *               image coordinates (y down): top goes +x, right +y, bottom -x, left -y
+ *   key         4 * (y * Ws + x) + side; Hs * Ws < 2^29 keeps it in i32 (C3D_E_UNSUPPORTED beyond)
+ *   successor   the first existing boundary edge of the same id out of the edge's end vertex among: the right turn (the next
+ *               side of the same pixel), straight on (the same side of the next pixel along the travel), the left turn (side
+ *               (s+3)%4 of the diagonal pixel ahead on the outside).  connectivity 4 tries right, straight, left;
+ *               connectivity 8 tries left, straight, right.  8-connected objects thus join across a diagonal and their holes
+ *               split there, 4-connected objects split and their holes join: labelled with the same connectivity, every object
+ *               has exactly one ring of positive area and one ring of negative area per hole.  A ring may touch itself at a
+ *               vertex; it never crosses itself
+ *   corners     a corner edge is one whose side differs from its predecessor's.  A ring's vertices are the start vertices of
+ *               its corner edges in ring order, beginning at the corner edge with the smallest key (NOT the ring's smallest
+ *               edge: the bottom side that a wide hole begins with is reached straight on and is no corner)
+ *   order       rings ascend by that starting key over the whole scene; the rings of one object are not contiguous
+ *   area        shoelace sum / 2 over the vertices: an integer, positive for outlines, negative for holes, fits i32
+ *   perimeter   the number of unit edges of the ring
+ * Inputs (device):
+ *   labels, counts_obj   labels i32 [Hs][Ws] and counts i32 [2] of c3d_scene_objects;  max_objects as given to that call
+ *   connectivity 4 or 8: the one the labels were made with
+ * Outputs:
+ *   rings     i32 [max_rings][8], 16-byte aligned, row r = (id, start, n_vertices, area, perimeter, x, y, 0): start = offset
+ *             of the ring's first vertex in `vertices` = the vertices of all rings before it; (x, y) = that first vertex.
+ *             Rows past the last written ring are 0, written by the call
+ *   vertices  i32 [max_vertices][2] = (vx, vy), 8-byte aligned; rings contiguous, in ring order; neither the closing repeat of
+ *             the first vertex nor a collinear vertex is stored.  Rows past counts[3] are left as they were
+ *   counts    i32 [5] = (rings found, ring rows written, vertices found, vertices written, status)
+ *   ws        c3d_scene_outlines_ws_bytes(Hs, Ws) bytes (about 133 per pixel: two buffers of 16 bytes for each of the 4 Hs Ws
+ *             edges that some label map can own), 256-byte aligned
+ * Truncation is prefix-shaped: ring rows are written for ring index < max_rings; a ring's vertices are written only if start +
+ * n_vertices <= max_vertices, otherwise its row gets start = -1 and none of its vertices is written (so is every later ring's).
+ * Nothing is ever written out of range.  status bits:
+ *   C3D_OUTLINE_ST_TRUNCATED   found > written on either count, or counts_obj[0] > counts_obj[1]
+ *   C3D_OUTLINE_ST_BAD_COUNTS  counts_obj[0] < 0 (c3d_scene_objects reported an error): nothing is traced, the counts are 0
+ *   C3D_OUTLINE_ST_STEP_CAP    the fixed number of pointer-doubling rounds left a ring without an agreed start, or an index
+ *                              derived from the workspace fell out of range (neither can happen: 2^rounds edges cover any ring;
+ *                              the checks keep a corrupted workspace from being written through)
+ * Refused before anything is enqueued: a NULL labels / counts_obj / rings / vertices / counts / ws, Hs or Ws <= 0, connectivity
+ * other than 4 / 8, max_objects, max_rings or max_vertices < 1 (C3D_E_BADARG); Hs * Ws >= 2^29 (C3D_E_UNSUPPORTED).          */
+#define C3D_OUTLINE_ST_TRUNCATED 1
+#define C3D_OUTLINE_ST_BAD_COUNTS 2
+#define C3D_OUTLINE_ST_STEP_CAP 4
+int64_t c3d_scene_outlines_ws_bytes(int32_t Hs, int32_t Ws);            /* < 0: C3D_E_* */
+int c3d_scene_outlines(const int32_t* labels, const int32_t* counts_obj, int32_t Hs, int32_t Ws, int32_t connectivity,
+                       int32_t max_objects, int32_t max_rings, int32_t max_vertices, int32_t* rings, int32_t* vertices,
+                       int32_t* counts, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
  * stage (reference model/x3d.py:331-412 = ResStage of ResBlocks, driven by `self.x3d.blocks[i](x)` at
