@@ -101,6 +101,8 @@ CAP_ST_TABLE_FULL, CAP_ST_BAD_SELECTION, CAP_ST_BAD_SENTENCE = 1, 2, 4  # bits o
 
 MATCH_ST_TABLE_FULL, MATCH_ST_TRUNCATED, MATCH_ST_BAD_COUNTS = 1, 2, 4     # C3D_MATCH_ST_*: bits of counts[4] / totals[4]
 OUTLINE_ST_TRUNCATED, OUTLINE_ST_BAD_COUNTS, OUTLINE_ST_STEP_CAP = 1, 2, 4  # C3D_OUTLINE_ST_*: bits of c3d_scene_outlines' counts[4]
+SIMPLIFY_ST_BAD_INPUT = 8                                # C3D_SIMPLIFY_ST_BAD_INPUT: added by c3d_outlines_simplify
+SIMPLIFY_TOL2_Q_MAX = 16 * 1024 * 1024                   # C3D_SIMPLIFY_TOL2_Q_MAX
 
 
 class CapMetricsArgs(C.Structure):
@@ -180,6 +182,9 @@ SIGNATURES = {
     "c3d_objects_match": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "c3d_scene_outlines_ws_bytes": (i64, [i32, i32]),
     "c3d_scene_outlines": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "c3d_outlines_simplify_limits": (None, [C.POINTER(i32)]),
+    "c3d_outlines_simplify_ws_bytes": (i64, [i32, i32]),
+    "c3d_outlines_simplify": (i32, [vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]),
     "c3d_cap_embed_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_embed_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_dropout": (i32, [vp, vp, i64, i32, f32, C.c_uint64, i32, vp]),

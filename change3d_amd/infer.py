@@ -24,6 +24,10 @@ synchronisation per scene, nothing is read back.
 `predict(scene, objects=True, outlines=True)` appends the polygons of those objects (`SceneOutlines`) after them:
 `c3d_scene_outlines` traces the label map into closed rings on the device, one outline per object and one ring per hole, as
 a ring table and a vertex list; it is enqueued behind the labelling, before the same one synchronisation.
+
+`predict(scene, objects=True, outlines=True, simplify=tol)` appends one more `SceneOutlines` after the raw one: the same rings
+simplified by `c3d_outlines_simplify` (Douglas-Peucker, `tol` in pixels), enqueued behind the tracing, before the same one
+synchronisation.  Its rows are `(id, start, n_vertices, 2 * area, perimeter, x, y, raw n_vertices)`.
 """
 from collections import namedtuple
 
@@ -129,6 +133,9 @@ class SceneInferencer:
     and `max_vertices` default to `ops.scene_outlines_defaults`: 4 rings per row of the object table and 16 vertices per ring,
     cut to Hs * Ws and 4 * Hs * Ws.  The worst case, a 4-connected checkerboard, has Hs * Ws / 2 rings and 2 * Hs * Ws
     vertices; a scene past the limits sets `OUTLINE_ST_TRUNCATED` in `counts[4]` and keeps a prefix of its rings.
+    `simplify=tol` (with `outlines=True`) appends one more `SceneOutlines`: the rings simplified with a tolerance of `tol`
+    pixels in [0, 1024] (`ops.outlines_simplify`); column 3 of its rows is twice the signed area of the simplified ring and
+    column 7 the ring's raw vertex count.  With `simplify=None` the result is the one without the argument.
     All results stay on the device."""
 
     def __init__(self, model, task, stride=None, window="hann", batch=32, mean=BCDTransforms.DEFAULT_MEAN,
@@ -174,9 +181,13 @@ class SceneInferencer:
 
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
-                max_vertices=None):
+                max_vertices=None, simplify=None):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
+        if simplify is not None:
+            if not outlines:
+                raise ValueError("simplify=tol simplifies the outlines of the objects: it needs outlines=True")
+            ops.simplify_tol2_q(simplify)               # raises outside [0, 1024] before anything is enqueued
         if any(v is not None and int(v) < 1 for v in (max_rings, max_vertices)):
             raise ValueError(f"max_rings and max_vertices must be positive, got {max_rings} and {max_vertices}")
         dev = self._device()
@@ -239,5 +250,7 @@ class SceneInferencer:
             if outlines:
                 result += (SceneOutlines(*ops.scene_outlines(labels, counts, connectivity=connectivity, max_objects=max_objects,
                                                              max_rings=max_rings, max_vertices=max_vertices)),)
+                if simplify is not None:
+                    result += (SceneOutlines(*ops.outlines_simplify(*result[-1], simplify)),)
         torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
         return result

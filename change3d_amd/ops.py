@@ -907,6 +907,49 @@ def scene_outlines(labels, counts, connectivity=8, max_objects=65536, max_rings=
     return rings, vertices, out
 
 
+def simplify_tol2_q(tol):
+    """The tolerance of `outlines_simplify` as the call takes it: round(16 * tol * tol), sixteenths of a square pixel.  Raises
+    outside [0, 1024] pixels."""
+    tol = float(tol)
+    if not 0.0 <= tol <= 1024.0:                          # also refuses NaN
+        raise ValueError(f"the simplification tolerance must lie in [0, 1024] pixels, got {tol}")
+    return int(round(16.0 * tol * tol))
+
+
+def outlines_simplify_limits():
+    """(most vertices of a ring that one wave simplifies, most of a ring that one workgroup keeps in LDS)."""
+    out = (L.C.c_int32 * 2)()
+    L.lib().c3d_outlines_simplify_limits(out)
+    return int(out[0]), int(out[1])
+
+
+def outlines_simplify(rings, vertices, counts, tol, ws=None):
+    """c3d_outlines_simplify on the `rings` i32 [max_rings, 8], `vertices` i32 [max_vertices, 2] and `counts` i32 [5] of
+    `scene_outlines` (or any table of that shape): Douglas-Peucker with the tolerance `tol` in pixels, by the integer rule of
+    include/change3d_hip.h.  Returns `(rings_out i32 [max_rings, 8] = (id, start', n', area2', perimeter, x, y, n),
+    vertices_out i32 [max_vertices, 2], counts_out i32 [5] = (rings found, rows written, vertices kept, vertices written,
+    status))`, all on the device; nothing is read back.  Vertex rows past counts_out[3] are not initialised."""
+    tol2_q = simplify_tol2_q(tol)
+    for t in (rings, vertices, counts):
+        require_gpu(t, "outlines_simplify input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    max_rings, max_vertices = int(rings.shape[0]), int(vertices.shape[0])
+    nbytes = L.lib().c3d_outlines_simplify_ws_bytes(max_rings, max_vertices)
+    if nbytes < 0:
+        raise L.Change3DHipError(f"c3d_outlines_simplify refuses max_rings = {max_rings}, max_vertices = {max_vertices} (code {nbytes})")
+    dev = rings.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    rings_out = torch.empty((max_rings, 8), dtype=torch.int32, device=dev)
+    vertices_out = torch.empty((max_vertices, 2), dtype=torch.int32, device=dev)
+    out = torch.empty(5, dtype=torch.int32, device=dev)
+    _launch("c3d_outlines_simplify", (max_rings + max_vertices) * 64, L.lib().c3d_outlines_simplify, _p(rings), _p(vertices),
+            _p(counts), max_rings, max_vertices, tol2_q, _p(rings_out), _p(vertices_out), _p(out), _p(ws), _stream())
+    return rings_out, vertices_out, out
+
+
 def build_clip(pre, post, frames, clip, B, K, H, W):
     _launch("c3d_build_clip", clip.numel() * 8, L.lib().c3d_build_clip, _p(pre), _p(post), _p(frames), _p(clip), B, K, H, W,
             _stream())

@@ -21,6 +21,9 @@ the post class map, no score) with at least `--min_area` pixels (`id,area,x0,y0,
 traced on the device by `c3d_scene_outlines` -- `[outline, hole, ...]`, every ring closed by repeating its first vertex, holes
 in ring order -- with the CSV's `id, area, cls, score` and the outline's `perimeter` as properties.  An object whose rings did
 not fit `--max_rings` / `--max_vertices` is left out and the run ends with an error that says so.
+`--simplify TOL` (with `--polygons`) simplifies every ring on the device first (`c3d_outlines_simplify`, Douglas-Peucker with a
+tolerance of TOL pixels): the coordinates then come from the simplified rings and each feature also gets `vertices_raw` and
+`vertices`, its vertex counts before and after.  A ring whose simplified area is zero or has changed sign keeps its raw vertices.
 
 `--objects` with labels also scores the objects themselves (change3d_amd/object_metrics.py, `c3d_objects_match`): the
 predicted objects against the objects of the label mask (BCD), of the change label voted over label2 (SCD) or the buildings
@@ -110,15 +113,21 @@ def save_objects(path, objects):
     return found, rows
 
 
-def polygons_geojson(table, rings, vertices):
+def polygons_geojson(table, rings, vertices, simplified=None):
     """(FeatureCollection dict, ids left out) from host arrays: `table` [rows, 8] of the objects, `rings` [ring rows, 8] and
     `vertices` [vertices written, 2] of their outlines.  An object is complete iff it has one ring of positive area, every
     ring of it has its vertices (start >= 0) and the signed areas add up to the table's area -- a hole ring cut off by
-    max_rings leaves the sum too large.  Incomplete objects are left out."""
+    max_rings leaves the sum too large.  Incomplete objects are left out.
+    `simplified` = (rings, vertices) of `c3d_outlines_simplify` on the same table, row for row: the coordinates of a ring then
+    come from the simplified list -- unless its doubled area there is zero or has the other sign than the raw area, or its row
+    has no vertices, in which case the ring keeps its raw vertices -- and every feature gets the counts `vertices_raw` and
+    `vertices`.  Completeness is judged on the raw rings either way."""
     table, rings, vertices = np.asarray(table), np.asarray(rings), np.asarray(vertices)
+    if simplified is not None:
+        rings_s, vertices_s = np.asarray(simplified[0]).tolist(), np.asarray(simplified[1])
     by_id = {}
-    for row in rings.tolist():
-        by_id.setdefault(row[0], []).append(row)
+    for at, row in enumerate(rings.tolist()):
+        by_id.setdefault(row[0], []).append(row + [at])
     features, skipped = [], []
     for k, (area, _, _, _, _, cls, _, score_q) in enumerate(table.tolist()):
         own = by_id.get(k + 1, [])
@@ -126,22 +135,32 @@ def polygons_geojson(table, rings, vertices):
         if len(outline) != 1 or any(r[1] < 0 or r[1] + r[2] > len(vertices) for r in own) or sum(r[3] for r in own) != area:
             skipped.append(k + 1)
             continue
-        coords = []
+        coords, n_raw, n_out = [], 0, 0
         for r in outline + [r for r in own if r[3] <= 0]:  # the outline, then the holes in ring order
             ring = vertices[r[1]:r[1] + r[2]].tolist()
+            n_raw += len(ring)
+            if simplified is not None:
+                s = rings_s[r[8]]
+                if s[1] >= 0 and s[1] + s[2] <= len(vertices_s) and s[3] != 0 and (s[3] > 0) == (r[3] > 0):
+                    ring = vertices_s[s[1]:s[1] + s[2]].tolist()
+            n_out += len(ring)
             coords.append(ring + ring[:1])
-        features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords},
-                         "properties": {"id": k + 1, "area": area, "cls": cls, "score": round(score_q / 65535, 4),
-                                        "perimeter": outline[0][4]}})
+        properties = {"id": k + 1, "area": area, "cls": cls, "score": round(score_q / 65535, 4), "perimeter": outline[0][4]}
+        if simplified is not None:
+            properties.update(vertices_raw=n_raw, vertices=n_out)
+        features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords}, "properties": properties})
     return {"type": "FeatureCollection", "features": features}, skipped
 
 
-def save_polygons(path, objects, outlines):
-    """objects/<name>.geojson; the one read-back of the rings.  Returns the ids that were left out."""
+def save_polygons(path, objects, outlines, simplified=None):
+    """objects/<name>.geojson; the one read-back of the rings (`simplified`: the second `SceneOutlines` of
+    `predict(..., simplify=tol)`, read back with them).  Returns the ids that were left out."""
     ring_rows, written = int(outlines.counts[1]), int(outlines.counts[3])
     rows = int(objects.counts[1])
+    if simplified is not None:
+        simplified = (simplified.rings[:ring_rows].cpu().numpy(), simplified.vertices[:int(simplified.counts[3])].cpu().numpy())
     doc, skipped = polygons_geojson(objects.table[:rows].cpu().numpy(), outlines.rings[:ring_rows].cpu().numpy(),
-                                    outlines.vertices[:written].cpu().numpy())
+                                    outlines.vertices[:written].cpu().numpy(), simplified)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
         json.dump(doc, f)
@@ -194,11 +213,20 @@ def iou_threshold(text):
     return v
 
 
+def simplify_tolerance(text):
+    v = float(text)
+    if not 0.0 <= v <= 1024.0:
+        raise ArgumentTypeError(f"the tolerance must lie in [0, 1024] pixels, got {text}")
+    return v
+
+
 def parse_args(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.polygons and not args.objects:
         parser.error("--polygons outlines the objects of the map: it needs --objects")
+    if args.simplify is not None and not args.polygons:
+        parser.error("--simplify simplifies the polygons: it needs --polygons")
     return args
 
 
@@ -229,8 +257,11 @@ def main(argv=None):
         scene = torch.from_numpy(np.ascontiguousarray(img))
         if args.polygons:                 # the outlines come last; every `out[-1]` below is the objects
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, outlines=True,
-                              max_rings=args.max_rings, max_vertices=args.max_vertices)
-            cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1]))
+                              max_rings=args.max_rings, max_vertices=args.max_vertices, simplify=args.simplify)
+            simplified = None
+            if args.simplify is not None:
+                out, simplified = out[:-1], out[-1]
+            cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified))
             out = out[:-1]
         elif args.objects:
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity)
@@ -321,6 +352,8 @@ def build_parser():
     p.add_argument("--polygons", action="store_true", help="--objects: also their outlines, as objects/<name>.geojson")
     p.add_argument("--max_rings", type=int, default=None, help="--polygons: rows of the ring table (default: 4 per object row)")
     p.add_argument("--max_vertices", type=int, default=None, help="--polygons: rows of the vertex list (default: 16 per ring row)")
+    p.add_argument("--simplify", type=simplify_tolerance, default=None, metavar="TOL", help="--polygons: simplify the rings on the "
+                   "device (Douglas-Peucker) with this tolerance in pixels, in [0, 1024]")
     p.add_argument("--iou_thr", type=iou_threshold, default=0.5, help="--objects with labels: a predicted and a labelled object match iff "
                    "their IoU is strictly above this; in [0.5, 1)")
     p.add_argument("--pretrained", default="./pretrained/X3D_L.pyth")

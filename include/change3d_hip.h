@@ -673,6 +673,60 @@ int c3d_scene_outlines(const int32_t* labels, const int32_t* counts_obj, int32_t
                        int32_t max_objects, int32_t max_rings, int32_t max_vertices, int32_t* rings, int32_t* vertices,
                        int32_t* counts, void* ws, void* stream);
 
+/* Simplified polygons (csrc/scene_simplify.hip): Douglas-Peucker with a pixel tolerance on the ring table and vertex list of
+ * c3d_scene_outlines while they stay in HBM, or on any table of that shape (rings may repeat a lattice point and may hold
+ * collinear vertices).  Integer arithmetic only: floating point appears nowhere in a decision, every output is exact and two
+ * runs agree bit for bit.  One memset and 6 launches on `stream`, nothing is read back by the host, no workgroup waits for
+ * another: the rounds of the recursion run inside the kernels, one wave or one workgroup per ring.  The rule:
+ *   tolerance   tol2_q = round(16 * tol * tol), sixteenths of a square pixel, 0 <= tol2_q <= C3D_SIMPLIFY_TOL2_Q_MAX
+ *               (tol <= 1024).  Coordinates must lie in [0, 16384]; every quantity below then fits an unsigned 64-bit integer
+ *   distance    a ring has the vertices v[0 .. n-1] in stored order, v[n] = v[0].  For a chord (a, b) and a vertex p let
+ *               L2 = |b-a|^2, t = (p-a).(b-a), c = cross(b-a, p-a).  The squared distance of p to the SEGMENT is num / den:
+ *                 L2 == 0     num = |p-a|^2        den = 1
+ *                 t <= 0      num = |p-a|^2 * L2   den = L2
+ *                 t >= L2     num = |p-b|^2 * L2   den = L2
+ *                 otherwise   num = c * c          den = L2
+ *               p is far iff 16 * num > tol2_q * den, strictly.  The vertices of one chord share den: the farthest has the
+ *               largest num, the smallest index on ties
+ *   per ring    n <= 3: copied.  Otherwise the anchors are A = 0 and B = the vertex with the largest |v[k]-v[0]|^2, smallest k
+ *               on ties; the chains A..B and B..n are simplified by Douglas-Peucker: on a chord (i, j), j > i + 1, take the
+ *               farthest interior vertex m; if m is far keep it and go on with (i, m) and (m, j), otherwise drop the whole
+ *               interior.  If at most A and B survive, the vertex with the largest |cross(v[B]-v[A], v[k]-v[A])|, smallest k
+ *               on ties, is kept too: a ring of non-zero area never falls under 3 vertices
+ *   topology    none is promised: a simplified ring may touch or cross itself or its holes, as with any plain
+ *               Douglas-Peucker.  Every dropped vertex lies within tol of the kept chord that spans it
+ * Inputs (device): rings i32 [max_rings][8], vertices i32 [max_vertices][2], counts i32 [5] as c3d_scene_outlines writes them.
+ * Rows r < clamp(counts[1], 0, max_rings) are read; vertex rows below clamp(counts[3], 0, max_vertices) may be named by them.
+ * Like the outputs, `rings` must be 16-byte aligned and `vertices` 8-byte aligned: rows are loaded as vectors.
+ * Outputs (must not alias the inputs):
+ *   rings_out     i32 [max_rings][8], 16-byte aligned, same row order: (id, start', n', area2', perimeter, x, y, n): start'
+ *                 and n' index vertices_out; area2' = the shoelace sum of the kept vertices = twice the signed area, an
+ *                 integer that may be odd.  It is exact wherever it fits i32, which holds for every ring that does not wind
+ *                 round the coordinate range several times (a traced ring never does); beyond that it is the sum modulo
+ *                 2^32.  id, perimeter, x, y are copied; column 7 = the input's n_vertices.  Rows past the last are 0
+ *   vertices_out  i32 [max_vertices][2], 8-byte aligned: the kept vertices, rings contiguous and in row order.  n' <= n, so
+ *                 the input's written-vertex count always suffices.  Rows past counts_out[3] are left as they were
+ *   counts_out    i32 [5] = (rings found, rows written, vertices kept, vertices written, status): kept == written; status =
+ *                 the input's status with C3D_SIMPLIFY_ST_BAD_INPUT added where it applies
+ *   ws            c3d_outlines_simplify_ws_bytes(max_rings, max_vertices) bytes (16 per ring row, 17 per vertex row),
+ *                 256-byte aligned; the call zeroes what it needs of it
+ * Rows that are not simplified get start' = -1, n' = 0, area2' = 0:
+ *   start < 0                       a ring the outlines call had no room for: passed through, no new status bit
+ *   out of range                    n < 0, start + n above the written vertices, a coordinate outside [0, 16384], or vertex
+ *                                   ranges that overlap so far that the n of this and all earlier valid rows add up to more
+ *                                   than max_vertices: C3D_SIMPLIFY_ST_BAD_INPUT.  Nothing is read or written out of range
+ * Input status C3D_OUTLINE_ST_BAD_COUNTS: counts_out = (0, 0, 0, 0, C3D_OUTLINE_ST_BAD_COUNTS), all ring rows 0.
+ * Refused before anything is enqueued (C3D_E_BADARG): a NULL pointer, max_rings or max_vertices < 1, tol2_q out of range.
+ * c3d_outlines_simplify_limits: out[0] = the most vertices of a ring that one wave simplifies in registers, out[1] = the most
+ * of a ring whose state one workgroup keeps in LDS; larger rings keep it in `ws`.  The results do not depend on the tier.      */
+#define C3D_SIMPLIFY_ST_BAD_INPUT 8
+#define C3D_SIMPLIFY_TOL2_Q_MAX (16ll * 1024 * 1024)
+void c3d_outlines_simplify_limits(int32_t out[2]);
+int64_t c3d_outlines_simplify_ws_bytes(int32_t max_rings, int32_t max_vertices);   /* < 0: C3D_E_* */
+int c3d_outlines_simplify(const int32_t* rings, const int32_t* vertices, const int32_t* counts, int32_t max_rings,
+                          int32_t max_vertices, int64_t tol2_q, int32_t* rings_out, int32_t* vertices_out, int32_t* counts_out,
+                          void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
  * stage (reference model/x3d.py:331-412 = ResStage of ResBlocks, driven by `self.x3d.blocks[i](x)` at
