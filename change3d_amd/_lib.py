@@ -100,6 +100,7 @@ CAP_ST_TABLE_FULL, CAP_ST_BAD_SELECTION, CAP_ST_BAD_SENTENCE = 1, 2, 4  # bits o
 
 
 MATCH_ST_TABLE_FULL, MATCH_ST_TRUNCATED, MATCH_ST_BAD_COUNTS = 1, 2, 4     # C3D_MATCH_ST_*: bits of counts[4] / totals[4]
+VIEWS_NONE, VIEWS_HFLIP, VIEWS_FLIPS, VIEWS_D4 = 0x01, 0x03, 0x0f, 0xff  # C3D_VIEWS_*: view masks of c3d_scene_gather_views / c3d_scene_fold_views
 OUTLINE_ST_TRUNCATED, OUTLINE_ST_BAD_COUNTS, OUTLINE_ST_STEP_CAP = 1, 2, 4  # C3D_OUTLINE_ST_*: bits of c3d_scene_outlines' counts[4]
 SIMPLIFY_ST_BAD_INPUT = 8                                # C3D_SIMPLIFY_ST_BAD_INPUT: added by c3d_outlines_simplify
 SIMPLIFY_TOL2_Q_MAX = 16 * 1024 * 1024                   # C3D_SIMPLIFY_TOL2_Q_MAX
@@ -175,6 +176,8 @@ SIGNATURES = {
     "c3d_augment_gather": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "c3d_scene_gather": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "c3d_scene_stitch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "c3d_scene_gather_views": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "c3d_scene_fold_views": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "c3d_scene_label_ws_bytes": (i64, [i32, i32, i32]),
     "c3d_scene_label_tile": (i32, [vp, vp]),
     "c3d_scene_objects": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),

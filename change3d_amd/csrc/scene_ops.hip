@@ -15,7 +15,11 @@
 //                      (tile row ascending, then tile column ascending), w = wy[y] * wx[x].  Gather form: every output
 //                      pixel is written once by one thread, no atomics, so two runs agree bit for bit.
 //
-// Both are streaming kernels: a thread owns 4 consecutive pixels of one output row and stores them as one 16-byte vector;
+//   c3d_scene_gather_views / c3d_scene_fold_views   test-time augmentation: the same tiles under the views of a mask over
+//                      the eight flips and rotations of the square, and the mean of the model's outputs with each view
+//                      undone, written straight into a slot range of the stitch ring (see "test-time augmentation" below).
+//
+// All are streaming kernels: a thread owns 4 consecutive pixels of one output row and stores them as one 16-byte vector;
 // rows of a scene whose width is no multiple of 4 are shifted so that the vectors stay aligned and the edges go out as
 // scalars.  Tables (normalised byte values, window vectors) live in LDS; a thread's tile set is found once, outside its
 // channel / tap loops.
@@ -188,6 +192,189 @@ __global__ __launch_bounds__(256) void scene_stitch_kernel(const StitchArgs a) {
   }
 }
 
+// ---- test-time augmentation: the eight views of the square (include/change3d_hip.h "Views") ----
+// V_v: transpose if v & 4, then reverse the rows if v & 2, then the columns if v & 1.  Both kernels below walk a plane in
+// 32 x 32 blocks, one block per workgroup pass: thread (r, q) = (tid >> 3, tid & 7) owns the quad 4q .. 4q + 3 of block row r,
+// so 8 neighbouring lanes read and write 128 B (192 B of scene) runs of one row whatever the view is.  A transposing view
+// goes through an LDS block [32][33] (pitch 33 dwords): written by rows, lane (r, q) word k at r*33 + 4q + k, read by columns,
+// lane (r, q) word k at (4q + k)*33 + r.  A 32-lane half holds 4 consecutive r and all 8 q, and r + 4q takes 32 different
+// values mod 32 there, so both directions touch every bank once (tools/tta_lds_check.py prints the model's cycle counts).
+// A column-reversing view keeps its 16-byte accesses: the quad at x0 maps to the quad at tw - 4 - x0 with its words reversed.
+constexpr int kVB = 32, kVP = kVB + 1;                       // block edge, LDS pitch in dwords
+
+__device__ __forceinline__ int view_slot(int mask, int v) { return __popc(mask & ((1 << v) - 1)); }
+
+// 4 words of row `row` of a th x tw plane that view bit 0 (`rev`) maps onto columns x0 .. x0 + 3: d[k] = p[row][rev ? tw-1-(x0+k) : x0+k]
+template <bool VEC>
+__device__ __forceinline__ void quad_load(const float* __restrict__ p, int row, int x0, bool rev, int tw, float (&d)[4]) {
+  const float* r = p + (int64_t)row * tw;
+  if (VEC) {                                                 // tw % 4 == 0: the quad is whole and aligned on either side
+    const float4 a = *reinterpret_cast<const float4*>(r + (rev ? tw - 4 - x0 : x0));
+    d[0] = rev ? a.w : a.x; d[1] = rev ? a.z : a.y; d[2] = rev ? a.y : a.z; d[3] = rev ? a.x : a.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = x0 + k < tw ? r[rev ? tw - 1 - (x0 + k) : x0 + k] : 0.f;
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void quad_store(float* __restrict__ p, int row, int x0, bool rev, int tw, const float (&d)[4]) {
+  float* r = p + (int64_t)row * tw;
+  if (VEC) {
+    *reinterpret_cast<float4*>(r + (rev ? tw - 4 - x0 : x0)) =
+        rev ? make_float4(d[3], d[2], d[1], d[0]) : make_float4(d[0], d[1], d[2], d[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (x0 + k < tw) r[rev ? tw - 1 - (x0 + k) : x0 + k] = d[k];
+  }
+}
+
+// Work item = (tile, 32 x 32 block of the tile): the block's pixels are read and normalised once, every plain view of the
+// mask is stored from registers, every transposing one from the LDS copy of the block (6 channels).  A block that overhangs
+// the tile (th no multiple of 32) keeps its out-of-tile lanes idle on both sides of the LDS: they neither write nor read it.
+template <bool VEC>
+__global__ __launch_bounds__(256) void scene_gather_views_kernel(const uint8_t* __restrict__ scene, const int32_t* __restrict__ origins,
+                                                                 const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                                 float* __restrict__ pre, float* __restrict__ post, int Hs, int Ws,
+                                                                 int n, int th, int tw, int mask, int nv) {
+  extern __shared__ float views_smem[];
+  float* lut = views_smem;                                   // [6][256], as in scene_gather_kernel
+  float* blk = views_smem + 6 * 256;                         // [6][32][33], transposing views only
+  for (int i = threadIdx.x; i < 6 * 256; i += 256) {
+    const int c = i >> 8;
+    const float v = (float)(i & 255) / 255.0f;
+    lut[i] = (v - mean[c]) / stdv[c];
+  }
+  __syncthreads();
+  const int q = threadIdx.x & 7, r = threadIdx.x >> 3;
+  const int nby = (th + kVB - 1) / kVB, nbx = (tw + kVB - 1) / kVB;
+  const int64_t plane = (int64_t)th * tw;
+  for (int64_t g = blockIdx.x; g < (int64_t)n * nby * nbx; g += gridDim.x) {
+    const int tile = (int)(g / (nby * nbx)), b = (int)(g % (nby * nbx)), Y0 = (b / nbx) * kVB, X0 = (b % nbx) * kVB;
+    const int y = Y0 + r, x0 = X0 + 4 * q;
+    const bool live = y < th && x0 < tw;
+    int64_t e = (int64_t)tile * nv * 3 * plane;              // entry tile * nv + j of both outputs, j counting the mask's views
+    float o[6][4];
+    if (live) {
+      const int64_t oy = origins[2 * tile], ox = origins[2 * tile + 1];
+      const uint8_t* row = scene + (int64_t)scene_fold(oy + y, Hs) * Ws * 6;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {                          // a column past the tile folds to a pixel of the scene: read, never stored
+        const uint16_t* p = reinterpret_cast<const uint16_t*>(row + (int64_t)scene_fold(ox + x0 + k, Ws) * 6);
+        const uint32_t a = p[0], bb = p[1], c = p[2];
+        o[0][k] = lut[a & 255]; o[1][k] = lut[256 + (a >> 8)]; o[2][k] = lut[512 + (bb & 255)];
+        o[3][k] = lut[768 + (bb >> 8)]; o[4][k] = lut[1024 + (c & 255)]; o[5][k] = lut[1280 + (c >> 8)];
+      }
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        if (!(mask >> v & 1)) continue;
+        const int64_t ev = e + (int64_t)view_slot(mask, v) * 3 * plane;
+        const int yo = v & 2 ? th - 1 - y : y;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          quad_store<VEC>(pre + ev + c * plane, yo, x0, v & 1, tw, o[c]);
+          quad_store<VEC>(post + ev + c * plane, yo, x0, v & 1, tw, o[c + 3]);
+        }
+      }
+    }
+    if (mask >> 4) {                                         // uniform over the grid: th == tw here
+      __syncthreads();                                       // the previous block's column reads are done
+      if (live) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) blk[(c * kVB + r) * kVP + 4 * q + k] = o[c][k];
+      }
+      __syncthreads();
+      // the transposed block: T[X0 + r][Y0 + 4q + k] = A[Y0 + 4q + k][X0 + r]
+      const int yt = X0 + r, xt = Y0 + 4 * q;
+      if (yt < tw && xt < th) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) o[c][k] = blk[(c * kVB + 4 * q + k) * kVP + r];   // rows past th: stale words, never stored
+#pragma unroll
+        for (int v = 4; v < 8; ++v) {
+          if (!(mask >> v & 1)) continue;
+          const int64_t ev = e + (int64_t)view_slot(mask, v) * 3 * plane;
+          const int yo = v & 2 ? th - 1 - yt : yt;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            quad_store<VEC>(pre + ev + c * plane, yo, xt, v & 1, tw, o[c]);
+            quad_store<VEC>(post + ev + c * plane, yo, xt, v & 1, tw, o[c + 3]);
+          }
+        }
+      }
+    }
+  }
+}
+
+// Work item = (entry, channel, 32 x 32 block of the OUTPUT plane).  V_v^-1 of a plain view reads row f2(y), quad f1(x0 ..) of
+// that view's plane directly; of a transposing one, A[y][x] = B[f2(x)][f1(y)]: the block B[f2(X0 + r)][f1(Y0 + 4q + k)] is
+// read by rows into LDS slot s (one slot per transposing view of the mask) and summed by columns.  The sum runs in
+// ascending view order from the first view's value (plain views are codes 0 .. 3, so they come first), then one divide.
+template <bool VEC>
+__global__ __launch_bounds__(256) void scene_fold_views_kernel(const float* __restrict__ values, float* __restrict__ dst, int cnt,
+                                                               int C, int th, int tw, int mask, int nv) {
+  extern __shared__ float views_smem[];                      // [popcount(mask >> 4)][32][33]
+  const int q = threadIdx.x & 7, r = threadIdx.x >> 3;
+  const int nby = (th + kVB - 1) / kVB, nbx = (tw + kVB - 1) / kVB;
+  const int64_t plane = (int64_t)th * tw;
+  const float fnv = (float)nv;
+  for (int64_t g = blockIdx.x; g < (int64_t)cnt * C * nby * nbx; g += gridDim.x) {
+    const int64_t ic = g / (nby * nbx);                      // entry * C + channel
+    const int b = (int)(g % (nby * nbx)), Y0 = (b / nbx) * kVB, X0 = (b % nbx) * kVB;
+    const int64_t i = ic / C;
+    const int c = (int)(ic % C);
+    const float* src = values + (i * nv * C + c) * plane;    // view j of this entry and channel: + j * C * plane
+    const int y = Y0 + r, x0 = X0 + 4 * q;
+    const bool live = y < th && x0 < tw;
+    if (mask >> 4) {
+      __syncthreads();
+      const int xs = X0 + r, ys = Y0 + 4 * q;                // this lane stages A[ys + k][xs], k = 0 .. 3, of every transposing view
+      if (xs < tw && ys < th) {
+#pragma unroll
+        for (int v = 4; v < 8; ++v) {
+          if (!(mask >> v & 1)) continue;
+          float d[4];
+          quad_load<VEC>(src + (int64_t)view_slot(mask, v) * C * plane, v & 2 ? th - 1 - xs : xs, ys, v & 1, tw, d);
+          float* s = views_smem + (view_slot(mask >> 4, v - 4) * kVB + r) * kVP + 4 * q;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) s[k] = d[k];
+        }
+      }
+      __syncthreads();
+    }
+    if (!live) continue;
+    float acc[4];
+    bool first = true;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      if (!(mask >> v & 1)) continue;
+      float d[4];
+      quad_load<VEC>(src + (int64_t)view_slot(mask, v) * C * plane, v & 2 ? th - 1 - y : y, x0, v & 1, tw, d);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[k] = first ? d[k] : acc[k] + d[k];
+      first = false;
+    }
+#pragma unroll
+    for (int v = 4; v < 8; ++v) {
+      if (!(mask >> v & 1)) continue;
+      const float* s = views_smem + (view_slot(mask >> 4, v - 4) * kVB + 4 * q) * kVP + r;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {                          // words past tw: stale, never stored
+        const float d = s[k * kVP];
+        acc[k] = first ? d : acc[k] + d;
+      }
+      first = false;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = acc[k] / fnv;
+    quad_store<VEC>(dst + ic * plane, y, x0, false, tw, acc);
+  }
+}
+
 // margin, tile count and ring depth of one axis; false where the geometry is refused
 bool scene_axis(int extent, int t, int s, int& m, int& n, int& k) {
   if (extent <= 0 || t <= 0 || s < 1 || s > t || ((t - s) & 1)) return false;
@@ -242,4 +429,50 @@ extern "C" int c3d_scene_stitch(const float* ring, const float* wy, const float*
   if (grid > 256 * 8) grid = 256 * 8;
   const size_t lds = (size_t)(((th + 3) & ~3) + ((tw + 3) & ~3)) * 4;
   return c3d_launch_lds<scene_stitch_kernel>(dim3((unsigned)grid), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
+}
+
+namespace {
+// C3D_E_BADARG for an empty mask, bits above 7, or a transposing view of a tile that is not square
+bool views_ok(int32_t view_mask, int32_t th, int32_t tw) {
+  return view_mask >= 1 && view_mask <= 255 && !((view_mask >> 4) && th != tw);
+}
+}  // namespace
+
+extern "C" int c3d_scene_gather_views(const uint8_t* scene, const int32_t* origins, const float* mean6, const float* std6,
+                                      float* pre, float* post, int32_t Hs, int32_t Ws, int32_t n, int32_t th, int32_t tw,
+                                      int32_t view_mask, void* stream) {
+  if (!scene || !origins || !mean6 || !std6 || !pre || !post || Hs <= 0 || Ws <= 0 || n <= 0 || th <= 0 || tw <= 0)
+    return C3D_E_BADARG;
+  if (reinterpret_cast<uintptr_t>(scene) & 1) return C3D_E_BADARG;
+  if (!views_ok(view_mask, th, tw)) return C3D_E_BADARG;
+  if (th > 32768 || tw > 32768) return C3D_E_UNSUPPORTED;
+  const int nv = __builtin_popcount((unsigned)view_mask);
+  const bool vec = !(tw & 3) && !((reinterpret_cast<uintptr_t>(pre) | reinterpret_cast<uintptr_t>(post)) & 15);
+  int64_t grid = (int64_t)n * ((th + kVB - 1) / kVB) * ((tw + kVB - 1) / kVB);
+  if (grid > 256 * 8) grid = 256 * 8;
+  const size_t lds = (size_t)(6 * 256 + ((view_mask >> 4) ? 6 * kVB * kVP : 0)) * sizeof(float);
+  const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return vec ? c3d_launch_lds<scene_gather_views_kernel<true>>(dim3((unsigned)grid), dim3(256), lds, st, scene, origins, mean6, std6,
+                                                               pre, post, (int)Hs, (int)Ws, (int)n, (int)th, (int)tw,
+                                                               (int)view_mask, nv)
+             : c3d_launch_lds<scene_gather_views_kernel<false>>(dim3((unsigned)grid), dim3(256), lds, st, scene, origins, mean6,
+                                                                std6, pre, post, (int)Hs, (int)Ws, (int)n, (int)th, (int)tw,
+                                                                (int)view_mask, nv);
+}
+
+extern "C" int c3d_scene_fold_views(const float* values, float* dst, int32_t cnt, int32_t C, int32_t th, int32_t tw,
+                                    int32_t view_mask, void* stream) {
+  if (!values || !dst || cnt <= 0 || C <= 0 || th <= 0 || tw <= 0) return C3D_E_BADARG;
+  if (!views_ok(view_mask, th, tw)) return C3D_E_BADARG;
+  if (th > 32768 || tw > 32768) return C3D_E_UNSUPPORTED;
+  const int nv = __builtin_popcount((unsigned)view_mask), nt = __builtin_popcount((unsigned)view_mask >> 4);
+  const bool vec = !(tw & 3) && !((reinterpret_cast<uintptr_t>(values) | reinterpret_cast<uintptr_t>(dst)) & 15);
+  int64_t grid = (int64_t)cnt * C * ((th + kVB - 1) / kVB) * ((tw + kVB - 1) / kVB);
+  if (grid > 256 * 8) grid = 256 * 8;
+  const size_t lds = (size_t)(nt ? nt : 1) * kVB * kVP * sizeof(float);
+  const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return vec ? c3d_launch_lds<scene_fold_views_kernel<true>>(dim3((unsigned)grid), dim3(256), lds, st, values, dst, (int)cnt, (int)C,
+                                                             (int)th, (int)tw, (int)view_mask, nv)
+             : c3d_launch_lds<scene_fold_views_kernel<false>>(dim3((unsigned)grid), dim3(256), lds, st, values, dst, (int)cnt,
+                                                              (int)C, (int)th, (int)tw, (int)view_mask, nv);
 }

@@ -28,6 +28,15 @@ a ring table and a vertex list; it is enqueued behind the labelling, before the 
 `predict(scene, objects=True, outlines=True, simplify=tol)` appends one more `SceneOutlines` after the raw one: the same rings
 simplified by `c3d_outlines_simplify` (Douglas-Peucker, `tol` in pixels), enqueued behind the tracing, before the same one
 synchronisation.  Its rows are `(id, start, n_vertices, 2 * area, perimeter, x, y, raw n_vertices)`.
+
+`SceneInferencer(..., tta="hflip" | "flips" | "d4" | codes)` is test-time augmentation: every tile is predicted under a set of
+the eight flips and rotations of the square, each view is undone on the output and the views are averaged before the
+stitch.  A view code `v` in 0..7 transposes the tile if `v & 4`, then reverses its rows if `v & 2`, then its columns if
+`v & 1`; a set is taken in ascending code order.  `c3d_scene_gather_views` cuts a tile under all views of the set at once
+(one read of the scene), the model sees `batch // nv` tiles times `nv` views per forward, and `c3d_scene_fold_views` writes
+the mean of the inverted views of every head straight into that head's ring slots -- it replaces the ring copy.  Averaged
+are the maps the stitch blends: the BCD probability, the SCD logits and change probability, the BDA damage logits and
+localisation probability; masks and argmax come after, from the stitch.  Still one upload and one synchronisation.
 """
 from collections import namedtuple
 
@@ -48,6 +57,30 @@ SceneObjects = namedtuple("SceneObjects", "labels table counts object_cls hist")
 SceneOutlines = namedtuple("SceneOutlines", "rings vertices counts")
 TASKS = ("bcd", "scd", "bda")
 WINDOWS = ("hann", "flat")
+VIEW_SETS = {"none": (0,), "hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def view_codes(tta):
+    """The ascending view codes of `tta`: one of the names of VIEW_SETS, or a sequence of codes in 0..7 (repeats count once)."""
+    if isinstance(tta, str):
+        if tta not in VIEW_SETS:
+            raise ValueError(f"tta must be one of {tuple(VIEW_SETS)} or a sequence of view codes, got {tta!r}")
+        return VIEW_SETS[tta]
+    try:
+        codes = [v for v in tta]
+    except TypeError:
+        raise ValueError(f"tta must be one of {tuple(VIEW_SETS)} or a sequence of view codes, got {tta!r}") from None
+    if not codes or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 7 for v in codes):
+        raise ValueError(f"view codes must be integers in 0..7 and at least one, got {tta!r}")
+    return tuple(sorted({int(v) for v in codes}))
+
+
+def view_mask(codes):
+    """Bit mask of a set of view codes, as c3d_scene_gather_views and c3d_scene_fold_views take it."""
+    mask = 0
+    for v in codes:
+        mask |= 1 << v
+    return mask
 
 
 def axis_plan(extent, tile, stride):
@@ -114,6 +147,13 @@ class SceneStitcher:
     def put(self, row, col, values):
         self.ring[row % self.py.k, col:col + values.shape[0]].copy_(values.reshape(values.shape[0], self.C, self.py.tile, self.px.tile))
 
+    def fold(self, row, col, values, mask):
+        """`put` for test-time augmentation: `values` holds every tile under the views of `mask`, tile-major; their mean with
+        the views undone goes into the ring slots, no copy follows."""
+        nv = ops.view_count(mask)
+        ops.scene_fold_views(values.contiguous(), self.ring[row % self.py.k, col:col + values.shape[0] // nv], values.shape[0] // nv,
+                             self.C, self.py.tile, self.px.tile, mask)
+
     def stitch(self, row, gate=None):
         ops.scene_stitch(self.ring, self.wy, self.wx, self.blend, self.cls, self.py.extent, self.px.extent, self.C, self.py.tile,
                          self.px.tile, self.py.stride, self.px.stride, row, gate=gate)
@@ -136,10 +176,14 @@ class SceneInferencer:
     `simplify=tol` (with `outlines=True`) appends one more `SceneOutlines`: the rings simplified with a tolerance of `tol`
     pixels in [0, 1024] (`ops.outlines_simplify`); column 3 of its rows is twice the signed area of the simplified ring and
     column 7 the ring's raw vertex count.  With `simplify=None` the result is the one without the argument.
+    `tta` is None, a name of `VIEW_SETS` ("none", "hflip", "flips", "d4") or a sequence of view codes: the tiles are predicted
+    under those `nv` views and averaged with the views undone (module docstring).  `batch` stays the number of model inputs
+    per forward, so a forward takes `batch // nv` tiles; a transposing view (codes 4..7) needs a square model input.  With
+    `tta=None` nothing changes.
     All results stay on the device."""
 
     def __init__(self, model, task, stride=None, window="hann", batch=32, mean=BCDTransforms.DEFAULT_MEAN,
-                 std=BCDTransforms.DEFAULT_STD):
+                 std=BCDTransforms.DEFAULT_STD, tta=None):
         if task not in TASKS:
             raise ValueError(f"task must be one of {TASKS}, got {task!r}")
         if task == "bda" and not (hasattr(model, "decoder_loc") and hasattr(model, "decoder_cls")):
@@ -153,6 +197,12 @@ class SceneInferencer:
         sy, sx = (stride, stride) if not isinstance(stride, (tuple, list)) else stride
         self.sy, self.sx = int(self.th // 2 if sy is None else sy), int(self.tw // 2 if sx is None else sx)
         axis_plan(self.th, self.th, self.sy), axis_plan(self.tw, self.tw, self.sx)      # refuse a bad stride here
+        self.views = None if tta is None else view_codes(tta)
+        if self.views is not None:
+            if self.views[-1] >= 4 and self.th != self.tw:
+                raise ValueError(f"tta views {self.views} transpose the tile: the model input must be square, got {self.th} x {self.tw}")
+            if self.batch < len(self.views):
+                raise ValueError(f"batch = {self.batch} model inputs per forward cannot hold one tile under {len(self.views)} views")
         self.num_class = int(model.args.num_class)
         self.mean, self.std = [float(v) for v in mean], [float(v) for v in std]
         self._consts, self._origins = {}, {}             # device tables: uploaded once, not per scene
@@ -209,20 +259,27 @@ class SceneInferencer:
             heads = [SceneStitcher(py, px, C, self.window, dev, blend=True, windows=(wy, wx)) for C in (self.num_class, 1)]
         else:
             heads = [SceneStitcher(py, px, C, self.window, dev, windows=(wy, wx)) for C in (self.num_class, self.num_class, 1)]
-        nb = min(self.batch, n)
-        pre = torch.empty((nb, 3, self.th, self.tw), dtype=torch.float32, device=dev)
+        mask, nv = (0, 1) if self.views is None else (view_mask(self.views), len(self.views))
+        nb = min(self.batch // nv, n)                   # tiles per forward; each under nv views
+        pre = torch.empty((nb * nv, 3, self.th, self.tw), dtype=torch.float32, device=dev)
         post = torch.empty_like(pre)
         for j0 in range(0, n, nb):
             b = min(nb, n - j0)
-            ops.scene_gather(scene, origins[j0:j0 + b], mean, std, pre, post, Hs, Ws, b, self.th, self.tw)
-            out = getattr(self.model, "update_" + self.task)(pre[:b], post[:b])
+            if mask:
+                ops.scene_gather_views(scene, origins[j0:j0 + b], mean, std, pre, post, Hs, Ws, b, self.th, self.tw, mask)
+            else:
+                ops.scene_gather(scene, origins[j0:j0 + b], mean, std, pre, post, Hs, Ws, b, self.th, self.tw)
+            out = getattr(self.model, "update_" + self.task)(pre[:b * nv], post[:b * nv])
             outs = [out] if self.task == "bcd" else list(out)
             j = j0
             while j < j0 + b:                           # the batch, one tile row at a time: a strip goes out once its row is whole
                 row, col = divmod(j, px.n)
                 cnt = min(px.n - col, j0 + b - j)
                 for head, o in zip(heads, outs):
-                    head.put(row, col, o[j - j0:j - j0 + cnt].float())
+                    if mask:
+                        head.fold(row, col, o[(j - j0) * nv:(j - j0 + cnt) * nv].float(), mask)
+                    else:
+                        head.put(row, col, o[j - j0:j - j0 + cnt].float())
                 if col + cnt == px.n:
                     if self.task == "bcd":
                         heads[0].stitch(row)

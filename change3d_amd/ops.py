@@ -790,6 +790,33 @@ def scene_stitch(ring, wy, wx, blend, cls, Hs, Ws, C, th, tw, sy, sx, row, gate=
             C, th, tw, sy, sx, row, _stream())
 
 
+def view_count(view_mask):
+    """Number of views of a view mask (bit v = view code v, include/change3d_hip.h "Views"); host only."""
+    return bin(int(view_mask) & 0xff).count("1")
+
+
+def scene_gather_views(scene, origins, mean6, std6, pre, post, Hs, Ws, n, th, tw, view_mask):
+    """c3d_scene_gather_views: `scene_gather` under every view of `view_mask`; `pre`, `post` f32 [n * nv, 3, th, tw], entry
+    i * nv + j is view j (ascending code) of tile i."""
+    nv = view_count(view_mask)
+    if pre.numel() < n * nv * 3 * th * tw or post.numel() < n * nv * 3 * th * tw:
+        raise ValueError(f"pre and post must hold {n} tiles x {nv} views of 3 x {th} x {tw}")
+    _launch("c3d_scene_gather_views", n * th * tw * (6 + 24 * nv), L.lib().c3d_scene_gather_views, _p(scene), _p(origins), _p(mean6),
+            _p(std6), _p(pre), _p(post), Hs, Ws, n, th, tw, int(view_mask), _stream())
+
+
+def scene_fold_views(values, dst, cnt, C, th, tw, view_mask):
+    """c3d_scene_fold_views: `values` f32 [cnt * nv, C, th, tw] (the model's outputs, tile-major, view-minor) -> `dst` f32
+    [cnt, C, th, tw] = the mean over the views with each view undone; `dst` may be a slot range of a stitch ring."""
+    nv = view_count(view_mask)
+    if values.dtype != torch.float32 or dst.dtype != torch.float32 or not values.is_contiguous() or not dst.is_contiguous():
+        raise ValueError("values and dst must be contiguous float32 tensors")
+    if values.numel() != cnt * nv * C * th * tw or dst.numel() != cnt * C * th * tw:
+        raise ValueError(f"values must hold {cnt} x {nv} and dst {cnt} entries of {C} x {th} x {tw}")
+    _launch("c3d_scene_fold_views", cnt * C * th * tw * 4 * (nv + 1), L.lib().c3d_scene_fold_views, _p(values), _p(dst), cnt, C, th,
+            tw, int(view_mask), _stream())
+
+
 def scene_label_tile():
     """(th, tw) of the LDS tile of c3d_scene_objects' local phase; host only."""
     th, tw = C.c_int32(0), C.c_int32(0)

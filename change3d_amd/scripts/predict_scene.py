@@ -25,6 +25,12 @@ not fit `--max_rings` / `--max_vertices` is left out and the run ends with an er
 tolerance of TOL pixels): the coordinates then come from the simplified rings and each feature also gets `vertices_raw` and
 `vertices`, its vertex counts before and after.  A ring whose simplified area is zero or has changed sign keeps its raw vertices.
 
+`--tta hflip|flips|d4` is test-time augmentation: every tile is predicted under the two mirror views, the four flips or all
+eight flips and rotations of the square, each view is undone on the device and the views are averaged before the stitch
+(`c3d_scene_gather_views`, `c3d_scene_fold_views`; change3d_amd/infer.py).  `--batch_size` stays the number of model inputs
+per forward, so it must be at least the number of views; `d4` needs `--in_height` = `--in_width`.  The default `none` is the
+plain path.  Everything downstream -- masks, objects, polygons, score lines -- takes the averaged map unchanged.
+
 `--objects` with labels also scores the objects themselves (change3d_amd/object_metrics.py, `c3d_objects_match`): the
 predicted objects against the objects of the label mask (BCD), of the change label voted over label2 (SCD) or the buildings
 of `label_loc > 0` voted over `label_loc * label_cls` (BDA).  A pair matches iff its IoU is strictly above `--iou_thr`.  One
@@ -238,7 +244,8 @@ def main(argv=None):
     device = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(device)
     model = build_model(args, device)
-    inf = SceneInferencer(model, args.task.lower(), stride=args.stride, window=args.window, batch=args.batch_size)
+    inf = SceneInferencer(model, args.task.lower(), stride=args.stride, window=args.window, batch=args.batch_size,
+                          tta=None if args.tta == "none" else args.tta)
     meter = {"BCD": lambda: ConfuseMatrixMeter(n_class=2), "SCD": lambda: SCDHistogram(num_class, device),
              "BDA": lambda: BDAEvaluator(num_class, device)}[args.task]()
     object_hist = SCDHistogram(num_class, device) if args.task == "BDA" and args.objects else None
@@ -341,7 +348,9 @@ def build_parser():
     p.add_argument("--out_dir", default="./scene_out")
     p.add_argument("--stride", type=int, default=None, help="tile stride; default: half the tile")
     p.add_argument("--window", choices=["hann", "flat"], default="hann")
-    p.add_argument("--batch_size", type=int, default=32, help="tiles per forward")
+    p.add_argument("--batch_size", type=int, default=32, help="model inputs per forward (tiles times --tta views)")
+    p.add_argument("--tta", choices=["none", "hflip", "flips", "d4"], default="none", help="test-time augmentation: average every "
+                   "tile over these views (hflip: 2, flips: 4, d4: all 8 flips and rotations) on the device")
     p.add_argument("--act_dtype", choices=["f32", "bf16"], default="bf16")
     p.add_argument("--in_height", type=int, default=256)
     p.add_argument("--in_width", type=int, default=256)

@@ -535,6 +535,30 @@ int c3d_scene_stitch(const float* ring, const float* wy, const float* wx, float*
                      int32_t Hs, int32_t Ws, int32_t C, int32_t th, int32_t tw, int32_t sy, int32_t sx, int32_t row,
                      void* stream);
 
+/* Test-time augmentation of whole-scene inference: every tile is predicted under a set of the eight flips and rotations of
+ * the square, each view is undone on the output, and the results are averaged.  Views: a code v in 0..7 acts on a tile
+ * A[th][tw] as  1. transpose if v & 4,  2. reverse the rows if v & 2,  3. reverse the columns if v & 1; in numpy
+ *   V = A.swapaxes(-2, -1) if v & 4 else A;  V = V[..., ::-1, :] if v & 2 else V;  V = V[..., ::-1] if v & 1 else V
+ * The inverse undoes the two reversals and then transposes; codes 5 and 6 (the quarter turns) are each other's inverse, every
+ * other code is its own.  A view set is a bit mask over the codes (bit v = code v), its nv = popcount(view_mask) views are taken
+ * in ascending code order: none = 0x01, hflip = 0x03, flips = 0x0f, d4 = 0xff.  C3D_E_BADARG for an empty mask, bits above 7,
+ * or a transposing view (bits 4..7) with th != tw.
+ *
+ * c3d_scene_gather_views: the arguments of c3d_scene_gather; pre, post f32 [n * nv][3][th][tw], entry i * nv + j = view j of
+ * exactly what c3d_scene_gather writes for tile i (same reflect fold, same 6 x 256 table, same values).  One launch: every
+ * pixel of the scene is read once for all views; a transposing view goes through a 32 x 32 LDS block.                    */
+enum { C3D_VIEWS_NONE = 0x01, C3D_VIEWS_HFLIP = 0x03, C3D_VIEWS_FLIPS = 0x0f, C3D_VIEWS_D4 = 0xff };
+int c3d_scene_gather_views(const uint8_t* scene, const int32_t* origins, const float* mean6, const float* std6, float* pre,
+                           float* post, int32_t Hs, int32_t Ws, int32_t n, int32_t th, int32_t tw, int32_t view_mask,
+                           void* stream);
+/* values f32 [cnt * nv][C][th][tw], the model's output for those entries in that order; dst f32 [cnt][C][th][tw], in
+ * whole-scene inference the slot range ring[row % ky][col .. col + cnt) of c3d_scene_stitch's ring (the fold is the put):
+ *   dst[i][c] = (V_v0^-1(values[i*nv + 0][c]) + V_v1^-1(values[i*nv + 1][c]) + ...) / (float)nv
+ * plain f32 adds in ascending view order starting from the first view's value, one divide; every element is written once by
+ * one thread, no atomics: two runs agree bit for bit, and view_mask == 1 copies `values` bit for bit.  One launch.          */
+int c3d_scene_fold_views(const float* values, float* dst, int32_t cnt, int32_t C, int32_t th, int32_t tw, int32_t view_mask,
+                         void* stream);
+
 /* Objects of a scene map (csrc/scene_objects.hip): connected components of a u8 mask that stays in HBM, a minimum-area filter,
  * raster numbering and one table row per object.  Integer arithmetic and integer atomics only: every output is exact and two
  * runs agree bit for bit.  Nine launches and at most three memsets on `stream`, nothing is read back by the host; the
