@@ -5,7 +5,7 @@ computation below is a hand-written gfx950 kernel in libchange3d_hip.so.  All fu
 launch on `torch.cuda.current_stream()` and never synchronise.
 """
 import ctypes as C
-
+import math
 import os
 
 import torch
@@ -975,6 +975,76 @@ def outlines_simplify(rings, vertices, counts, tol, ws=None):
     _launch("c3d_outlines_simplify", (max_rings + max_vertices) * 64, L.lib().c3d_outlines_simplify, _p(rings), _p(vertices),
             _p(counts), max_rings, max_vertices, tol2_q, _p(rings_out), _p(vertices_out), _p(out), _p(ws), _stream())
     return rings_out, vertices_out, out
+
+
+def scene_edt_tile():
+    """(rows of a chunk of c3d_scene_edt's column pass, pixels of a row per workgroup of its row pass); host only."""
+    out = (C.c_int32 * 2)()
+    L.check(L.lib().c3d_scene_edt_tile(out), "c3d_scene_edt_tile")
+    return int(out[0]), int(out[1])
+
+
+def _u8_map(t, what):
+    require_gpu(t, what)
+    if t.dtype != torch.uint8 or t.dim() != 2 or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous u8 [Hs, Ws] map, got {t.dtype} {tuple(t.shape)}")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def _scene_ws(ws, nbytes, dev, what, Hs, Ws):
+    if nbytes < 0:
+        raise L.Change3DHipError(f"{what} refuses a {Hs} x {Ws} scene (code {nbytes})")
+    if ws is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    return ws
+
+
+def scene_edt(mask, invert=False, border=False, cap2=0, out=None, ws=None):
+    """c3d_scene_edt on the u8 map `mask` [Hs, Ws]: `dist2` i32 [Hs, Ws], the exact squared Euclidean distance of every pixel to
+    the nearest site -- the zero pixels, the nonzero ones with `invert`, and everything outside the scene with `border`.
+    `cap2` > 0: values above it come out as `EDT_FAR`.  On the device; nothing is read back."""
+    Hs, Ws = _u8_map(mask, "scene_edt mask")
+    cap2 = int(cap2)
+    if not 0 <= cap2 < 2 ** 31:
+        raise ValueError(f"cap2 must lie in [0, 2^31), got {cap2}")
+    ws = _scene_ws(ws, L.lib().c3d_scene_edt_ws_bytes(Hs, Ws), mask.device, "c3d_scene_edt", Hs, Ws)
+    if out is None:
+        out = torch.empty((Hs, Ws), dtype=torch.int32, device=mask.device)
+    assert out.dtype == torch.int32 and out.shape == mask.shape and out.is_contiguous() and out.device == mask.device
+    flags = (L.EDT_INVERT if invert else 0) | (L.EDT_BORDER if border else 0)
+    _launch("c3d_scene_edt", Hs * Ws * 9, L.lib().c3d_scene_edt, _p(mask), Hs, Ws, flags, cap2, _p(out), _p(ws), _stream())
+    return out
+
+
+def boundary_radius2(r):
+    """A radius in pixels as `boundary_counts` takes it: floor(r * r) -- on the lattice dist <= r iff dist2 <= floor(r^2).
+    Raises outside (0, 1024].  A radius below 1 gives 0, a band that holds no pixel, which `boundary_counts` refuses."""
+    r = float(r)
+    if not 0.0 < r <= 1024.0:                             # also refuses NaN
+        raise ValueError(f"a boundary radius must lie in (0, 1024] pixels, got {r}")
+    return int(math.floor(r * r))
+
+
+def boundary_counts(pred, gt, d, tau=None, border=True, totals=None, ws=None):
+    """c3d_boundary_counts on two u8 maps [Hs, Ws] (nonzero = object): `counts` i64 [8] = (|Pd and Gd|, |Pd or Gd|, |Pc|, hits of
+    Pc, |Gc|, hits of Gc, 1, 0) for the band width `d` and the contour tolerance `tau` (default `d`), both in pixels; `border`:
+    the outside of the scene counts as background.  `totals` i64 [8], zeroed once by the caller, is added into.  On the device;
+    nothing is read back."""
+    d2 = boundary_radius2(d)
+    tau2 = d2 if tau is None else boundary_radius2(tau)
+    if d2 < 1 or tau2 < 1:
+        raise ValueError(f"d and tau must be at least 1 pixel: no lattice distance above 0 is smaller; got {d}, {tau}")
+    Hs, Ws = _u8_map(pred, "boundary_counts prediction")
+    if _u8_map(gt, "boundary_counts ground truth") != (Hs, Ws) or gt.device != pred.device:
+        raise ValueError(f"the prediction is {Hs} x {Ws} on {pred.device}, the ground truth {tuple(gt.shape)} on {gt.device}")
+    ws = _scene_ws(ws, L.lib().c3d_boundary_counts_ws_bytes(Hs, Ws), pred.device, "c3d_boundary_counts", Hs, Ws)
+    if totals is not None:
+        assert totals.dtype == torch.int64 and totals.numel() == 8 and totals.is_contiguous() and totals.device == pred.device
+    counts = torch.empty(8, dtype=torch.int64, device=pred.device)
+    _launch("c3d_boundary_counts", Hs * Ws * 40, L.lib().c3d_boundary_counts, _p(pred), _p(gt), Hs, Ws, d2, tau2,
+            L.EDT_BORDER if border else 0, _p(counts), _p(totals), _p(ws), _stream())
+    return counts
 
 
 def build_clip(pre, post, frames, clip, B, K, H, W):

@@ -37,6 +37,12 @@ of `label_loc > 0` voted over `label_loc * label_cls` (BDA).  A pair matches iff
 more line follows the score line, `objects: tp fp fn precision recall f1 sq rq pq` (BDA: and the object F1 per damage
 class), and `objects/<name>.match.csv` lists `id,gt_id,inter,union,covered` per predicted object and, under a `# gt` line,
 `id,pred_id,inter,union,covered` per ground-truth object.
+
+`--boundary D` with labels scores how well the outlines fit (change3d_amd/boundary_metrics.py, `c3d_boundary_counts` on the exact
+distance transform `c3d_scene_edt`): Boundary IoU over the bands of width D pixels, and the precision, recall and F1 of the
+contour pixels with a tolerance of `--boundary_tol` pixels (default D), on the masks that `--objects` scores: the mask against
+`label > 0` (BCD), the change mask against the change label (SCD), `loc_mask` against `label_loc > 0` (BDA).  One more line
+follows the score lines, `boundary: d tol biou precision recall f1`.  Without labels the option does nothing.
 """
 import json
 import os
@@ -55,6 +61,7 @@ if ROOT not in sys.path:
 from change3d_amd.data.dataset import BCDDataset, BDADataset, SCDDataset, read_label, read_rgb  # noqa: E402
 from change3d_amd.infer import SceneInferencer  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
+from change3d_amd.boundary_metrics import BoundaryEvaluator  # noqa: E402
 from change3d_amd.object_metrics import ObjectEvaluator  # noqa: E402
 from change3d_amd.model.utils import BDAEvaluator, Evaluator, SCDHistogram, bda_scores  # noqa: E402
 from change3d_amd.utils.metric_tool import ConfuseMatrixMeter  # noqa: E402
@@ -212,6 +219,20 @@ def print_bda_scores(evaluator, object_hist, num_class):
     return loc_f1, harmonic, oaf1, damage_f1
 
 
+def print_boundary_scores(evaluator):
+    s = evaluator.scores()
+    print(f"boundary: d = {evaluator.d:g} tol = {evaluator.tau:g} biou = {s['boundary_iou']:.4f} precision = {s['boundary_precision']:.4f} "
+          f"recall = {s['boundary_recall']:.4f} f1 = {s['boundary_f1']:.4f}")
+    return s
+
+
+def boundary_radius(text):
+    v = float(text)
+    if not 1.0 <= v <= 1024.0:                            # below 1 pixel a band or a tolerance holds no pixel of the lattice
+        raise ArgumentTypeError(f"the radius must lie in [1, 1024] pixels, got {text}")
+    return v
+
+
 def iou_threshold(text):
     v = float(text)
     if not 0.5 <= v < 1.0:
@@ -233,6 +254,8 @@ def parse_args(argv=None):
         parser.error("--polygons outlines the objects of the map: it needs --objects")
     if args.simplify is not None and not args.polygons:
         parser.error("--simplify simplifies the polygons: it needs --polygons")
+    if args.boundary_tol is not None and args.boundary is None:
+        parser.error("--boundary_tol is the tolerance of the boundary scores: it needs --boundary")
     return args
 
 
@@ -250,6 +273,7 @@ def main(argv=None):
              "BDA": lambda: BDAEvaluator(num_class, device)}[args.task]()
     object_hist = SCDHistogram(num_class, device) if args.task == "BDA" and args.objects else None
     object_eval = None                                    # made by the first labelled scene of a run with --objects
+    boundary_eval = None                                  # made by the first labelled scene of a run with --boundary
     scored = 0
     cut_off = 0                                           # objects whose polygon was left out of a .geojson
 
@@ -259,6 +283,14 @@ def main(argv=None):
             object_eval = ObjectEvaluator(n_cls=num_class, iou_thr=args.iou_thr, connectivity=args.connectivity, device=device)
         match_p, match_g = object_eval.update(objects, gt_mask.to(torch.uint8), None if gt_cls is None else gt_cls.to(torch.uint8))
         save_matches(os.path.join(args.out_dir, "objects", name + ".match.csv"), objects, object_eval.last_gt_counts, match_p, match_g)
+
+    def score_boundary(mask, gt_mask):
+        nonlocal boundary_eval
+        if args.boundary is None:
+            return
+        if boundary_eval is None:
+            boundary_eval = BoundaryEvaluator(args.boundary, args.boundary_tol, device=device)
+        boundary_eval.update(mask.to(torch.uint8), gt_mask.to(torch.uint8))
 
     for name, img, label in scenes(args):
         scene = torch.from_numpy(np.ascontiguousarray(img))
@@ -284,6 +316,7 @@ def main(argv=None):
                 meter.update_cm_device(mask.float(), (lab > 0).float())
                 if args.objects:
                     score_objects(name, out[-1], lab > 0)
+                score_boundary(mask, lab > 0)
                 scored += 1
         elif args.task == "BDA":
             loc_prob, loc_mask, damage_map, cls_logits = out[:4]
@@ -300,6 +333,7 @@ def main(argv=None):
                     inside = label_cls > 0
                     object_hist.update(out[-1].object_cls[inside], label_cls[inside])
                     score_objects(name, out[-1], lab[..., 0] > 0, label_cls)
+                score_boundary(loc_mask, lab[..., 0] > 0)
                 scored += 1
         else:
             for sub, m in zip(("pred1", "pred2", "change"), out[:3]):
@@ -312,6 +346,7 @@ def main(argv=None):
                 meter.update(out[1], lab[..., 1] * lab[..., 2])
                 if args.objects:         # the objects of the change label; cls: the majority class of label2 inside
                     score_objects(name, out[-1], lab[..., 2] > 0, lab[..., 1])
+                score_boundary(out[2], lab[..., 2] > 0)
                 scored += 1
         print(f"{name}: {img.shape[0]} x {img.shape[1]} -> {args.out_dir}")
     if cut_off:
@@ -329,6 +364,8 @@ def main(argv=None):
         print(f"Fscd: {result[0] * 100:.2f} IoU: {result[1] * 100:.2f} Sek: {result[2] * 100:.2f}")
     if object_eval is not None:
         print_object_scores(object_eval, per_class=args.task == "BDA")
+    if boundary_eval is not None:
+        print_boundary_scores(boundary_eval)
     return result
 
 
@@ -365,6 +402,10 @@ def build_parser():
                    "device (Douglas-Peucker) with this tolerance in pixels, in [0, 1024]")
     p.add_argument("--iou_thr", type=iou_threshold, default=0.5, help="--objects with labels: a predicted and a labelled object match iff "
                    "their IoU is strictly above this; in [0.5, 1)")
+    p.add_argument("--boundary", type=boundary_radius, default=None, metavar="D", help="with labels: also the boundary scores, Boundary IoU "
+                   "over bands of this width in pixels and the contour precision / recall / F1; in [1, 1024]")
+    p.add_argument("--boundary_tol", type=boundary_radius, default=None, metavar="T", help="--boundary: the contour tolerance in pixels "
+                   "(default: D)")
     p.add_argument("--pretrained", default="./pretrained/X3D_L.pyth")
     p.add_argument("--gpu_id", default=0, type=int)
     return p

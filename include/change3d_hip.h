@@ -751,6 +751,56 @@ int c3d_outlines_simplify(const int32_t* rings, const int32_t* vertices, const i
                           int32_t max_vertices, int64_t tol2_q, int32_t* rings_out, int32_t* vertices_out, int32_t* counts_out,
                           void* ws, void* stream);
 
+/* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
+ * in HBM.  The rule:
+ *   sites       the pixels with mask == 0; with C3D_EDT_INVERT (bit 0 of flags) the pixels with mask != 0
+ *   border      with C3D_EDT_BORDER (bit 1) every position outside the scene is a site as well: the transform of the mask padded
+ *               by one ring of sites (the outside is infinite, but one ring decides)
+ *   distance    dist2[y][x] = the minimum over the sites (y', x') of (y - y')^2 + (x - x')^2, as i32; a site gets 0
+ *   no site     where no site exists (none in the mask and no BORDER bit) every pixel gets C3D_EDT_FAR
+ *   cap         cap2 = 0: none.  cap2 > 0: every pixel whose true value exceeds cap2 gets exactly C3D_EDT_FAR, every other pixel
+ *               its true value; the search then stops after isqrt(cap2) steps and the output is still fully specified
+ *   limits      1 <= Hs, Ws <= 16384, so that the largest true value, 2 * 16383^2, stays below FAR (C3D_E_UNSUPPORTED beyond)
+ * Integer arithmetic only; three launches on `stream` (column sites as bits, column distances, row minimum), nothing is read
+ * back by the host, no workgroup waits for another, and every word of `ws` is written before it is read: two runs agree bit for
+ * bit, on a dirty workspace too.  The uncapped cost of a pixel grows with the distance to its nearest site along the row: a
+ * scene with (nearly) no site costs O(Ws) per pixel.
+ *   mask    u8 [Hs][Ws];  dist2  i32 [Hs][Ws], must not alias the mask
+ *   ws      c3d_scene_edt_ws_bytes(Hs, Ws) bytes, 256-byte aligned: one u64 of site bits per column and chunk of rows, then
+ *           the column distances as u16 [Hs][Ws]
+ * Refused before anything is enqueued: a NULL mask, dist2 or ws, flags outside bits 0..1, cap2 < 0, Hs or Ws < 1
+ * (C3D_E_BADARG); Hs or Ws > 16384 (C3D_E_UNSUPPORTED).
+ * c3d_scene_edt_tile: out[0] = the rows of one chunk of the column pass, out[1] = the pixels of a row that one workgroup of the
+ * row pass handles: the two extents at which the implementation changes path.  Host only.                                     */
+#define C3D_EDT_INVERT 1
+#define C3D_EDT_BORDER 2
+#define C3D_EDT_FAR 0x3fffffff
+int64_t c3d_scene_edt_ws_bytes(int32_t Hs, int32_t Ws);                 /* < 0: C3D_E_* */
+int c3d_scene_edt_tile(int32_t out[2]);
+int c3d_scene_edt(const uint8_t* mask, int32_t Hs, int32_t Ws, int32_t flags, int32_t cap2, int32_t* dist2, void* ws, void* stream);
+
+/* Boundary counts of two u8 maps [Hs][Ws], a prediction and a ground truth (csrc/scene_edt.hip): what Boundary IoU (Cheng et
+ * al., 2021) and the boundary F-measure with a pixel tolerance are made of.  P and G are the nonzero pixels of `pred` and `gt`.
+ *   distances   dP, dG = the transform above of P and of G to their background (sites: mask == 0); `flags` may hold
+ *               C3D_EDT_BORDER, which both take, and nothing else
+ *   bands       Pd = P and dP <= d2, Gd likewise: the band of Boundary IoU of width d, with d2 = floor(d * d) (on the lattice
+ *               dist <= d iff dist2 <= floor(d^2))
+ *   contours    Pc = P and dP == 1: the pixels of P that are 4-adjacent to background; Gc likewise
+ *   tolerance   eG = the transform with INVERT of Gc, the squared distance to the nearest ground-truth contour pixel; eP the
+ *               same of Pc.  These two never take the BORDER bit.  An empty contour set is hit by nothing
+ *   counts      i64 [8] = (|Pd and Gd|, |Pd or Gd|, |Pc|, |{p in Pc : eG <= tau2}|, |Gc|, |{p in Gc : eP <= tau2}|, 1, 0)
+ *   totals      i64 [8] or NULL: the counts are ADDED into it by one thread at the end of the last launch, so calls on one
+ *               stream accumulate in stream order (the convention of c3d_objects_match)
+ *   ws          c3d_boundary_counts_ws_bytes(Hs, Ws) bytes, 256-byte aligned; the call zeroes what it needs of it
+ * One memset and eight launches on `stream` (the transforms run capped at d2 and tau2, two maps per launch); integer atomics
+ * only, so every count is exact and the same from run to run; nothing is read back by the host.
+ * Refused before anything is enqueued: a NULL pred, gt, counts or ws, flags other than 0 or C3D_EDT_BORDER, d2 or tau2 outside
+ * [1, C3D_BOUNDARY_R2_MAX] (radii up to 1024 px), Hs or Ws < 1 (C3D_E_BADARG); Hs or Ws > 16384 (C3D_E_UNSUPPORTED).          */
+#define C3D_BOUNDARY_R2_MAX (1024 * 1024)
+int64_t c3d_boundary_counts_ws_bytes(int32_t Hs, int32_t Ws);           /* < 0: C3D_E_* */
+int c3d_boundary_counts(const uint8_t* pred, const uint8_t* gt, int32_t Hs, int32_t Ws, int32_t d2, int32_t tau2, int32_t flags,
+                        int64_t* counts, int64_t* totals, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
  * stage (reference model/x3d.py:331-412 = ResStage of ResBlocks, driven by `self.x3d.blocks[i](x)` at
