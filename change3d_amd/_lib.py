@@ -106,6 +106,7 @@ SIMPLIFY_ST_BAD_INPUT = 8                                # C3D_SIMPLIFY_ST_BAD_I
 SIMPLIFY_TOL2_Q_MAX = 16 * 1024 * 1024                   # C3D_SIMPLIFY_TOL2_Q_MAX
 EDT_INVERT, EDT_BORDER, EDT_FAR = 1, 2, 0x3fffffff       # C3D_EDT_*: flag bits of c3d_scene_edt, and its "no site within the cap"
 BOUNDARY_R2_MAX = 1024 * 1024                            # C3D_BOUNDARY_R2_MAX
+SPLIT_ST_NOT_CONVERGED, SPLIT_ST_BAD_LABELS = 1, 2       # C3D_SPLIT_ST_*: bits of c3d_scene_split's info[0]
 
 
 class CapMetricsArgs(C.Structure):
@@ -195,6 +196,9 @@ SIGNATURES = {
     "c3d_scene_edt": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
     "c3d_boundary_counts_ws_bytes": (i64, [i32, i32]),
     "c3d_boundary_counts": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "c3d_scene_split_ws_bytes": (i64, [i32, i32, i32]),
+    "c3d_scene_split_tile": (i32, [C.POINTER(i32)]),
+    "c3d_scene_split": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "c3d_cap_embed_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_embed_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_dropout": (i32, [vp, vp, i64, i32, f32, C.c_uint64, i32, vp]),

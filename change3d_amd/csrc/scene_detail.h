@@ -1,0 +1,47 @@
+// The three stages of c3d_scene_objects (csrc/scene_objects.hip) as host functions, for the entries that build on them
+// (csrc/scene_split.hip).  c3d_scene_objects itself is clear + label_roots + objects_tail; the kernels live in
+// scene_objects.hip only.  The front of every such workspace is the one of c3d_scene_label_ws_bytes: a header of 256 bytes
+// (word 0: the error word of the union-find walks, word 1: the objects found; the words from C3D_DETAIL_HEADER_FREE on are
+// the caller's), then the u32 [N] of areas at c3d_detail_area_offset().
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+enum { C3D_DETAIL_WS_ERR = 0, C3D_DETAIL_WS_FOUND = 1, C3D_DETAIL_HEADER_FREE = 8, C3D_DETAIL_HEADER_WORDS = 64 };
+
+// area[r] += 1 for every lane with r >= 0, called by whole waves.  One atomic per wave and root for the two most frequent
+// leaders' roots (a wave is 64 consecutive pixels: inside a large object all of them share the root), one per lane for what
+// is left.
+__device__ __forceinline__ void c3d_detail_wave_area_add(uint32_t* area, int r) {
+  const int lane = threadIdx.x & 63;
+  bool open = r >= 0;
+  for (int round = 0; round < 2; ++round) {
+    const unsigned long long m = __ballot(open);
+    if (!m) break;
+    const int leader = __ffsll((long long)m) - 1;
+    const int r0 = __shfl(r, leader);
+    const unsigned long long same = __ballot(open && r == r0);
+    if (lane == leader) atomicAdd(area + r0, (uint32_t)__popcll(same));
+    if (r == r0) open = false;
+  }
+  if (open) atomicAdd(area + r, 1u);
+}
+
+int64_t c3d_detail_label_ws_bytes(int64_t N, int n_cls);   // what c3d_scene_label_ws_bytes returns for N pixels
+int64_t c3d_detail_area_offset();                          // byte offset of the u32 [N] of areas
+
+// The memsets: header and areas, and the score sums and votes of the rows that can be used.  hist / n_cls as the entry got them.
+int c3d_detail_objects_clear(void* ws, int64_t N, const uint8_t* cls_map, const float* score, int n_cls, uint32_t* hist,
+                             int max_objects, hipStream_t st);
+
+// Launches 1..3 (local, seam, flatten): L[p] = the smallest linear index of p's component, -1 on the background.  `area`
+// u32 [N], zeroed, gets the pixel count at every root; NULL: not counted.  `phases` < 3 stops after that many launches
+// (the instrumented build of c3d_scene_objects; 3 everywhere else).
+int c3d_detail_label_roots(const uint8_t* mask, int32_t* L, uint32_t* err, uint32_t* area, int Hs, int Ws, int conn8, int phases,
+                           hipStream_t st);
+
+// Launches 4..9 (count, scan, number, relabel_stats, finalise, paint) on a root map: L[p] = the index of the first pixel of
+// p's object (L[r] == r there), -1 elsewhere, with the area of every object at its root in the workspace.
+int c3d_detail_objects_tail(const uint8_t* cls_map, const float* score, int Hs, int Ws, int min_area, int n_cls, int first_class,
+                            int max_objects, int32_t* labels, int32_t* table, uint32_t* hist, uint8_t* object_cls, int32_t* counts,
+                            void* ws, int phases, hipStream_t st);

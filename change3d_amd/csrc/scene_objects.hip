@@ -37,6 +37,7 @@
 #include <climits>
 
 #include "common.h"
+#include "scene_detail.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
@@ -200,11 +201,11 @@ __global__ __launch_bounds__(256) void label_seam_kernel(const uint8_t* __restri
   }
 }
 
-// One atomic per wave and root for the two most frequent leaders' roots (a wave is 64 consecutive pixels: inside a large
-// object all of them share the root), one per lane for what is left.
+// Every pixel gets its root; the areas per root through c3d_detail_wave_area_add (scene_detail.h).  AREA = false only
+// flattens (csrc/scene_split.hip counts the areas of its pieces itself).
+template <bool AREA>
 __global__ __launch_bounds__(256) void label_flatten_kernel(int32_t* __restrict__ L, uint32_t* __restrict__ area,
                                                             uint32_t* __restrict__ err, int N, int cap) {
-  const int lane = threadIdx.x & 63;
   for (int64_t base = (int64_t)blockIdx.x * 256; base < N; base += (int64_t)gridDim.x * 256) {
     const int64_t i = base + threadIdx.x;
     int r = -1;
@@ -215,17 +216,7 @@ __global__ __launch_bounds__(256) void label_flatten_kernel(int32_t* __restrict_
         if (r != p) __hip_atomic_store(L + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ever stored is an ancestor
       }
     }
-    bool open = r >= 0;
-    for (int round = 0; round < 2; ++round) {
-      const unsigned long long m = __ballot(open);
-      if (!m) break;
-      const int leader = __ffsll((long long)m) - 1;
-      const int r0 = __shfl(r, leader);
-      const unsigned long long same = __ballot(open && r == r0);
-      if (lane == leader) atomicAdd(area + r0, (uint32_t)__popcll(same));
-      if (r == r0) open = false;
-    }
-    if (open) atomicAdd(area + r, 1u);
+    if (AREA) c3d_detail_wave_area_add(area, r);
   }
 }
 
@@ -426,6 +417,78 @@ extern "C" int c3d_scene_label_tile(int32_t* th, int32_t* tw) {
   return 0;
 }
 
+// ---- the stages as host functions (scene_detail.h): c3d_scene_objects below, and csrc/scene_split.hip
+int64_t c3d_detail_label_ws_bytes(int64_t N, int n_cls) { return workspace_plan(N, n_cls).bytes; }
+int64_t c3d_detail_area_offset() { return workspace_plan(1, 1).area; }
+
+// header and area; the sums and votes of the rows that can be used.  The table needs none: number_roots writes the rows of
+// the objects, finalise zeroes the others.
+int c3d_detail_objects_clear(void* ws, int64_t N, const uint8_t* cls_map, const float* score, int n_cls, uint32_t* hist,
+                             int max_objects, hipStream_t st) {
+  if (!cls_map) { n_cls = 1; hist = nullptr; }
+  const Workspace w = workspace_plan(N, n_cls);
+  char* base = static_cast<char*>(ws);
+  const int64_t rows_cap = max_objects < w.cap ? max_objects : w.cap;   // no id with a table row can be larger
+  uint32_t* votes = hist ? hist : reinterpret_cast<uint32_t*>(base + w.hist);
+  hipError_t e = hipMemsetAsync(base, 0, (size_t)(w.chunks), st);
+  if (e == hipSuccess && score) e = hipMemsetAsync(base + w.ssum, 0, (size_t)rows_cap * 8, st);
+  if (e == hipSuccess && cls_map) e = hipMemsetAsync(votes, 0, (size_t)(hist ? (int64_t)max_objects : rows_cap) * n_cls * 4, st);
+  return (int)e;
+}
+
+int c3d_detail_label_roots(const uint8_t* mask, int32_t* L, uint32_t* err, uint32_t* area, int Hs, int Ws, int conn8, int phases,
+                           hipStream_t st) {
+  const int N = Hs * Ws;
+  const int tiles_x = (Ws + TW - 1) / TW, tiles_y = (Hs + TH - 1) / TH;
+  const int n_tiles = tiles_x * tiles_y;                   // <= N / 4096 + ...: far below 2^31
+  int rc = c3d_launch_lds<label_local_kernel>(dim3((unsigned)(n_tiles > 65536 ? 65536 : n_tiles)), dim3(256), TH * TW * 4, st,
+                                              mask, L, err, Hs, Ws, tiles_x, n_tiles, conn8);
+  if (rc || phases == 1) return rc;
+  const int64_t row_items = (int64_t)(tiles_y - 1) * Ws, items = row_items + (int64_t)(tiles_x - 1) * Hs;
+  if (items > 0) {
+    rc = c3d_launch_lds<label_seam_kernel>(dim3(grid_for(items, 256)), dim3(256), 0, st, mask, L, err, Hs, Ws, row_items, items, N,
+                                           conn8);
+    if (rc) return rc;
+  }
+  if (phases == 2) return 0;
+  if (area) return c3d_launch_lds<label_flatten_kernel<true>>(dim3(grid_for(N, 256)), dim3(256), 0, st, L, area, err, N, N);
+  return c3d_launch_lds<label_flatten_kernel<false>>(dim3(grid_for(N, 256)), dim3(256), 0, st, L, area, err, N, N);
+}
+
+int c3d_detail_objects_tail(const uint8_t* cls_map, const float* score, int Hs, int Ws, int min_area, int n_cls, int first_class,
+                            int max_objects, int32_t* labels, int32_t* table, uint32_t* hist, uint8_t* object_cls, int32_t* counts,
+                            void* ws, int phases, hipStream_t st) {
+  if (!cls_map) { n_cls = 1; hist = nullptr; }            // no class map, no votes: `hist` is left alone
+  const int N = Hs * Ws;
+  const Workspace w = workspace_plan(N, n_cls);
+  char* base = static_cast<char*>(ws);
+  uint32_t* header = reinterpret_cast<uint32_t*>(base);
+  uint32_t* area = reinterpret_cast<uint32_t*>(base + w.area);
+  uint32_t* chunks = reinterpret_cast<uint32_t*>(base + w.chunks);
+  unsigned long long* ssum = reinterpret_cast<unsigned long long*>(base + w.ssum);
+  uint32_t* votes = hist ? hist : reinterpret_cast<uint32_t*>(base + w.hist);
+  const uint32_t min_a = min_area < 1 ? 1u : (uint32_t)min_area;
+  int rc = c3d_launch_lds<count_roots_kernel>(dim3(grid_for(w.n_chunks, 1)), dim3(256), 16, st, (const int32_t*)labels,
+                                              (const uint32_t*)area, chunks, N, w.n_chunks, min_a);
+  if (rc || phases == 4) return rc;
+  rc = c3d_launch_lds<scan_chunks_kernel>(dim3(1), dim3(256), 1024, st, chunks, header, w.n_chunks);
+  if (rc || phases == 5) return rc;
+  rc = c3d_launch_lds<number_roots_kernel>(dim3(grid_for(w.n_chunks, 1)), dim3(256), 16, st, (const int32_t*)labels, area,
+                                           (const uint32_t*)chunks, table, N, w.n_chunks, min_a, max_objects);
+  if (rc || phases == 6) return rc;
+  rc = c3d_launch_lds<relabel_stats_kernel>(dim3(grid_for(N, 256)), dim3(256), 0, st, labels, (const uint32_t*)area, cls_map,
+                                            score, table, votes, ssum, N, Ws, n_cls, max_objects);
+  if (rc || phases == 7) return rc;
+  rc = c3d_launch_lds<finalise_kernel>(dim3(grid_for(max_objects, 256)), dim3(256), 0, st, table, (const uint32_t*)votes,
+                                       (const unsigned long long*)ssum, (const uint32_t*)header, counts, n_cls, first_class,
+                                       max_objects, cls_map ? 1 : 0, score ? 1 : 0);
+  if (rc || phases == 8) return rc;
+  if (object_cls)
+    rc = c3d_launch_lds<paint_kernel>(dim3(grid_for(N, 256)), dim3(256), 0, st, (const int32_t*)labels, (const int32_t*)table,
+                                      object_cls, N, max_objects);
+  return rc;
+}
+
 extern "C" int c3d_scene_objects(const uint8_t* mask, const uint8_t* cls_map, const float* score, int32_t Hs, int32_t Ws,
                                  int32_t connectivity, int32_t min_area, int32_t n_cls, int32_t first_class, int32_t max_objects,
                                  int32_t* labels, int32_t* table, uint32_t* hist, uint8_t* object_cls, int32_t* counts, void* ws,
@@ -434,61 +497,18 @@ extern "C" int c3d_scene_objects(const uint8_t* mask, const uint8_t* cls_map, co
   if (connectivity != 4 && connectivity != 8) return C3D_E_BADARG;
   if ((int64_t)Hs * Ws >= (1ll << 31)) return C3D_E_UNSUPPORTED;
   if (cls_map && (n_cls < 1 || n_cls > 16)) return C3D_E_BADARG;
-  if (!cls_map) { n_cls = 1; hist = nullptr; }            // no class map, no votes: `hist` is left alone
-  const int N = Hs * Ws, conn8 = connectivity == 8;
-  const Workspace w = workspace_plan(N, n_cls);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  uint32_t* header = reinterpret_cast<uint32_t*>(base);
-  uint32_t* area = reinterpret_cast<uint32_t*>(base + w.area);
-  uint32_t* chunks = reinterpret_cast<uint32_t*>(base + w.chunks);
-  unsigned long long* ssum = reinterpret_cast<unsigned long long*>(base + w.ssum);
-  const int64_t rows_cap = max_objects < w.cap ? max_objects : w.cap;   // no id with a table row can be larger
-  uint32_t* votes = hist ? hist : reinterpret_cast<uint32_t*>(base + w.hist);
-  const uint32_t min_a = min_area < 1 ? 1u : (uint32_t)min_area;
+  uint32_t* header = static_cast<uint32_t*>(ws);
+  uint32_t* area = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + c3d_detail_area_offset());
 
   // instrumented build only (common.h c3d_knob): tools/objects_step.py times prefixes of the nine launches.  The product
-  // library compiles this to 9, and every `phases == k` below to false.
+  // library compiles this to 9, and every `phases == k` in the stages to false.
   const int phases = c3d_knob("C3D_OBJECTS_PHASES", 9);
 
-  // header and area; the sums and votes of the rows that can be used.  The table needs none: number_roots writes the rows of
-  // the objects, finalise zeroes the others.
-  hipError_t e = hipMemsetAsync(base, 0, (size_t)(w.chunks), st);
-  if (e == hipSuccess && score) e = hipMemsetAsync(ssum, 0, (size_t)rows_cap * 8, st);
-  if (e == hipSuccess && cls_map) e = hipMemsetAsync(votes, 0, (size_t)(hist ? (int64_t)max_objects : rows_cap) * n_cls * 4, st);
-  if (e != hipSuccess) return (int)e;
-
-  const int tiles_x = (Ws + TW - 1) / TW, tiles_y = (Hs + TH - 1) / TH;
-  const int n_tiles = tiles_x * tiles_y;                   // <= N / 4096 + ...: far below 2^31
-  int rc = c3d_launch_lds<label_local_kernel>(dim3((unsigned)(n_tiles > 65536 ? 65536 : n_tiles)), dim3(256), TH * TW * 4, st,
-                                              mask, labels, header + WS_ERR, (int)Hs, (int)Ws, tiles_x, n_tiles, conn8);
-  if (rc || phases == 1) return rc;
-  const int64_t row_items = (int64_t)(tiles_y - 1) * Ws, items = row_items + (int64_t)(tiles_x - 1) * Hs;
-  if (items > 0) {
-    rc = c3d_launch_lds<label_seam_kernel>(dim3(grid_for(items, 256)), dim3(256), 0, st, mask, labels, header + WS_ERR, (int)Hs,
-                                           (int)Ws, row_items, items, N, conn8);
-    if (rc) return rc;
-  }
-  if (phases == 2) return 0;
-  rc = c3d_launch_lds<label_flatten_kernel>(dim3(grid_for(N, 256)), dim3(256), 0, st, labels, area, header + WS_ERR, N, N);
-  if (rc || phases == 3) return rc;
-  rc = c3d_launch_lds<count_roots_kernel>(dim3(grid_for(w.n_chunks, 1)), dim3(256), 16, st, (const int32_t*)labels,
-                                          (const uint32_t*)area, chunks, N, w.n_chunks, min_a);
-  if (rc || phases == 4) return rc;
-  rc = c3d_launch_lds<scan_chunks_kernel>(dim3(1), dim3(256), 1024, st, chunks, header, w.n_chunks);
-  if (rc || phases == 5) return rc;
-  rc = c3d_launch_lds<number_roots_kernel>(dim3(grid_for(w.n_chunks, 1)), dim3(256), 16, st, (const int32_t*)labels, area,
-                                           (const uint32_t*)chunks, table, N, w.n_chunks, min_a, (int)max_objects);
-  if (rc || phases == 6) return rc;
-  rc = c3d_launch_lds<relabel_stats_kernel>(dim3(grid_for(N, 256)), dim3(256), 0, st, labels, (const uint32_t*)area, cls_map,
-                                            score, table, votes, ssum, N, (int)Ws, (int)n_cls, (int)max_objects);
-  if (rc || phases == 7) return rc;
-  rc = c3d_launch_lds<finalise_kernel>(dim3(grid_for(max_objects, 256)), dim3(256), 0, st, table, (const uint32_t*)votes,
-                                       (const unsigned long long*)ssum, (const uint32_t*)header, counts, (int)n_cls,
-                                       (int)first_class, (int)max_objects, cls_map ? 1 : 0, score ? 1 : 0);
-  if (rc || phases == 8) return rc;
-  if (object_cls)
-    rc = c3d_launch_lds<paint_kernel>(dim3(grid_for(N, 256)), dim3(256), 0, st, (const int32_t*)labels, (const int32_t*)table,
-                                      object_cls, N, (int)max_objects);
-  return rc;
+  int rc = c3d_detail_objects_clear(ws, (int64_t)Hs * Ws, cls_map, score, n_cls, hist, max_objects, st);
+  if (rc) return rc;
+  rc = c3d_detail_label_roots(mask, labels, header + WS_ERR, area, Hs, Ws, connectivity == 8, phases, st);
+  if (rc || phases <= 3) return rc;
+  return c3d_detail_objects_tail(cls_map, score, Hs, Ws, min_area, n_cls, first_class, max_objects, labels, table, hist, object_cls,
+                                 counts, ws, phases, st);
 }

@@ -51,6 +51,16 @@ AxisPlan = namedtuple("AxisPlan", "extent tile stride margin n k starts")
 # labels i32 [Hs, Ws]; table i32 [max_objects, 8] = (area, x0, y0, x1, y1, cls, first, score_q); counts i32 [2] = (found, rows
 # written); object_cls u8 [Hs, Ws]; hist i32 [max_objects, num_class] or None (BCD has no class map)
 SceneObjects = namedtuple("SceneObjects", "labels table counts object_cls hist")
+
+
+class SceneSplitObjects(SceneObjects):
+    """The `SceneObjects` of `predict(objects=True, split=R)`: the same five fields, so everything that takes a `SceneObjects`
+    takes it, plus `.info` i32 [4] = (status, seeds, growth rounds used, 0) of `c3d_scene_split`."""
+
+    def __new__(cls, labels, table, counts, object_cls, hist, info):
+        self = super().__new__(cls, labels, table, counts, object_cls, hist)
+        self.info = info
+        return self
 # rings i32 [max_rings, 8] = (id, start, n_vertices, area, perimeter, x, y, 0) in the order of their starting edge; vertices i32
 # [max_vertices, 2] = (vx, vy) lattice points, ring after ring; counts i32 [5] = (rings found, rows written, vertices found,
 # vertices written, status: _lib.OUTLINE_ST_*)
@@ -176,6 +186,11 @@ class SceneInferencer:
     `simplify=tol` (with `outlines=True`) appends one more `SceneOutlines`: the rings simplified with a tolerance of `tol`
     pixels in [0, 1024] (`ops.outlines_simplify`); column 3 of its rows is twice the signed area of the simplified ring and
     column 7 the ring's raw vertex count.  With `simplify=None` the result is the one without the argument.
+    `split=R` (with `objects=True`) splits touching objects (`ops.scene_split`): the mask is eroded by R pixels, in (0, 1024], and
+    the components of what is left grow back inside the mask; the appended object is a `SceneSplitObjects`, a `SceneObjects`
+    with `.info` = (status, seeds, rounds used, 0) that outlines, simplification, votes and `ObjectEvaluator` take unchanged.
+    `split_rounds` (default 32) limits the growth rounds: `info[0] & SPLIT_ST_NOT_CONVERGED` says that it was too small.  With
+    `split=None` the launches are the ones without the argument.
     `tta` is None, a name of `VIEW_SETS` ("none", "hflip", "flips", "d4") or a sequence of view codes: the tiles are predicted
     under those `nv` views and averaged with the views undone (module docstring).  `batch` stays the number of model inputs
     per forward, so a forward takes `batch // nv` tiles; a transposing view (codes 4..7) needs a square model input.  With
@@ -231,9 +246,18 @@ class SceneInferencer:
 
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
-                max_vertices=None, simplify=None):
+                max_vertices=None, simplify=None, split=None, split_rounds=None):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
+        if split is None and split_rounds is not None:
+            raise ValueError("split_rounds limits the growth rounds of split=R: it needs split")
+        if split is not None:
+            if not objects:
+                raise ValueError("split=R splits the objects of the map: it needs objects=True")
+            ops.boundary_radius2(split)                 # raises outside (0, 1024] before anything is enqueued
+            split_rounds = 32 if split_rounds is None else int(split_rounds)
+            if not 1 <= split_rounds <= 65536:
+                raise ValueError(f"split_rounds must lie in [1, 65536], got {split_rounds}")
         if simplify is not None:
             if not outlines:
                 raise ValueError("simplify=tol simplifies the outlines of the objects: it needs outlines=True")
@@ -301,9 +325,15 @@ class SceneInferencer:
             result = (heads[0].cls, heads[1].cls, heads[2].cls)
             found = dict(mask=heads[2].cls, cls_map=heads[1].cls, n_cls=self.num_class)
         if objects:
-            labels, table, hist, object_cls, counts = ops.scene_objects(first_class=1, connectivity=connectivity, min_area=min_area,
-                                                                        max_objects=max_objects, **found)
-            result += (SceneObjects(labels, table, counts, object_cls, hist),)
+            if split is not None:
+                labels, table, hist, object_cls, counts, info = ops.scene_split(
+                    found.pop("mask"), split, first_class=1, connectivity=connectivity, min_area=min_area, max_objects=max_objects,
+                    max_rounds=split_rounds, **found)
+                result += (SceneSplitObjects(labels, table, counts, object_cls, hist, info),)
+            else:
+                labels, table, hist, object_cls, counts = ops.scene_objects(first_class=1, connectivity=connectivity,
+                                                                            min_area=min_area, max_objects=max_objects, **found)
+                result += (SceneObjects(labels, table, counts, object_cls, hist),)
             if outlines:
                 result += (SceneOutlines(*ops.scene_outlines(labels, counts, connectivity=connectivity, max_objects=max_objects,
                                                              max_rings=max_rings, max_vertices=max_vertices)),)

@@ -1047,6 +1047,45 @@ def boundary_counts(pred, gt, d, tau=None, border=True, totals=None, ws=None):
     return counts
 
 
+def scene_split_tile():
+    """(rows, columns) of the tile that one workgroup of c3d_scene_split's growth relaxes in LDS; host only."""
+    out = (C.c_int32 * 2)()
+    L.check(L.lib().c3d_scene_split_tile(out), "c3d_scene_split_tile")
+    return int(out[0]), int(out[1])
+
+
+def scene_split(mask, r, cls_map=None, score=None, connectivity=8, min_area=1, n_cls=1, first_class=1, max_objects=65536,
+                max_rounds=32, want_hist=True, want_object_cls=True, ws=None):
+    """c3d_scene_split on the u8 map `mask` [Hs, Ws]: `scene_objects` with every component cut into the pieces that are joined
+    by necks narrower than the radius `r` in pixels (`boundary_radius2`: r2 = floor(r * r); r = 0 splits nothing and equals
+    `scene_objects`).  Returns `scene_objects`' tuple plus `info` i32 [4] = (status, seeds, rounds used, 0), all on the
+    device; nothing is read back.  A status with `SPLIT_ST_NOT_CONVERGED` asks for a larger `max_rounds`."""
+    Hs, Ws = _u8_map(mask, "scene_split mask")
+    r2 = 0 if float(r) == 0.0 else boundary_radius2(r)
+    if not 1 <= int(max_rounds) <= 65536:
+        raise ValueError(f"max_rounds must lie in [1, 65536], got {max_rounds}")
+    if cls_map is not None:
+        assert cls_map.dtype == torch.uint8 and cls_map.shape == mask.shape and cls_map.is_contiguous()
+    if score is not None:
+        assert score.dtype == torch.float32 and score.shape == mask.shape and score.is_contiguous()
+    nbytes = L.lib().c3d_scene_split_ws_bytes(Hs, Ws, int(n_cls) if cls_map is not None else 1)
+    if nbytes < 0 or int(max_objects) < 1:
+        raise L.Change3DHipError(f"c3d_scene_split refuses a {Hs} x {Ws} scene with n_cls = {n_cls}, max_objects = "
+                                 f"{max_objects} (code {nbytes if nbytes < 0 else -1})")
+    dev = mask.device
+    ws = _scene_ws(ws, nbytes, dev, "c3d_scene_split", Hs, Ws)
+    labels = torch.empty((Hs, Ws), dtype=torch.int32, device=dev)
+    table = torch.empty((int(max_objects), 8), dtype=torch.int32, device=dev)
+    hist = torch.empty((int(max_objects), int(n_cls)), dtype=torch.int32, device=dev) if want_hist and cls_map is not None else None
+    object_cls = torch.empty((Hs, Ws), dtype=torch.uint8, device=dev) if want_object_cls else None
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    _launch("c3d_scene_split", Hs * Ws * 80, L.lib().c3d_scene_split, _p(mask), _p(cls_map), _p(score), Hs, Ws, int(connectivity),
+            int(min_area), int(n_cls), int(first_class), int(max_objects), r2, int(max_rounds), _p(labels), _p(table), _p(hist),
+            _p(object_cls), _p(counts), _p(info), _p(ws), _stream())
+    return labels, table, hist, object_cls, counts, info
+
+
 def build_clip(pre, post, frames, clip, B, K, H, W):
     _launch("c3d_build_clip", clip.numel() * 8, L.lib().c3d_build_clip, _p(pre), _p(post), _p(frames), _p(clip), B, K, H, W,
             _stream())

@@ -43,6 +43,12 @@ distance transform `c3d_scene_edt`): Boundary IoU over the bands of width D pixe
 contour pixels with a tolerance of `--boundary_tol` pixels (default D), on the masks that `--objects` scores: the mask against
 `label > 0` (BCD), the change mask against the change label (SCD), `loc_mask` against `label_loc > 0` (BDA).  One more line
 follows the score lines, `boundary: d tol biou precision recall f1`.  Without labels the option does nothing.
+
+`--objects --split_objects R` splits touching objects before anything else sees them (`c3d_scene_split`): the mask is eroded
+by R pixels, the components of what is left are seeds, and every seed grows back inside the mask, so two footprints joined by
+a neck narrower than about 2 R become two rows, two polygons and two votes.  (`--split` alone is the data set split of
+`--file_root`.)  The growth runs at most `--split_rounds` rounds (default 32); a scene that needs more ends the run with an
+error that says so.  The labels that `--objects` scores against are NOT split.
 """
 import json
 import os
@@ -59,6 +65,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from change3d_amd.data.dataset import BCDDataset, BDADataset, SCDDataset, read_label, read_rgb  # noqa: E402
+from change3d_amd import _lib as L  # noqa: E402
 from change3d_amd.infer import SceneInferencer  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
 from change3d_amd.boundary_metrics import BoundaryEvaluator  # noqa: E402
@@ -233,6 +240,20 @@ def boundary_radius(text):
     return v
 
 
+def split_rounds(text):
+    v = int(text)
+    if not 1 <= v <= 65536:
+        raise ArgumentTypeError(f"--split_rounds must lie in [1, 65536], got {text}")
+    return v
+
+
+def check_split(name, objects):
+    """Ends the run when the growth of `--split_objects` did not reach its fixed point on this scene."""
+    info = getattr(objects, "info", None)
+    if info is not None and int(info[0]) & L.SPLIT_ST_NOT_CONVERGED:
+        raise SystemExit(f"{name}: the pieces of --split_objects were still growing after {int(info[2])} rounds; raise --split_rounds")
+
+
 def iou_threshold(text):
     v = float(text)
     if not 0.5 <= v < 1.0:
@@ -256,6 +277,10 @@ def parse_args(argv=None):
         parser.error("--simplify simplifies the polygons: it needs --polygons")
     if args.boundary_tol is not None and args.boundary is None:
         parser.error("--boundary_tol is the tolerance of the boundary scores: it needs --boundary")
+    if args.split_objects is not None and not args.objects:
+        parser.error("--split_objects splits the objects of the map: it needs --objects")
+    if args.split_rounds is not None and args.split_objects is None:
+        parser.error("--split_rounds is the round limit of --split_objects: it needs --split_objects")
     return args
 
 
@@ -292,18 +317,21 @@ def main(argv=None):
             boundary_eval = BoundaryEvaluator(args.boundary, args.boundary_tol, device=device)
         boundary_eval.update(mask.to(torch.uint8), gt_mask.to(torch.uint8))
 
+    split = {} if args.split_objects is None else dict(split=args.split_objects, split_rounds=args.split_rounds)
     for name, img, label in scenes(args):
         scene = torch.from_numpy(np.ascontiguousarray(img))
         if args.polygons:                 # the outlines come last; every `out[-1]` below is the objects
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, outlines=True,
-                              max_rings=args.max_rings, max_vertices=args.max_vertices, simplify=args.simplify)
+                              max_rings=args.max_rings, max_vertices=args.max_vertices, simplify=args.simplify, **split)
             simplified = None
             if args.simplify is not None:
                 out, simplified = out[:-1], out[-1]
+            check_split(name, out[-2])
             cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified))
             out = out[:-1]
         elif args.objects:
-            out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity)
+            out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, **split)
+            check_split(name, out[-1])
         else:
             out = inf.predict(scene)
         if args.task == "BCD":
@@ -406,6 +434,12 @@ def build_parser():
                    "over bands of this width in pixels and the contour precision / recall / F1; in [1, 1024]")
     p.add_argument("--boundary_tol", type=boundary_radius, default=None, metavar="T", help="--boundary: the contour tolerance in pixels "
                    "(default: D)")
+    p.add_argument("--split_objects", type=boundary_radius, default=None, metavar="R", help="--objects: split touching objects "
+                   "(c3d_scene_split): erode the mask by R pixels, in [1, 1024], and grow what is left back inside the mask, so that "
+                   "objects joined by a neck narrower than about 2 R come apart.  Only the prediction is split: the labels that "
+                   "--objects scores against stay whole components")
+    p.add_argument("--split_rounds", type=split_rounds, default=None, metavar="N", help="--split_objects: the most growth rounds, "
+                   "in [1, 65536] (default 32); a scene that needs more ends the run with an error")
     p.add_argument("--pretrained", default="./pretrained/X3D_L.pyth")
     p.add_argument("--gpu_id", default=0, type=int)
     return p

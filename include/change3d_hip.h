@@ -801,6 +801,47 @@ int64_t c3d_boundary_counts_ws_bytes(int32_t Hs, int32_t Ws);           /* < 0: 
 int c3d_boundary_counts(const uint8_t* pred, const uint8_t* gt, int32_t Hs, int32_t Ws, int32_t d2, int32_t tau2, int32_t flags,
                         int64_t* counts, int64_t* totals, void* ws, void* stream);
 
+/* Touching objects split apart (csrc/scene_split.hip): c3d_scene_objects with every connected component cut into the pieces that
+ * its necks join.  The arguments of c3d_scene_objects plus r2 >= 0, a squared radius in pixels, and max_rounds >= 1; the
+ * connectivity c (4 or 8) is used everywhere below.
+ *   core      mask != 0 and dist2 > r2, with dist2 = c3d_scene_edt(mask, flags = C3D_EDT_BORDER, cap2 = r2): the outside of the
+ *             scene is background, and C3D_EDT_FAR is > r2.  With r2 == 0 the core is the mask and no transform is run
+ *   seeds     the c-connected components of the core; a seed's id is the linear index y * Ws + x of its first pixel in raster
+ *             order
+ *   growth    inside one c-connected component of the mask, d(p, s) = the length of the shortest c-connected path from pixel p to
+ *             any pixel of seed s with every step inside the mask.  A pixel of a component that holds at least one seed belongs
+ *             to the seed with the lexicographically smallest (d(p, s), id(s)): the unique fixed point of
+ *               key(p) = min(key(p), min over the c-neighbours q of p in the mask of key(q) + (1, 0)),  key = (0, id) on seeds.
+ *             A component without a seed (thinner than the radius everywhere) stays one piece
+ *   pieces    every piece is c-connected; with min_area <= 1 the pieces partition the mask.  Touching pieces share pixel edges,
+ *             which c3d_scene_outlines cuts (it cuts wherever the neighbour has another label)
+ *   outputs   labels, table, hist, object_cls, counts exactly as c3d_scene_objects defines them with "component" read as
+ *             "piece": min_area filters pieces, pieces are numbered 1..N in raster order of their own first pixel (which may
+ *             precede the seed's), the same eight columns, vote rule, score_q and truncation at max_objects
+ *   info      i32 [4] = (status, number of seeds, relaxation rounds that changed something, 0)
+ *               C3D_SPLIT_ST_NOT_CONVERGED  round max_rounds still changed something: the outputs are those of the partition
+ *                                           reached so far with the unreached pixels as label 0 -- in bounds, otherwise
+ *                                           unspecified
+ *               C3D_SPLIT_ST_BAD_LABELS     the component labelling reported its error word (counts[0] = -1 as well)
+ *   identity  r2 == 0 gives exactly the outputs of c3d_scene_objects
+ *   ws        c3d_scene_split_ws_bytes(Hs, Ws, n_cls) bytes, 256-byte aligned
+ * Integer arithmetic and integer atomics only: two runs agree bit for bit.  Nothing is read back by the host, no workgroup waits
+ * for another, every in-kernel loop is capped, and no workspace word is read before the call wrote it (a dirty workspace gives the
+ * same result).  Launches on `stream`: the memsets of c3d_scene_objects and four more, the labelling (3), with r2 > 0 the transform (3), the core (1)
+ * and the labelling of the core (3), the keys (1), max_rounds growth rounds -- round k returns at once when round k-1 changed
+ * nothing, and only the tiles next to a change run --, the piece roots (2), the tail of c3d_scene_objects (6) and info (1).
+ * Refused before anything is enqueued: what c3d_scene_objects refuses, r2 outside [0, 2^20], max_rounds outside [1, 65536], a
+ * NULL info (C3D_E_BADARG); r2 > 0 with Hs or Ws > 16384, the limit of c3d_scene_edt (C3D_E_UNSUPPORTED).
+ * c3d_scene_split_tile: out[0], out[1] = rows and columns of the tile that one workgroup grows in LDS.  Host only.            */
+#define C3D_SPLIT_ST_NOT_CONVERGED 1
+#define C3D_SPLIT_ST_BAD_LABELS 2
+int64_t c3d_scene_split_ws_bytes(int32_t Hs, int32_t Ws, int32_t n_cls);      /* < 0: C3D_E_* */
+int c3d_scene_split_tile(int32_t out[2]);
+int c3d_scene_split(const uint8_t* mask, const uint8_t* cls_map, const float* score, int32_t Hs, int32_t Ws, int32_t connectivity,
+                    int32_t min_area, int32_t n_cls, int32_t first_class, int32_t max_objects, int32_t r2, int32_t max_rounds,
+                    int32_t* labels, int32_t* table, uint32_t* hist, uint8_t* object_cls, int32_t* counts, int32_t* info, void* ws,
+                    void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
  * stage (reference model/x3d.py:331-412 = ResStage of ResBlocks, driven by `self.x3d.blocks[i](x)` at
