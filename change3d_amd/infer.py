@@ -29,6 +29,11 @@ a ring table and a vertex list; it is enqueued behind the labelling, before the 
 simplified by `c3d_outlines_simplify` (Douglas-Peucker, `tol` in pixels), enqueued behind the tracing, before the same one
 synchronisation.  Its rows are `(id, start, n_vertices, 2 * area, perimeter, x, y, raw n_vertices)`.
 
+`predict(..., simplify=tol, simplify_check=True)` appends a `SceneFill` after that: the simplified rings filled back into a
+label map of the scene's size (`c3d_rings_fill`, centre sampling, even-odd per id) and joined to the raw objects with
+`c3d_objects_match` at the lowest threshold, 0.5 -- per object what the simplification cost: its partner, intersection and union
+in pixels.  Enqueued behind the simplification, before the same one synchronisation.
+
 `SceneInferencer(..., tta="hflip" | "flips" | "d4" | codes)` is test-time augmentation: every tile is predicted under a set of
 the eight flips and rotations of the square, each view is undone on the output and the views are averaged before the
 stitch.  A view code `v` in 0..7 transposes the tile if `v & 4`, then reverses its rows if `v & 2`, then its columns if
@@ -65,6 +70,10 @@ class SceneSplitObjects(SceneObjects):
 # [max_vertices, 2] = (vx, vy) lattice points, ring after ring; counts i32 [5] = (rings found, rows written, vertices found,
 # vertices written, status: _lib.OUTLINE_ST_*)
 SceneOutlines = namedtuple("SceneOutlines", "rings vertices counts")
+# the simplified rings filled back into pixels (`c3d_rings_fill`) and joined to the raw objects (`c3d_objects_match`, prediction =
+# the raw objects): labels, table [max_objects, 8] and counts [2] as in SceneObjects; info i32 [4] = (status, ring rows used, K,
+# 0); match = (match_raw i32 [max_objects, 4], match_filled i32 [max_objects, 4], conf, counts i64 [6], sum_iou f64 [1])
+SceneFill = namedtuple("SceneFill", "labels table counts info match")
 TASKS = ("bcd", "scd", "bda")
 WINDOWS = ("hann", "flat")
 VIEW_SETS = {"none": (0,), "hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
@@ -186,6 +195,10 @@ class SceneInferencer:
     `simplify=tol` (with `outlines=True`) appends one more `SceneOutlines`: the rings simplified with a tolerance of `tol`
     pixels in [0, 1024] (`ops.outlines_simplify`); column 3 of its rows is twice the signed area of the simplified ring and
     column 7 the ring's raw vertex count.  With `simplify=None` the result is the one without the argument.
+    `simplify_check=True` (with `simplify=tol`) appends a `SceneFill`: the simplified rings filled back into pixels
+    (`ops.rings_fill`) and matched to the raw objects (`ops.objects_match`, raw objects first, threshold 0.5): row id-1 of
+    `match[0]` is (partner id, intersection, union, covered) of raw object `id`.  With `simplify_check=False` the launches are
+    the ones without the argument.
     `split=R` (with `objects=True`) splits touching objects (`ops.scene_split`): the mask is eroded by R pixels, in (0, 1024], and
     the components of what is left grow back inside the mask; the appended object is a `SceneSplitObjects`, a `SceneObjects`
     with `.info` = (status, seeds, rounds used, 0) that outlines, simplification, votes and `ObjectEvaluator` take unchanged.
@@ -246,7 +259,7 @@ class SceneInferencer:
 
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
-                max_vertices=None, simplify=None, split=None, split_rounds=None):
+                max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
         if split is None and split_rounds is not None:
@@ -262,6 +275,8 @@ class SceneInferencer:
             if not outlines:
                 raise ValueError("simplify=tol simplifies the outlines of the objects: it needs outlines=True")
             ops.simplify_tol2_q(simplify)               # raises outside [0, 1024] before anything is enqueued
+        if simplify_check and simplify is None:
+            raise ValueError("simplify_check=True measures what simplify=tol cost: it needs simplify")
         if any(v is not None and int(v) < 1 for v in (max_rings, max_vertices)):
             raise ValueError(f"max_rings and max_vertices must be positive, got {max_rings} and {max_vertices}")
         dev = self._device()
@@ -339,5 +354,9 @@ class SceneInferencer:
                                                              max_rings=max_rings, max_vertices=max_vertices)),)
                 if simplify is not None:
                     result += (SceneOutlines(*ops.outlines_simplify(*result[-1], simplify)),)
+                    if simplify_check:
+                        f_labels, f_table, f_counts, _, _, f_info = ops.rings_fill(*result[-1], Hs, Ws, max_objects=max_objects)
+                        match = ops.objects_match(labels, table, counts, f_labels, f_table, f_counts, n_cls=1, iou_thr=0.5)
+                        result += (SceneFill(f_labels, f_table, f_counts, f_info, match),)
         torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
         return result

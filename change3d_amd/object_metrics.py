@@ -5,7 +5,9 @@ found ones fit.  The reference has no counterpart; its scores are per pixel.
 the ground truth with the same entry (`c3d_scene_objects`, votes over `gt_cls`, `first_class = 1`) and joins the two labelings
 with `c3d_objects_match`: a predicted object and a ground-truth object match iff their IoU is strictly above `iou_thr` (>=
 0.5, so a match is unique on both sides).  Everything stays on the device and nothing synchronises until `scores()`, which
-reads the accumulated integers and the summed IoU back once and does the arithmetic in float64 on the host:
+reads the accumulated integers and the summed IoU back once and does the arithmetic in float64 on the host.
+`update_labeled(objects, labels_g, table_g, counts_g)` is the same join for a ground truth that is already objects, such as
+polygon labels filled by `c3d_rings_fill`:
 
     precision = TP / (TP + FP)    recall = TP / (TP + FN)    f1 = 2 TP / (2 TP + FP + FN)
     sq = sum_iou / TP    rq = TP / (TP + FP / 2 + FN / 2)    pq = sq * rq          (the panoptic-quality triple)
@@ -68,6 +70,22 @@ class ObjectEvaluator:
         labels_g, table_g, _, _, counts_g = ops.scene_objects(
             gt_mask_u8, gt_cls_u8, None, connectivity=self.connectivity, min_area=self.gt_min_area, n_cls=self.n_cls,
             first_class=1, max_objects=self.max_objects, want_hist=False, want_object_cls=False)
+        match_p, match_g, _, _, _ = ops.objects_match(
+            objects.labels, objects.table, objects.counts, labels_g, table_g, counts_g, n_cls=self.n_cls, iou_thr=self.iou_thr,
+            table_capacity=self.table_capacity, totals=self.totals, total_iou=self.total_iou)
+        self.scenes += 1
+        self.last_gt_counts = counts_g
+        return match_p, match_g
+
+    def update_labeled(self, objects, labels_g, table_g, counts_g):
+        """Adds one scene whose ground truth is already objects: the join of `update` without the relabelling.  `labels_g` i32
+        [Hs, Ws], `table_g` i32 [max_g, 8] and `counts_g` i32 [2] as `c3d_scene_objects` or `c3d_rings_fill` write them
+        (`ops.rings_fill` on polygon labels: touching buildings stay two objects).  Returns `(match_p, match_g)`; does not
+        synchronise."""
+        for what, t in (("ground-truth labels", labels_g), ("ground-truth table", table_g), ("ground-truth counts", counts_g),
+                        ("labels", objects.labels), ("table", objects.table), ("counts", objects.counts)):
+            if t.device != self.device:
+                raise ValueError(f"the {what} are on {t.device}, the evaluator's totals are on {self.device}")
         match_p, match_g, _, _, _ = ops.objects_match(
             objects.labels, objects.table, objects.counts, labels_g, table_g, counts_g, n_cls=self.n_cls, iou_thr=self.iou_thr,
             table_capacity=self.table_capacity, totals=self.totals, total_iou=self.total_iou)

@@ -977,6 +977,52 @@ def outlines_simplify(rings, vertices, counts, tol, ws=None):
     return rings_out, vertices_out, out
 
 
+def rings_fill_limits():
+    """(most rows and columns of an id's pixel box that one wave fills, rows of a band of a larger box); host only."""
+    out = (C.c_int32 * 2)()
+    L.lib().c3d_rings_fill_limits(out)
+    return int(out[0]), int(out[1])
+
+
+def rings_fill(rings, vertices, counts, Hs, Ws, frac_bits=0, id_cls=None, max_objects=65536, want_mask=False, want_cls_map=False,
+               ws=None):
+    """c3d_rings_fill on the `rings` i32 [max_rings, 8], `vertices` i32 [max_vertices, 2] and `counts` i32 [5] of
+    `scene_outlines` / `outlines_simplify` (or any table of that shape, coordinates in units of 2^-frac_bits pixel): the
+    polygons filled into an Hs x Ws label map by the integer rule of include/change3d_hip.h -- centre sampling, even-odd per
+    id, the largest id wins.  Returns `(labels i32 [Hs, Ws], table i32 [max_objects, 8] in `scene_objects`' row format,
+    counts_obj i32 [2] = (K, K), mask u8 [Hs, Ws] or None, cls_map u8 [Hs, Ws] or None, info i32 [4] = (status, ring rows
+    used, K, 0))`, all on the device; nothing is read back.  `id_cls` u8 [max_objects] gives every id its class."""
+    for t in (rings, vertices, counts):
+        require_gpu(t, "rings_fill input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    max_rings, max_vertices, max_objects = int(rings.shape[0]), int(vertices.shape[0]), int(max_objects)
+    Hs, Ws, frac_bits = int(Hs), int(Ws), int(frac_bits)
+    if not 0 <= frac_bits <= 8:
+        raise ValueError(f"frac_bits must lie in [0, 8], got {frac_bits}")
+    nbytes = L.lib().c3d_rings_fill_ws_bytes(max_rings, max_vertices, max_objects, Hs, Ws)
+    if nbytes < 0:
+        raise L.Change3DHipError(f"c3d_rings_fill refuses a {Hs} x {Ws} scene with max_rings = {max_rings}, max_vertices = "
+                                 f"{max_vertices}, max_objects = {max_objects} (code {nbytes})")
+    dev = rings.device
+    if id_cls is not None:
+        require_gpu(id_cls, "rings_fill id_cls")
+        assert id_cls.dtype == torch.uint8 and id_cls.numel() == max_objects and id_cls.is_contiguous() and id_cls.device == dev
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    labels = torch.empty((Hs, Ws), dtype=torch.int32, device=dev)
+    table = torch.empty((max_objects, 8), dtype=torch.int32, device=dev)
+    counts_obj = torch.empty(2, dtype=torch.int32, device=dev)
+    mask = torch.empty((Hs, Ws), dtype=torch.uint8, device=dev) if want_mask else None
+    cls_map = torch.empty((Hs, Ws), dtype=torch.uint8, device=dev) if want_cls_map else None
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    _launch("c3d_rings_fill", Hs * Ws * 10 + (max_rings + max_vertices) * 16, L.lib().c3d_rings_fill, _p(rings), _p(vertices),
+            _p(counts), max_rings, max_vertices, frac_bits, _p(id_cls), max_objects, Hs, Ws, _p(labels), _p(table), _p(counts_obj),
+            _p(mask), _p(cls_map), _p(info), _p(ws), _stream())
+    return labels, table, counts_obj, mask, cls_map, info
+
+
 def scene_edt_tile():
     """(rows of a chunk of c3d_scene_edt's column pass, pixels of a row per workgroup of its row pass); host only."""
     out = (C.c_int32 * 2)()

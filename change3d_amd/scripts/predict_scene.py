@@ -25,6 +25,21 @@ not fit `--max_rings` / `--max_vertices` is left out and the run ends with an er
 tolerance of TOL pixels): the coordinates then come from the simplified rings and each feature also gets `vertices_raw` and
 `vertices`, its vertex counts before and after.  A ring whose simplified area is zero or has changed sign keeps its raw vertices.
 
+`--simplify_check` (with `--simplify`) measures what the simplification cost, on the device: the simplified rings are filled back
+into pixels (`c3d_rings_fill`: a pixel belongs to a polygon iff its centre lies inside, even-odd over the rings of an object) and
+joined to the raw objects (`c3d_objects_match`, whose partners are unique because a pair needs an IoU above 0.5: an object that
+drifted further has no partner and the IoU 0).  Every feature gets an `iou` property and the run ends with a line `simplify: tol
+objects kept vanished iou_mean iou_min`: `kept` counts the objects whose partner is their own id, `vanished` those without a
+pixel after the fill.  `--simplify_min_iou F` implies the check and leaves every object whose IoU is not above F on its raw
+vertices, in every ring.
+
+`--label_polygons FILE` (BCD, BDA) takes the ground truth as polygons instead of a label raster: a GeoJSON `FeatureCollection`
+in pixel coordinates, such as `--polygons` writes, or an xBD label JSON (change3d_amd/vector_labels.py); with `--file_root` it
+names a directory holding `<name>.json` or `<name>.geojson`.  The polygons are filled on the device (`c3d_rings_fill`) and
+everything that scores reads the result: the pixel scores its mask (BDA: and its class map), `--objects` its labels -- one
+ground-truth object per feature, so two labelled buildings that touch stay two, where a raster would join them --, `--boundary`
+its mask.
+
 `--tta hflip|flips|d4` is test-time augmentation: every tile is predicted under the two mirror views, the four flips or all
 eight flips and rotations of the square, each view is undone on the device and the views are averaged before the stitch
 (`c3d_scene_gather_views`, `c3d_scene_fold_views`; change3d_amd/infer.py).  `--batch_size` stays the number of model inputs
@@ -66,6 +81,7 @@ if ROOT not in sys.path:
 
 from change3d_amd.data.dataset import BCDDataset, BDADataset, SCDDataset, read_label, read_rgb  # noqa: E402
 from change3d_amd import _lib as L  # noqa: E402
+from change3d_amd import ops, vector_labels  # noqa: E402
 from change3d_amd.infer import SceneInferencer  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
 from change3d_amd.boundary_metrics import BoundaryEvaluator  # noqa: E402
@@ -133,7 +149,7 @@ def save_objects(path, objects):
     return found, rows
 
 
-def polygons_geojson(table, rings, vertices, simplified=None):
+def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=None):
     """(FeatureCollection dict, ids left out) from host arrays: `table` [rows, 8] of the objects, `rings` [ring rows, 8] and
     `vertices` [vertices written, 2] of their outlines.  An object is complete iff it has one ring of positive area, every
     ring of it has its vertices (start >= 0) and the signed areas add up to the table's area -- a hole ring cut off by
@@ -141,7 +157,9 @@ def polygons_geojson(table, rings, vertices, simplified=None):
     `simplified` = (rings, vertices) of `c3d_outlines_simplify` on the same table, row for row: the coordinates of a ring then
     come from the simplified list -- unless its doubled area there is zero or has the other sign than the raw area, or its row
     has no vertices, in which case the ring keeps its raw vertices -- and every feature gets the counts `vertices_raw` and
-    `vertices`.  Completeness is judged on the raw rings either way."""
+    `vertices`.  Completeness is judged on the raw rings either way.
+    `iou` [rows] (with `simplified`): the IoU of every object with its simplified polygon filled back into pixels; each feature
+    gets it as a property, and with `min_iou` an object whose IoU is not above it keeps its raw vertices in every ring."""
     table, rings, vertices = np.asarray(table), np.asarray(rings), np.asarray(vertices)
     if simplified is not None:
         rings_s, vertices_s = np.asarray(simplified[0]).tolist(), np.asarray(simplified[1])
@@ -156,10 +174,11 @@ def polygons_geojson(table, rings, vertices, simplified=None):
             skipped.append(k + 1)
             continue
         coords, n_raw, n_out = [], 0, 0
+        drifted = simplified is not None and iou is not None and min_iou is not None and not float(iou[k]) > min_iou
         for r in outline + [r for r in own if r[3] <= 0]:  # the outline, then the holes in ring order
             ring = vertices[r[1]:r[1] + r[2]].tolist()
             n_raw += len(ring)
-            if simplified is not None:
+            if simplified is not None and not drifted:
                 s = rings_s[r[8]]
                 if s[1] >= 0 and s[1] + s[2] <= len(vertices_s) and s[3] != 0 and (s[3] > 0) == (r[3] > 0):
                     ring = vertices_s[s[1]:s[1] + s[2]].tolist()
@@ -168,25 +187,69 @@ def polygons_geojson(table, rings, vertices, simplified=None):
         properties = {"id": k + 1, "area": area, "cls": cls, "score": round(score_q / 65535, 4), "perimeter": outline[0][4]}
         if simplified is not None:
             properties.update(vertices_raw=n_raw, vertices=n_out)
+            if iou is not None:
+                properties.update(iou=round(float(iou[k]), 4))
         features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords}, "properties": properties})
     return {"type": "FeatureCollection", "features": features}, skipped
 
 
-def save_polygons(path, objects, outlines, simplified=None):
+def simplify_ious(objects, fill):
+    """(iou f64 [rows], kept, vanished) of a `SceneFill` against the raw `objects`: the IoU of every raw object with its partner
+    among the filled simplified polygons, 0 without one; how many objects have their own id as partner; how many own no pixel
+    after the fill."""
+    rows = int(objects.counts[1])
+    if int(fill.info[0]) & (L.FILL_ST_BAD_ID | L.FILL_ST_BAD_RING) or int(fill.match[3][4]):
+        raise SystemExit(f"--simplify_check: c3d_rings_fill status {int(fill.info[0])}, c3d_objects_match status {int(fill.match[3][4])}")
+    match = fill.match[0][:rows].cpu().numpy().astype(np.int64)
+    iou = np.where(match[:, 2] > 0, match[:, 1] / np.maximum(match[:, 2], 1), 0.0)
+    kept = int((match[:, 0] == np.arange(1, rows + 1)).sum())
+    vanished = int((fill.table[:rows, 0].cpu().numpy() == 0).sum())
+    return iou, kept, vanished
+
+
+def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=None):
     """objects/<name>.geojson; the one read-back of the rings (`simplified`: the second `SceneOutlines` of
-    `predict(..., simplify=tol)`, read back with them).  Returns the ids that were left out."""
+    `predict(..., simplify=tol)`, read back with them; `iou`, `min_iou`: see `polygons_geojson`).  Returns the ids that were
+    left out."""
     ring_rows, written = int(outlines.counts[1]), int(outlines.counts[3])
     rows = int(objects.counts[1])
     if simplified is not None:
         simplified = (simplified.rings[:ring_rows].cpu().numpy(), simplified.vertices[:int(simplified.counts[3])].cpu().numpy())
     doc, skipped = polygons_geojson(objects.table[:rows].cpu().numpy(), outlines.rings[:ring_rows].cpu().numpy(),
-                                    outlines.vertices[:written].cpu().numpy(), simplified)
+                                    outlines.vertices[:written].cpu().numpy(), simplified, iou, min_iou)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
         json.dump(doc, f)
     if skipped:
         print(f"{path}: {len(skipped)} of {rows} objects left out, their rings were cut off (status {int(outlines.counts[4])})")
     return skipped
+
+
+LABEL_FRAC_BITS = 4                                       # polygon labels are rounded to 1/16 pixel
+
+
+def polygon_labels(args, name, Hs, Ws, device):
+    """The ground truth of `--label_polygons` for the scene `name`, filled on the device: labels, table, counts (what
+    `ObjectEvaluator.update_labeled` takes), mask and cls_map u8 [Hs, Ws]."""
+    path = args.label_polygons
+    if os.path.isdir(path):
+        found = [f for f in (os.path.join(path, name + ext) for ext in (".json", ".geojson")) if os.path.isfile(f)]
+        if not found:
+            raise SystemExit(f"--label_polygons: neither {name}.json nor {name}.geojson in {path}")
+        path = found[0]
+    try:
+        rings, vertices, counts, id_cls = vector_labels.read_polygons(path, LABEL_FRAC_BITS)
+    except (OSError, vector_labels.PolygonFileError) as e:
+        raise SystemExit(f"--label_polygons: {e}")
+    n = max(len(id_cls), 1)
+    cls = np.zeros(n, dtype=np.uint8)
+    cls[:len(id_cls)] = id_cls
+    labels, table, counts_obj, mask, cls_map, info = ops.rings_fill(
+        *(torch.from_numpy(a).to(device) for a in (rings, vertices, counts)), Hs, Ws, frac_bits=LABEL_FRAC_BITS,
+        id_cls=torch.from_numpy(cls).to(device), max_objects=n, want_mask=True, want_cls_map=True)
+    if int(info[0]):
+        raise SystemExit(f"{path}: c3d_rings_fill status {int(info[0])}")
+    return SimpleNamespace(labels=labels, table=table, counts=counts_obj, mask=mask, cls_map=cls_map)
 
 
 def save_matches(path, objects, gt_counts, match_p, match_g):
@@ -261,6 +324,13 @@ def iou_threshold(text):
     return v
 
 
+def unit_interval(text):
+    v = float(text)
+    if not 0.0 <= v <= 1.0:
+        raise ArgumentTypeError(f"the IoU bound must lie in [0, 1], got {text}")
+    return v
+
+
 def simplify_tolerance(text):
     v = float(text)
     if not 0.0 <= v <= 1024.0:
@@ -275,6 +345,14 @@ def parse_args(argv=None):
         parser.error("--polygons outlines the objects of the map: it needs --objects")
     if args.simplify is not None and not args.polygons:
         parser.error("--simplify simplifies the polygons: it needs --polygons")
+    if args.simplify_min_iou is not None:
+        args.simplify_check = True
+    if args.simplify_check and args.simplify is None:
+        parser.error("--simplify_check and --simplify_min_iou measure what --simplify cost: they need --simplify")
+    if args.label_polygons and args.task == "SCD":
+        parser.error("--label_polygons gives objects with one class each: it serves --task BCD and BDA")
+    if args.label_polygons and any((args.label, args.label1, args.label2, args.change)):
+        parser.error("--label_polygons replaces the label rasters: give one or the other")
     if args.boundary_tol is not None and args.boundary is None:
         parser.error("--boundary_tol is the tolerance of the boundary scores: it needs --boundary")
     if args.split_objects is not None and not args.objects:
@@ -302,11 +380,14 @@ def main(argv=None):
     scored = 0
     cut_off = 0                                           # objects whose polygon was left out of a .geojson
 
-    def score_objects(name, objects, gt_mask, gt_cls=None):
+    def score_objects(name, objects, gt_mask, gt_cls=None, gt=None):
         nonlocal object_eval
         if object_eval is None:
             object_eval = ObjectEvaluator(n_cls=num_class, iou_thr=args.iou_thr, connectivity=args.connectivity, device=device)
-        match_p, match_g = object_eval.update(objects, gt_mask.to(torch.uint8), None if gt_cls is None else gt_cls.to(torch.uint8))
+        if gt is not None:                                # polygon labels are objects already: no relabelling
+            match_p, match_g = object_eval.update_labeled(objects, gt.labels, gt.table, gt.counts)
+        else:
+            match_p, match_g = object_eval.update(objects, gt_mask.to(torch.uint8), None if gt_cls is None else gt_cls.to(torch.uint8))
         save_matches(os.path.join(args.out_dir, "objects", name + ".match.csv"), objects, object_eval.last_gt_counts, match_p, match_g)
 
     def score_boundary(mask, gt_mask):
@@ -318,16 +399,26 @@ def main(argv=None):
         boundary_eval.update(mask.to(torch.uint8), gt_mask.to(torch.uint8))
 
     split = {} if args.split_objects is None else dict(split=args.split_objects, split_rounds=args.split_rounds)
+    if args.simplify_check:
+        split["simplify_check"] = True
+    drift = dict(objects=0, kept=0, vanished=0, iou_sum=0.0, iou_min=1.0)   # --simplify_check over all scenes
     for name, img, label in scenes(args):
         scene = torch.from_numpy(np.ascontiguousarray(img))
+        gt = polygon_labels(args, name, img.shape[0], img.shape[1], device) if args.label_polygons else None
         if args.polygons:                 # the outlines come last; every `out[-1]` below is the objects
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, outlines=True,
                               max_rings=args.max_rings, max_vertices=args.max_vertices, simplify=args.simplify, **split)
-            simplified = None
+            simplified, iou = None, None
+            if args.simplify_check:
+                out, fill = out[:-1], out[-1]
+                iou, kept, vanished = simplify_ious(out[-3], fill)
+                drift = dict(objects=drift["objects"] + len(iou), kept=drift["kept"] + kept, vanished=drift["vanished"] + vanished,
+                             iou_sum=drift["iou_sum"] + float(iou.sum()), iou_min=min([drift["iou_min"]] + iou.tolist()))
             if args.simplify is not None:
                 out, simplified = out[:-1], out[-1]
             check_split(name, out[-2])
-            cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified))
+            cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified, iou,
+                                         args.simplify_min_iou))
             out = out[:-1]
         elif args.objects:
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, **split)
@@ -339,12 +430,12 @@ def main(argv=None):
             save_png(os.path.join(args.out_dir, name + ".png"), mask.cpu().numpy() * 255)
             if args.objects:
                 save_objects(os.path.join(args.out_dir, "objects", name + ".csv"), out[-1])
-            if label is not None:        # ceil(u8 / 255), the label side of c3d_bcd_preprocess
-                lab = torch.from_numpy(np.ascontiguousarray(label)).to(device)
-                meter.update_cm_device(mask.float(), (lab > 0).float())
+            if gt is not None or label is not None:   # ceil(u8 / 255), the label side of c3d_bcd_preprocess
+                lab = gt.mask > 0 if gt is not None else torch.from_numpy(np.ascontiguousarray(label)).to(device) > 0
+                meter.update_cm_device(mask.float(), lab.float())
                 if args.objects:
-                    score_objects(name, out[-1], lab > 0)
-                score_boundary(mask, lab > 0)
+                    score_objects(name, out[-1], lab, gt=gt)
+                score_boundary(mask, lab)
                 scored += 1
         elif args.task == "BDA":
             loc_prob, loc_mask, damage_map, cls_logits = out[:4]
@@ -353,15 +444,19 @@ def main(argv=None):
             if args.objects:
                 save_png(os.path.join(args.out_dir, "damage_objects", name + ".png"), out[-1].object_cls.cpu().numpy())
                 save_objects(os.path.join(args.out_dir, "objects", name + ".csv"), out[-1])
-            if label is not None:        # scripts/train_BDA.py: label[:, 0].float() and the product of the two channels
-                lab = torch.from_numpy(np.ascontiguousarray(label)).to(device)
-                label_loc, label_cls = lab[..., 0].float(), lab[..., 0].long() * lab[..., 1].long()
+            if gt is not None or label is not None:   # scripts/train_BDA.py: label[:, 0].float() and the product of the two channels
+                if gt is not None:       # the filled polygons: building mask and one damage class per building
+                    loc, label_cls = gt.mask, gt.cls_map.long()
+                else:
+                    lab = torch.from_numpy(np.ascontiguousarray(label)).to(device)
+                    loc, label_cls = lab[..., 0], lab[..., 0].long() * lab[..., 1].long()
+                label_loc = loc.float()
                 meter.add_batch(cls_logits[None], loc_prob[None, None], label_loc[None], label_cls[None])
                 if args.objects:         # the per-building majority map against the damage labels, where there is one
                     inside = label_cls > 0
                     object_hist.update(out[-1].object_cls[inside], label_cls[inside])
-                    score_objects(name, out[-1], lab[..., 0] > 0, label_cls)
-                score_boundary(loc_mask, lab[..., 0] > 0)
+                    score_objects(name, out[-1], loc > 0, label_cls, gt=gt)
+                score_boundary(loc_mask, loc > 0)
                 scored += 1
         else:
             for sub, m in zip(("pred1", "pred2", "change"), out[:3]):
@@ -377,6 +472,9 @@ def main(argv=None):
                 score_boundary(out[2], lab[..., 2] > 0)
                 scored += 1
         print(f"{name}: {img.shape[0]} x {img.shape[1]} -> {args.out_dir}")
+    if args.simplify_check:
+        print(f"simplify: tol = {args.simplify:g} objects = {drift['objects']} kept = {drift['kept']} vanished = {drift['vanished']} "
+              f"iou_mean = {drift['iou_sum'] / max(drift['objects'], 1):.4f} iou_min = {drift['iou_min'] if drift['objects'] else 0.0:.4f}")
     if cut_off:
         raise SystemExit(f"{cut_off} objects have no polygon: their rings did not fit; raise --max_rings / --max_vertices")
     if not scored:
@@ -428,6 +526,13 @@ def build_parser():
     p.add_argument("--max_vertices", type=int, default=None, help="--polygons: rows of the vertex list (default: 16 per ring row)")
     p.add_argument("--simplify", type=simplify_tolerance, default=None, metavar="TOL", help="--polygons: simplify the rings on the "
                    "device (Douglas-Peucker) with this tolerance in pixels, in [0, 1024]")
+    p.add_argument("--simplify_check", action="store_true", help="--simplify: fill the simplified polygons back into pixels on the device "
+                   "and join them to the raw objects: an `iou` per feature and a closing `simplify:` line")
+    p.add_argument("--simplify_min_iou", type=unit_interval, default=None, metavar="F", help="--simplify: implies --simplify_check; an "
+                   "object whose IoU with its simplified polygon is not above F, in [0, 1], keeps its raw vertices")
+    p.add_argument("--label_polygons", default="", metavar="FILE", help="BCD, BDA: the ground truth as polygons, a GeoJSON FeatureCollection "
+                   "in pixel coordinates or an xBD label JSON, instead of label rasters; with --file_root a directory of <name>.json / "
+                   "<name>.geojson.  Filled on the device (c3d_rings_fill); one ground-truth object per feature")
     p.add_argument("--iou_thr", type=iou_threshold, default=0.5, help="--objects with labels: a predicted and a labelled object match iff "
                    "their IoU is strictly above this; in [0.5, 1)")
     p.add_argument("--boundary", type=boundary_radius, default=None, metavar="D", help="with labels: also the boundary scores, Boundary IoU "

@@ -751,6 +751,56 @@ int c3d_outlines_simplify(const int32_t* rings, const int32_t* vertices, const i
                           int32_t max_vertices, int64_t tol2_q, int32_t* rings_out, int32_t* vertices_out, int32_t* counts_out,
                           void* ws, void* stream);
 
+/* Polygon rings back to pixels (csrc/scene_fill.hip): the ring table and vertex list of c3d_scene_outlines or
+ * c3d_outlines_simplify, or any table of that shape, filled into a label map and an object table while they stay in HBM.
+ * Integer arithmetic only: floating point appears nowhere in a decision, every output is exact and two runs agree bit for bit.
+ * Two memsets (the workspace header, the labels) and 8 launches on `stream`, nothing is read back by the host, no workgroup
+ * waits for another, every loop is capped, and no workspace word is read before the call wrote it.  The rule:
+ *   coordinates a vertex coordinate is an integer in units of 2^-f pixel, f = frac_bits in [0, 8], |coordinate| <= 32768 * 2^f.
+ *               Pixel (y, x) is the square [x, x+1] x [y, y+1]; with s = 2^f and all coordinates doubled (X = 2 vx, Y = 2 vy)
+ *               its centre is (Cx, Cy) = ((2x + 1) s, (2y + 1) s).  Every product below stays under 2^51
+ *   crossing    a ring with the vertices v[0 .. n-1], closed by v[n] = v[0], has the edges (v[k-1], v[k]).  Rings with n < 3 and
+ *               horizontal edges contribute nothing.  With an edge ordered so that Y0 < Y1 it is active on row y iff
+ *               Y0 <= Cy < Y1, and it lies left of pixel (y, x) iff (Cx - X0) * (Y1 - Y0) > (X1 - X0) * (Cy - Y0), strictly
+ *   inside      a pixel is inside object `id` iff the number of pairs (used ring of that id, active edge left of the pixel) is
+ *               odd: even-odd over all rings of the id together.  Orientation does not matter, holes are further rings, a
+ *               ring listed twice cancels itself, self-crossing rings follow even-odd.  The rings of one id need not be
+ *               contiguous in the table
+ *   label       labels[y][x] = the largest id the pixel is inside of, or 0: polygons that share an edge partition the pixels,
+ *               overlapping ones are decided, not summed
+ *   rows used   a row r < clamp(counts[1], 0, max_rings) with (id, start, n) = columns 0..2 (the others are ignored) is used iff
+ *               start >= 0, n >= 0, start + n <= clamp(counts[3], 0, max_vertices), 1 <= id <= max_objects and every
+ *               coordinate of the ring is in range.  A row with start < 0 (a ring the outlines call had no room for, or one
+ *               the simplifier passed through) is skipped silently, whatever else it holds.  Any other skipped row sets
+ *               C3D_FILL_ST_BAD_ID if its id is out of range, and C3D_FILL_ST_BAD_RING if its n is negative, its vertex range
+ *               ends past the written vertices or -- where that range could be read -- a coordinate is out of range (a row
+ *               may set both).  Nothing is read or written out of range
+ * Inputs (device): rings i32 [max_rings][8], vertices i32 [max_vertices][2] (8-byte aligned), counts i32 [5];
+ *   id_cls      u8 [max_objects] or NULL: the class of every id
+ * Outputs:
+ *   labels      i32 [Hs][Ws], 1 <= Hs, Ws <= 16384
+ *   table       i32 [max_objects][8], 16-byte aligned, in the row format of c3d_scene_objects for the ids 1 .. K, K = the
+ *               largest id of a used row: (area, x0, y0, x1, y1, cls, first, 0) with the inclusive box and first = the
+ *               smallest linear index of the pixels labelled id, cls = id_cls[id-1], or 0 without id_cls.  An id that owns
+ *               no pixel keeps a row of zeros except cls.  Rows past K are 0
+ *   counts_obj  i32 [2] = (K, K): with labels and table, what c3d_objects_match takes
+ *   mask        u8 [Hs][Ws] or NULL: labels > 0;   cls_map  u8 [Hs][Ws] or NULL: the table's cls painted over the object
+ *   info        i32 [4] = (status, ring rows used, K, 0); status = counts[4] as it came, with the bits below added
+ *   ws          c3d_rings_fill_ws_bytes(max_rings, max_vertices, max_objects, Hs, Ws) bytes, 256-byte aligned; a dirty one
+ *               gives the same result
+ * Input status C3D_OUTLINE_ST_BAD_COUNTS: labels, table, mask and cls_map all 0, counts_obj = (-1, 0), info = (counts[4], 0, 0, 0).
+ * Refused before anything is enqueued: a NULL rings, vertices, counts, labels, table, counts_obj, info or ws, frac_bits outside
+ * [0, 8], max_rings, max_vertices, max_objects, Hs or Ws < 1 (C3D_E_BADARG); Hs or Ws > 16384 (C3D_E_UNSUPPORTED).
+ * c3d_rings_fill_limits: out[0] = the most rows and columns of an id's pixel box that one wave fills in registers, out[1] = the
+ * rows of a band of a larger box, one workgroup each, bits in LDS.  The results do not depend on the tier.  Host only.       */
+#define C3D_FILL_ST_BAD_ID 16
+#define C3D_FILL_ST_BAD_RING 32
+void c3d_rings_fill_limits(int32_t out[2]);
+int64_t c3d_rings_fill_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_objects, int32_t Hs, int32_t Ws);   /* < 0: C3D_E_* */
+int c3d_rings_fill(const int32_t* rings, const int32_t* vertices, const int32_t* counts, int32_t max_rings, int32_t max_vertices,
+                   int32_t frac_bits, const uint8_t* id_cls, int32_t max_objects, int32_t Hs, int32_t Ws, int32_t* labels,
+                   int32_t* table, int32_t* counts_obj, uint8_t* mask, uint8_t* cls_map, int32_t* info, void* ws, void* stream);
+
 /* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
  * in HBM.  The rule:
  *   sites       the pixels with mask == 0; with C3D_EDT_INVERT (bit 0 of flags) the pixels with mask != 0
