@@ -140,6 +140,10 @@ inline int c3d_knob(const char* name, int dflt) {
 inline thread_local const void* c3d_last_launch = nullptr;
 inline thread_local int64_t c3d_launches = 0;   // launches of this thread through c3d_launch_lds (c3d_launch_count)
 
+// A plain <<< >>> launch that wants to be named by c3d_last_kernel notes its kernel's host-side handle the same way (the
+// launch count stays c3d_launch_lds's own).
+inline void c3d_note_launch(const void* kernel) { c3d_last_launch = kernel; }
+
 template <auto Kernel, class... Args>
 int c3d_launch_lds(const dim3 grid, const dim3 block, const size_t lds, hipStream_t stream, const Args&... args) {
   static const hipError_t raised =

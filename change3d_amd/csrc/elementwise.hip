@@ -521,6 +521,7 @@ int block_out_fwd_launch(const void* c, const float* ss_c, const void* shortcut,
   if (fin_c && grid > (env_grid > 0 ? env_grid : 1024)) grid = env_grid > 0 ? env_grid : 1024;
   return ew_typed(dtype, stream, [&](auto t, hipStream_t s) {
     typedef decltype(t) E;
+    c3d_note_launch(reinterpret_cast<const void*>(&block_out_fwd_kernel<E>));
     block_out_fwd_kernel<E><<<grid, blk, 0, s>>>((const E*)c, ss_c, (const E*)shortcut, ss_1, sc_mode, (E*)y, nvec, G, C, fc,
                                                   f1);
   });
@@ -534,6 +535,7 @@ void block_out_bwd_launch(const void* dy, const void* y, const void* c, const vo
   typedef typename Ops::elem_t E;
   const int blk = ew_block(G);
   const size_t lds = (size_t)blk * 24 * sizeof(float);
+  c3d_note_launch(reinterpret_cast<const void*>(&block_out_bwd_kernel<Ops, Extra...>));
   block_out_bwd_kernel<Ops, Extra...><<<bob_grid(nvec, blk), blk, lds, stream>>>(
       (const E*)dy, (const E*)y, (const E*)c, (const E*)s, (E*)g, mr_c, mr_1, dsums_c, dsums_1, nvec, G, C, fin_c, fin_1, extra...);
 }
@@ -593,6 +595,7 @@ extern "C" int c3d_frame_absdiff(const void* y, void* d, int32_t B, int32_t T, i
   if (!y || !d || !fg.ok() || !fg.has(t_pre) || !fg.has(t_post)) return C3D_E_BADARG;
   return ew_typed(dtype, stream, [&](auto t, hipStream_t s) {
     typedef decltype(t) E;
+    c3d_note_launch(reinterpret_cast<const void*>(&frame_absdiff_kernel<E>));
     frame_absdiff_kernel<E><<<ew_grid(fg.nvec, 256), 256, 0, s>>>((const E*)y, (E*)d, fg.nvec, fg.hwv, T, t_pre, t_post);
   });
 }
@@ -604,6 +607,7 @@ extern "C" int c3d_enhance_apply(const void* y, const void* e, void* out, int32_
   const int64_t nvec = fg.nvec_all();
   return ew_typed(dtype, stream, [&](auto t, hipStream_t s) {
     typedef decltype(t) E;
+    c3d_note_launch(reinterpret_cast<const void*>(&enhance_apply_kernel<E>));
     enhance_apply_kernel<E><<<ew_grid(nvec, 256), 256, 0, s>>>((const E*)y, (const E*)e, (E*)out, nvec, fg.hwv, T, t_mid);
   });
 }
@@ -614,6 +618,7 @@ extern "C" int c3d_enhance_bwd_mask(const void* dout, const void* e, void* de, i
   if (!dout || !e || !de || !fg.ok() || !fg.has(t_mid)) return C3D_E_BADARG;
   return ew_typed(dtype, stream, [&](auto t, hipStream_t s) {
     typedef decltype(t) E;
+    c3d_note_launch(reinterpret_cast<const void*>(&enhance_bwd_mask_kernel<E>));
     enhance_bwd_mask_kernel<E><<<ew_grid(fg.nvec, 256), 256, 0, s>>>((const E*)dout, (const E*)e, (E*)de, fg.nvec, fg.hwv, T,
                                                                       t_mid);
   });
@@ -625,9 +630,13 @@ extern "C" int c3d_enhance_bwd_apply(const void* dout, const void* y, const void
   const FrameGeom fg(B, T, HW, Cp);
   // t_pre / t_post outside [0, T) match no frame (the kernel reads y only on a matching frame): dy = dout then
   if (!dout || !y || !dd || !dy || !fg.ok()) return C3D_E_BADARG;
+  // ... but BOTH: on a matching frame the kernel reads y on t_pre AND t_post, so one index in range with the other outside
+  // would read outside y
+  if (fg.has(t_pre) != fg.has(t_post)) return C3D_E_BADARG;
   const int64_t nvec = fg.nvec_all();
   return ew_typed(dtype, stream, [&](auto t, hipStream_t s) {
     typedef decltype(t) E;
+    c3d_note_launch(reinterpret_cast<const void*>(&enhance_bwd_apply_kernel<E>));
     enhance_bwd_apply_kernel<E><<<ew_grid(nvec, 256), 256, 0, s>>>((const E*)dout, (const E*)y, (const E*)dd, (E*)dy, nvec,
                                                                     fg.hwv, T, t_pre, t_post);
   });
@@ -644,6 +653,7 @@ extern "C" int c3d_stem_enhance_fwd(const void* u, const float* ss, void* out, v
   const int blk = ew_block(fg.G);
   return ew_typed(dtype, stream, [&](auto t, hipStream_t s) {
     typedef decltype(t) E;
+    c3d_note_launch(reinterpret_cast<const void*>(&stem_enhance_fwd_kernel<E>));
     stem_enhance_fwd_kernel<E><<<ew_grid(fg.nvec, blk), blk, 0, s>>>((const E*)u, ss, (E*)out, (E*)d, fg.nvec, fg.hwv, fg.G, T,
                                                                       t_pre, t_post, t_mid);
   });
@@ -657,6 +667,7 @@ extern "C" int c3d_stem_enhance_mid(const void* u, const float* ss, const void* 
   const int blk = ew_block(fg.G);
   return ew_typed(dtype, stream, [&](auto t, hipStream_t s) {
     typedef decltype(t) E;
+    c3d_note_launch(reinterpret_cast<const void*>(&stem_enhance_mid_kernel<E>));
     stem_enhance_mid_kernel<E><<<ew_grid(fg.nvec, blk), blk, 0, s>>>((const E*)u, ss, (const E*)e, (E*)out, fg.nvec, fg.hwv,
                                                                       fg.G, T, t_mid);
   });
@@ -683,6 +694,7 @@ extern "C" int c3d_frame_scatter(const void* src, void* dst, int32_t B, int32_t 
   if (!src || !dst || !fg.ok() || !fg.has(t_dst)) return C3D_E_BADARG;
   return ew_typed(dtype, stream, [&](auto t, hipStream_t s) {
     typedef decltype(t) E;
+    c3d_note_launch(reinterpret_cast<const void*>(&frame_scatter_kernel<E>));
     frame_scatter_kernel<E><<<ew_grid(fg.nvec, 256), 256, 0, s>>>((const E*)src, (E*)dst, fg.nvec, fg.hwv, T, t_dst, accumulate);
   });
 }

@@ -325,6 +325,7 @@ int c3d_enhance_apply(const void* y, const void* e, void* out, int32_t B, int32_
                       int32_t Cp, int32_t t_mid, int32_t dtype, void* stream);
 int c3d_enhance_bwd_mask(const void* dout, const void* e, void* de, int32_t B, int32_t T, int64_t HW,
                          int32_t Cp, int32_t t_mid, int32_t dtype, void* stream);
+/* t_pre and t_post both outside [0, T): no frame matches, dy = dout.  One inside and one outside: C3D_E_BADARG. */
 int c3d_enhance_bwd_apply(const void* dout, const void* y, const void* dd, void* dy, int32_t B, int32_t T,
                           int64_t HW, int32_t Cp, int32_t t_pre, int32_t t_post, int32_t dtype,
                           void* stream);

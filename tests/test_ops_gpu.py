@@ -1116,10 +1116,12 @@ def test_dw_fwd_with_folded_bn_finalize_is_bit_identical(dtype, C, T, stride, sh
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("C,mode,M", [(96, 1, 3000), (48, 2, 777), (24, 3, 5000), (192, 1, 640)])
+@pytest.mark.parametrize("C,mode,M", [(96, 1, 3000), (48, 2, 777), (24, 3, 5000), (192, 1, 640), (54, 2, 1024 * 36 + 3000)])
 def test_block_out_fwd_with_folded_bn_finalize_is_bit_identical(dtype, C, mode, M):
     """c3d_block_out_fwd_fin against c3d_bn_finalize (x1 or x2) + c3d_block_out_fwd: identical y, vectors and buffers
-    (modes: 1 identity shortcut, 2 shortcut conv + BatchNorm, 3 shortcut conv without BatchNorm)."""
+    (modes: 1 identity shortcut, 2 shortcut conv + BatchNorm, 3 shortcut conv without BatchNorm).  The last case (C = 54:
+    36 rows per workgroup) walks past the folded launch's cap of 1024 workgroups; the unfolded leg is tied to float64 by
+    tests/test_elementwise_gpu.py."""
     _need_gpu()
     from change3d_amd import ops
     Cp = ops.cpad(C)

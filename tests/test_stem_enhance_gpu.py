@@ -5,7 +5,8 @@ The fused kernels only move where values are computed, so the yardstick is the s
   * op level   : d, out and g bit-identical to block_out_fwd -> frame_absdiff -> pw_gemm -> enhance_apply and
                  enhance_bwd_mask -> pw_gemm -> enhance_bwd_apply -> block_out_bwd; the BatchNorm-backward sums of both
                  against a float64 torch sum over the same stored tensors (the fused error at most twice the existing
-                 kernel's, floor 1e-13 relative: the existing kernel's cross-workgroup f64 atomics are order dependent)
+                 kernel's, floor 1e-13 relative: the existing kernel's cross-workgroup f64 atomics are order dependent), and
+                 each within the derived absolute bound of tests/test_elementwise_gpu.py
   * model level: Trainer.update_bcd forward + backward, switch on against off: output and loss equal, every parameter
                  gradient within twice the off-vs-off spread of the same test; SCD (T = 5) runs through the new kernels
   * CPU        : which ops each setting of the switch calls, in order (no launch is made)
@@ -112,6 +113,17 @@ def test_stem_enhance_kernels_equal_the_separate_launches(dtype, T, B, HW):
           f"fused {(err1 / ref.abs()).max().item():.3e}  max |fused - existing| / |ref| "
           f"{((ds1 - ds0).abs() / ref.abs()).max().item():.3e}")
     assert bool((err1 <= lim).all()), (worst, err1[worst].item(), err0[worst].item(), ref[worst].item())
+
+    # ---- and each against the derived absolute bound of tests/test_elementwise_gpu.py (both launches share one kernel body, so
+    # "no worse than the other" alone passes a shared bug): a thread adds n = chain_steps(M, C) terms in f32, three roundings
+    # per term, everything after it in f64 -> (n + 3) u of the magnitude sums, n <= 8 at these shapes
+    import elementwise_reference as E
+    assert E.chain_steps(M, C) <= 8
+    mean, rstd = mr[:C].double(), mr[C:].double()
+    mag = torch.cat([gd.abs().sum(0), (gd.abs() * (u.double().reshape(-1, C).abs() + mean.abs()) * rstd.abs()).sum(0)])
+    r0, r1 = E.sums_ratio(ds0, ref, mag, E.sums_eps(8)), E.sums_ratio(ds1, ref, mag, E.sums_eps(8))
+    print(f"dsums error / derived bound: existing {r0:.3f} fused {r1:.3f}")
+    assert r0 <= 1.0 and r1 <= 1.0, (r0, r1)
 
 
 @gpu
