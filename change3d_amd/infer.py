@@ -34,6 +34,10 @@ label map of the scene's size (`c3d_rings_fill`, centre sampling, even-odd per i
 `c3d_objects_match` at the lowest threshold, 0.5 -- per object what the simplification cost: its partner, intersection and union
 in pixels.  Enqueued behind the simplification, before the same one synchronisation.
 
+`predict(..., outlines=True, shapes=True)` appends a `SceneShapes` last: the convex hull and the minimum-area rectangle of
+every object (`c3d_rings_hull`, integer rule of include/change3d_hip.h), taken from the raw rings whatever else was asked
+for, enqueued before the same one synchronisation.
+
 `SceneInferencer(..., tta="hflip" | "flips" | "d4" | codes)` is test-time augmentation: every tile is predicted under a set of
 the eight flips and rotations of the square, each view is undone on the output and the views are averaged before the
 stitch.  A view code `v` in 0..7 transposes the tile if `v & 4`, then reverses its rows if `v & 2`, then its columns if
@@ -74,6 +78,9 @@ SceneOutlines = namedtuple("SceneOutlines", "rings vertices counts")
 # the raw objects): labels, table [max_objects, 8] and counts [2] as in SceneObjects; info i32 [4] = (status, ring rows used, K,
 # 0); match = (match_raw i32 [max_objects, 4], match_filled i32 [max_objects, 4], conf, counts i64 [6], sum_iou f64 [1])
 SceneFill = namedtuple("SceneFill", "labels table counts info match")
+# `predict(..., shapes=True)`: the convex hull and the minimum-area rectangle of every object (`ops.rings_hull`): hulls i32
+# [max_objects, 8], vertices i32 [., 2], rects i64 [max_objects, 8], counts i32 [5]
+SceneShapes = namedtuple("SceneShapes", "hulls vertices rects counts")
 TASKS = ("bcd", "scd", "bda")
 WINDOWS = ("hann", "flat")
 VIEW_SETS = {"none": (0,), "hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
@@ -204,6 +211,9 @@ class SceneInferencer:
     with `.info` = (status, seeds, rounds used, 0) that outlines, simplification, votes and `ObjectEvaluator` take unchanged.
     `split_rounds` (default 32) limits the growth rounds: `info[0] & SPLIT_ST_NOT_CONVERGED` says that it was too small.  With
     `split=None` the launches are the ones without the argument.
+    `shapes=True` (with `outlines=True`) appends a `SceneShapes` last: the convex hull and the minimum-area rectangle of every
+    object (`ops.rings_hull`), taken from the raw rings -- also with `simplify=tol` -- and from the pieces with `split=R`.  Its
+    `hulls` rows are a ring table that `ops.rings_fill` takes.  With `shapes=False` the launches are the ones without it.
     `tta` is None, a name of `VIEW_SETS` ("none", "hflip", "flips", "d4") or a sequence of view codes: the tiles are predicted
     under those `nv` views and averaged with the views undone (module docstring).  `batch` stays the number of model inputs
     per forward, so a forward takes `batch // nv` tiles; a transposing view (codes 4..7) needs a square model input.  With
@@ -259,9 +269,11 @@ class SceneInferencer:
 
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
-                max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False):
+                max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False, shapes=False):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
+        if shapes and not outlines:
+            raise ValueError("shapes=True takes the hulls and rectangles of the traced rings: it needs outlines=True")
         if split is None and split_rounds is not None:
             raise ValueError("split_rounds limits the growth rounds of split=R: it needs split")
         if split is not None:
@@ -352,11 +364,14 @@ class SceneInferencer:
             if outlines:
                 result += (SceneOutlines(*ops.scene_outlines(labels, counts, connectivity=connectivity, max_objects=max_objects,
                                                              max_rings=max_rings, max_vertices=max_vertices)),)
+                raw = result[-1]
                 if simplify is not None:
                     result += (SceneOutlines(*ops.outlines_simplify(*result[-1], simplify)),)
                     if simplify_check:
                         f_labels, f_table, f_counts, _, _, f_info = ops.rings_fill(*result[-1], Hs, Ws, max_objects=max_objects)
                         match = ops.objects_match(labels, table, counts, f_labels, f_table, f_counts, n_cls=1, iou_thr=0.5)
                         result += (SceneFill(f_labels, f_table, f_counts, f_info, match),)
+                if shapes:                              # of the raw rings, whatever else was asked for
+                    result += (SceneShapes(*ops.rings_hull(*raw, max_objects=max_objects)),)
         torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
         return result

@@ -1023,6 +1023,66 @@ def rings_fill(rings, vertices, counts, Hs, Ws, frac_bits=0, id_cls=None, max_ob
     return labels, table, counts_obj, mask, cls_map, info
 
 
+def rings_hull_limits():
+    """(most points of an id that one wave keeps in registers, most points of an id whose candidates one workgroup is sure
+    to keep in LDS); host only."""
+    out = (C.c_int32 * 2)()
+    L.lib().c3d_rings_hull_limits(out)
+    return int(out[0]), int(out[1])
+
+
+def rings_hull(rings, vertices, counts, max_objects=65536, max_hull_vertices=None, ws=None):
+    """c3d_rings_hull on the `rings` i32 [max_rings, 8], `vertices` i32 [max_vertices, 2] and `counts` i32 [5] of
+    `scene_outlines` (or any table of that shape with integer pixel corners): the strictly convex hull and the minimum-area
+    rectangle of every id, by the integer rule of include/change3d_hip.h.  Returns `(hulls i32 [max_objects, 8] = (id, start,
+    m, area2, 0, x, y, n_points), hull_vertices i32 [max_hull_vertices, 2], rects i64 [max_objects, 8] = (k, L, t_min, t_max,
+    c_max, j_tmin, j_tmax, j_cmax), counts_out i32 [5] = (ids with points, K, hull vertices found, written, status))`, all on
+    the device; nothing is read back.  `max_hull_vertices` defaults to `vertices.shape[0]`, which never truncates a table
+    whose rows share no vertices.  Vertex rows past counts_out[3] are not initialised."""
+    for t in (rings, vertices, counts):
+        require_gpu(t, "rings_hull input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    max_rings, max_vertices, max_objects = int(rings.shape[0]), int(vertices.shape[0]), int(max_objects)
+    max_hull_vertices = max_vertices if max_hull_vertices is None else int(max_hull_vertices)
+    nbytes = L.lib().c3d_rings_hull_ws_bytes(max_rings, max_vertices, max_objects)
+    if nbytes < 0 or max_hull_vertices < 1:
+        raise L.Change3DHipError(f"c3d_rings_hull refuses max_rings = {max_rings}, max_vertices = {max_vertices}, max_objects = "
+                                 f"{max_objects}, max_hull_vertices = {max_hull_vertices} (code {nbytes if nbytes < 0 else -1})")
+    dev = rings.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    hulls = torch.empty((max_objects, 8), dtype=torch.int32, device=dev)
+    hull_vertices = torch.empty((max_hull_vertices, 2), dtype=torch.int32, device=dev)
+    rects = torch.empty((max_objects, 8), dtype=torch.int64, device=dev)
+    out = torch.empty(5, dtype=torch.int32, device=dev)
+    _launch("c3d_rings_hull", (max_rings + max_vertices) * 32 + max_objects * 120, L.lib().c3d_rings_hull, _p(rings), _p(vertices),
+            _p(counts), max_rings, max_vertices, max_objects, max_hull_vertices, _p(hulls), _p(hull_vertices), _p(rects), _p(out),
+            _p(ws), _stream())
+    return hulls, hull_vertices, rects, out
+
+
+def rect_corners(P, d, rect_row):
+    """The rectangle of a `rings_hull` rects row on the hull edge that starts at `P` = (x, y) and runs along `d` = (dx, dy):
+    `(corners float64 [4, 2], long, short, angle)`.  The corners are P + d t/L (+ n c_max/L) for t = t_min, t_max with n =
+    (-d.y, d.x), in the order (t_min, 0), (t_max, 0), (t_max, c_max), (t_min, c_max); long and short are the side lengths in
+    pixels; angle is the direction of the long side in image coordinates (y down), in degrees in [0, 180), the side along d
+    where the two are equal.  Host only."""
+    import numpy as np
+    k, Lq, t0, t1, c = (int(v) for v in list(rect_row)[:5])
+    dx, dy = int(d[0]), int(d[1])
+    if k < 0 or Lq <= 0 or dx * dx + dy * dy != Lq:
+        raise ValueError("rect_corners needs a rects row with k >= 0 and the edge vector it was made on")
+    x0, y0, nx, ny = float(P[0]), float(P[1]), -dy, dx
+    corners = np.array([[x0 + (dx * t + nx * s) / Lq, y0 + (dy * t + ny * s) / Lq] for t, s in ((t0, 0), (t1, 0), (t1, c), (t0, c))],
+                       dtype=np.float64)
+    along, across = (t1 - t0) / math.sqrt(Lq), c / math.sqrt(Lq)
+    ax, ay = (dx, dy) if t1 - t0 >= c else (nx, ny)        # compared as integers: both share the divisor
+    angle = math.degrees(math.atan2(ay, ax)) % 180.0
+    return corners, max(along, across), min(along, across), angle
+
+
 def scene_edt_tile():
     """(rows of a chunk of c3d_scene_edt's column pass, pixels of a row per workgroup of its row pass); host only."""
     out = (C.c_int32 * 2)()

@@ -33,6 +33,12 @@ objects kept vanished iou_mean iou_min`: `kept` counts the objects whose partner
 pixel after the fill.  `--simplify_min_iou F` implies the check and leaves every object whose IoU is not above F on its raw
 vertices, in every ring.
 
+`--shapes` (with `--polygons`) describes every object's shape, on the device (`c3d_rings_hull` on the raw rings): each feature
+gains `hull_area`, `hull_vertices`, `solidity` = area / hull area, `rect_area`, `rect_long`, `rect_short`, `rect_angle` (the long
+side's direction, degrees in [0, 180), y down) and `rectangularity` = area / area of the minimum-area rectangle; the hulls and
+the rectangles go to `objects/<name>.hulls.geojson` and `objects/<name>.rects.geojson`, and the run ends with a line `shapes:
+objects = .. solidity_mean = .. rectangularity_mean = ..`.
+
 `--label_polygons FILE` (BCD, BDA) takes the ground truth as polygons instead of a label raster: a GeoJSON `FeatureCollection`
 in pixel coordinates, such as `--polygons` writes, or an xBD label JSON (change3d_amd/vector_labels.py); with `--file_root` it
 names a directory holding `<name>.json` or `<name>.geojson`.  The polygons are filled on the device (`c3d_rings_fill`) and
@@ -149,7 +155,7 @@ def save_objects(path, objects):
     return found, rows
 
 
-def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=None):
+def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=None, extra=None):
     """(FeatureCollection dict, ids left out) from host arrays: `table` [rows, 8] of the objects, `rings` [ring rows, 8] and
     `vertices` [vertices written, 2] of their outlines.  An object is complete iff it has one ring of positive area, every
     ring of it has its vertices (start >= 0) and the signed areas add up to the table's area -- a hole ring cut off by
@@ -159,7 +165,8 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
     has no vertices, in which case the ring keeps its raw vertices -- and every feature gets the counts `vertices_raw` and
     `vertices`.  Completeness is judged on the raw rings either way.
     `iou` [rows] (with `simplified`): the IoU of every object with its simplified polygon filled back into pixels; each feature
-    gets it as a property, and with `min_iou` an object whose IoU is not above it keeps its raw vertices in every ring."""
+    gets it as a property, and with `min_iou` an object whose IoU is not above it keeps its raw vertices in every ring.
+    `extra`: id -> further properties of that object's feature (`--shapes`)."""
     table, rings, vertices = np.asarray(table), np.asarray(rings), np.asarray(vertices)
     if simplified is not None:
         rings_s, vertices_s = np.asarray(simplified[0]).tolist(), np.asarray(simplified[1])
@@ -189,6 +196,8 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
             properties.update(vertices_raw=n_raw, vertices=n_out)
             if iou is not None:
                 properties.update(iou=round(float(iou[k]), 4))
+        if extra is not None:
+            properties.update(extra.get(k + 1, {}))
         features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords}, "properties": properties})
     return {"type": "FeatureCollection", "features": features}, skipped
 
@@ -207,7 +216,7 @@ def simplify_ious(objects, fill):
     return iou, kept, vanished
 
 
-def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=None):
+def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=None, extra=None):
     """objects/<name>.geojson; the one read-back of the rings (`simplified`: the second `SceneOutlines` of
     `predict(..., simplify=tol)`, read back with them; `iou`, `min_iou`: see `polygons_geojson`).  Returns the ids that were
     left out."""
@@ -216,13 +225,54 @@ def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=No
     if simplified is not None:
         simplified = (simplified.rings[:ring_rows].cpu().numpy(), simplified.vertices[:int(simplified.counts[3])].cpu().numpy())
     doc, skipped = polygons_geojson(objects.table[:rows].cpu().numpy(), outlines.rings[:ring_rows].cpu().numpy(),
-                                    outlines.vertices[:written].cpu().numpy(), simplified, iou, min_iou)
+                                    outlines.vertices[:written].cpu().numpy(), simplified, iou, min_iou, extra)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
         json.dump(doc, f)
     if skipped:
         print(f"{path}: {len(skipped)} of {rows} objects left out, their rings were cut off (status {int(outlines.counts[4])})")
     return skipped
+
+
+def object_shapes(name, objects, shapes):
+    """The read-back of a `SceneShapes`: (id -> shape properties, id -> closed hull ring, id -> closed rectangle ring) for the
+    rows of the object table.  hull_area and rect_area are in square pixels, rect_long and rect_short in pixels, rect_angle
+    is the direction of the long side in degrees in [0, 180), image coordinates; solidity and rectangularity divide the
+    table's pixel area by them and are at most 1, because the pixels lie inside the hull of their corners."""
+    status = int(shapes.counts[4])
+    if status & (L.HULL_ST_BAD_ROW | L.HULL_ST_TRUNCATED):
+        raise SystemExit(f"{name}: --shapes: c3d_rings_hull status {status}")
+    rows, written = min(int(objects.counts[1]), int(shapes.counts[1])), int(shapes.counts[3])
+    areas = objects.table[:rows, 0].cpu().tolist()
+    hulls, rects = shapes.hulls[:rows].cpu().tolist(), shapes.rects[:rows].cpu().tolist()
+    vertices = shapes.vertices[:written].cpu().tolist()
+    props, hull_rings, rect_rings = {}, {}, {}
+    for k, (h, r) in enumerate(zip(hulls, rects)):
+        if h[1] < 0 or h[2] < 3 or r[0] < 0:             # an id without rings: its polygon is left out as well
+            continue
+        ring = vertices[h[1]:h[1] + h[2]]
+        P, Q = ring[r[0]], ring[(r[0] + 1) % h[2]]
+        corners, long_side, short_side, angle = ops.rect_corners(P, (Q[0] - P[0], Q[1] - P[1]), r)
+        hull_area, rect_area = h[3] / 2, (r[3] - r[2]) * r[4] / r[1]
+        props[k + 1] = dict(hull_area=hull_area, hull_vertices=h[2], solidity=round(areas[k] / hull_area, 4),
+                            rect_area=round(rect_area, 4), rect_long=round(long_side, 4), rect_short=round(short_side, 4),
+                            rect_angle=round(angle, 4), rectangularity=round(areas[k] / rect_area, 4))
+        hull_rings[k + 1] = ring + ring[:1]
+        rect_rings[k + 1] = corners.tolist() + corners[:1].tolist()
+    return props, hull_rings, rect_rings
+
+
+def save_shapes(path, objects, rings_by_id, skipped):
+    """objects/<name>.hulls.geojson or .rects.geojson: one `Polygon` per object that has a feature in objects/<name>.geojson,
+    with the CSV's id, area, cls and score."""
+    table = objects.table[:int(objects.counts[1])].cpu().tolist()
+    features = []
+    for k, (area, _, _, _, _, cls, _, score_q) in enumerate(table):
+        if k + 1 in rings_by_id and k + 1 not in skipped:
+            features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": [rings_by_id[k + 1]]},
+                             "properties": {"id": k + 1, "area": area, "cls": cls, "score": round(score_q / 65535, 4)}})
+    with open(path, "w") as f:
+        json.dump({"type": "FeatureCollection", "features": features}, f)
 
 
 LABEL_FRAC_BITS = 4                                       # polygon labels are rounded to 1/16 pixel
@@ -345,6 +395,8 @@ def parse_args(argv=None):
         parser.error("--polygons outlines the objects of the map: it needs --objects")
     if args.simplify is not None and not args.polygons:
         parser.error("--simplify simplifies the polygons: it needs --polygons")
+    if args.shapes and not args.polygons:
+        parser.error("--shapes describes the polygons: it needs --polygons")
     if args.simplify_min_iou is not None:
         args.simplify_check = True
     if args.simplify_check and args.simplify is None:
@@ -401,14 +453,19 @@ def main(argv=None):
     split = {} if args.split_objects is None else dict(split=args.split_objects, split_rounds=args.split_rounds)
     if args.simplify_check:
         split["simplify_check"] = True
+    if args.shapes:
+        split["shapes"] = True
     drift = dict(objects=0, kept=0, vanished=0, iou_sum=0.0, iou_min=1.0)   # --simplify_check over all scenes
+    shape_sums = dict(objects=0, solidity=0.0, rectangularity=0.0)          # --shapes over all scenes
     for name, img, label in scenes(args):
         scene = torch.from_numpy(np.ascontiguousarray(img))
         gt = polygon_labels(args, name, img.shape[0], img.shape[1], device) if args.label_polygons else None
         if args.polygons:                 # the outlines come last; every `out[-1]` below is the objects
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, outlines=True,
                               max_rings=args.max_rings, max_vertices=args.max_vertices, simplify=args.simplify, **split)
-            simplified, iou = None, None
+            simplified, iou, shapes = None, None, None
+            if args.shapes:               # appended last
+                out, shapes = out[:-1], out[-1]
             if args.simplify_check:
                 out, fill = out[:-1], out[-1]
                 iou, kept, vanished = simplify_ious(out[-3], fill)
@@ -417,8 +474,20 @@ def main(argv=None):
             if args.simplify is not None:
                 out, simplified = out[:-1], out[-1]
             check_split(name, out[-2])
-            cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified, iou,
-                                         args.simplify_min_iou))
+            if shapes is None:
+                cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified,
+                                             iou, args.simplify_min_iou))
+            else:
+                props, hull_rings, rect_rings = object_shapes(name, out[-2], shapes)
+                skipped = save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified, iou,
+                                        args.simplify_min_iou, props)
+                cut_off += len(skipped)
+                save_shapes(os.path.join(args.out_dir, "objects", name + ".hulls.geojson"), out[-2], hull_rings, set(skipped))
+                save_shapes(os.path.join(args.out_dir, "objects", name + ".rects.geojson"), out[-2], rect_rings, set(skipped))
+                kept = [v for k, v in props.items() if k not in set(skipped)]
+                shape_sums = dict(objects=shape_sums["objects"] + len(kept),
+                                  solidity=shape_sums["solidity"] + sum(v["solidity"] for v in kept),
+                                  rectangularity=shape_sums["rectangularity"] + sum(v["rectangularity"] for v in kept))
             out = out[:-1]
         elif args.objects:
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, **split)
@@ -475,6 +544,10 @@ def main(argv=None):
     if args.simplify_check:
         print(f"simplify: tol = {args.simplify:g} objects = {drift['objects']} kept = {drift['kept']} vanished = {drift['vanished']} "
               f"iou_mean = {drift['iou_sum'] / max(drift['objects'], 1):.4f} iou_min = {drift['iou_min'] if drift['objects'] else 0.0:.4f}")
+    if args.shapes:
+        n_shapes = max(shape_sums["objects"], 1)
+        print(f"shapes: objects = {shape_sums['objects']} solidity_mean = {shape_sums['solidity'] / n_shapes:.4f} "
+              f"rectangularity_mean = {shape_sums['rectangularity'] / n_shapes:.4f}")
     if cut_off:
         raise SystemExit(f"{cut_off} objects have no polygon: their rings did not fit; raise --max_rings / --max_vertices")
     if not scored:
@@ -530,6 +603,9 @@ def build_parser():
                    "and join them to the raw objects: an `iou` per feature and a closing `simplify:` line")
     p.add_argument("--simplify_min_iou", type=unit_interval, default=None, metavar="F", help="--simplify: implies --simplify_check; an "
                    "object whose IoU with its simplified polygon is not above F, in [0, 1], keeps its raw vertices")
+    p.add_argument("--shapes", action="store_true", help="--polygons: also the convex hull and the minimum-area rectangle of every "
+                   "object, on the device (c3d_rings_hull): shape properties on every feature, objects/<name>.hulls.geojson and "
+                   "objects/<name>.rects.geojson, and a closing `shapes:` line")
     p.add_argument("--label_polygons", default="", metavar="FILE", help="BCD, BDA: the ground truth as polygons, a GeoJSON FeatureCollection "
                    "in pixel coordinates or an xBD label JSON, instead of label rasters; with --file_root a directory of <name>.json / "
                    "<name>.geojson.  Filled on the device (c3d_rings_fill); one ground-truth object per feature")

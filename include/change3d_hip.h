@@ -802,6 +802,63 @@ int c3d_rings_fill(const int32_t* rings, const int32_t* vertices, const int32_t*
                    int32_t frac_bits, const uint8_t* id_cls, int32_t max_objects, int32_t Hs, int32_t Ws, int32_t* labels,
                    int32_t* table, int32_t* counts_obj, uint8_t* mask, uint8_t* cls_map, int32_t* info, void* ws, void* stream);
 
+/* Convex hulls and minimum-area rectangles (csrc/scene_hull.hip): the ring table and vertex list of c3d_scene_outlines, or any
+ * table of that shape with integer pixel corners (frac_bits 0), turned into the strictly convex hull and the oriented bounding
+ * rectangle of every id while they stay in HBM.  Integer arithmetic only: floating point appears in no decision, every output
+ * is exact and two runs agree bit for bit.  One memset and 9 launches on `stream`, nothing is read back by the host, no
+ * workgroup waits for another, every loop is capped, and no workspace word is read before the call wrote it.  The rule:
+ *   rows used   a row r < clamp(counts[1], 0, max_rings) with (id, start, n) = columns 0..2 (the others are ignored) is used iff
+ *               start >= 0, n >= 0, start + n <= clamp(counts[3], 0, max_vertices), 1 <= id <= max_objects and every
+ *               coordinate of the ring lies in [0, 16384].  A row with start < 0 is skipped silently; any other skipped row
+ *               sets C3D_HULL_ST_BAD_ROW.  Nothing is read or written out of range.  K = the largest id of a used row
+ *   points      the points of object `id` are all vertices of all used rows with that id: holes count and so do duplicates,
+ *               this is a point set, not a polygon.  The rings of an id need not be contiguous in the table
+ *   hull        the vertices of the strictly convex hull of the points: no vertex is collinear between its neighbours, a
+ *               repeated point appears once.  With cross(a, b, c) = (b.x-a.x)(c.y-a.y) - (b.y-a.y)(c.x-a.x) it is stored as
+ *               h[0 .. m-1]: h[0] = the point with the smallest (y, x); h[k+1] = the point q != h[k] for which
+ *               cross(h[k], q, r) >= 0 holds for every point r, the farthest such q where several are collinear; the walk
+ *               ends when it returns to h[0].  This is the direction the outlines are traced in (top goes +x, then +y):
+ *               cross(h[k-1], h[k], h[k+1]) > 0 and the shoelace sum is positive.  m = 1 for a single point, 2 for collinear
+ *               points
+ *   rectangle   for m >= 3 and the hull edge k from P = h[k] to h[(k+1) % m]: d = the edge vector, L = |d|^2,
+ *               t_j = (h[j]-P).d, c_j = cross(P, P+d, h[j]) >= 0.  The rectangle on that edge has the area
+ *               (t_max - t_min) * c_max / L; the edge with the smallest area is chosen, the smallest k on ties.  Areas are
+ *               compared exactly by cross-multiplication: t_max - t_min <= 2^30, c_max <= 2^29, L <= 2^29, so the products
+ *               stay under 2^88 and the comparison is one of 128-bit integers.  The rectangle's corners are
+ *               P + d t/L (+ n c_max/L) for t = t_min, t_max and n = (-d.y, d.x): rational, left to the caller
+ * Inputs (device): rings i32 [max_rings][8], vertices i32 [max_vertices][2] (8-byte aligned), counts i32 [5].
+ * Outputs:
+ *   hulls          i32 [max_objects][8], 16-byte aligned.  Row id-1 for id <= K = (id, start, m, area2, 0, x, y, n_points):
+ *                  start = the offset into hull_vertices = the m of all smaller ids; area2 = the shoelace sum of the hull,
+ *                  twice its area, below 2^30; (x, y) = h[0]; n_points = the vertex rows of the id's used rings (INT32_MAX
+ *                  where rows that share vertices add up to more).  An id without points gets (id, -1, 0, 0, 0, 0, 0, 0).
+ *                  Rows past K are 0.  Columns 0..2 make this a ring table that c3d_rings_fill and c3d_outlines_simplify
+ *                  accept as it is
+ *   hull_vertices  i32 [max_hull_vertices][2], 8-byte aligned: the hulls, contiguous, in id order.  Rows past counts_out[3]
+ *                  are left as they were
+ *   rects          i64 [max_objects][8].  Row id-1 = (k, L, t_min, t_max, c_max, j_tmin, j_tmax, j_cmax) for the chosen edge,
+ *                  the j being the smallest hull indices that attain the extremes; (-1, 0, ...) for m < 3.  Rows past K are 0
+ *   counts_out     i32 [5] = (ids with points, K, hull vertices found, hull vertices written, status); status = counts[4] as
+ *                  it came, with the bits below added
+ *   ws             c3d_rings_hull_ws_bytes(max_rings, max_vertices, max_objects) bytes (5 per ring row, 4 per vertex row, 28
+ *                  per id), 256-byte aligned; a dirty one gives the same result
+ * Truncation is prefix-shaped as in c3d_scene_outlines: an id whose hull does not fit below max_hull_vertices gets start = -1
+ * and none of its vertices is written, and so does every later id; the other columns and the rects rows stay correct;
+ * C3D_HULL_ST_TRUNCATED is set.  max_hull_vertices >= the vertices written by the outlines call never truncates.
+ * Input status C3D_OUTLINE_ST_BAD_COUNTS: all rows 0, counts_out = (0, 0, 0, 0, C3D_OUTLINE_ST_BAD_COUNTS).
+ * Refused before anything is enqueued (C3D_E_BADARG): a NULL pointer, max_rings, max_vertices, max_objects or
+ * max_hull_vertices < 1.
+ * c3d_rings_hull_limits: out[0] = the most points of an id that one wave keeps in registers, out[1] = the most points of an
+ * id whose candidate set one workgroup is sure to keep in LDS; a larger id whose candidates (the points not strictly inside the
+ * octagon of its eight directional extremes) do not fit is walked in HBM.  The results do not depend on the tier.  Host only.  */
+#define C3D_HULL_ST_BAD_ROW 64
+#define C3D_HULL_ST_TRUNCATED 128
+void c3d_rings_hull_limits(int32_t out[2]);
+int64_t c3d_rings_hull_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_objects);   /* < 0: C3D_E_* */
+int c3d_rings_hull(const int32_t* rings, const int32_t* vertices, const int32_t* counts, int32_t max_rings,
+                   int32_t max_vertices, int32_t max_objects, int32_t max_hull_vertices, int32_t* hulls,
+                   int32_t* hull_vertices, int64_t* rects, int32_t* counts_out, void* ws, void* stream);
+
 /* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
  * in HBM.  The rule:
  *   sites       the pixels with mask == 0; with C3D_EDT_INVERT (bit 0 of flags) the pixels with mask != 0
