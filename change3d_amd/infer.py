@@ -38,6 +38,11 @@ in pixels.  Enqueued behind the simplification, before the same one synchronisat
 every object (`c3d_rings_hull`, integer rule of include/change3d_hip.h), taken from the raw rings whatever else was asked
 for, enqueued before the same one synchronisation.
 
+`predict(..., outlines=True, simplify=tol, regularize=True)` appends a `SceneRegular` after those: the simplified rings with
+every edge parallel or perpendicular to the chosen rectangle edge of their object (`c3d_rings_regularize` on the hulls of the
+raw rings; the hull call is shared with `shapes=True`), in sixteenths of a pixel.  `regularize_check=True` appends a `SceneFill`
+of those rings after it, as `simplify_check` does for the simplified ones.  Still the same one synchronisation.
+
 `SceneInferencer(..., tta="hflip" | "flips" | "d4" | codes)` is test-time augmentation: every tile is predicted under a set of
 the eight flips and rotations of the square, each view is undone on the output and the views are averaged before the
 stitch.  A view code `v` in 0..7 transposes the tile if `v & 4`, then reverses its rows if `v & 2`, then its columns if
@@ -81,6 +86,11 @@ SceneFill = namedtuple("SceneFill", "labels table counts info match")
 # `predict(..., shapes=True)`: the convex hull and the minimum-area rectangle of every object (`ops.rings_hull`): hulls i32
 # [max_objects, 8], vertices i32 [., 2], rects i64 [max_objects, 8], counts i32 [5]
 SceneShapes = namedtuple("SceneShapes", "hulls vertices rects counts")
+# `predict(..., regularize=True)`: the simplified rings squared to the axes of their object's minimum-area rectangle
+# (`ops.rings_regularize`): rings i32 [max_rings, 8] = (id, start, n, regularised?, perimeter, x, y, simplified n), vertices in
+# units of 2^-REGULAR_FRAC_BITS pixel, counts i32 [5]
+SceneRegular = namedtuple("SceneRegular", "rings vertices counts")
+REGULAR_FRAC_BITS = 4
 TASKS = ("bcd", "scd", "bda")
 WINDOWS = ("hann", "flat")
 VIEW_SETS = {"none": (0,), "hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
@@ -214,6 +224,11 @@ class SceneInferencer:
     `shapes=True` (with `outlines=True`) appends a `SceneShapes` last: the convex hull and the minimum-area rectangle of every
     object (`ops.rings_hull`), taken from the raw rings -- also with `simplify=tol` -- and from the pieces with `split=R`.  Its
     `hulls` rows are a ring table that `ops.rings_fill` takes.  With `shapes=False` the launches are the ones without it.
+    `regularize=True` (with `simplify=tol`) appends a `SceneRegular` after all of those: the simplified rings with every edge
+    parallel or perpendicular to the chosen rectangle edge of their object (`ops.rings_regularize` on the hulls of the raw
+    rings, the one `ops.rings_hull` call that `shapes=True` makes, shared when both are asked for), coordinates in sixteenths of
+    a pixel.  `regularize_check=True` appends a `SceneFill` after it: those rings filled at 1/16 px and matched to the raw
+    objects, as `simplify_check` does for the simplified ones.  With `regularize=False` the launches are the ones without it.
     `tta` is None, a name of `VIEW_SETS` ("none", "hflip", "flips", "d4") or a sequence of view codes: the tiles are predicted
     under those `nv` views and averaged with the views undone (module docstring).  `batch` stays the number of model inputs
     per forward, so a forward takes `batch // nv` tiles; a transposing view (codes 4..7) needs a square model input.  With
@@ -269,7 +284,8 @@ class SceneInferencer:
 
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
-                max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False, shapes=False):
+                max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False, shapes=False,
+                regularize=False, regularize_check=False):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
         if shapes and not outlines:
@@ -289,6 +305,10 @@ class SceneInferencer:
             ops.simplify_tol2_q(simplify)               # raises outside [0, 1024] before anything is enqueued
         if simplify_check and simplify is None:
             raise ValueError("simplify_check=True measures what simplify=tol cost: it needs simplify")
+        if regularize and simplify is None:
+            raise ValueError("regularize=True squares the simplified rings: it needs simplify")
+        if regularize_check and not regularize:
+            raise ValueError("regularize_check=True measures what regularize=True cost: it needs regularize")
         if any(v is not None and int(v) < 1 for v in (max_rings, max_vertices)):
             raise ValueError(f"max_rings and max_vertices must be positive, got {max_rings} and {max_vertices}")
         dev = self._device()
@@ -367,11 +387,20 @@ class SceneInferencer:
                 raw = result[-1]
                 if simplify is not None:
                     result += (SceneOutlines(*ops.outlines_simplify(*result[-1], simplify)),)
+                    simple = result[-1]
                     if simplify_check:
                         f_labels, f_table, f_counts, _, _, f_info = ops.rings_fill(*result[-1], Hs, Ws, max_objects=max_objects)
                         match = ops.objects_match(labels, table, counts, f_labels, f_table, f_counts, n_cls=1, iou_thr=0.5)
                         result += (SceneFill(f_labels, f_table, f_counts, f_info, match),)
+                hull = ops.rings_hull(*raw, max_objects=max_objects) if shapes or regularize else None   # one call for both
                 if shapes:                              # of the raw rings, whatever else was asked for
-                    result += (SceneShapes(*ops.rings_hull(*raw, max_objects=max_objects)),)
+                    result += (SceneShapes(*hull),)
+                if regularize:                          # the simplified rings along the rectangle edge of the raw object
+                    result += (SceneRegular(*ops.rings_regularize(*simple, *hull, frac_bits=REGULAR_FRAC_BITS)),)
+                    if regularize_check:
+                        f_labels, f_table, f_counts, _, _, f_info = ops.rings_fill(*result[-1], Hs, Ws, frac_bits=REGULAR_FRAC_BITS,
+                                                                                   max_objects=max_objects)
+                        match = ops.objects_match(labels, table, counts, f_labels, f_table, f_counts, n_cls=1, iou_thr=0.5)
+                        result += (SceneFill(f_labels, f_table, f_counts, f_info, match),)
         torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
         return result

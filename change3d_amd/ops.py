@@ -1063,6 +1063,50 @@ def rings_hull(rings, vertices, counts, max_objects=65536, max_hull_vertices=Non
     return hulls, hull_vertices, rects, out
 
 
+def rings_regularize_limits():
+    """(most edges of a ring that one wave regularises, most of a ring whose state one workgroup keeps in LDS); host only."""
+    out = (C.c_int32 * 2)()
+    L.lib().c3d_rings_regularize_limits(out)
+    return int(out[0]), int(out[1])
+
+
+def rings_regularize(rings, vertices, counts, hulls, hull_vertices, rects, hull_counts, frac_bits=4, ws=None):
+    """c3d_rings_regularize on the `rings` i32 [max_rings, 8], `vertices` i32 [max_vertices, 2] and `counts` i32 [5] of
+    `outlines_simplify` (or any table of that shape with integer pixel corners) and the four outputs of `rings_hull` for the
+    same ids: every ring squared to the axes of its id's minimum-area rectangle by the integer rule of
+    include/change3d_hip.h.  Returns `(rings_out i32 [max_rings, 8] = (id, start', n', flag, perimeter, x, y, n), vertices_out
+    i32 [max_vertices, 2] in units of 2^-frac_bits pixel, counts_out i32 [5] = (rings found, rows written, vertices out,
+    vertices out, status))`, all on the device; nothing is read back.  `rings_fill(..., frac_bits=frac_bits)` takes them as
+    they are.  Vertex rows past counts_out[3] are not initialised."""
+    for t in (rings, vertices, counts, hulls, hull_vertices, hull_counts):
+        require_gpu(t, "rings_regularize input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    require_gpu(rects, "rings_regularize input")
+    assert rects.dtype == torch.int64 and rects.is_contiguous()
+    assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    assert hulls.dim() == 2 and hulls.shape[1] == 8 and tuple(rects.shape) == tuple(hulls.shape)
+    assert hull_vertices.dim() == 2 and hull_vertices.shape[1] == 2 and hull_counts.numel() == 5
+    max_rings, max_vertices = int(rings.shape[0]), int(vertices.shape[0])
+    max_objects, max_hull_vertices, frac_bits = int(hulls.shape[0]), int(hull_vertices.shape[0]), int(frac_bits)
+    if not 0 <= frac_bits <= 8:
+        raise ValueError(f"frac_bits must lie in [0, 8], got {frac_bits}")
+    nbytes = L.lib().c3d_rings_regularize_ws_bytes(max_rings, max_vertices, max_objects)
+    if nbytes < 0 or max_hull_vertices < 1:
+        raise L.Change3DHipError(f"c3d_rings_regularize refuses max_rings = {max_rings}, max_vertices = {max_vertices}, max_objects "
+                                 f"= {max_objects}, max_hull_vertices = {max_hull_vertices} (code {nbytes if nbytes < 0 else -1})")
+    dev = rings.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    rings_out = torch.empty((max_rings, 8), dtype=torch.int32, device=dev)
+    vertices_out = torch.empty((max_vertices, 2), dtype=torch.int32, device=dev)
+    out = torch.empty(5, dtype=torch.int32, device=dev)
+    _launch("c3d_rings_regularize", (max_rings + max_vertices) * 48, L.lib().c3d_rings_regularize, _p(rings), _p(vertices),
+            _p(counts), max_rings, max_vertices, _p(hulls), _p(hull_vertices), _p(rects), _p(hull_counts), max_objects,
+            max_hull_vertices, frac_bits, _p(rings_out), _p(vertices_out), _p(out), _p(ws), _stream())
+    return rings_out, vertices_out, out
+
+
 def rect_corners(P, d, rect_row):
     """The rectangle of a `rings_hull` rects row on the hull edge that starts at `P` = (x, y) and runs along `d` = (dx, dy):
     `(corners float64 [4, 2], long, short, angle)`.  The corners are P + d t/L (+ n c_max/L) for t = t_min, t_max with n =

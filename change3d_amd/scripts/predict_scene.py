@@ -39,6 +39,14 @@ side's direction, degrees in [0, 180), y down) and `rectangularity` = area / are
 the rectangles go to `objects/<name>.hulls.geojson` and `objects/<name>.rects.geojson`, and the run ends with a line `shapes:
 objects = .. solidity_mean = .. rectangularity_mean = ..`.
 
+`--regularize` (with `--polygons --simplify TOL`) squares every simplified ring to the axes of its object's minimum-area rectangle,
+on the device (`c3d_rings_regularize`), and writes `objects/<name>.regular.geojson`: the features and properties of
+`objects/<name>.geojson` with coordinates at 1/16 px as floats and `regular` (true or false) per feature.  An object with a ring
+that was copied, or whose regularised area is zero or has changed sign, keeps its simplified rings there (`regular: false`).
+`--regularize_min_iou F` also fills the regularised polygons back into pixels and joins them to the raw objects: every feature of
+that file gets `iou`, and an object whose IoU is not above F keeps its simplified rings.  Nothing else that the run writes or
+prints changes; it ends with a line `regularize: objects = .. regular = .. fallback = .. iou_mean = .. iou_min = ..`.
+
 `--label_polygons FILE` (BCD, BDA) takes the ground truth as polygons instead of a label raster: a GeoJSON `FeatureCollection`
 in pixel coordinates, such as `--polygons` writes, or an xBD label JSON (change3d_amd/vector_labels.py); with `--file_root` it
 names a directory holding `<name>.json` or `<name>.geojson`.  The polygons are filled on the device (`c3d_rings_fill`) and
@@ -88,7 +96,7 @@ if ROOT not in sys.path:
 from change3d_amd.data.dataset import BCDDataset, BDADataset, SCDDataset, read_label, read_rgb  # noqa: E402
 from change3d_amd import _lib as L  # noqa: E402
 from change3d_amd import ops, vector_labels  # noqa: E402
-from change3d_amd.infer import SceneInferencer  # noqa: E402
+from change3d_amd.infer import REGULAR_FRAC_BITS, SceneInferencer  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
 from change3d_amd.boundary_metrics import BoundaryEvaluator  # noqa: E402
 from change3d_amd.object_metrics import ObjectEvaluator  # noqa: E402
@@ -232,6 +240,59 @@ def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=No
     if skipped:
         print(f"{path}: {len(skipped)} of {rows} objects left out, their rings were cut off (status {int(outlines.counts[4])})")
     return skipped
+
+
+def regular_geojson(doc, rings, regular, iou=None, min_iou=None):
+    """(FeatureCollection dict, objects regularised, objects on their fallback) for objects/<name>.regular.geojson: the
+    features and properties of `doc` (objects/<name>.geojson), each with `regular` and the coordinates of the regularised
+    rings, sixteenths of a pixel as floats.  `rings` [ring rows, 8] are the raw rings, `regular` = (rings, vertices) of
+    `c3d_rings_regularize`, row for row.  An object keeps the coordinates it has in `doc` and gets `regular: false` where one of
+    its rings was copied or has no vertices, where the doubled area of a regularised ring is zero or has the other sign than
+    the raw ring's, or where `iou` [rows] (its regularised polygon filled back, against its raw pixels; every feature gets it
+    as `iou`) is not above `min_iou`."""
+    rings_q, vertices_q = np.asarray(regular[0]).tolist(), np.asarray(regular[1]).astype(np.int64)
+    scale = float(1 << REGULAR_FRAC_BITS)
+    by_id = {}
+    for at, row in enumerate(np.asarray(rings).tolist()):
+        by_id.setdefault(row[0], []).append(row + [at])
+    features, done = [], 0
+    for feature in doc["features"]:
+        k = feature["properties"]["id"]
+        own = by_id.get(k, [])
+        coords, ok = [], not (iou is not None and min_iou is not None and not float(iou[k - 1]) > min_iou)
+        for r in [r for r in own if r[3] > 0] + [r for r in own if r[3] <= 0]:   # the order of polygons_geojson
+            q = rings_q[r[8]]
+            if not ok or q[3] != 1 or q[1] < 0 or q[1] + q[2] > len(vertices_q):
+                ok = False
+                break
+            v = vertices_q[q[1]:q[1] + q[2]]
+            area2 = int((np.roll(v[:, 0], 1) * v[:, 1] - v[:, 0] * np.roll(v[:, 1], 1)).sum())
+            if area2 == 0 or (area2 > 0) != (r[3] > 0):
+                ok = False
+                break
+            ring = (v / scale).tolist()
+            coords.append(ring + ring[:1])
+        properties = dict(feature["properties"], regular=ok)
+        if iou is not None:
+            properties["iou"] = round(float(iou[k - 1]), 4)
+        done += ok
+        features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords if ok else feature["geometry"]["coordinates"]},
+                         "properties": properties})
+    return {"type": "FeatureCollection", "features": features}, done, len(features) - done
+
+
+def save_regular(path, main_path, outlines, regular, iou=None, min_iou=None):
+    """objects/<name>.regular.geojson from objects/<name>.geojson, which was just written, and the read-back of a `SceneRegular`."""
+    with open(main_path) as f:
+        doc = json.load(f)
+    ring_rows = int(outlines.counts[1])
+    out, done, fallback = regular_geojson(doc, outlines.rings[:ring_rows].cpu().numpy(),
+                                          (regular.rings[:ring_rows].cpu().numpy(), regular.vertices[:int(regular.counts[3])].cpu().numpy()),
+                                          iou, min_iou)
+    with open(path, "w") as f:
+        json.dump(out, f)
+    ids = [feat["properties"]["id"] for feat in out["features"]]
+    return done, fallback, ids
 
 
 def object_shapes(name, objects, shapes):
@@ -401,6 +462,10 @@ def parse_args(argv=None):
         args.simplify_check = True
     if args.simplify_check and args.simplify is None:
         parser.error("--simplify_check and --simplify_min_iou measure what --simplify cost: they need --simplify")
+    if args.regularize_min_iou is not None and not args.regularize:
+        parser.error("--regularize_min_iou is the fallback threshold of --regularize: it needs --regularize")
+    if args.regularize and (not args.polygons or args.simplify is None):
+        parser.error("--regularize squares the simplified polygons: it needs --polygons --simplify TOL")
     if args.label_polygons and args.task == "SCD":
         parser.error("--label_polygons gives objects with one class each: it serves --task BCD and BDA")
     if args.label_polygons and any((args.label, args.label1, args.label2, args.change)):
@@ -455,6 +520,10 @@ def main(argv=None):
         split["simplify_check"] = True
     if args.shapes:
         split["shapes"] = True
+    if args.regularize:
+        split["regularize"] = True
+        split["regularize_check"] = args.regularize_min_iou is not None
+    squared = dict(objects=0, regular=0, fallback=0, iou_sum=0.0, iou_min=1.0)   # --regularize over all scenes
     drift = dict(objects=0, kept=0, vanished=0, iou_sum=0.0, iou_min=1.0)   # --simplify_check over all scenes
     shape_sums = dict(objects=0, solidity=0.0, rectangularity=0.0)          # --shapes over all scenes
     for name, img, label in scenes(args):
@@ -463,8 +532,12 @@ def main(argv=None):
         if args.polygons:                 # the outlines come last; every `out[-1]` below is the objects
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, outlines=True,
                               max_rings=args.max_rings, max_vertices=args.max_vertices, simplify=args.simplify, **split)
-            simplified, iou, shapes = None, None, None
-            if args.shapes:               # appended last
+            simplified, iou, shapes, regular, regular_iou = None, None, None, None, None
+            if args.regularize:           # appended last: the regularised rings, then their check
+                if args.regularize_min_iou is not None:
+                    out, regular_fill = out[:-1], out[-1]
+                out, regular = out[:-1], out[-1]
+            if args.shapes:               # appended after the simplified rings and their check
                 out, shapes = out[:-1], out[-1]
             if args.simplify_check:
                 out, fill = out[:-1], out[-1]
@@ -488,6 +561,18 @@ def main(argv=None):
                 shape_sums = dict(objects=shape_sums["objects"] + len(kept),
                                   solidity=shape_sums["solidity"] + sum(v["solidity"] for v in kept),
                                   rectangularity=shape_sums["rectangularity"] + sum(v["rectangularity"] for v in kept))
+            if regular is not None:
+                if int(regular.counts[4]) & (L.OUTLINE_ST_BAD_COUNTS | L.REGULAR_ST_BAD_ROW):
+                    raise SystemExit(f"{name}: --regularize: c3d_rings_regularize status {int(regular.counts[4])}")
+                if args.regularize_min_iou is not None:
+                    regular_iou = simplify_ious(out[-2], regular_fill)[0]
+                main_path = os.path.join(args.out_dir, "objects", name + ".geojson")
+                done, fallback, ids = save_regular(os.path.join(args.out_dir, "objects", name + ".regular.geojson"), main_path, out[-1],
+                                                   regular, regular_iou, args.regularize_min_iou)
+                ious = [float(regular_iou[k - 1]) for k in ids] if regular_iou is not None else []
+                squared = dict(objects=squared["objects"] + len(ids), regular=squared["regular"] + done,
+                               fallback=squared["fallback"] + fallback, iou_sum=squared["iou_sum"] + sum(ious),
+                               iou_min=min([squared["iou_min"]] + ious))
             out = out[:-1]
         elif args.objects:
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, **split)
@@ -548,6 +633,11 @@ def main(argv=None):
         n_shapes = max(shape_sums["objects"], 1)
         print(f"shapes: objects = {shape_sums['objects']} solidity_mean = {shape_sums['solidity'] / n_shapes:.4f} "
               f"rectangularity_mean = {shape_sums['rectangularity'] / n_shapes:.4f}")
+    if args.regularize:
+        checked = args.regularize_min_iou is not None and squared["objects"]
+        print(f"regularize: objects = {squared['objects']} regular = {squared['regular']} fallback = {squared['fallback']} "
+              f"iou_mean = {squared['iou_sum'] / max(squared['objects'], 1) if checked else 0.0:.4f} "
+              f"iou_min = {squared['iou_min'] if checked else 0.0:.4f}")
     if cut_off:
         raise SystemExit(f"{cut_off} objects have no polygon: their rings did not fit; raise --max_rings / --max_vertices")
     if not scored:
@@ -606,6 +696,12 @@ def build_parser():
     p.add_argument("--shapes", action="store_true", help="--polygons: also the convex hull and the minimum-area rectangle of every "
                    "object, on the device (c3d_rings_hull): shape properties on every feature, objects/<name>.hulls.geojson and "
                    "objects/<name>.rects.geojson, and a closing `shapes:` line")
+    p.add_argument("--regularize", action="store_true", help="--polygons --simplify TOL: also square every simplified ring to the axes "
+                   "of its object's minimum-area rectangle, on the device (c3d_rings_regularize): objects/<name>.regular.geojson with "
+                   "coordinates at 1/16 px and `regular` per feature, and a closing `regularize:` line")
+    p.add_argument("--regularize_min_iou", type=unit_interval, default=None, metavar="F", help="--regularize: fill the regularised "
+                   "polygons back into pixels on the device; an object whose IoU with them is not above F, in [0, 1], keeps its "
+                   "simplified rings in objects/<name>.regular.geojson; every feature there gets `iou`")
     p.add_argument("--label_polygons", default="", metavar="FILE", help="BCD, BDA: the ground truth as polygons, a GeoJSON FeatureCollection "
                    "in pixel coordinates or an xBD label JSON, instead of label rasters; with --file_root a directory of <name>.json / "
                    "<name>.geojson.  Filled on the device (c3d_rings_fill); one ground-truth object per feature")

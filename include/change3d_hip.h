@@ -859,6 +859,66 @@ int c3d_rings_hull(const int32_t* rings, const int32_t* vertices, const int32_t*
                    int32_t max_vertices, int32_t max_objects, int32_t max_hull_vertices, int32_t* hulls,
                    int32_t* hull_vertices, int64_t* rects, int32_t* counts_out, void* ws, void* stream);
 
+/* Regularised footprints (csrc/scene_regular.hip): a ring table and vertex list with integer pixel corners, normally the
+ * output of c3d_outlines_simplify, and the four outputs of c3d_rings_hull for the same ids, turned into rings whose edges are
+ * parallel or perpendicular to the chosen rectangle edge of their id while everything stays in HBM.  Integer arithmetic only
+ * in every decision, every output is exact and two runs agree bit for bit.  One memset and 5 launches on `stream`, nothing is
+ * read back by the host, no workgroup waits for another, every loop is capped, and no workspace word is read before the call
+ * wrote it.  The rule:
+ *   rows used   as in c3d_rings_hull: a row r < clamp(counts[1], 0, max_rings) is used iff start >= 0, n >= 0,
+ *               start + n <= clamp(counts[3], 0, max_vertices), 1 <= id <= max_objects and every coordinate of the ring lies
+ *               in [0, 16384].  A row with start < 0 passes through (start' = -1, n' = 0) and sets no bit; any other skipped
+ *               row gets the same and sets C3D_REGULAR_ST_BAD_ROW.  Nothing is read or written out of range
+ *   direction   an id has one iff id <= clamp(counts_hull[1], 0, max_objects), rects[id-1][0] = k >= 0, hulls[id-1] has
+ *               start >= 0, m >= 3, k < m and start + m <= clamp(counts_hull[3], 0, max_hull_vertices), and the hull vertices
+ *               h[k], h[(k+1) % m] lie in [0, 16384] and differ.  Then d = h[(k+1) % m] - h[k], g = gcd(|d.x|, |d.y|),
+ *               u = d / g, N = u.x^2 + u.y^2 <= 2^29.  Every ring of an id without a direction is copied
+ *   frame       for a vertex (x, y): T = x u.x + y u.y, C = y u.x - x u.y, the frame coordinates times |u|; |T|, |C| <= 2^29
+ *   classes     a ring v[0 .. n-1], closed by v[n] = v[0], has the edges e_k = (v[k], v[k+1]); e_k is H iff |dT| >= |dC|,
+ *               otherwise V.  A ring with n < 4 or with a zero-length edge is copied
+ *   runs        the junctions are the k in 0 .. n-1 with class(e_{k-1}) != class(e_k), indices cyclic, ascending
+ *               k_0 < ... < k_{R-1}; R is even.  R < 4: the ring is copied.  The run that ends at k_j has the edges
+ *               k_{j-1} .. k_j - 1, cyclic
+ *   levels      with S = 2^frac_bits and fdiv the floor division, an H run gets Cq = fdiv(S * A + W, 2 W), W = sum |dT_e| > 0,
+ *               A = sum |dT_e| * (C_e0 + C_e1) over its edges: the length-weighted mean of the edge midpoints' C, rounded half
+ *               up at 1/S of a frame unit.  A V run gets Tq the same way from |dC_e| and T_e0 + T_e1.  A needs 128 bits; the
+ *               quotient fits 38
+ *   vertices    output vertex j belongs to junction k_j: Cq from whichever of the two runs that meet there is H, Tq from the
+ *               other, and back in pixels at 1/S
+ *                 Xq = fdiv(2 (Tq u.x - Cq u.y) + N, 2 N)      Yq = fdiv(2 (Tq u.y + Cq u.x) + N, 2 N)
+ *               n' = R, in junction order.  Coincident or collinear output vertices stay; no topology is promised, as with
+ *               c3d_outlines_simplify: compare the filled result with the pixels (c3d_rings_fill, c3d_objects_match)
+ *   copied      n' = n, every coordinate times S
+ * Inputs (device): rings i32 [max_rings][8] (16-byte aligned), vertices i32 [max_vertices][2] (8-byte aligned), counts i32 [5];
+ * hulls i32 [max_objects][8], hull_vertices i32 [max_hull_vertices][2], rects i64 [max_objects][8], counts_hull i32 [5] as
+ * c3d_rings_hull writes them.
+ * Outputs (must not alias the inputs):
+ *   rings_out     i32 [max_rings][8], 16-byte aligned, same row order: (id, start', n', flag, perimeter, x, y, n): flag = 1 for
+ *                 a regularised ring, 0 for a copied one; id, perimeter, x, y are copied; column 7 = the input's n.  Rows past
+ *                 the last are 0
+ *   vertices_out  i32 [max_vertices][2], 8-byte aligned, in units of 2^-frac_bits pixel, rings contiguous and in row order:
+ *                 what c3d_rings_fill takes with the same frac_bits.  Rows past counts_out[3] are left as they were
+ *   counts_out    i32 [5] = (rings found, rows written, vertices out, vertices out, status); status = counts[4] |
+ *                 counts_hull[4] with C3D_REGULAR_ST_BAD_ROW added where it applies
+ *   ws            c3d_rings_regularize_ws_bytes(max_rings, max_vertices, max_objects) bytes (13 per ring row, 12 per vertex
+ *                 row), 256-byte aligned; a dirty one gives the same result
+ * n' <= n, so a table whose rows share no vertices always fits.  Where rows share so many that the n' of a row and all used
+ * rows before it add up to more than max_vertices, that row is a skipped row (C3D_REGULAR_ST_BAD_ROW), and so is every later
+ * row that would be used.
+ * C3D_OUTLINE_ST_BAD_COUNTS in counts[4] or counts_hull[4]: all rows 0, counts_out = (0, 0, 0, 0, status).
+ * Refused before anything is enqueued (C3D_E_BADARG): a NULL pointer, max_rings, max_vertices, max_objects or
+ * max_hull_vertices < 1, frac_bits outside [0, 8].
+ * c3d_rings_regularize_limits: out[0] = the most edges of a ring that one wave handles, a lane per edge, out[1] = the most of
+ * a ring whose vertices, junctions and levels one workgroup keeps in LDS; a larger ring is read from HBM and keeps its lists
+ * in `ws`.  The results do not depend on the tier.  Host only.                                                              */
+#define C3D_REGULAR_ST_BAD_ROW 256
+void c3d_rings_regularize_limits(int32_t out[2]);
+int64_t c3d_rings_regularize_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_objects);   /* < 0: C3D_E_* */
+int c3d_rings_regularize(const int32_t* rings, const int32_t* vertices, const int32_t* counts, int32_t max_rings,
+                         int32_t max_vertices, const int32_t* hulls, const int32_t* hull_vertices, const int64_t* rects,
+                         const int32_t* counts_hull, int32_t max_objects, int32_t max_hull_vertices, int32_t frac_bits,
+                         int32_t* rings_out, int32_t* vertices_out, int32_t* counts_out, void* ws, void* stream);
+
 /* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
  * in HBM.  The rule:
  *   sites       the pixels with mask == 0; with C3D_EDT_INVERT (bit 0 of flags) the pixels with mask != 0
