@@ -107,6 +107,7 @@ SIMPLIFY_TOL2_Q_MAX = 16 * 1024 * 1024                   # C3D_SIMPLIFY_TOL2_Q_M
 FILL_ST_BAD_ID, FILL_ST_BAD_RING = 16, 32                # C3D_FILL_ST_*: added by c3d_rings_fill to the status it carries
 HULL_ST_BAD_ROW, HULL_ST_TRUNCATED = 64, 128             # C3D_HULL_ST_*: added by c3d_rings_hull to the status it carries
 REGULAR_ST_BAD_ROW = 256                                 # C3D_REGULAR_ST_BAD_ROW: added by c3d_rings_regularize
+POLIS_ST_BAD_PARTNER = 512                               # C3D_POLIS_ST_BAD_PARTNER: added by c3d_rings_polis
 EDT_INVERT, EDT_BORDER, EDT_FAR = 1, 2, 0x3fffffff       # C3D_EDT_*: flag bits of c3d_scene_edt, and its "no site within the cap"
 BOUNDARY_R2_MAX = 1024 * 1024                            # C3D_BOUNDARY_R2_MAX
 SPLIT_ST_NOT_CONVERGED, SPLIT_ST_BAD_LABELS = 1, 2       # C3D_SPLIT_ST_*: bits of c3d_scene_split's info[0]
@@ -203,6 +204,10 @@ SIGNATURES = {
     "c3d_rings_regularize_limits": (None, [C.POINTER(i32)]),
     "c3d_rings_regularize_ws_bytes": (i64, [i32, i32, i32]),
     "c3d_rings_regularize": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "c3d_rings_polis_limits": (None, [C.POINTER(i32)]),
+    "c3d_rings_polis_ws_bytes": (i64, [i32, i32, i32, i32, i32, i32]),
+    "c3d_rings_polis": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp,
+                              vp]),
     "c3d_scene_edt_ws_bytes": (i64, [i32, i32]),
     "c3d_scene_edt_tile": (i32, [C.POINTER(i32)]),
     "c3d_scene_edt": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),

@@ -1107,6 +1107,63 @@ def rings_regularize(rings, vertices, counts, hulls, hull_vertices, rects, hull_
     return rings_out, vertices_out, out
 
 
+def rings_polis_limits():
+    """(most vertices of either id in the wave tier, vertices of a job, edges of an LDS tile, most rings of an id, most vertices
+    of a ring that one wave regroups); host only."""
+    out = (C.c_int32 * 5)()
+    L.lib().c3d_rings_polis_limits(out)
+    return tuple(int(v) for v in out)
+
+
+def rings_polis(rings_p, vertices_p, counts_p, frac_bits_p, rings_g, vertices_g, counts_g, frac_bits_g, match_p, max_g,
+                max_pair_work=2 ** 32, totals=None, total_sums=None, ws=None):
+    """c3d_rings_polis on two ring tables (`rings` i32 [max_rings, 8], `vertices` i32 [max_vertices, 2], `counts` i32 [5],
+    coordinates in units of 2^-frac_bits pixel), prediction first, and the `match_p` i32 [max_p, 4] of `objects_match`: PoLiS
+    and the vertex-to-boundary Hausdorff distance of every matched pair by the rule of include/change3d_hip.h.  Returns `(pair
+    f64 [max_p, 4] = (polis, hausdorff, mean_pg, mean_gp) in pixels, pair_n i32 [max_p, 4] = (g, n_p, n_g, flag), counts i64
+    [8] = (scored, no partner, incomplete, over work, sum n_p, sum n_g, status, 0), sums f64 [4] = (sum polis, sum hausdorff,
+    max hausdorff, sum n_p / n_g))`, all on the device; nothing is read back.  `totals` i64 [8] and `total_sums` f64 [4],
+    zeroed once by the caller, are accumulated into.  A pair that would cost more than `max_pair_work` point-edge
+    evaluations is not scored (flag 3)."""
+    for t in (rings_p, vertices_p, counts_p, rings_g, vertices_g, counts_g, match_p):
+        require_gpu(t, "rings_polis input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    for rings, vertices, counts in ((rings_p, vertices_p, counts_p), (rings_g, vertices_g, counts_g)):
+        assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    assert match_p.dim() == 2 and match_p.shape[1] == 4
+    frac_bits_p, frac_bits_g, max_pair_work = int(frac_bits_p), int(frac_bits_g), int(max_pair_work)
+    if not (0 <= frac_bits_p <= 8 and 0 <= frac_bits_g <= 8):
+        raise ValueError(f"frac_bits must lie in [0, 8], got {frac_bits_p} and {frac_bits_g}")
+    if not 0 <= max_pair_work < 2 ** 63:
+        raise ValueError(f"max_pair_work must lie in [0, 2^63), got {max_pair_work}")
+    sizes = (int(rings_p.shape[0]), int(vertices_p.shape[0]), int(match_p.shape[0]), int(rings_g.shape[0]),
+             int(vertices_g.shape[0]), int(max_g))
+    nbytes = L.lib().c3d_rings_polis_ws_bytes(*sizes)
+    if nbytes < 0:
+        raise L.Change3DHipError(f"c3d_rings_polis refuses (max_rings, max_vertices, max_objects) = {sizes[:3]} against {sizes[3:]} "
+                                 f"(code {nbytes})")
+    dev = rings_p.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    if totals is not None:
+        require_gpu(totals, "rings_polis totals")
+        assert totals.dtype == torch.int64 and totals.numel() == 8 and totals.is_contiguous()
+    if total_sums is not None:
+        require_gpu(total_sums, "rings_polis total_sums")
+        assert total_sums.dtype == torch.float64 and total_sums.numel() == 4 and total_sums.is_contiguous()
+    max_p = sizes[2]
+    pair = torch.empty((max_p, 4), dtype=torch.float64, device=dev)
+    pair_n = torch.empty((max_p, 4), dtype=torch.int32, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    sums = torch.empty(4, dtype=torch.float64, device=dev)
+    _launch("c3d_rings_polis", (sizes[0] + sizes[3]) * 48 + (sizes[1] + sizes[4]) * 40 + max_p * 64, L.lib().c3d_rings_polis,
+            _p(rings_p), _p(vertices_p), _p(counts_p), sizes[0], sizes[1], frac_bits_p, _p(rings_g), _p(vertices_g), _p(counts_g),
+            sizes[3], sizes[4], frac_bits_g, _p(match_p), max_p, sizes[5], max_pair_work, _p(pair), _p(pair_n), _p(counts),
+            _p(sums), _p(totals), _p(total_sums), _p(ws), _stream())
+    return pair, pair_n, counts, sums
+
+
 def rect_corners(P, d, rect_row):
     """The rectangle of a `rings_hull` rects row on the hull edge that starts at `P` = (x, y) and runs along `d` = (dx, dy):
     `(corners float64 [4, 2], long, short, angle)`.  The corners are P + d t/L (+ n c_max/L) for t = t_min, t_max with n =

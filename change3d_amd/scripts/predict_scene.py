@@ -54,6 +54,18 @@ everything that scores reads the result: the pixel scores its mask (BDA: and its
 ground-truth object per feature, so two labelled buildings that touch stay two, where a raster would join them --, `--boundary`
 its mask.
 
+`--polygon_scores` (with `--label_polygons` and `--objects --polygons`) scores the predicted polygons against the labelled ones,
+on the device (change3d_amd/polygon_metrics.py, `c3d_rings_polis`): for every predicted object that `--objects` matched to a
+labelled one, PoLiS -- the mean distance of the vertices of either polygon to the boundary of the other, averaged over the two
+directions -- and the largest of those vertex distances, in pixels, against the label's rings at 1/16 px.  That maximum is the
+vertex-to-boundary Hausdorff distance, not the Hausdorff distance of the two boundaries, whose maximum may fall inside an edge.
+Every stage the run has is scored: the raw rings, the simplified rings with `--simplify`, and the regularised rings as
+`c3d_rings_regularize` left them with `--regularize`; the host-side fallbacks of `--simplify_min_iou` and `--regularize_min_iou`,
+which only change the written files, are not reflected.  `objects/<name>.polis.csv` lists `stage,id,gt_id,n,n_gt,polis,hausdorff,
+flag` per predicted object (flag 0 scored, 1 no partner, 2 an incomplete or empty polygon, 3 too large a pair), and the run ends
+with one line per stage, `polygons[raw]: pairs polis hausdorff_mean hausdorff_max n_ratio skipped`: the means over the scored
+pairs, `n_ratio` the mean of predicted over labelled vertices, `skipped` the matched pairs that were not scored.
+
 `--tta hflip|flips|d4` is test-time augmentation: every tile is predicted under the two mirror views, the four flips or all
 eight flips and rotations of the square, each view is undone on the device and the views are averaged before the stitch
 (`c3d_scene_gather_views`, `c3d_scene_fold_views`; change3d_amd/infer.py).  `--batch_size` stays the number of model inputs
@@ -100,6 +112,7 @@ from change3d_amd.infer import REGULAR_FRAC_BITS, SceneInferencer  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
 from change3d_amd.boundary_metrics import BoundaryEvaluator  # noqa: E402
 from change3d_amd.object_metrics import ObjectEvaluator  # noqa: E402
+from change3d_amd.polygon_metrics import PolygonEvaluator  # noqa: E402
 from change3d_amd.model.utils import BDAEvaluator, Evaluator, SCDHistogram, bda_scores  # noqa: E402
 from change3d_amd.utils.metric_tool import ConfuseMatrixMeter  # noqa: E402
 
@@ -355,12 +368,14 @@ def polygon_labels(args, name, Hs, Ws, device):
     n = max(len(id_cls), 1)
     cls = np.zeros(n, dtype=np.uint8)
     cls[:len(id_cls)] = id_cls
+    d_rings, d_vertices, d_counts = (torch.from_numpy(a).to(device) for a in (rings, vertices, counts))
     labels, table, counts_obj, mask, cls_map, info = ops.rings_fill(
-        *(torch.from_numpy(a).to(device) for a in (rings, vertices, counts)), Hs, Ws, frac_bits=LABEL_FRAC_BITS,
+        d_rings, d_vertices, d_counts, Hs, Ws, frac_bits=LABEL_FRAC_BITS,
         id_cls=torch.from_numpy(cls).to(device), max_objects=n, want_mask=True, want_cls_map=True)
     if int(info[0]):
         raise SystemExit(f"{path}: c3d_rings_fill status {int(info[0])}")
-    return SimpleNamespace(labels=labels, table=table, counts=counts_obj, mask=mask, cls_map=cls_map)
+    return SimpleNamespace(labels=labels, table=table, counts=counts_obj, mask=mask, cls_map=cls_map, rings=d_rings, vertices=d_vertices,
+                           ring_counts=d_counts)
 
 
 def save_matches(path, objects, gt_counts, match_p, match_g):
@@ -398,6 +413,25 @@ def print_bda_scores(evaluator, object_hist, num_class):
     f1 = per_object.Damage_F1_socore()
     print(f"Objects:\tharmonic_mean_f1 = {len(f1) / np.sum(1.0 / f1):.4f}\tdamage_f1_score = [{', '.join(f'{v:.4f}' for v in f1)}]")
     return loc_f1, harmonic, oaf1, damage_f1
+
+
+def save_polygon_scores(path, rows, results):
+    """objects/<name>.polis.csv: per stage the rows of the predicted objects; `results` = (stage, pair, pair_n) device tensors."""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("stage,id,gt_id,n,n_gt,polis,hausdorff,flag\n")
+        for stage, pair, pair_n in results:
+            for k, ((polis, hausdorff, _, _), (g, n_p, n_g, flag)) in enumerate(zip(pair[:rows].cpu().tolist(), pair_n[:rows].cpu().tolist())):
+                f.write(f"{stage},{k + 1},{g},{n_p},{n_g},{polis:.4f},{hausdorff:.4f},{flag}\n")
+
+
+def print_polygon_scores(evaluators):
+    out = {}
+    for stage, evaluator in evaluators.items():
+        s = out[stage] = evaluator.scores()
+        print(f"polygons[{stage}]: pairs = {s['pairs']} polis = {s['polis']:.4f} hausdorff_mean = {s['hausdorff_mean']:.4f} "
+              f"hausdorff_max = {s['hausdorff_max']:.4f} n_ratio = {s['n_ratio']:.4f} skipped = {s['incomplete'] + s['over_work']}")
+    return out
 
 
 def print_boundary_scores(evaluator):
@@ -476,6 +510,8 @@ def parse_args(argv=None):
         parser.error("--split_objects splits the objects of the map: it needs --objects")
     if args.split_rounds is not None and args.split_objects is None:
         parser.error("--split_rounds is the round limit of --split_objects: it needs --split_objects")
+    if args.polygon_scores and not (args.label_polygons and args.polygons):
+        parser.error("--polygon_scores compares the polygons of the map with labelled ones: it needs --label_polygons and --objects --polygons")
     return args
 
 
@@ -494,6 +530,7 @@ def main(argv=None):
     object_hist = SCDHistogram(num_class, device) if args.task == "BDA" and args.objects else None
     object_eval = None                                    # made by the first labelled scene of a run with --objects
     boundary_eval = None                                  # made by the first labelled scene of a run with --boundary
+    polygon_evals = {}                                    # --polygon_scores: stage -> PolygonEvaluator, in the order of the stages
     scored = 0
     cut_off = 0                                           # objects whose polygon was left out of a .geojson
 
@@ -506,6 +543,17 @@ def main(argv=None):
         else:
             match_p, match_g = object_eval.update(objects, gt_mask.to(torch.uint8), None if gt_cls is None else gt_cls.to(torch.uint8))
         save_matches(os.path.join(args.out_dir, "objects", name + ".match.csv"), objects, object_eval.last_gt_counts, match_p, match_g)
+        return match_p
+
+    def score_polygons(name, objects, stages, gt, match_p):
+        results = []
+        for stage, rings, frac_bits in stages:            # each a SceneOutlines or SceneRegular of this scene
+            if stage not in polygon_evals:
+                polygon_evals[stage] = PolygonEvaluator(device=device)
+            pair, pair_n, _, _ = polygon_evals[stage].update(rings.rings, rings.vertices, rings.counts, frac_bits, gt.rings, gt.vertices,
+                                                             gt.ring_counts, LABEL_FRAC_BITS, match_p, gt.table.shape[0])
+            results.append((stage, pair, pair_n))
+        save_polygon_scores(os.path.join(args.out_dir, "objects", name + ".polis.csv"), int(objects.counts[1]), results)
 
     def score_boundary(mask, gt_mask):
         nonlocal boundary_eval
@@ -573,6 +621,9 @@ def main(argv=None):
                 squared = dict(objects=squared["objects"] + len(ids), regular=squared["regular"] + done,
                                fallback=squared["fallback"] + fallback, iou_sum=squared["iou_sum"] + sum(ious),
                                iou_min=min([squared["iou_min"]] + ious))
+            if args.polygon_scores:
+                stages = [("raw", out[-1], 0)] + ([("simplified", simplified, 0)] if simplified is not None else []) + \
+                         ([("regularised", regular, REGULAR_FRAC_BITS)] if regular is not None else [])
             out = out[:-1]
         elif args.objects:
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, **split)
@@ -588,7 +639,9 @@ def main(argv=None):
                 lab = gt.mask > 0 if gt is not None else torch.from_numpy(np.ascontiguousarray(label)).to(device) > 0
                 meter.update_cm_device(mask.float(), lab.float())
                 if args.objects:
-                    score_objects(name, out[-1], lab, gt=gt)
+                    match_p = score_objects(name, out[-1], lab, gt=gt)
+                    if args.polygon_scores:
+                        score_polygons(name, out[-1], stages, gt, match_p)
                 score_boundary(mask, lab)
                 scored += 1
         elif args.task == "BDA":
@@ -609,7 +662,9 @@ def main(argv=None):
                 if args.objects:         # the per-building majority map against the damage labels, where there is one
                     inside = label_cls > 0
                     object_hist.update(out[-1].object_cls[inside], label_cls[inside])
-                    score_objects(name, out[-1], loc > 0, label_cls, gt=gt)
+                    match_p = score_objects(name, out[-1], loc > 0, label_cls, gt=gt)
+                    if args.polygon_scores:
+                        score_polygons(name, out[-1], stages, gt, match_p)
                 score_boundary(loc_mask, loc > 0)
                 scored += 1
         else:
@@ -655,6 +710,8 @@ def main(argv=None):
         print_object_scores(object_eval, per_class=args.task == "BDA")
     if boundary_eval is not None:
         print_boundary_scores(boundary_eval)
+    if polygon_evals:
+        print_polygon_scores(polygon_evals)
     return result
 
 
@@ -705,6 +762,9 @@ def build_parser():
     p.add_argument("--label_polygons", default="", metavar="FILE", help="BCD, BDA: the ground truth as polygons, a GeoJSON FeatureCollection "
                    "in pixel coordinates or an xBD label JSON, instead of label rasters; with --file_root a directory of <name>.json / "
                    "<name>.geojson.  Filled on the device (c3d_rings_fill); one ground-truth object per feature")
+    p.add_argument("--polygon_scores", action="store_true", help="--label_polygons --objects --polygons: also score every matched polygon "
+                   "against its labelled one on the device (c3d_rings_polis): PoLiS and the vertex-to-boundary Hausdorff distance of "
+                   "the raw, the simplified and the regularised rings, objects/<name>.polis.csv and a closing `polygons[stage]:` line each")
     p.add_argument("--iou_thr", type=iou_threshold, default=0.5, help="--objects with labels: a predicted and a labelled object match iff "
                    "their IoU is strictly above this; in [0.5, 1)")
     p.add_argument("--boundary", type=boundary_radius, default=None, metavar="D", help="with labels: also the boundary scores, Boundary IoU "

@@ -919,6 +919,76 @@ int c3d_rings_regularize(const int32_t* rings, const int32_t* vertices, const in
                          const int32_t* counts_hull, int32_t max_objects, int32_t max_hull_vertices, int32_t frac_bits,
                          int32_t* rings_out, int32_t* vertices_out, int32_t* counts_out, void* ws, void* stream);
 
+/* Polygon scores (csrc/scene_polis.hip): PoLiS (Avbelj et al., 2015), a vertex Hausdorff distance and the vertex counts of
+ * every pair (predicted object, its ground-truth partner) from two ring tables and the match_p of c3d_objects_match while all
+ * of them stay in HBM.  One memset and 10 launches on `stream`, nothing is read back by the host, no workgroup waits for
+ * another, every loop is capped, and no workspace word is read before the call wrote it.  Integers decide everything but the
+ * distances, and every floating-point sum is taken in an order that depends on the inputs only: two runs agree bit for bit.
+ * The rule:
+ *   sides       P, the prediction, and G, the ground truth, each a ring table in the layout of c3d_scene_outlines: rings i32
+ *               [max_rings][8] with (id, start, n) in columns 0..2 (the others are ignored), vertices i32 [max_vertices][2]
+ *               (8-byte aligned), counts i32 [5]; each with its own f = frac_bits in [0, 8], coordinates in units of 2^-f pixel,
+ *               |coordinate| <= 32768 * 2^f.  The ids of P are 1 .. max_p, those of G 1 .. max_g
+ *   units       F = max(f_p, f_g); every coordinate is shifted left by F - f.  Distances are computed in those units and divided
+ *               by 2^F at the end, which is exact
+ *   rows used   as in c3d_rings_fill: a row r < clamp(counts[1], 0, max_rings) whose id lies in [1, max] is used iff start >= 0,
+ *               n >= 0, start + n <= clamp(counts[3], 0, max_vertices) and every coordinate of the ring is in range.  A used
+ *               ring with n < 3 contributes nothing.  An id that has a row with start < 0, or any other row that is not used,
+ *               is INCOMPLETE; so is an id with more than RING_LIMIT rings of n >= 3 (c3d_rings_polis_limits: the step that
+ *               restores the row order holds no more), and an id of a table whose rows share vertices once the vertices of
+ *               the ids up to it add up to more than max_vertices.  Rows whose id lies outside [1, max] are ignored.  The rings
+ *               of an id need not be contiguous in the table
+ *   geometry    V(id) = the vertices of its used rings with n >= 3, in ascending row order and then by index; E(id) = the edges
+ *               (v[k], v[(k+1) mod n]) of each of those rings, the closing edge included.  Edges never join two rings; holes
+ *               are rings like any other
+ *   distance    of a point p to an edge (a, b): e = b - a, w = p - a, L = e.e, t = w.e, c = w x e, all integers below 2^53 and
+ *               so exact in a double.  L == 0 or t <= 0: v = (double)(w.w); t >= L: v = (double)|p - b|^2; otherwise
+ *               v = ((double)c * (double)c) / (double)L.  d(p, E) = sqrt(min over the edges of v)
+ *   objects     K_p = the largest id in [1, max_p] of a row r < clamp(counts_p[1], 0, max_rings_p) of P, used or not
+ *   pair        for p <= K_p: g = match_p[p-1][0].  g outside [0, max_g] sets C3D_POLIS_ST_BAD_PARTNER and counts as 0.  The
+ *               pair is scored iff g >= 1, neither id is incomplete, n_p = |V(p)| >= 1, n_g = |V(g)| >= 1 and
+ *               2 * n_p * n_g <= max_pair_work.  Then mean_pg = the mean of d(v, E(g)) over V(p), mean_gp the other way round,
+ *               PoLiS = (mean_pg + mean_gp) / 2, and hausdorff = the largest of all those n_p + n_g distances.  This is the
+ *               VERTEX-TO-BOUNDARY form: it is NOT the Hausdorff distance of the two boundaries, whose maximum may fall
+ *               inside an edge (a long edge of one polygon that passes far from the other is seen at its two ends only)
+ * Inputs (device): the two sides; match_p i32 [max_p][4] as c3d_objects_match writes it (column 0 is read); max_pair_work >= 0,
+ * the most point-edge evaluations one pair may cost.
+ * Outputs:
+ *   pair       f64 [max_p][4], 16-byte aligned, row p-1 = (polis, hausdorff, mean_pg, mean_gp) in pixels; zeros where the pair is
+ *              not scored
+ *   pair_n     i32 [max_p][4], 16-byte aligned, row p-1 = (g or 0, n_p, n_g, flag): n_p and n_g are 0 for an incomplete id and
+ *              n_g is 0 without a partner; flag 0 scored, 1 no partner, 2 an incomplete or empty id on either side, 3 over
+ *              max_pair_work.  Rows past K_p of both tables are 0, written by the call
+ *   counts     i64 [8] = (scored, no partner, incomplete or empty, over work, sum n_p, sum n_g, status, 0), the sums over the
+ *              scored pairs; status = counts_p[4] | counts_g[4] as they came, with C3D_POLIS_ST_BAD_PARTNER added
+ *   sums       f64 [4] = (sum polis, sum hausdorff, max hausdorff, sum (double)n_p / (double)n_g) over the scored pairs, added
+ *              by one workgroup in ascending p (256 interleaved partial sums, then a fixed tree)
+ *   totals     i64 [8] or NULL, total_sums f64 [4] or NULL: counts[0..5] are ADDED into totals, status is OR-ed into totals[6];
+ *              sums[0], [1], [3] are added into total_sums and slot 2 takes the maximum; by one thread at the end of the last
+ *              launch, so calls on one stream accumulate in stream order (the convention of c3d_objects_match).  The caller
+ *              zeroes them once
+ *   ws         c3d_rings_polis_ws_bytes(...) bytes, 256-byte aligned; a dirty one gives the same result
+ * Tiers.  A pair with n_p, n_g <= out[0] runs in one wave.  Every other pair is cut into jobs of (direction, out[1] vertices of
+ * the id's vertex list) that read the other id's edges in tiles of out[2]; the sum of a job is a fixed tree, the jobs of a
+ * pair are added in job order.  The tiers round a sum differently; both stay within (n + 8) 2^-53 relative of the exact mean.
+ * The job table holds ceil(max_vertices_p / out[1]) + ceil(max_vertices_g / out[1]) + 2 max_p jobs, which suffices whenever no
+ * ground-truth id is named twice (c3d_objects_match with iou_thr >= 0.5 never does); a pair of the job tier whose jobs no longer
+ * fit, and every such pair after it, gets flag 3.  C3D_OUTLINE_ST_BAD_COUNTS in counts_p[4] or counts_g[4] empties that side.
+ * Refused before anything is enqueued (C3D_E_BADARG): a NULL pointer other than totals / total_sums / stream, a frac_bits outside
+ * [0, 8], a max below 1, max_pair_work < 0.
+ * c3d_rings_polis_limits: out[0] = the most vertices of either id in the wave tier, out[1] = the vertices of a job, out[2] = the
+ * edges of an LDS tile, out[3] = RING_LIMIT, out[4] = the most vertices of a ring that one wave checks and regroups; a longer ring
+ * is spread over many workgroups.  The results do not depend on that.  Host only.                                             */
+#define C3D_POLIS_ST_BAD_PARTNER 512
+void c3d_rings_polis_limits(int32_t out[5]);
+int64_t c3d_rings_polis_ws_bytes(int32_t max_rings_p, int32_t max_vertices_p, int32_t max_p, int32_t max_rings_g,
+                                 int32_t max_vertices_g, int32_t max_g);   /* < 0: C3D_E_* */
+int c3d_rings_polis(const int32_t* rings_p, const int32_t* vertices_p, const int32_t* counts_p, int32_t max_rings_p,
+                    int32_t max_vertices_p, int32_t frac_bits_p, const int32_t* rings_g, const int32_t* vertices_g,
+                    const int32_t* counts_g, int32_t max_rings_g, int32_t max_vertices_g, int32_t frac_bits_g,
+                    const int32_t* match_p, int32_t max_p, int32_t max_g, int64_t max_pair_work, double* pair, int32_t* pair_n,
+                    int64_t* counts, double* sums, int64_t* totals, double* total_sums, void* ws, void* stream);
+
 /* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
  * in HBM.  The rule:
  *   sites       the pixels with mask == 0; with C3D_EDT_INVERT (bit 0 of flags) the pixels with mask != 0
