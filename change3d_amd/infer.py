@@ -43,6 +43,12 @@ every edge parallel or perpendicular to the chosen rectangle edge of their objec
 raw rings; the hull call is shared with `shapes=True`), in sixteenths of a pixel.  `regularize_check=True` appends a `SceneFill`
 of those rings after it, as `simplify_check` does for the simplified ones.  Still the same one synchronisation.
 
+`predict(..., outlines=True, validity=True)` appends one `SceneValidity` per stage the call has, after everything above so that
+no position moves: of the raw rings, then of the simplified ones with `simplify=tol`, then of the regularised ones (at 1/16 px)
+with `regularize=True`.  `c3d_rings_valid` counts the proper crossings, collinear overlaps and touches among the edges of every
+object, holes included; an object is valid iff it was checked and has no crossing and no overlap.  Edges of different objects
+are never compared.  Still the same one synchronisation; with `validity=False` the launches are the ones without it.
+
 `SceneInferencer(..., tta="hflip" | "flips" | "d4" | codes)` is test-time augmentation: every tile is predicted under a set of
 the eight flips and rotations of the square, each view is undone on the output and the views are averaged before the
 stitch.  A view code `v` in 0..7 transposes the tile if `v & 4`, then reverses its rows if `v & 2`, then its columns if
@@ -90,6 +96,11 @@ SceneShapes = namedtuple("SceneShapes", "hulls vertices rects counts")
 # (`ops.rings_regularize`): rings i32 [max_rings, 8] = (id, start, n, regularised?, perimeter, x, y, simplified n), vertices in
 # units of 2^-REGULAR_FRAC_BITS pixel, counts i32 [5]
 SceneRegular = namedtuple("SceneRegular", "rings vertices counts")
+# `predict(..., validity=True)`: the crossings, overlaps and touches among the edges of every object of one ring table
+# (`ops.rings_valid`): valid i64 [max_objects, 8] = (flag, rings, m, degenerate, cross, overlap, touch_vv, touch_ve), counts i64
+# [8] = (checked, invalid, empty, incomplete, over work, sum cross, sum overlap, status).  An object is valid iff flag == 0 and
+# cross == overlap == 0
+SceneValidity = namedtuple("SceneValidity", "valid counts")
 REGULAR_FRAC_BITS = 4
 TASKS = ("bcd", "scd", "bda")
 WINDOWS = ("hann", "flat")
@@ -229,6 +240,9 @@ class SceneInferencer:
     rings, the one `ops.rings_hull` call that `shapes=True` makes, shared when both are asked for), coordinates in sixteenths of
     a pixel.  `regularize_check=True` appends a `SceneFill` after it: those rings filled at 1/16 px and matched to the raw
     objects, as `simplify_check` does for the simplified ones.  With `regularize=False` the launches are the ones without it.
+    `validity=True` (with `outlines=True`) appends, last of all, a `SceneValidity` of the raw rings, one of the simplified rings
+    with `simplify=tol` and one of the regularised rings with `regularize=True` (`ops.rings_valid`): per object its crossings,
+    overlaps and touches.  With `validity=False` the launches are the ones without it.
     `tta` is None, a name of `VIEW_SETS` ("none", "hflip", "flips", "d4") or a sequence of view codes: the tiles are predicted
     under those `nv` views and averaged with the views undone (module docstring).  `batch` stays the number of model inputs
     per forward, so a forward takes `batch // nv` tiles; a transposing view (codes 4..7) needs a square model input.  With
@@ -285,9 +299,11 @@ class SceneInferencer:
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
                 max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False, shapes=False,
-                regularize=False, regularize_check=False):
+                regularize=False, regularize_check=False, validity=False):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
+        if validity and not outlines:
+            raise ValueError("validity=True tests the traced rings of the objects: it needs outlines=True")
         if shapes and not outlines:
             raise ValueError("shapes=True takes the hulls and rectangles of the traced rings: it needs outlines=True")
         if split is None and split_rounds is not None:
@@ -402,5 +418,12 @@ class SceneInferencer:
                                                                                    max_objects=max_objects)
                         match = ops.objects_match(labels, table, counts, f_labels, f_table, f_counts, n_cls=1, iou_thr=0.5)
                         result += (SceneFill(f_labels, f_table, f_counts, f_info, match),)
+                    regular = result[-2] if regularize_check else result[-1]
+                if validity:                            # last, so that no position above moves: raw, simplified, regularised
+                    result += (SceneValidity(*ops.rings_valid(*raw, max_objects=max_objects)),)
+                    if simplify is not None:
+                        result += (SceneValidity(*ops.rings_valid(*simple, max_objects=max_objects)),)
+                    if regularize:
+                        result += (SceneValidity(*ops.rings_valid(*regular, frac_bits=REGULAR_FRAC_BITS, max_objects=max_objects)),)
         torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
         return result

@@ -1164,6 +1164,51 @@ def rings_polis(rings_p, vertices_p, counts_p, frac_bits_p, rings_g, vertices_g,
     return pair, pair_n, counts, sums
 
 
+def rings_valid_limits():
+    """(most edges of an id in the wave tier, edges of a chunk, edges of an LDS tile, most rings of an id, most vertices of a
+    ring that one wave regroups); host only."""
+    out = (C.c_int32 * 5)()
+    L.lib().c3d_rings_valid_limits(out)
+    return tuple(int(v) for v in out)
+
+
+def rings_valid(rings, vertices, counts, frac_bits=0, max_objects=65536, max_id_work=2 ** 32, totals=None, ws=None):
+    """c3d_rings_valid on one ring table (`rings` i32 [max_rings, 8], `vertices` i32 [max_vertices, 2], `counts` i32 [5],
+    coordinates in units of 2^-frac_bits pixel): the crossings, overlaps and touches among the edges of every object id by the
+    rule of include/change3d_hip.h.  Returns `(valid i64 [max_objects, 8] = (flag, rings, m, degenerate, cross, overlap,
+    touch_vv, touch_ve) per id, counts i64 [8] = (checked, invalid, empty, incomplete, over work, sum cross, sum overlap,
+    status))`, both on the device; nothing is read back.  An id is valid iff flag == 0 and cross == overlap == 0.  `totals` i64
+    [8], zeroed once by the caller, is accumulated into.  An id whose m (m - 1) / 2 edge pairs exceed `max_id_work` is not
+    checked (flag 3)."""
+    for t in (rings, vertices, counts):
+        require_gpu(t, "rings_valid input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    frac_bits, max_objects, max_id_work = int(frac_bits), int(max_objects), int(max_id_work)
+    if not 0 <= frac_bits <= 8:
+        raise ValueError(f"frac_bits must lie in [0, 8], got {frac_bits}")
+    if not 0 <= max_id_work < 2 ** 63:
+        raise ValueError(f"max_id_work must lie in [0, 2^63), got {max_id_work}")
+    max_rings, max_vertices = int(rings.shape[0]), int(vertices.shape[0])
+    nbytes = L.lib().c3d_rings_valid_ws_bytes(max_rings, max_vertices, max_objects) if max_objects < 2 ** 31 else -1
+    if nbytes < 0:
+        raise L.Change3DHipError(f"c3d_rings_valid refuses max_rings = {max_rings}, max_vertices = {max_vertices}, max_objects = "
+                                 f"{max_objects} (code {nbytes})")
+    dev = rings.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    if totals is not None:
+        require_gpu(totals, "rings_valid totals")
+        assert totals.dtype == torch.int64 and totals.numel() == 8 and totals.is_contiguous()
+    valid = torch.empty((max_objects, 8), dtype=torch.int64, device=dev)
+    out = torch.empty(8, dtype=torch.int64, device=dev)
+    _launch("c3d_rings_valid", max_rings * 48 + max_vertices * 56 + max_objects * 128, L.lib().c3d_rings_valid, _p(rings),
+            _p(vertices), _p(counts), max_rings, max_vertices, frac_bits, max_objects, max_id_work, _p(valid), _p(out), _p(totals),
+            _p(ws), _stream())
+    return valid, out
+
+
 def rect_corners(P, d, rect_row):
     """The rectangle of a `rings_hull` rects row on the hull edge that starts at `P` = (x, y) and runs along `d` = (dx, dy):
     `(corners float64 [4, 2], long, short, angle)`.  The corners are P + d t/L (+ n c_max/L) for t = t_min, t_max with n =

@@ -66,6 +66,17 @@ flag` per predicted object (flag 0 scored, 1 no partner, 2 an incomplete or empt
 with one line per stage, `polygons[raw]: pairs polis hausdorff_mean hausdorff_max n_ratio skipped`: the means over the scored
 pairs, `n_ratio` the mean of predicted over labelled vertices, `skipped` the matched pairs that were not scored.
 
+`--validity` (with `--polygons`) tests every polygon against itself, on the device (`c3d_rings_valid`): proper crossings and
+collinear overlaps among the edges of an object, holes included, make it invalid; touches are counted and never disqualify.
+Every feature of `objects/<name>.geojson` gains `valid`, `crossings`, `overlaps` and `touches` of the simplified stage with
+`--simplify`, else of the raw rings; every feature of `objects/<name>.regular.geojson` the same of the regularised stage.  The
+run ends with one line per stage, `validity[raw|simplified|regular]: objects valid invalid unchecked crossings overlaps`; an
+object that could not be checked (rings cut off, or more edge pairs than the call's work cap) is named there as
+`<scene>:<id>` and counts as not valid.  `--simplify_valid` implies `--validity` and leaves every object that is not valid on
+its raw vertices in every ring, as `--simplify_min_iou` does (with both, either one suffices); `--regularize_valid` leaves such
+an object on its simplified rings with `regular: false`, beside `--regularize_min_iou`.  Edges of different objects are never
+compared, and whether a hole lies inside its outline is not examined.
+
 `--tta hflip|flips|d4` is test-time augmentation: every tile is predicted under the two mirror views, the four flips or all
 eight flips and rotations of the square, each view is undone on the device and the views are averaged before the stitch
 (`c3d_scene_gather_views`, `c3d_scene_fold_views`; change3d_amd/infer.py).  `--batch_size` stays the number of model inputs
@@ -176,7 +187,22 @@ def save_objects(path, objects):
     return found, rows
 
 
-def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=None, extra=None):
+EMPTY_ROW = (1, 0, 0, 0, 0, 0, 0, 0)                      # an id past the last one of the ring table: flag 1, nothing to check
+
+
+def validity_properties(row):
+    """The feature properties of one row of a `SceneValidity`: valid iff the object was checked and neither crosses nor overlaps
+    itself; touches (vertex on vertex, vertex inside an edge) are reported and never disqualify."""
+    flag, _, _, _, cross, overlap, touch_vv, touch_ve = (int(v) for v in row)
+    return dict(valid=flag == 0 and cross == 0 and overlap == 0, crossings=cross, overlaps=overlap, touches=touch_vv + touch_ve)
+
+
+def not_valid_ids(rows):
+    """The ids of the rows of a `SceneValidity` (host array [rows, 8]) that are not valid; an unchecked object is one of them."""
+    return {k + 1 for k, row in enumerate(np.asarray(rows).tolist()) if not validity_properties(row)["valid"]}
+
+
+def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=None, extra=None, validity=None, not_valid=None):
     """(FeatureCollection dict, ids left out) from host arrays: `table` [rows, 8] of the objects, `rings` [ring rows, 8] and
     `vertices` [vertices written, 2] of their outlines.  An object is complete iff it has one ring of positive area, every
     ring of it has its vertices (start >= 0) and the signed areas add up to the table's area -- a hole ring cut off by
@@ -187,7 +213,10 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
     `vertices`.  Completeness is judged on the raw rings either way.
     `iou` [rows] (with `simplified`): the IoU of every object with its simplified polygon filled back into pixels; each feature
     gets it as a property, and with `min_iou` an object whose IoU is not above it keeps its raw vertices in every ring.
-    `extra`: id -> further properties of that object's feature (`--shapes`)."""
+    `extra`: id -> further properties of that object's feature (`--shapes`).
+    `validity` [rows, 8]: the rows of `c3d_rings_valid` on the stage that is written (the simplified one with `simplified`);
+    every feature gets `valid`, `crossings`, `overlaps` and `touches`.  `not_valid` (with `simplified`): ids that keep their raw
+    vertices in every ring, as an object below `min_iou` does."""
     table, rings, vertices = np.asarray(table), np.asarray(rings), np.asarray(vertices)
     if simplified is not None:
         rings_s, vertices_s = np.asarray(simplified[0]).tolist(), np.asarray(simplified[1])
@@ -203,6 +232,7 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
             continue
         coords, n_raw, n_out = [], 0, 0
         drifted = simplified is not None and iou is not None and min_iou is not None and not float(iou[k]) > min_iou
+        drifted = drifted or (simplified is not None and not_valid is not None and k + 1 in not_valid)
         for r in outline + [r for r in own if r[3] <= 0]:  # the outline, then the holes in ring order
             ring = vertices[r[1]:r[1] + r[2]].tolist()
             n_raw += len(ring)
@@ -219,8 +249,24 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
                 properties.update(iou=round(float(iou[k]), 4))
         if extra is not None:
             properties.update(extra.get(k + 1, {}))
+        if validity is not None:
+            properties.update(validity_properties(validity[k] if k < len(validity) else EMPTY_ROW))
         features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords}, "properties": properties})
     return {"type": "FeatureCollection", "features": features}, skipped
+
+
+def add_validity(sums, stage, name, found):
+    """Adds the counts of one `SceneValidity` to the run's sums of its stage and returns its rows [K, 8] on the host, K = the
+    largest object id of the ring table.  An object that could not be checked (its rings were cut off, or its edge pairs
+    exceed the work cap) is remembered as `<scene>:<id>` for the closing line."""
+    checked, invalid, empty, incomplete, over, crossings, overlaps, _ = (int(v) for v in found.counts.cpu().tolist())
+    objects = checked + empty + incomplete + over
+    rows = found.valid[:objects].cpu().numpy()
+    s = sums.setdefault(stage, dict(counts=dict(objects=0, checked=0, invalid=0, crossings=0, overlaps=0), unchecked=[]))
+    for key, value in (("objects", objects), ("checked", checked), ("invalid", invalid), ("crossings", crossings), ("overlaps", overlaps)):
+        s["counts"][key] += value
+    s["unchecked"] += [f"{name}:{k + 1}" for k in np.nonzero(rows[:, 0])[0].tolist()]
+    return rows
 
 
 def simplify_ious(objects, fill):
@@ -237,7 +283,7 @@ def simplify_ious(objects, fill):
     return iou, kept, vanished
 
 
-def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=None, extra=None):
+def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=None, extra=None, validity=None, not_valid=None):
     """objects/<name>.geojson; the one read-back of the rings (`simplified`: the second `SceneOutlines` of
     `predict(..., simplify=tol)`, read back with them; `iou`, `min_iou`: see `polygons_geojson`).  Returns the ids that were
     left out."""
@@ -246,7 +292,7 @@ def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=No
     if simplified is not None:
         simplified = (simplified.rings[:ring_rows].cpu().numpy(), simplified.vertices[:int(simplified.counts[3])].cpu().numpy())
     doc, skipped = polygons_geojson(objects.table[:rows].cpu().numpy(), outlines.rings[:ring_rows].cpu().numpy(),
-                                    outlines.vertices[:written].cpu().numpy(), simplified, iou, min_iou, extra)
+                                    outlines.vertices[:written].cpu().numpy(), simplified, iou, min_iou, extra, validity, not_valid)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
         json.dump(doc, f)
@@ -255,14 +301,15 @@ def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=No
     return skipped
 
 
-def regular_geojson(doc, rings, regular, iou=None, min_iou=None):
+def regular_geojson(doc, rings, regular, iou=None, min_iou=None, validity=None, not_valid=None):
     """(FeatureCollection dict, objects regularised, objects on their fallback) for objects/<name>.regular.geojson: the
     features and properties of `doc` (objects/<name>.geojson), each with `regular` and the coordinates of the regularised
     rings, sixteenths of a pixel as floats.  `rings` [ring rows, 8] are the raw rings, `regular` = (rings, vertices) of
     `c3d_rings_regularize`, row for row.  An object keeps the coordinates it has in `doc` and gets `regular: false` where one of
     its rings was copied or has no vertices, where the doubled area of a regularised ring is zero or has the other sign than
     the raw ring's, or where `iou` [rows] (its regularised polygon filled back, against its raw pixels; every feature gets it
-    as `iou`) is not above `min_iou`."""
+    as `iou`) is not above `min_iou`, or where its id is in `not_valid`.  `validity` [rows, 8]: the rows of `c3d_rings_valid` on
+    the regularised rings, which replace the `valid`, `crossings`, `overlaps` and `touches` of `doc`."""
     rings_q, vertices_q = np.asarray(regular[0]).tolist(), np.asarray(regular[1]).astype(np.int64)
     scale = float(1 << REGULAR_FRAC_BITS)
     by_id = {}
@@ -273,6 +320,7 @@ def regular_geojson(doc, rings, regular, iou=None, min_iou=None):
         k = feature["properties"]["id"]
         own = by_id.get(k, [])
         coords, ok = [], not (iou is not None and min_iou is not None and not float(iou[k - 1]) > min_iou)
+        ok = ok and not (not_valid is not None and k in not_valid)
         for r in [r for r in own if r[3] > 0] + [r for r in own if r[3] <= 0]:   # the order of polygons_geojson
             q = rings_q[r[8]]
             if not ok or q[3] != 1 or q[1] < 0 or q[1] + q[2] > len(vertices_q):
@@ -288,20 +336,22 @@ def regular_geojson(doc, rings, regular, iou=None, min_iou=None):
         properties = dict(feature["properties"], regular=ok)
         if iou is not None:
             properties["iou"] = round(float(iou[k - 1]), 4)
+        if validity is not None:
+            properties.update(validity_properties(validity[k - 1] if k - 1 < len(validity) else EMPTY_ROW))
         done += ok
         features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords if ok else feature["geometry"]["coordinates"]},
                          "properties": properties})
     return {"type": "FeatureCollection", "features": features}, done, len(features) - done
 
 
-def save_regular(path, main_path, outlines, regular, iou=None, min_iou=None):
+def save_regular(path, main_path, outlines, regular, iou=None, min_iou=None, validity=None, not_valid=None):
     """objects/<name>.regular.geojson from objects/<name>.geojson, which was just written, and the read-back of a `SceneRegular`."""
     with open(main_path) as f:
         doc = json.load(f)
     ring_rows = int(outlines.counts[1])
     out, done, fallback = regular_geojson(doc, outlines.rings[:ring_rows].cpu().numpy(),
                                           (regular.rings[:ring_rows].cpu().numpy(), regular.vertices[:int(regular.counts[3])].cpu().numpy()),
-                                          iou, min_iou)
+                                          iou, min_iou, validity, not_valid)
     with open(path, "w") as f:
         json.dump(out, f)
     ids = [feat["properties"]["id"] for feat in out["features"]]
@@ -500,6 +550,14 @@ def parse_args(argv=None):
         parser.error("--regularize_min_iou is the fallback threshold of --regularize: it needs --regularize")
     if args.regularize and (not args.polygons or args.simplify is None):
         parser.error("--regularize squares the simplified polygons: it needs --polygons --simplify TOL")
+    if args.simplify_valid and args.simplify is None:
+        parser.error("--simplify_valid is a fallback of --simplify: it needs --simplify")
+    if args.regularize_valid and not args.regularize:
+        parser.error("--regularize_valid is a fallback of --regularize: it needs --regularize")
+    if args.simplify_valid or args.regularize_valid:
+        args.validity = True
+    if args.validity and not args.polygons:
+        parser.error("--validity tests the polygons: it needs --polygons")
     if args.label_polygons and args.task == "SCD":
         parser.error("--label_polygons gives objects with one class each: it serves --task BCD and BDA")
     if args.label_polygons and any((args.label, args.label1, args.label2, args.change)):
@@ -571,7 +629,10 @@ def main(argv=None):
     if args.regularize:
         split["regularize"] = True
         split["regularize_check"] = args.regularize_min_iou is not None
-    squared = dict(objects=0, regular=0, fallback=0, iou_sum=0.0, iou_min=1.0)   # --regularize over all scenes
+    if args.validity:
+        split["validity"] = True
+    validity_sums = {}                                    # --validity over all scenes: stage -> counts, unchecked objects by name
+    squared =dict(objects=0, regular=0, fallback=0, iou_sum=0.0, iou_min=1.0)   # --regularize over all scenes
     drift = dict(objects=0, kept=0, vanished=0, iou_sum=0.0, iou_min=1.0)   # --simplify_check over all scenes
     shape_sums = dict(objects=0, solidity=0.0, rectangularity=0.0)          # --shapes over all scenes
     for name, img, label in scenes(args):
@@ -581,7 +642,13 @@ def main(argv=None):
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, outlines=True,
                               max_rings=args.max_rings, max_vertices=args.max_vertices, simplify=args.simplify, **split)
             simplified, iou, shapes, regular, regular_iou = None, None, None, None, None
-            if args.regularize:           # appended last: the regularised rings, then their check
+            valid_rows = {}                   # stage -> host rows of its `SceneValidity`
+            if args.validity:             # appended last of all: raw, then simplified, then regularised
+                stages_v = ["raw"] + (["simplified"] if args.simplify is not None else []) + (["regular"] if args.regularize else [])
+                out, found_v = out[:-len(stages_v)], out[-len(stages_v):]
+                for stage, v in zip(stages_v, found_v):
+                    valid_rows[stage] = add_validity(validity_sums, stage, name, v)
+            if args.regularize:         # appended last: the regularised rings, then their check
                 if args.regularize_min_iou is not None:
                     out, regular_fill = out[:-1], out[-1]
                 out, regular = out[:-1], out[-1]
@@ -595,13 +662,15 @@ def main(argv=None):
             if args.simplify is not None:
                 out, simplified = out[:-1], out[-1]
             check_split(name, out[-2])
+            written_v = valid_rows.get("simplified" if simplified is not None else "raw")   # of the coordinates that are written
+            bad_v = not_valid_ids(valid_rows["simplified"]) if args.simplify_valid else None
             if shapes is None:
                 cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified,
-                                             iou, args.simplify_min_iou))
+                                             iou, args.simplify_min_iou, None, written_v, bad_v))
             else:
                 props, hull_rings, rect_rings = object_shapes(name, out[-2], shapes)
                 skipped = save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified, iou,
-                                        args.simplify_min_iou, props)
+                                        args.simplify_min_iou, props, written_v, bad_v)
                 cut_off += len(skipped)
                 save_shapes(os.path.join(args.out_dir, "objects", name + ".hulls.geojson"), out[-2], hull_rings, set(skipped))
                 save_shapes(os.path.join(args.out_dir, "objects", name + ".rects.geojson"), out[-2], rect_rings, set(skipped))
@@ -616,7 +685,8 @@ def main(argv=None):
                     regular_iou = simplify_ious(out[-2], regular_fill)[0]
                 main_path = os.path.join(args.out_dir, "objects", name + ".geojson")
                 done, fallback, ids = save_regular(os.path.join(args.out_dir, "objects", name + ".regular.geojson"), main_path, out[-1],
-                                                   regular, regular_iou, args.regularize_min_iou)
+                                                   regular, regular_iou, args.regularize_min_iou, valid_rows.get("regular"),
+                                                   not_valid_ids(valid_rows["regular"]) if args.regularize_valid else None)
                 ious = [float(regular_iou[k - 1]) for k in ids] if regular_iou is not None else []
                 squared = dict(objects=squared["objects"] + len(ids), regular=squared["regular"] + done,
                                fallback=squared["fallback"] + fallback, iou_sum=squared["iou_sum"] + sum(ious),
@@ -693,6 +763,11 @@ def main(argv=None):
         print(f"regularize: objects = {squared['objects']} regular = {squared['regular']} fallback = {squared['fallback']} "
               f"iou_mean = {squared['iou_sum'] / max(squared['objects'], 1) if checked else 0.0:.4f} "
               f"iou_min = {squared['iou_min'] if checked else 0.0:.4f}")
+    for stage, v in validity_sums.items():
+        c = v["counts"]
+        print(f"validity[{stage}]: objects = {c['objects']} valid = {c['checked'] - c['invalid']} invalid = {c['invalid']} "
+              f"unchecked = {c['objects'] - c['checked']} crossings = {c['crossings']} overlaps = {c['overlaps']}" +
+              (f" (unchecked: {', '.join(v['unchecked'])})" if v["unchecked"] else ""))
     if cut_off:
         raise SystemExit(f"{cut_off} objects have no polygon: their rings did not fit; raise --max_rings / --max_vertices")
     if not scored:
@@ -759,6 +834,13 @@ def build_parser():
     p.add_argument("--regularize_min_iou", type=unit_interval, default=None, metavar="F", help="--regularize: fill the regularised "
                    "polygons back into pixels on the device; an object whose IoU with them is not above F, in [0, 1], keeps its "
                    "simplified rings in objects/<name>.regular.geojson; every feature there gets `iou`")
+    p.add_argument("--validity", action="store_true", help="--polygons: also test every polygon against itself on the device "
+                   "(c3d_rings_valid): `valid`, `crossings`, `overlaps` and `touches` on every feature, of the coordinates that are "
+                   "written, and a closing `validity[stage]:` line for the raw, the simplified and the regularised rings")
+    p.add_argument("--simplify_valid", action="store_true", help="--simplify: implies --validity; an object whose simplified polygon "
+                   "crosses or overlaps itself, or could not be checked, keeps its raw vertices")
+    p.add_argument("--regularize_valid", action="store_true", help="--regularize: implies --validity; an object whose regularised "
+                   "polygon crosses or overlaps itself, or could not be checked, keeps its simplified rings")
     p.add_argument("--label_polygons", default="", metavar="FILE", help="BCD, BDA: the ground truth as polygons, a GeoJSON FeatureCollection "
                    "in pixel coordinates or an xBD label JSON, instead of label rasters; with --file_root a directory of <name>.json / "
                    "<name>.geojson.  Filled on the device (c3d_rings_fill); one ground-truth object per feature")

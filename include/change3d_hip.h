@@ -989,6 +989,70 @@ int c3d_rings_polis(const int32_t* rings_p, const int32_t* vertices_p, const int
                     const int32_t* match_p, int32_t max_p, int32_t max_g, int64_t max_pair_work, double* pair, int32_t* pair_n,
                     int64_t* counts, double* sums, int64_t* totals, double* total_sums, void* ws, void* stream);
 
+/* Polygon validity (csrc/scene_valid.hip): for every object id of ONE ring table the proper crossings, collinear overlaps and
+ * touches among its own edges, while the table stays in HBM.  One memset and 10 launches on `stream`, nothing is read back by
+ * the host, no workgroup waits for another, every loop is capped, and no workspace word is read before the call wrote it.
+ * Everything is an integer: |coordinate| <= 32768 * 2^8 = 2^23, differences below 2^25, every cross or dot product below 2^50;
+ * nothing is rounded anywhere, and every sum is an integer atomic or a ballot count: the result is exact, equal from run to run
+ * and on a dirty workspace, and independent of the tier.  The rule:
+ *   table       a ring table in the layout of c3d_scene_outlines: rings i32 [max_rings][8] with (id, start, n) in columns 0..2
+ *               (the others are ignored), vertices i32 [max_vertices][2] (8-byte aligned), counts i32 [5]; frac_bits in [0, 8]
+ *               only sets the coordinate range, |coordinate| <= 32768 * 2^frac_bits.  The ids are 1 .. max_ids
+ *   rows used   the rule of c3d_rings_polis for one side: a row r < clamp(counts[1], 0, max_rings) whose id lies in [1, max_ids]
+ *               is used iff start >= 0, n >= 0, start + n <= clamp(counts[3], 0, max_vertices) and every coordinate of the ring
+ *               is in range.  A used ring with n < 3 contributes nothing.  An id that has a row with start < 0, or any other row
+ *               that is not used, is INCOMPLETE; so is an id with more than RING_LIMIT rings of n >= 3, and an id of a table
+ *               whose rows share vertices once the vertices of the ids up to it add up to more than max_vertices.  Rows whose
+ *               id lies outside [1, max_ids] are ignored.  C3D_OUTLINE_ST_BAD_COUNTS in counts[4] empties the table.  K = the
+ *               largest id in [1, max_ids] of a row r < clamp(counts[1], 0, max_rings), used or not
+ *   edges       E(id) = the edges (v[k], v[(k+1) mod n]) of its used rings with n >= 3, the closing edge included.  An edge with
+ *               a == b is DEGENERATE: it is counted and takes part in no pair.  m = the number of the other, live, edges
+ *   adjacent    two edges of the same ring whose indices differ by 1 modulo n.  In a triangle every pair is adjacent
+ *   pair        for live edges (a, b) and (c, d): o1 = sign((b-a) x (c-a)), o2 = sign((b-a) x (d-a)), o3 = sign((d-c) x (a-c)),
+ *               o4 = sign((d-c) x (b-c)).  The first class that applies:
+ *                 cross     o1 o2 < 0 and o3 o4 < 0
+ *                 overlap   all four are zero and the collinear segments share more than one point: with t(p) = (p-a).(b-a)
+ *                           and L = (b-a).(b-a), max(min(t(c), t(d)), 0) < min(max(t(c), t(d)), L).  Adjacent pairs ARE
+ *                           tested: a spike p -> q -> p' folded back on itself is an overlap
+ *                 touch     the segments share exactly one point.  For an adjacent pair that point is their joint and is NOT
+ *                           counted.  Otherwise touch_vv if the point is an end point of both edges, touch_ve if an end point
+ *                           of one lies strictly inside the other
+ *                 nothing   otherwise
+ *   checked     an id <= K is checked iff it is complete, m >= 1 and m (m - 1) / 2 <= max_id_work; otherwise every pair count
+ *               of its row is 0.  An id is VALID iff it is checked and cross == 0 and overlap == 0
+ * Touches are reported and never disqualify: the 8-connected pinches of c3d_scene_outlines are vertex-vertex touches, and raw
+ * traced rings are valid.  What this does NOT decide:
+ *   - a ring that passes from one side of another ring to its other side exactly through a vertex is counted as touches only;
+ *   - whether a hole still lies inside its shell is not examined;
+ *   - edges of different ids are never compared.
+ * Inputs (device): the table; max_id_work >= 0, the most edge pairs one id may cost (there is no spatial index: this cap stands
+ * in for one, as max_pair_work does in c3d_rings_polis; a bounding-box reject in front of the four products is the only pruning
+ * and changes no count).
+ * Outputs:
+ *   valid      i64 [max_ids][8], row id-1 = (flag, rings, m, degenerate, cross, overlap, touch_vv, touch_ve); flag 0 checked,
+ *              1 empty (no used ring with n >= 3, or no live edge), 2 incomplete, 3 over max_id_work.  rings, m and degenerate
+ *              are 0 for an incomplete id.  Rows past K are 0, written by the call
+ *   counts     i64 [8] = (checked, invalid, empty, incomplete, over work, sum cross, sum overlap, status) over the ids 1 .. K,
+ *              the sums over the checked ids; invalid = checked and not valid; status = counts[4] of the table as it came
+ *   totals     i64 [8] or NULL: counts[0..6] are ADDED into it and status is OR-ed into totals[7] by one thread at the end of
+ *              the last launch, so calls on one stream accumulate in stream order (the convention of c3d_objects_match).  The
+ *              caller zeroes it once
+ *   ws         c3d_rings_valid_ws_bytes(...) bytes, 256-byte aligned; a dirty one gives the same result
+ * Tiers.  An id with at most out[0] edges (degenerate ones included) runs in one wave: a lane per edge, the other edge by
+ * shuffle, counts by ballot.  A larger id is cut into chunks of out[1] edges; the job (id, chunk i) of an id of c chunks
+ * compares chunk i with the chunks i, i+1, .., i + floor(c/2) (mod c), staged through LDS out[2] edges at a time, so every
+ * unordered pair of chunks belongs to exactly one job; the job table holds ceil(max_vertices / out[1]) + max_ids jobs, which
+ * suffices for every table.
+ * Refused before anything is enqueued (C3D_E_BADARG): a NULL pointer other than totals / stream, frac_bits outside [0, 8],
+ * a max below 1, max_id_work < 0.
+ * c3d_rings_valid_limits: out[0] = the most edges of an id in the wave tier, out[1] = the edges of a chunk, out[2] = the edges
+ * of an LDS tile, out[3] = RING_LIMIT, out[4] = the most vertices of a ring that one wave checks and regroups.  Host only.     */
+void c3d_rings_valid_limits(int32_t out[5]);
+int64_t c3d_rings_valid_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_ids);   /* < 0: C3D_E_* */
+int c3d_rings_valid(const int32_t* rings, const int32_t* vertices, const int32_t* counts_in, int32_t max_rings,
+                    int32_t max_vertices, int32_t frac_bits, int32_t max_ids, int64_t max_id_work, int64_t* valid,
+                    int64_t* counts, int64_t* totals, void* ws, void* stream);
+
 /* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
  * in HBM.  The rule:
  *   sites       the pixels with mask == 0; with C3D_EDT_INVERT (bit 0 of flags) the pixels with mask != 0
