@@ -1,0 +1,660 @@
+// Polygon conflicts between the objects of a ring table: the proper crossings, collinear overlaps and touches of every pair
+// of live edges of DIFFERENT ids, while the table stays in HBM.  The rule is the header's (include/change3d_hip.h); this file
+// is one way to compute it.  The all-pairs walk across ids is quadratic in the edges of the whole scene, so the edges are
+// binned into a uniform grid of square cells and only the entries of one cell are compared.  The rows pass, the ids scan and
+// the pair predicate are those of csrc/scene_valid.hip (csrc/scene_rings.h).  Everything is an integer, every sum an integer
+// atomic or a ballot count, and nothing depends on the order in which entries land in a cell.  No workgroup waits for
+// another, nothing is read back, every loop is capped.
+//
+//   1 rows     a wave per ring row: the used rows, the incomplete ids, K                                   (scene_rings.h)
+//     check    the coordinates of the rings above BIG_RING vertices                                        (scene_rings.h)
+//   2 ids      one workgroup: which ids are complete                                                       (scene_rings.h)
+//   3 edges    a wave per used row of a complete id: its live edges go to one flat list (id, a, b), 64 at a time behind one
+//              atomic; m per id; the bounding box of all of them
+//     edges    the same for the rings above BIG_RING: many workgroups, 64 edges of a wave at a time
+//   4 cost     a thread per edge: for every candidate shift s the cells its bounding box would cover; a saturating sum per
+//              wave, then one 64-bit atomic per wave and candidate
+//   5 choose   one wave, a lane per candidate: the smallest s within the entry and the cell budget, both taken per live edge:
+//              a table that fills a fraction of max_vertices gets a grid sized for what it holds
+//   6 count    a thread per edge: one atomic per covered cell
+//   7 starts   a thread per cell: where its entries go (a wave scan, one atomic per wave), its share of `work`, and the jobs
+//              of a cell above WAVE_LIMIT entries
+//   8 scatter  a thread per edge: its index into every covered cell
+//   9 rows     a thread per id: flag, m and zeros; the rows past K
+//  10 wave     a wave per 64 cells: each cell of 2 .. WAVE_LIMIT entries in turn, a lane per entry, the partner by shuffle
+//  11 jobs     a workgroup per (cell, chunk i): a thread per entry, the chunks i, i+1, .., i + floor(c/2) (mod c) through LDS
+//  12 tail     one workgroup: the partner column, counts, info, totals
+//
+// A pair of entries of one cell is evaluated iff the ids differ, the bounding boxes meet, and the cell holds the lower corner
+// of the boxes' intersection: that point lies in both boxes, so exactly one cell that holds both edges evaluates the pair.
+#include <climits>
+#include <type_traits>
+
+#include "scene_rings.h"
+
+namespace {
+
+using namespace c3d_rings;
+
+constexpr int WAVE_LIMIT = 64;                             // entries of a cell in the wave tier: a lane each
+constexpr int CHUNK = 256;                                 // entries of a chunk: a thread each
+constexpr int TILE = 256;                                  // entries of an LDS tile: 20 bytes each; a chunk is one tile
+constexpr int BUDGET_E = 2;                                // entries the grid may hold per live edge, so per vertex of max_vertices
+constexpr int BUDGET_C = 4;                                // cells the grid may have per live edge, so per vertex of max_vertices
+constexpr int N_SHIFT = 26;                                // candidate shifts 0 .. 25: extents stay below 2^25, so s = 25 is one cell
+constexpr int BLOCK_T = 256;
+constexpr int MAX_GRID = 4096;
+constexpr int BIAS = 1 << 24;                              // above every |coordinate|: biased values are positive, 0 means none
+constexpr u64 NO_PARTNER = ~0ull;
+
+// 32-bit words of the workspace header (512 bytes, zeroed by the call's memset); WS_K, WS_JOBS and WS_BIG are scene_rings.h's
+enum { WS_EDGES = 4, WS_LO_X = 5, WS_LO_Y = 6, WS_HI_X = 7, WS_HI_Y = 8, WS_SHIFT = 9, WS_CX = 10, WS_CY = 11, WS_X0 = 12,
+       WS_Y0 = 13, WS_AT = 14 };
+// 64-bit words of the header, counted from byte 64
+enum { WQ_WORK = 0, WQ_ENTRIES = 1, WQ_SUM = 2 /* cross, same, opposite, vv, ve */, WQ_COST = 8 /* N_SHIFT of them */ };
+enum { COL_FLAG = 0, COL_PARTNER = 1, COL_M = 2, COL_CROSS = 3, COL_SAME = 4, COL_OPP = 5, COL_VV = 6, COL_VE = 7 };
+enum { HIT_CROSS = 0, HIT_SAME = 1, HIT_OPP = 2, HIT_VV = 3, HIT_VE = 4, HIT_NONE = 5 };
+
+struct Tab : Rows {
+  uint32_t* id_live;                                       // [max_ids] live edges of the id
+  int4* e_xy;                                              // [max_vertices] (a.x, a.y, b.x, b.y) of the live edges, in any order
+  uint32_t* e_id;                                          // [max_vertices]
+  uint32_t* cell_n;                                        // [cap_c] entries of the cell
+  uint32_t* cell_at;                                       // [cap_c] where they start; after the scatter, where they end
+  uint32_t* entry;                                         // [cap_e] edge indices grouped by cell
+  uint2* jobs;                                             // [cap_j] (cell, chunk)
+  int64_t cap_e, cap_c, cap_j;
+  int64_t max_work;
+};
+
+struct Plan {
+  Tab t;                                                   // offsets until bind() adds the base
+  int64_t zero_bytes, bytes;
+};
+
+Plan plan_of(int64_t max_rings, int64_t max_vertices, int64_t max_ids) {
+  Plan pl{};
+  auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+  int64_t at = 512;
+  auto take = [&](auto*& p, int64_t bytes) {
+    p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(at);
+    at += up(bytes);
+  };
+  Tab& t = pl.t;
+  // both budgets hold for one cell whatever the table holds (at most max_vertices live edges, one entry each), and a grid
+  // within the budgets of the live edges is within those of max_vertices, so the sizes are a function of the maxima alone;
+  // the caps keep every index in 32 bits
+  t.cap_e = BUDGET_E * max_vertices < 0xFFFFFFF0ll ? BUDGET_E * max_vertices : 0xFFFFFFF0ll;
+  t.cap_c = BUDGET_C * max_vertices < 0x7FFFFFF0ll ? BUDGET_C * max_vertices : 0x7FFFFFF0ll;
+  // a cell above WAVE_LIMIT entries has ceil(n / CHUNK) jobs: at most entries / CHUNK + entries / (WAVE_LIMIT + 1) in all
+  t.cap_j = t.cap_e / CHUNK + t.cap_e / (WAVE_LIMIT + 1) + 1;
+  take(t.id_rings, max_ids * 4);                           // zeroed part first
+  take(t.id_verts, max_ids * 8);
+  take(t.id_flags, max_ids * 4);
+  take(t.id_live, max_ids * 4);
+  take(t.cell_n, t.cap_c * 4);
+  pl.zero_bytes = at;
+  take(t.kind, max_rings);
+  take(t.big, max_rings * 4);
+  take(t.id_list, max_ids * 4);
+  take(t.id_start, max_ids * 4);
+  take(t.e_xy, max_vertices * 16);
+  take(t.e_id, max_vertices * 4);
+  take(t.cell_at, t.cap_c * 4);
+  take(t.entry, t.cap_e * 4);
+  take(t.jobs, t.cap_j * 8);
+  pl.bytes = at;
+  t.max_rings = (int)max_rings; t.max_vertices = (int)max_vertices; t.max_ids = (int)max_ids;
+  return pl;
+}
+
+template <class T> void rebase(T*& p, char* base) { p = reinterpret_cast<T*>(base + reinterpret_cast<intptr_t>(p)); }
+void bind(Tab& t, char* base) {
+  rebase(t.kind, base); rebase(t.big, base); rebase(t.id_rings, base); rebase(t.id_verts, base); rebase(t.id_flags, base);
+  rebase(t.id_list, base); rebase(t.id_start, base); rebase(t.id_live, base); rebase(t.e_xy, base); rebase(t.e_id, base);
+  rebase(t.cell_n, base); rebase(t.cell_at, base); rebase(t.entry, base); rebase(t.jobs, base);
+}
+
+__device__ __forceinline__ u64* quad(uint32_t* header) { return reinterpret_cast<u64*>(header + 16); }
+__device__ __forceinline__ const u64* quad(const uint32_t* header) { return reinterpret_cast<const u64*>(header + 16); }
+__device__ __forceinline__ uint32_t edges_of(const Tab& s, const uint32_t* header) {
+  return min(header[WS_EDGES], (uint32_t)s.max_vertices);
+}
+__device__ __forceinline__ bool over_work(const Tab& s, const uint32_t* header) { return quad(header)[WQ_WORK] > (u64)s.max_work; }
+
+// the grid as the later launches read it
+struct Grid {
+  int shift, x0, y0;
+  uint32_t cx, cy;
+};
+__device__ __forceinline__ Grid grid_of(const uint32_t* header) {
+  Grid g;
+  g.shift = (int)header[WS_SHIFT]; g.x0 = (int)header[WS_X0]; g.y0 = (int)header[WS_Y0];
+  g.cx = header[WS_CX]; g.cy = header[WS_CY];
+  return g;
+}
+// the cells (x0 .. x1, y0 .. y1) that the bounding box of e covers; e lies inside the box of all edges, so no index leaves the grid
+__device__ __forceinline__ void span_of(const Grid& g, int4 e, uint32_t& x0, uint32_t& x1, uint32_t& y0, uint32_t& y1) {
+  x0 = (uint32_t)(min(e.x, e.z) - g.x0) >> g.shift; x1 = (uint32_t)(max(e.x, e.z) - g.x0) >> g.shift;
+  y0 = (uint32_t)(min(e.y, e.w) - g.y0) >> g.shift; y1 = (uint32_t)(max(e.y, e.w) - g.y0) >> g.shift;
+  x1 = min(x1, g.cx - 1u); y1 = min(y1, g.cy - 1u);        // cannot bind: the box was taken over these edges
+}
+
+// ---------------------------------------------------------------------------------------------------------- 1, 2: shared
+__global__ __launch_bounds__(256) void conflicts_rows_kernel(Tab s, uint32_t* __restrict__ header) { rows_pass(s, header); }
+__global__ __launch_bounds__(256) void conflicts_check_big_kernel(Tab s, const uint32_t* __restrict__ header) {
+  check_big_pass(s, header);
+}
+__global__ __launch_bounds__(SCAN_T) void conflicts_ids_kernel(Tab s, const uint32_t* __restrict__ header) {
+  extern __shared__ u64 part_ids[];                        // [2][SCAN_T / 64]
+  ids_pass(s, header, reinterpret_cast<u64(*)[SCAN_T / 64]>(part_ids));
+}
+
+// -------------------------------------------------------------------------------------------------------------- 3: edges
+// What a wave keeps while it walks: the box of its live edges, folded into the header once at the end.
+struct Box {
+  int lo_x, lo_y, hi_x, hi_y;                              // biased: BIAS - min and BIAS + max, 0 where nothing was seen
+};
+__device__ __forceinline__ void box_out(Box b, uint32_t* header) {
+  for (int o = 32; o > 0; o >>= 1) {
+    b.lo_x = max(b.lo_x, __shfl_xor(b.lo_x, o, 64)); b.lo_y = max(b.lo_y, __shfl_xor(b.lo_y, o, 64));
+    b.hi_x = max(b.hi_x, __shfl_xor(b.hi_x, o, 64)); b.hi_y = max(b.hi_y, __shfl_xor(b.hi_y, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0 && b.lo_x) {
+    atomicMax(header + WS_LO_X, (uint32_t)b.lo_x); atomicMax(header + WS_LO_Y, (uint32_t)b.lo_y);
+    atomicMax(header + WS_HI_X, (uint32_t)b.hi_x); atomicMax(header + WS_HI_Y, (uint32_t)b.hi_y);
+  }
+}
+// 64 edges j0 + lane of the ring (start, n) of `id`, the same j0 in every lane of the wave: the live ones are appended
+__device__ __forceinline__ uint32_t emit64(const Tab& s, uint32_t* header, int id, int64_t start, int n, int64_t j0, Box& box) {
+  const int lane = threadIdx.x & 63;
+  const int64_t j = j0 + lane;
+  int4 e = make_int4(0, 0, 0, 0);
+  if (j < n) {
+    const int2 a = s.vertices[start + j], b = s.vertices[start + (j + 1 < n ? j + 1 : 0)];
+    e = make_int4(a.x, a.y, b.x, b.y);
+  }
+  const bool live = live_of(e);
+  const u64 mask = __ballot(live);
+  const uint32_t cnt = (uint32_t)__popcll(mask);
+  if (!cnt) return 0;
+  uint32_t base = 0;
+  if (lane == 0) base = atomicAdd(header + WS_EDGES, cnt);
+  base = (uint32_t)__shfl((int)base, 0);
+  if (live) {
+    const u64 at = (u64)base + (u64)__popcll(mask & ((1ull << lane) - 1ull));
+    if (at < (u64)s.max_vertices) {                        // cannot fail: the complete ids fit (ids_pass)
+      s.e_xy[at] = e;
+      s.e_id[at] = (uint32_t)id;
+    }
+    box.lo_x = max(box.lo_x, BIAS - min(e.x, e.z)); box.lo_y = max(box.lo_y, BIAS - min(e.y, e.w));
+    box.hi_x = max(box.hi_x, BIAS + max(e.x, e.z)); box.hi_y = max(box.hi_y, BIAS + max(e.y, e.w));
+  }
+  return cnt;
+}
+
+__global__ __launch_bounds__(256) void conflicts_edges_kernel(Tab s, uint32_t* __restrict__ header) {
+  const int rows = rows_of(s), lane = threadIdx.x & 63;
+  Box box = {0, 0, 0, 0};
+  for (int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6); r < rows; r += gridDim.x * 4) {   // r is uniform over the wave
+    if (s.kind[r] != ROW_USED) continue;
+    const int id = s.rings[(int64_t)r * 8], n = s.rings[(int64_t)r * 8 + 2];
+    const int64_t start = s.rings[(int64_t)r * 8 + 1];
+    if (!s.id_rings[id - 1] || n > BIG_RING) continue;     // the id became incomplete; a long ring is the next kernel's
+    uint32_t m = 0;
+    for (int j0 = 0; j0 < n; j0 += 64) m += emit64(s, header, id, start, n, j0, box);
+    if (m && lane == 0) atomicAdd(s.id_live + (id - 1), m);
+  }
+  box_out(box, header);
+}
+
+__global__ __launch_bounds__(256) void conflicts_edges_big_kernel(Tab s, uint32_t* __restrict__ header) {
+  const uint32_t n_big = min(header[WS_BIG], (uint32_t)s.max_rings);
+  const int lane = threadIdx.x & 63;
+  Box box = {0, 0, 0, 0};
+  for (uint32_t li = 0; li < n_big; ++li) {
+    const int r = (int)s.big[li];
+    if (s.kind[r] != ROW_USED) continue;
+    const int id = s.rings[(int64_t)r * 8], n = s.rings[(int64_t)r * 8 + 2];
+    const int64_t start = s.rings[(int64_t)r * 8 + 1];
+    if (!s.id_rings[id - 1]) continue;
+    uint32_t m = 0;
+    for (int64_t j0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; j0 < n; j0 += (int64_t)gridDim.x * 256)
+      m += emit64(s, header, id, start, n, j0, box);
+    if (m && lane == 0) atomicAdd(s.id_live + (id - 1), m);
+  }
+  box_out(box, header);
+}
+
+// --------------------------------------------------------------------------------------------------------------- 4: cost
+// Per candidate s the entries that s would cost.  A sum only has to tell "within the budget" from "above it": an edge adds at
+// most budget + 1 and a wave keeps its sum at or below that, so with at most 4 MAX_GRID waves no 64-bit counter overflows.
+__device__ __forceinline__ u64 entry_budget(const Tab& s, uint32_t n) { return min((u64)BUDGET_E * n, (u64)s.cap_e); }
+__device__ __forceinline__ u64 cell_budget(const Tab& s, uint32_t n) { return min((u64)BUDGET_C * max(n, 1u), (u64)s.cap_c); }
+__global__ __launch_bounds__(256) void conflicts_cost_kernel(Tab s, uint32_t* __restrict__ header) {
+  const uint32_t n = edges_of(s, header);
+  const int lane = threadIdx.x & 63;
+  if ((uint32_t)blockIdx.x * 256u >= n) return;             // the grid is sized by max_vertices
+  const int x0 = BIAS - (int)header[WS_LO_X], y0 = BIAS - (int)header[WS_LO_Y];
+  const u64 top = entry_budget(s, n) + 1ull;
+  u64 cost[N_SHIFT];
+#pragma unroll
+  for (int k = 0; k < N_SHIFT; ++k) cost[k] = 0;
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int4 e = s.e_xy[i];
+    const uint32_t ax = (uint32_t)(min(e.x, e.z) - x0), bx = (uint32_t)(max(e.x, e.z) - x0);
+    const uint32_t ay = (uint32_t)(min(e.y, e.w) - y0), by = (uint32_t)(max(e.y, e.w) - y0);
+#pragma unroll
+    for (int k = 0; k < N_SHIFT; ++k) {
+      const u64 c = (u64)((bx >> k) - (ax >> k) + 1u) * (u64)((by >> k) - (ay >> k) + 1u);   // below 2^50
+      cost[k] = min(cost[k] + min(c, top), top);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < N_SHIFT; ++k) {
+    u64 v = cost[k];
+    for (int o = 32; o > 0; o >>= 1) v = min(v + shfl64(v, lane ^ o), top);
+    if (lane == 0 && v) atomicAdd(quad(header) + WQ_COST + k, v);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- 5: choose
+__global__ __launch_bounds__(64) void conflicts_choose_kernel(Tab s, uint32_t* __restrict__ header) {
+  const int k = threadIdx.x;
+  const uint32_t n = edges_of(s, header);
+  int x0 = 0, y0 = 0;
+  uint32_t wx = 0, wy = 0;                                 // the extent of the box: below 2^25
+  if (n) {
+    x0 = BIAS - (int)header[WS_LO_X]; y0 = BIAS - (int)header[WS_LO_Y];
+    wx = (uint32_t)((int)header[WS_HI_X] - BIAS - x0); wy = (uint32_t)((int)header[WS_HI_Y] - BIAS - y0);
+  }
+  bool ok = false;
+  u64 cells = 0, cost = 0;
+  if (k < N_SHIFT) {
+    cells = (u64)((wx >> k) + 1u) * (u64)((wy >> k) + 1u);
+    cost = quad(header)[WQ_COST + k];
+    ok = cost <= entry_budget(s, n) && cells <= cell_budget(s, n);
+  }
+  const u64 fit = __ballot(ok);
+  const int pick = fit ? __ffsll((long long)fit) - 1 : N_SHIFT - 1;   // s = 25 always fits: one cell, an entry per edge
+  if (k == pick) {
+    header[WS_SHIFT] = (uint32_t)pick;
+    header[WS_CX] = (wx >> pick) + 1u;
+    header[WS_CY] = (wy >> pick) + 1u;
+    header[WS_X0] = (uint32_t)x0;
+    header[WS_Y0] = (uint32_t)y0;
+    quad(header)[WQ_ENTRIES] = min(cost, entry_budget(s, n));
+  }
+}
+
+// -------------------------------------------------------------------------------------------------------------- 6: count
+__global__ __launch_bounds__(256) void conflicts_count_kernel(Tab s, const uint32_t* __restrict__ header) {
+  const uint32_t n = edges_of(s, header);
+  const Grid g = grid_of(header);
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    uint32_t x0, x1, y0, y1;
+    span_of(g, s.e_xy[i], x0, x1, y0, y1);
+    for (uint32_t y = y0; y <= y1; ++y)                    // at most cap_e cells in all: the chosen s is within the budget
+      for (uint32_t x = x0; x <= x1; ++x) atomicAdd(s.cell_n + ((u64)y * g.cx + x), 1u);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- 7: starts
+__global__ __launch_bounds__(256) void conflicts_starts_kernel(Tab s, uint32_t* __restrict__ header) {
+  const Grid g = grid_of(header);
+  const u64 cells = (u64)g.cx * g.cy;                      // at most cap_c
+  const int lane = threadIdx.x & 63;
+  u64 work = 0;
+  for (u64 c0 = ((u64)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; c0 < cells; c0 += (u64)gridDim.x * 256) {   // uniform over the wave
+    const u64 c = c0 + lane;
+    const uint32_t cnt = c < cells ? s.cell_n[c] : 0u;
+    uint32_t inc = cnt;
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t t = (uint32_t)__shfl((int)inc, lane >= d ? lane - d : lane);
+      if (lane >= d) inc += t;
+    }
+    uint32_t base = 0;
+    if (lane == 63 && inc) base = atomicAdd(header + WS_AT, inc);
+    base = (uint32_t)__shfl((int)base, 63);
+    if (c < cells) s.cell_at[c] = base + inc - cnt;
+    work += (u64)cnt * (u64)(cnt ? cnt - 1u : 0u) / 2ull;   // cnt < 2^31: an edge enters a cell once
+    if (cnt > (uint32_t)WAVE_LIMIT) {
+      const uint32_t chunks = (cnt + CHUNK - 1) / CHUNK;
+      const uint32_t at = atomicAdd(header + WS_JOBS, chunks);
+      for (uint32_t i = 0; i < chunks; ++i)                // at most cap_e / CHUNK + 1 steps
+        if ((u64)at + i < (u64)s.cap_j) s.jobs[at + i] = make_uint2((uint32_t)c, i);   // cannot fail: see plan_of
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) work += shfl64(work, lane ^ o);
+  if (lane == 0 && work) atomicAdd(quad(header) + WQ_WORK, work);
+}
+
+// ------------------------------------------------------------------------------------------------------------ 8: scatter
+__global__ __launch_bounds__(256) void conflicts_scatter_kernel(Tab s, const uint32_t* __restrict__ header) {
+  if (over_work(s, header)) return;
+  const uint32_t n = edges_of(s, header);
+  const Grid g = grid_of(header);
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    uint32_t x0, x1, y0, y1;
+    span_of(g, s.e_xy[i], x0, x1, y0, y1);
+    for (uint32_t y = y0; y <= y1; ++y)
+      for (uint32_t x = x0; x <= x1; ++x) {
+        const uint32_t at = atomicAdd(s.cell_at + ((u64)y * g.cx + x), 1u);
+        if ((u64)at < (u64)s.cap_e) s.entry[at] = i;       // cannot fail: the counts are those of kernel 6
+      }
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- 9: rows
+__global__ __launch_bounds__(256) void conflicts_init_kernel(Tab s, const uint32_t* __restrict__ header, u64* __restrict__ conflict) {
+  const int top = clampi((int)header[WS_K], 0, s.max_ids);
+  const bool over = over_work(s, header);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < s.max_ids; i += (int64_t)gridDim.x * 256) {
+    u64* row = conflict + i * 8;
+    u64 flag = 0, m = 0, partner = 0;
+    if (i < top) {
+      m = s.id_live[i];
+      if (s.id_flags[i] & ID_INCOMPLETE) { flag = 2; m = 0; }
+      else if (m == 0) flag = 1;
+      else if (over) flag = 3;
+      else partner = NO_PARTNER;                           // what atomicMin starts from; the tail turns it into 0
+    }
+    row[COL_FLAG] = flag; row[COL_PARTNER] = partner; row[COL_M] = m;
+    for (int k = COL_CROSS; k < 8; ++k) row[k] = 0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------- 10, 11: pairs
+// one entry as the pair kernels hold it
+struct Ent {
+  int4 e;
+  uint32_t id;                                             // 0: no entry
+};
+// the header's classes for a pair of different ids: cross, same, opposite, touch_vv, touch_ve
+__device__ __forceinline__ int hit_class(int4 p, int4 q) {
+  const int cls = pair_class(p, q, false);
+  if (cls == PAIR_NONE) return HIT_NONE;
+  if (cls == PAIR_CROSS) return HIT_CROSS;
+  if (cls == PAIR_VV) return HIT_VV;
+  if (cls == PAIR_VE) return HIT_VE;
+  const int64_t dot = (int64_t)(p.z - p.x) * (q.z - q.x) + (int64_t)(p.w - p.y) * (q.w - q.y);   // below 2^51; never 0 here
+  return dot > 0 ? HIT_SAME : HIT_OPP;
+}
+// does this cell evaluate the pair: different ids, boxes that meet, and the lower corner of their intersection in the cell
+__device__ __forceinline__ bool owned(const Grid& g, uint32_t cell_x, uint32_t cell_y, const Ent& p, const Ent& q) {
+  if (!p.id || !q.id || p.id == q.id || !boxes_meet(p.e, q.e)) return false;
+  const int px = max(min(p.e.x, p.e.z), min(q.e.x, q.e.z)), py = max(min(p.e.y, p.e.w), min(q.e.y, q.e.w));
+  return ((uint32_t)(px - g.x0) >> g.shift) == cell_x && ((uint32_t)(py - g.y0) >> g.shift) == cell_y;
+}
+// Adds 1 to column `col` of the row of `id` for every lane with `hit`; the lanes that share the first such lane's id are
+// counted by one ballot and added by one atomic.  Called by every lane of the wave.
+__device__ __forceinline__ void wave_add(u64* __restrict__ conflict, uint32_t id, int col, bool hit) {
+  const u64 mask = __ballot(hit);
+  if (!mask) return;
+  const int lane = threadIdx.x & 63, leader = __ffsll((long long)mask) - 1;
+  const uint32_t lid = (uint32_t)__shfl((int)id, leader);
+  const u64 same = __ballot(hit && id == lid);
+  if (lane == leader) atomicAdd(conflict + (u64)(lid - 1) * 8 + col, (u64)__popcll(same));
+  else if (hit && id != lid) atomicAdd(conflict + (u64)(id - 1) * 8 + col, 1ull);
+}
+// what every lane of a wave does with the class of its pair (HIT_NONE where it had none): both rows, both partner columns,
+// and the lane's own tally of pairs, each counted once
+__device__ __forceinline__ void record(u64* __restrict__ conflict, uint32_t id_p, uint32_t id_q, int hit, uint32_t (&tally)[5]) {
+  if (!__any(hit != HIT_NONE)) return;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    wave_add(conflict, id_p, COL_CROSS + k, hit == k);
+    wave_add(conflict, id_q, COL_CROSS + k, hit == k);
+    tally[k] += hit == k;
+  }
+  if (hit == HIT_CROSS || hit == HIT_SAME) {
+    atomicMin(conflict + (u64)(id_p - 1) * 8 + COL_PARTNER, (u64)id_q);
+    atomicMin(conflict + (u64)(id_q - 1) * 8 + COL_PARTNER, (u64)id_p);
+  }
+}
+__device__ __forceinline__ void tally_out(uint32_t (&tally)[5], uint32_t* header) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    u64 v = tally[k];
+    for (int o = 32; o > 0; o >>= 1) v += shfl64(v, lane ^ o);
+    if (lane == 0 && v) atomicAdd(quad(header) + WQ_SUM + k, v);
+  }
+}
+
+__global__ __launch_bounds__(256) void conflicts_wave_kernel(Tab s, uint32_t* __restrict__ header, u64* __restrict__ conflict) {
+  if (over_work(s, header)) return;
+  const Grid g = grid_of(header);
+  const u64 cells = (u64)g.cx * g.cy;
+  const int lane = threadIdx.x & 63;
+  uint32_t tally[5] = {0, 0, 0, 0, 0};
+  for (u64 c0 = ((u64)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; c0 < cells; c0 += (u64)gridDim.x * 256) {   // uniform over the wave
+    const uint32_t mine = c0 + lane < cells ? s.cell_n[c0 + lane] : 0u;
+    u64 todo = __ballot(mine >= 2u && mine <= (uint32_t)WAVE_LIMIT);
+    while (todo) {                                         // at most 64 cells
+      const int which = __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      const u64 c = c0 + which;
+      const int cnt = (int)(uint32_t)__shfl((int)mine, which);
+      const uint32_t first = s.cell_at[c] - (uint32_t)cnt;   // cell_at is the end since the scatter
+      const uint32_t cell_x = (uint32_t)(c % g.cx), cell_y = (uint32_t)(c / g.cx);
+      Ent own = {make_int4(0, 0, 0, 0), 0u};
+      if (lane < cnt) {
+        const uint32_t i = s.entry[first + lane];
+        own.e = s.e_xy[i];
+        own.id = s.e_id[i];
+      }
+      // most cells of a traced scene hold the edges of one object only
+      if (!__any(lane < cnt && own.id != (uint32_t)__shfl((int)own.id, 0))) continue;
+      // rotation r pairs lane l with lane (l + r) mod cnt: each unordered pair is met at r and at cnt - r, and counts where l
+      // is the smaller one
+      for (int r = 1; r < cnt; ++r) {
+        int other = lane + r;
+        other = other >= cnt ? other - cnt : other;
+        Ent q;
+        q.e = make_int4(__shfl(own.e.x, other), __shfl(own.e.y, other), __shfl(own.e.z, other), __shfl(own.e.w, other));
+        q.id = (uint32_t)__shfl((int)own.id, other);
+        const bool near = lane < cnt && lane < other && owned(g, cell_x, cell_y, own, q);
+        if (!__any(near)) continue;                        // uniform over the wave
+        int hit = HIT_NONE;
+        if (near) hit = hit_class(own.e, q.e);
+        record(conflict, own.id, q.id, hit, tally);
+      }
+    }
+  }
+  tally_out(tally, header);
+}
+
+// The job (cell, chunk i) of a cell of c chunks compares chunk i with the chunks i, i + 1, .., i + floor(c / 2) (mod c): every
+// unordered pair of chunks belongs to exactly one job.  For even c the offset c / 2 joins i and i + c / 2 from both ends, so
+// only i < c / 2 takes it; inside chunk i itself a thread takes the partners with a larger index.
+__global__ __launch_bounds__(BLOCK_T) void conflicts_jobs_kernel(Tab s, uint32_t* __restrict__ header, u64* __restrict__ conflict) {
+  extern __shared__ int4 t_edge[];                         // [TILE], then u32 [TILE]
+  uint32_t* t_id = reinterpret_cast<uint32_t*>(t_edge + TILE);
+  if (over_work(s, header)) return;
+  const Grid g = grid_of(header);
+  const int tid = threadIdx.x;
+  const u64 n_jobs = min((u64)header[WS_JOBS], (u64)s.cap_j);
+  uint32_t tally[5] = {0, 0, 0, 0, 0};
+  for (u64 job = blockIdx.x; job < n_jobs; job += gridDim.x) {
+    const uint2 jb = s.jobs[job];
+    const u64 cell = jb.x;
+    const uint32_t cnt = s.cell_n[cell], first = s.cell_at[cell] - cnt;
+    const uint32_t c = (cnt + CHUNK - 1) / CHUNK, i = jb.y;
+    if (i >= c) continue;                                  // cannot happen
+    const uint32_t cell_x = (uint32_t)(cell % g.cx), cell_y = (uint32_t)(cell / g.cx);
+    const uint32_t k = i * CHUNK + (uint32_t)tid;
+    Ent own = {make_int4(0, 0, 0, 0), 0u};
+    if (k < cnt) {
+      const uint32_t e = s.entry[first + k];
+      own.e = s.e_xy[e];
+      own.id = s.e_id[e];
+    }
+    const uint32_t half = c / 2;
+    for (uint32_t kk = 0; kk <= half; ++kk) {              // at most cap_e / (2 CHUNK) + 1 steps
+      if (kk * 2 == c && i >= half) break;
+      const uint32_t base = ((i + kk) % c) * CHUNK;
+      const int here = cnt - base < (uint32_t)TILE ? (int)(cnt - base) : TILE;
+      __syncthreads();                                     // the tile before has been read
+      if (tid < here) {
+        const uint32_t e = s.entry[first + base + tid];
+        t_edge[tid] = s.e_xy[e];
+        t_id[tid] = s.e_id[e];
+      } else {
+        t_edge[tid] = make_int4(0, 0, 0, 0);
+        t_id[tid] = 0u;                                    // past the end: no entry, which takes part in no pair
+      }
+      __syncthreads();
+      const int from = !own.id ? TILE : (kk == 0 ? tid + 1 : 0);   // the diagonal chunk: partners with a larger index only
+      for (int t0 = 0; t0 < here; t0 += 4) {               // four partners at a time: the same addresses in every lane
+        Ent q[4];
+        bool near[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          q[u].e = t_edge[t0 + u];                         // TILE is a multiple of 4 and the tile is padded
+          q[u].id = t_id[t0 + u];
+          near[u] = t0 + u >= from && owned(g, cell_x, cell_y, own, q[u]);
+        }
+        if (!__any(near[0] || near[1] || near[2] || near[3])) continue;   // uniform over the wave; most partners are far away
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (!__any(near[u])) continue;
+          int hit = HIT_NONE;
+          if (near[u]) hit = hit_class(own.e, q[u].e);
+          record(conflict, own.id, q[u].id, hit, tally);
+        }
+      }
+    }
+  }
+  tally_out(tally, header);
+}
+
+// -------------------------------------------------------------------------------------------------------------- 12: tail
+__global__ __launch_bounds__(256) void conflicts_tail_kernel(Tab s, const uint32_t* __restrict__ header, int64_t* __restrict__ conflict,
+                                                              int64_t* __restrict__ counts, int64_t* __restrict__ info,
+                                                              int64_t* __restrict__ totals) {
+  extern __shared__ long long s_tail[];                    // [5][256]
+  long long(*s_i)[256] = reinterpret_cast<long long(*)[256]>(s_tail);
+  const int tid = threadIdx.x;
+  const int top = clampi((int)header[WS_K], 0, s.max_ids);
+  long long c[5] = {0, 0, 0, 0, 0};
+  for (int i = tid; i < top; i += 256) {
+    int64_t* row = conflict + (int64_t)i * 8;
+    const int flag = (int)row[COL_FLAG];
+    if (flag == 0) {
+      if ((u64)row[COL_PARTNER] == NO_PARTNER) row[COL_PARTNER] = 0;
+      c[0] += 1;
+      c[1] += (row[COL_CROSS] != 0 || row[COL_SAME] != 0) ? 1 : 0;
+    } else {
+      c[1 + flag] += 1;                                    // 1 empty, 2 incomplete, 3 over work
+    }
+  }
+  for (int k = 0; k < 5; ++k) s_i[k][tid] = c[k];
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if (tid < d)
+      for (int k = 0; k < 5; ++k) s_i[k][tid] += s_i[k][tid + d];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const u64* q = quad(header);
+    const int64_t status = (int64_t)(uint32_t)s.counts[4];
+    for (int k = 0; k < 5; ++k) counts[k] = s_i[k][0];
+    counts[5] = (int64_t)q[WQ_SUM + HIT_CROSS];
+    counts[6] = (int64_t)q[WQ_SUM + HIT_SAME];
+    counts[7] = status;
+    info[0] = edges_of(s, header);
+    info[1] = header[WS_SHIFT]; info[2] = header[WS_CX]; info[3] = header[WS_CY];
+    info[4] = (int64_t)q[WQ_ENTRIES];
+    info[5] = (int64_t)q[WQ_WORK];
+    info[6] = (int64_t)q[WQ_SUM + HIT_OPP];
+    info[7] = (int64_t)(q[WQ_SUM + HIT_VV] + q[WQ_SUM + HIT_VE]);
+    if (totals) {
+      for (int k = 0; k < 7; ++k) totals[k] += counts[k];
+      totals[7] |= status;
+    }
+  }
+}
+
+unsigned grid_for(int64_t items, int per_block) {
+  int64_t g = (items + per_block - 1) / per_block;
+  return (unsigned)(g < 1 ? 1 : (g > MAX_GRID ? MAX_GRID : g));
+}
+
+int refuse(int32_t max_rings, int32_t max_vertices, int32_t max_ids) {
+  if (max_rings < 1 || max_vertices < 1 || max_ids < 1) return C3D_E_BADARG;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" void c3d_rings_conflicts_limits(int32_t out[6]) {
+  if (!out) return;
+  out[0] = WAVE_LIMIT;
+  out[1] = CHUNK;
+  out[2] = TILE;
+  out[3] = RING_LIMIT;
+  out[4] = BUDGET_E;
+  out[5] = BUDGET_C;
+}
+
+extern "C" int64_t c3d_rings_conflicts_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_ids) {
+  const int rc = refuse(max_rings, max_vertices, max_ids);
+  if (rc) return rc;
+  return plan_of(max_rings, max_vertices, max_ids).bytes;
+}
+
+extern "C" int c3d_rings_conflicts(const int32_t* rings, const int32_t* vertices, const int32_t* counts_in, int32_t max_rings,
+                                   int32_t max_vertices, int32_t frac_bits, int32_t max_ids, int64_t max_work, int64_t* conflict,
+                                   int64_t* counts, int64_t* info, int64_t* totals, void* ws, void* stream) {
+  if (!rings || !vertices || !counts_in || !conflict || !counts || !info || !ws) return C3D_E_BADARG;
+  if (frac_bits < 0 || frac_bits > 8 || max_work < 0) return C3D_E_BADARG;
+  int rc = refuse(max_rings, max_vertices, max_ids);
+  if (rc) return rc;
+  Plan pl = plan_of(max_rings, max_vertices, max_ids);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  Tab s = pl.t;
+  bind(s, base);
+  s.rings = rings; s.vertices = reinterpret_cast<const int2*>(vertices); s.counts = counts_in;
+  s.coord_max = (int64_t)COORD_UNIT << frac_bits;
+  s.max_work = max_work;
+  uint32_t* header = reinterpret_cast<uint32_t*>(base);
+  const uint32_t* hdr = header;
+  u64* rows = reinterpret_cast<u64*>(conflict);
+
+  // the header, the per-id sums and the cell counts: every other word of the workspace is written by the call before the call
+  // reads it
+  hipError_t e = hipMemsetAsync(base, 0, (size_t)pl.zero_bytes, st);
+  if (e != hipSuccess) return (int)e;
+  // the ring, id, edge and cell counts are known on the device only: grids are sized by the maxima and surplus workgroups return
+  const unsigned g_rows = grid_for(max_rings, 4), g_edge = grid_for(max_vertices, 256), g_cell = grid_for(s.cap_c, 256);
+  const unsigned g_big = grid_for(max_vertices, 4 * 256) < 1024u ? grid_for(max_vertices, 4 * 256) : 1024u;
+  rc = c3d_launch_lds<conflicts_rows_kernel>(dim3(g_rows), dim3(256), 0, st, s, header);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_check_big_kernel>(dim3(g_big), dim3(256), 0, st, s, hdr);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_ids_kernel>(dim3(1), dim3(SCAN_T), 2 * (SCAN_T / 64) * 8, st, s, hdr);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_edges_kernel>(dim3(g_rows), dim3(256), 0, st, s, header);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_edges_big_kernel>(dim3(g_big), dim3(256), 0, st, s, header);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_cost_kernel>(dim3(g_edge), dim3(256), 0, st, s, header);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_choose_kernel>(dim3(1), dim3(64), 0, st, s, header);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_count_kernel>(dim3(g_edge), dim3(256), 0, st, s, hdr);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_starts_kernel>(dim3(g_cell), dim3(256), 0, st, s, header);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_scatter_kernel>(dim3(g_edge), dim3(256), 0, st, s, hdr);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_init_kernel>(dim3(grid_for(max_ids, 256)), dim3(256), 0, st, s, hdr, rows);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_wave_kernel>(dim3(g_cell), dim3(256), 0, st, s, header, rows);
+  if (rc) return rc;
+  rc = c3d_launch_lds<conflicts_jobs_kernel>(dim3(grid_for(s.cap_j, 1)), dim3(BLOCK_T), (size_t)TILE * 20, st, s, header, rows);
+  if (rc) return rc;
+  return c3d_launch_lds<conflicts_tail_kernel>(dim3(1), dim3(256), 5 * 256 * 8, st, s, hdr, conflict, counts, info, totals);
+}

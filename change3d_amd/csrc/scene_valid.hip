@@ -27,50 +27,28 @@
 #include <climits>
 #include <type_traits>
 
-#include "common.h"
-#include "../../include/change3d_hip.h"
+#include "scene_rings.h"
 
 namespace {
 
-typedef unsigned long long u64;
+using namespace c3d_rings;                                 // the rows pass, the ids scan and pair_class: shared with
+                                                           // csrc/scene_conflicts.hip
 
 constexpr int WAVE_LIMIT = 64;                             // edges of an id in the wave tier: a lane each
 constexpr int CHUNK = 256;                                 // edges of a chunk: a thread each
 constexpr int TILE = 256;                                  // edges of an LDS tile: 24 bytes each; a chunk is one tile
-constexpr int RING_LIMIT = 16384;                          // rings of an id whose order the gather step restores
-constexpr int BIG_RING = 4096;                             // a longer ring is checked and copied by many workgroups
 constexpr int BLOCK_T = 256;
 constexpr int MAX_GRID = 4096;
-constexpr int SCAN_T = 1024;
-constexpr int COORD_UNIT = 32768;
 
-enum : uint8_t { ROW_SKIP = 0, ROW_USED = 1 };             // ROW_USED: valid, n >= 3, listed under its id
 enum : uint8_t { TIER_NONE = 0, TIER_WAVE = 1, TIER_JOB = 2 };
-enum { ID_INCOMPLETE = 1 };
-enum { PAIR_NONE = 0, PAIR_CROSS = 1, PAIR_OVERLAP = 2, PAIR_VV = 3, PAIR_VE = 4 };
 
-// words of the workspace header (256 bytes, zeroed by the call's memset)
-enum { WS_K = 1, WS_JOBS = 2, WS_BIG = 3 };                // the largest id of a row, the jobs, the long rings
-
-struct Tab {
-  const int32_t* rings;
-  const int2* vertices;
-  const int32_t* counts;
-  int max_rings, max_vertices, max_ids;
-  int64_t coord_max;                                       // 32768 << frac_bits
-  // workspace
-  uint8_t* kind;                                           // [max_rings]
+// the workspace header is 256 bytes, zeroed by the call's memset; its words are those of scene_rings.h
+struct Tab : Rows {
   uint2* list;                                             // [max_rings] (ring row, its n) grouped by id
-  uint32_t* big;                                           // [max_rings] the rows of the rings above BIG_RING, in any order
   uint32_t* row_at;                                        // [max_rings] where such a ring's edges go within its id
-  uint32_t* id_rings;                                      // [max_ids] used rings with n >= 3
-  u64* id_verts;                                           // [max_ids] their edges, degenerate ones included
-  uint32_t* id_flags;                                      // [max_ids]
   uint32_t* id_claim;                                      // [max_ids]
   uint32_t* id_degen;                                      // [max_ids] edges with a == b
   u64* acc;                                                // [max_ids][4] what the jobs add up: cross, overlap, vv, ve
-  uint32_t* id_list;                                       // [max_ids] start in list
-  uint32_t* id_start;                                      // [max_ids] start in edges
   int4* edges;                                             // [max_vertices] (a.x, a.y, b.x, b.y) grouped by id
   u64* meta;                                               // [max_vertices] place of the edge's ring in the id's list | n << 32
   uint8_t* tier;                                           // [max_ids]
@@ -123,114 +101,20 @@ void bind(Tab& t, char* base) {
   rebase(t.job_start, base);
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int rows_of(const Tab& s) {
-  return (s.counts[4] & C3D_OUTLINE_ST_BAD_COUNTS) ? 0 : clampi(s.counts[1], 0, s.max_rings);
-}
-__device__ __forceinline__ bool coord_ok(const Tab& s, int2 p) {
-  return p.x >= -s.coord_max && p.x <= s.coord_max && p.y >= -s.coord_max && p.y <= s.coord_max;
-}
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ int sign_of(double v) { return (v > 0.0) - (v < 0.0); }
-
-// The bounding boxes of two segments that share a point meet, so this reject in front of pair_class changes no class.  The
-// callers branch on it wave by wave (__any): left to itself the compiler turns the test into selects and runs the fifty
-// double-precision instructions of pair_class for every pair: 12.6 ms against 5.1 ms on one id at the default cap.
-__device__ __forceinline__ bool boxes_meet(int4 p, int4 q) {
-  return !(max(p.x, p.z) < min(q.x, q.z) || max(q.x, q.z) < min(p.x, p.z) || max(p.y, p.w) < min(q.y, q.w) ||
-           max(q.y, q.w) < min(p.y, p.w));
-}
-// The class of the pair of live edges p = (a, b) and q = (c, d) by the header's rule.  Differences are below 2^25 in an int,
-// products below 2^50 and their sums and differences below 2^51 in a double: exact, fused or not.
-__device__ __noinline__ int pair_class(int4 p, int4 q, bool adjacent) {
-  const double ex = (double)(p.z - p.x), ey = (double)(p.w - p.y), fx = (double)(q.z - q.x), fy = (double)(q.w - q.y);
-  const double cx = (double)(q.x - p.x), cy = (double)(q.y - p.y), dx = (double)(q.z - p.x), dy = (double)(q.w - p.y);
-  const double bx = (double)(p.z - q.x), by = (double)(p.w - q.y);
-  const int o1 = sign_of(ex * cy - ey * cx), o2 = sign_of(ex * dy - ey * dx);
-  const int o3 = sign_of(fy * cx - fx * cy), o4 = sign_of(fx * by - fy * bx);   // a - c = -(c - a)
-  if (o1 * o2 < 0 && o3 * o4 < 0) return PAIR_CROSS;
-  if ((o1 | o2 | o3 | o4) == 0) {
-    const double tc = cx * ex + cy * ey, td = dx * ex + dy * ey, L = ex * ex + ey * ey;
-    const double lo = fmax(fmin(tc, td), 0.0), hi = fmin(fmax(tc, td), L);
-    if (lo < hi) return PAIR_OVERLAP;
-    return (lo == hi && !adjacent) ? PAIR_VV : PAIR_NONE;
-  }
-  if (o1 * o2 > 0 || o3 * o4 > 0 || adjacent) return PAIR_NONE;
-  const bool ends = (p.x == q.x && p.y == q.y) || (p.x == q.z && p.y == q.w) || (p.z == q.x && p.w == q.y) ||
-                    (p.z == q.z && p.w == q.w);
-  return ends ? PAIR_VV : PAIR_VE;
-}
 // edges at the places i and j of an id's list, with the packed (place of the ring, n) of each
 __device__ __forceinline__ bool adjacent_of(uint32_t i, u64 mi, uint32_t j, u64 mj) {
   if ((uint32_t)mi != (uint32_t)mj) return false;          // another ring
   const uint32_t d = i > j ? i - j : j - i, n = (uint32_t)(mi >> 32);
   return d == 1u || d == n - 1u;
 }
-__device__ __forceinline__ bool live_of(int4 e) { return e.x != e.z || e.y != e.w; }
 
 // --------------------------------------------------------------------------------------------------------------- 1: rows
 __global__ __launch_bounds__(256) void valid_rows_kernel(Tab s, uint32_t* __restrict__ header) {
-  const int rows = rows_of(s), lane = threadIdx.x & 63;
-  const int64_t vlimit = clampi(s.counts[3], 0, s.max_vertices);
-  // what a wave adds to an id is kept in registers while the id stays the same (the holes of a scene-filling object are
-  // thousands of rows of one id); integer sums: the grouping changes nothing
-  int top = 0, held = 0;
-  uint32_t held_rings = 0;
-  u64 held_verts = 0;
-  for (int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6); r < rows; r += gridDim.x * 4) {   // r is uniform over the wave
-    const int id = s.rings[(int64_t)r * 8], start = s.rings[(int64_t)r * 8 + 1], n = s.rings[(int64_t)r * 8 + 2];
-    uint8_t kind = ROW_SKIP;
-    if (id >= 1 && id <= s.max_ids) {
-      bool bad = start < 0 || n < 0 || (int64_t)start + n > vlimit;
-      if (!bad && n <= BIG_RING) {
-        bool out = false;
-        for (int k = lane; k < n; k += 64) out |= !coord_ok(s, s.vertices[(int64_t)start + k]);
-        bad = __any(out);
-      }
-      // a longer ring is counted now and checked by the next kernel: a bad coordinate there makes the id incomplete
-      if (!bad && n > BIG_RING && lane == 0) s.big[atomicAdd(header + WS_BIG, 1u)] = (uint32_t)r;
-      top = id > top ? id : top;
-      if (bad) {
-        if (lane == 0) atomicOr(s.id_flags + (id - 1), (uint32_t)ID_INCOMPLETE);
-      } else if (n >= 3) {
-        if (id != held) {
-          if (held_rings && lane == 0) {
-            atomicAdd(s.id_rings + (held - 1), held_rings);
-            atomicAdd(s.id_verts + (held - 1), held_verts);
-          }
-          held = id;
-          held_rings = 0;
-          held_verts = 0;
-        }
-        held_rings += 1;
-        held_verts += (u64)n;
-        kind = ROW_USED;
-      }
-    }
-    if (lane == 0) s.kind[r] = kind;
-  }
-  if (lane == 0) {
-    if (held_rings) {
-      atomicAdd(s.id_rings + (held - 1), held_rings);
-      atomicAdd(s.id_verts + (held - 1), held_verts);
-    }
-    if (top) atomicMax(header + WS_K, (uint32_t)top);
-  }
+  rows_pass(s, header);
 }
 
 __global__ __launch_bounds__(256) void valid_check_big_kernel(Tab s, const uint32_t* __restrict__ header) {
-  const uint32_t n_big = min(header[WS_BIG], (uint32_t)s.max_rings);
-  for (uint32_t li = 0; li < n_big; ++li) {
-    const int r = (int)s.big[li];
-    const int id = s.rings[(int64_t)r * 8], n = s.rings[(int64_t)r * 8 + 2];
-    const int64_t start = s.rings[(int64_t)r * 8 + 1];
-    bool out = false;
-    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) out |= !coord_ok(s, s.vertices[start + k]);
-    if (out) atomicOr(s.id_flags + (id - 1), (uint32_t)ID_INCOMPLETE);
-  }
+  check_big_pass(s, header);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- 2: ids
@@ -238,50 +122,7 @@ __global__ __launch_bounds__(256) void valid_check_big_kernel(Tab s, const uint3
 // vertices get there), becomes incomplete and takes no room.
 __global__ __launch_bounds__(SCAN_T) void valid_ids_kernel(Tab s, const uint32_t* __restrict__ header) {
   extern __shared__ u64 part_ids[];                        // [2][SCAN_T / 64]
-  u64(*part)[SCAN_T / 64] = reinterpret_cast<u64(*)[SCAN_T / 64]>(part_ids);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int top = clampi((int)header[WS_K], 0, s.max_ids);   // the ids above it have no row: their words stay 0
-  u64 run_r = 0, run_v = 0;
-  for (int base = 0; base < top; base += SCAN_T) {
-    const int i = base + (int)threadIdx.x;
-    u64 nr = 0, nv = 0;
-    uint32_t fl = 0;
-    if (i < top) {
-      nr = s.id_rings[i];
-      nv = s.id_verts[i];
-      fl = s.id_flags[i];
-      if (nr > (u64)RING_LIMIT) fl |= ID_INCOMPLETE;
-      if (fl & ID_INCOMPLETE) nr = nv = 0;
-    }
-    u64 ir = nr, iv = nv;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int from = lane >= d ? lane - d : lane;
-      const u64 tr = shfl64(ir, from), tv = shfl64(iv, from);
-      if (lane >= d) { ir += tr; iv += tv; }
-    }
-    if (lane == 63) { part[0][wave] = ir; part[1][wave] = iv; }
-    __syncthreads();
-    u64 br = 0, bv = 0, ar = 0, av = 0;
-    for (int w = 0; w < SCAN_T / 64; ++w) {
-      br += w < wave ? part[0][w] : 0ull;
-      bv += w < wave ? part[1][w] : 0ull;
-      ar += part[0][w];
-      av += part[1][w];
-    }
-    if (i < top) {
-      const u64 at_r = run_r + br + ir - nr, at_v = run_v + bv + iv - nv;
-      // at_v only grows: an id that does not fit takes its place in the sum all the same, so that no later id fits either
-      const bool fits = at_v + nv <= (u64)s.max_vertices;
-      if (!fits) fl |= ID_INCOMPLETE;
-      s.id_flags[i] = fl;
-      s.id_list[i] = (uint32_t)at_r;                       // at most max_rings
-      s.id_start[i] = fits ? (uint32_t)at_v : 0u;
-      if (fl & ID_INCOMPLETE) { s.id_rings[i] = 0; s.id_verts[i] = 0; }
-    }
-    run_r += ar;
-    run_v += av;
-    __syncthreads();
-  }
+  ids_pass(s, header, reinterpret_cast<u64(*)[SCAN_T / 64]>(part_ids));
 }
 
 // -------------------------------------------------------------------------------------------------------------- 3: place

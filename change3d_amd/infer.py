@@ -49,6 +49,14 @@ with `regularize=True`.  `c3d_rings_valid` counts the proper crossings, collinea
 object, holes included; an object is valid iff it was checked and has no crossing and no overlap.  Edges of different objects
 are never compared.  Still the same one synchronisation; with `validity=False` the launches are the ones without it.
 
+`predict(..., outlines=True, conflicts=True)` does compare them: it appends one `SceneConflicts` per stage the call has, after
+the `SceneValidity` entries and last of all, in the same order (raw, simplified, regularised).  `c3d_rings_conflicts` bins the
+edges of the whole table into a grid of cells on the device and counts, per object, the crossings, the collinear overlaps that
+run the same way or the opposite way, and the touches of its edges with those of every other object; an object is in conflict
+iff it was checked and has a crossing or a same-direction overlap.  Raw traced rings never conflict; the pieces of `split=R`
+simplified ring by ring usually do.  Still the same one synchronisation; with `conflicts=False` the launches are the ones
+without it.
+
 `SceneInferencer(..., tta="hflip" | "flips" | "d4" | codes)` is test-time augmentation: every tile is predicted under a set of
 the eight flips and rotations of the square, each view is undone on the output and the views are averaged before the
 stitch.  A view code `v` in 0..7 transposes the tile if `v & 4`, then reverses its rows if `v & 2`, then its columns if
@@ -101,6 +109,11 @@ SceneRegular = namedtuple("SceneRegular", "rings vertices counts")
 # [8] = (checked, invalid, empty, incomplete, over work, sum cross, sum overlap, status).  An object is valid iff flag == 0 and
 # cross == overlap == 0
 SceneValidity = namedtuple("SceneValidity", "valid counts")
+# `predict(..., conflicts=True)`: the crossings, overlaps and touches between the edges of different objects of one ring table
+# (`ops.rings_conflicts`): conflict i64 [max_objects, 8] = (flag, partner, m, cross, same, opposite, touch_vv, touch_ve), counts
+# i64 [8] = (checked, in conflict, empty, incomplete, over work, sum cross, sum same, status), info i64 [8] = (live edges, cell
+# shift, cells_x, cells_y, entries, work, sum opposite, sum touches).  An object is in conflict iff flag == 0 and cross + same > 0
+SceneConflicts = namedtuple("SceneConflicts", "conflict counts info")
 REGULAR_FRAC_BITS = 4
 TASKS = ("bcd", "scd", "bda")
 WINDOWS = ("hann", "flat")
@@ -243,6 +256,9 @@ class SceneInferencer:
     `validity=True` (with `outlines=True`) appends, last of all, a `SceneValidity` of the raw rings, one of the simplified rings
     with `simplify=tol` and one of the regularised rings with `regularize=True` (`ops.rings_valid`): per object its crossings,
     overlaps and touches.  With `validity=False` the launches are the ones without it.
+    `conflicts=True` (with `outlines=True`) appends, after those and last of all, a `SceneConflicts` per stage in the same order
+    (`ops.rings_conflicts`): per object its crossings, overlaps and touches with every other object.  With `conflicts=False` the
+    launches are the ones without it.
     `tta` is None, a name of `VIEW_SETS` ("none", "hflip", "flips", "d4") or a sequence of view codes: the tiles are predicted
     under those `nv` views and averaged with the views undone (module docstring).  `batch` stays the number of model inputs
     per forward, so a forward takes `batch // nv` tiles; a transposing view (codes 4..7) needs a square model input.  With
@@ -299,11 +315,13 @@ class SceneInferencer:
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
                 max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False, shapes=False,
-                regularize=False, regularize_check=False, validity=False):
+                regularize=False, regularize_check=False, validity=False, conflicts=False):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
         if validity and not outlines:
             raise ValueError("validity=True tests the traced rings of the objects: it needs outlines=True")
+        if conflicts and not outlines:
+            raise ValueError("conflicts=True compares the traced rings of different objects: it needs outlines=True")
         if shapes and not outlines:
             raise ValueError("shapes=True takes the hulls and rectangles of the traced rings: it needs outlines=True")
         if split is None and split_rounds is not None:
@@ -425,5 +443,11 @@ class SceneInferencer:
                         result += (SceneValidity(*ops.rings_valid(*simple, max_objects=max_objects)),)
                     if regularize:
                         result += (SceneValidity(*ops.rings_valid(*regular, frac_bits=REGULAR_FRAC_BITS, max_objects=max_objects)),)
+                if conflicts:                           # after the validity entries, in the same order
+                    result += (SceneConflicts(*ops.rings_conflicts(*raw, max_objects=max_objects)),)
+                    if simplify is not None:
+                        result += (SceneConflicts(*ops.rings_conflicts(*simple, max_objects=max_objects)),)
+                    if regularize:
+                        result += (SceneConflicts(*ops.rings_conflicts(*regular, frac_bits=REGULAR_FRAC_BITS, max_objects=max_objects)),)
         torch.cuda.current_stream().synchronize()       # the one host synchronisation after the scene's upload
         return result

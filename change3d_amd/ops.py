@@ -1209,6 +1209,53 @@ def rings_valid(rings, vertices, counts, frac_bits=0, max_objects=65536, max_id_
     return valid, out
 
 
+def rings_conflicts_limits():
+    """(most entries of a cell in the wave tier, entries of a chunk, entries of an LDS tile, most rings of an id, entries the
+    grid may hold per vertex of max_vertices, cells it may have per vertex); host only."""
+    out = (C.c_int32 * 6)()
+    L.lib().c3d_rings_conflicts_limits(out)
+    return tuple(int(v) for v in out)
+
+
+def rings_conflicts(rings, vertices, counts, frac_bits=0, max_objects=65536, max_work=2 ** 32, totals=None, ws=None):
+    """c3d_rings_conflicts on one ring table (`rings` i32 [max_rings, 8], `vertices` i32 [max_vertices, 2], `counts` i32 [5],
+    coordinates in units of 2^-frac_bits pixel): the crossings, collinear overlaps and touches between the edges of DIFFERENT
+    object ids by the rule of include/change3d_hip.h, found through a grid of edge cells built on the device.  Returns
+    `(conflict i64 [max_objects, 8] = (flag, partner, m, cross, same, opposite, touch_vv, touch_ve) per id, counts i64 [8] =
+    (checked, in conflict, empty, incomplete, over work, sum cross, sum same, status), info i64 [8] = (live edges, cell shift,
+    cells_x, cells_y, entries, work, sum opposite, sum touches))`, all on the device; nothing is read back.  An id is in
+    conflict iff flag == 0 and cross + same > 0.  `totals` i64 [8], zeroed once by the caller, is accumulated into.  If the
+    grid's `work` (candidate pairs) exceeds `max_work`, no pair is evaluated (flag 3)."""
+    for t in (rings, vertices, counts):
+        require_gpu(t, "rings_conflicts input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    frac_bits, max_objects, max_work = int(frac_bits), int(max_objects), int(max_work)
+    if not 0 <= frac_bits <= 8:
+        raise ValueError(f"frac_bits must lie in [0, 8], got {frac_bits}")
+    if not 0 <= max_work < 2 ** 63:
+        raise ValueError(f"max_work must lie in [0, 2^63), got {max_work}")
+    max_rings, max_vertices = int(rings.shape[0]), int(vertices.shape[0])
+    nbytes = L.lib().c3d_rings_conflicts_ws_bytes(max_rings, max_vertices, max_objects) if max_objects < 2 ** 31 else -1
+    if nbytes < 0:
+        raise L.Change3DHipError(f"c3d_rings_conflicts refuses max_rings = {max_rings}, max_vertices = {max_vertices}, "
+                                 f"max_objects = {max_objects} (code {nbytes})")
+    dev = rings.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    if totals is not None:
+        require_gpu(totals, "rings_conflicts totals")
+        assert totals.dtype == torch.int64 and totals.numel() == 8 and totals.is_contiguous()
+    conflict = torch.empty((max_objects, 8), dtype=torch.int64, device=dev)
+    out = torch.empty(8, dtype=torch.int64, device=dev)
+    info = torch.empty(8, dtype=torch.int64, device=dev)
+    _launch("c3d_rings_conflicts", max_rings * 40 + max_vertices * 100 + max_objects * 96, L.lib().c3d_rings_conflicts, _p(rings),
+            _p(vertices), _p(counts), max_rings, max_vertices, frac_bits, max_objects, max_work, _p(conflict), _p(out), _p(info),
+            _p(totals), _p(ws), _stream())
+    return conflict, out, info
+
+
 def rect_corners(P, d, rect_row):
     """The rectangle of a `rings_hull` rects row on the hull edge that starts at `P` = (x, y) and runs along `d` = (dx, dy):
     `(corners float64 [4, 2], long, short, angle)`.  The corners are P + d t/L (+ n c_max/L) for t = t_min, t_max with n =

@@ -77,6 +77,23 @@ its raw vertices in every ring, as `--simplify_min_iou` does (with both, either 
 an object on its simplified rings with `regular: false`, beside `--regularize_min_iou`.  Edges of different objects are never
 compared, and whether a hole lies inside its outline is not examined.
 
+`--conflicts` (with `--polygons`) compares the polygons of different objects, on the device (`c3d_rings_conflicts`, a grid of edge
+cells): an object is in conflict iff one of its edges properly crosses an edge of another object or overlaps one collinearly in
+the same direction; overlaps in opposite directions are the shared walls of pieces that meet, and touches never count.  Every
+feature of `objects/<name>.geojson` gains `conflicts` (crossings plus same-direction overlaps), `conflict_with` (the smallest id
+it conflicts with, 0 if none) and `shared_walls` of the coordinates that are written; every feature of
+`objects/<name>.regular.geojson` the same of the regularised stage.  The run ends with one line per stage,
+`conflicts[raw|simplified|regular]: objects clean in_conflict unchecked crossings overlaps shared_walls`.  Raw traced rings never
+conflict; the pieces of `--split_objects` simplified ring by ring usually do.  `--simplify_clean` implies `--conflicts` and puts
+every object in conflict back on its raw vertices in every ring, beside `--simplify_min_iou` and `--simplify_valid` (any one
+suffices).  A raw staircase can cross a neighbour's chord that the simplified ring did not, so the table that is about to be
+written is assembled on the host, uploaded and checked again, and its objects in conflict fall back too, for at most
+`--clean_rounds N` rounds (default 8; each is one more synchronisation, under this flag only).  The properties and the closing
+line then describe what is written, and the line adds `rounds` (the most any scene took) and `remaining`; objects still in
+conflict after N rounds are named `<scene>:<id>` and the run ends with an error.  `--regularize_clean` does the same for
+`objects/<name>.regular.geojson`, falling back to what the main file writes for that object, with `regular: false`.  An object
+that lies wholly inside another, and a boundary that passes through another exactly at a vertex, are not seen.
+
 `--tta hflip|flips|d4` is test-time augmentation: every tile is predicted under the two mirror views, the four flips or all
 eight flips and rotations of the square, each view is undone on the device and the views are averaged before the stitch
 (`c3d_scene_gather_views`, `c3d_scene_fold_views`; change3d_amd/infer.py).  `--batch_size` stays the number of model inputs
@@ -267,6 +284,82 @@ def add_validity(sums, stage, name, found):
         s["counts"][key] += value
     s["unchecked"] += [f"{name}:{k + 1}" for k in np.nonzero(rows[:, 0])[0].tolist()]
     return rows
+
+
+def conflict_properties(row):
+    """The feature properties of one row of a `SceneConflicts`."""
+    _, partner, _, cross, same, opposite, _, _ = (int(v) for v in row)
+    return dict(conflicts=cross + same, conflict_with=partner, shared_walls=opposite)
+
+
+def in_conflict_ids(rows):
+    """The ids of the rows of a `SceneConflicts` (host array [rows, 8]) that were checked and cross or overlap another object."""
+    return {k + 1 for k, row in enumerate(np.asarray(rows).tolist()) if row[0] == 0 and row[3] + row[4] > 0}
+
+
+def read_conflicts(found):
+    """(rows [K, 8] on the host, dict of the counts) of one `SceneConflicts`, K = the largest object id of the ring table."""
+    checked, bad, empty, incomplete, over, crossings, overlaps, _ = (int(v) for v in found.counts.cpu().tolist())
+    objects = checked + empty + incomplete + over
+    counts = dict(objects=objects, checked=checked, in_conflict=bad, crossings=crossings, overlaps=overlaps,
+                  shared_walls=int(found.info[6]))
+    return found.conflict[:objects].cpu().numpy(), counts
+
+
+def add_conflicts(sums, stage, name, rows, counts, rounds=None, remaining=()):
+    """Adds the counts of one scene to the run's sums of its stage; an object that could not be checked is remembered as
+    `<scene>:<id>`, and so is one that `--clean_rounds` left in conflict."""
+    s = sums.setdefault(stage, dict(counts=dict.fromkeys(counts, 0), unchecked=[], rounds=None, remaining=[]))
+    for key, value in counts.items():
+        s["counts"][key] += value
+    s["unchecked"] += [f"{name}:{k + 1}" for k in np.nonzero(rows[:, 0] > 1)[0].tolist()]
+    if rounds is not None:
+        s["rounds"] = max(s["rounds"] or 0, rounds)
+        s["remaining"] += [f"{name}:{k}" for k in sorted(remaining)]
+
+
+def doc_table(doc, frac_bits, device):
+    """The ring table (rings i32 [., 8], vertices i32 [., 2], counts i32 [5]) of the polygons of a FeatureCollection as it is
+    written, on `device`: one ring per linear ring without its closing vertex, coordinates times 2^frac_bits."""
+    rows, verts = [], []
+    for feature in doc["features"]:
+        for ring in feature["geometry"]["coordinates"]:
+            rows.append([feature["properties"]["id"], len(verts), len(ring) - 1, 0, 0, 0, 0, 0])
+            verts += [[int(round(x * (1 << frac_bits))), int(round(y * (1 << frac_bits)))] for x, y in ring[:-1]]
+    rings = torch.tensor(rows or [[0] * 8], dtype=torch.int32, device=device).reshape(-1, 8)
+    vertices = torch.tensor(verts or [[0, 0]], dtype=torch.int32, device=device).reshape(-1, 2)
+    counts = torch.tensor([len(rows), len(rows), len(verts), len(verts), 0], dtype=torch.int32, device=device)
+    return rings, vertices, counts
+
+
+def clean_file(path, write, first_bad, frac_bits, max_rounds, max_objects, device):
+    """The loop of `--simplify_clean` / `--regularize_clean` on one written file: `write(ids)` writes `path` with those ids on their
+    fallback; the file is read back, uploaded as a ring table and checked (`ops.rings_conflicts`), and what is in conflict falls
+    back, for at most `max_rounds` rounds.  Returns (rounds, the ids still in conflict, the last check or None)."""
+    from ..infer import SceneConflicts
+    bad, fallen, rounds, found = set(first_bad), set(), 0, None
+    while rounds < max_rounds:
+        fallen |= bad
+        rounds += 1
+        write(fallen)
+        with open(path) as f:
+            doc = json.load(f)
+        found = SceneConflicts(*ops.rings_conflicts(*doc_table(doc, frac_bits, device), frac_bits=frac_bits, max_objects=max_objects))
+        bad = in_conflict_ids(read_conflicts(found)[0])
+        if not bad:
+            break
+    return rounds, bad, found
+
+
+def add_conflict_properties(path, rows):
+    """Rewrites the FeatureCollection at `path` with `conflicts`, `conflict_with` and `shared_walls` on every feature."""
+    with open(path) as f:
+        doc = json.load(f)
+    for feature in doc["features"]:
+        k = feature["properties"]["id"]
+        feature["properties"].update(conflict_properties(rows[k - 1] if k - 1 < len(rows) else EMPTY_ROW))
+    with open(path, "w") as f:
+        json.dump(doc, f)
 
 
 def simplify_ious(objects, fill):
@@ -558,6 +651,16 @@ def parse_args(argv=None):
         args.validity = True
     if args.validity and not args.polygons:
         parser.error("--validity tests the polygons: it needs --polygons")
+    if args.simplify_clean and args.simplify is None:
+        parser.error("--simplify_clean is a fallback of --simplify: it needs --simplify")
+    if args.regularize_clean and not args.regularize:
+        parser.error("--regularize_clean is a fallback of --regularize: it needs --regularize")
+    if args.simplify_clean or args.regularize_clean:
+        args.conflicts = True
+    if args.conflicts and not args.polygons:
+        parser.error("--conflicts compares the polygons: it needs --polygons")
+    if args.clean_rounds < 0:
+        parser.error("--clean_rounds must not be negative")
     if args.label_polygons and args.task == "SCD":
         parser.error("--label_polygons gives objects with one class each: it serves --task BCD and BDA")
     if args.label_polygons and any((args.label, args.label1, args.label2, args.change)):
@@ -631,6 +734,9 @@ def main(argv=None):
         split["regularize_check"] = args.regularize_min_iou is not None
     if args.validity:
         split["validity"] = True
+    if args.conflicts:
+        split["conflicts"] = True
+    conflict_sums = {}                                    # --conflicts over all scenes: stage -> counts, objects by name
     validity_sums = {}                                    # --validity over all scenes: stage -> counts, unchecked objects by name
     squared =dict(objects=0, regular=0, fallback=0, iou_sum=0.0, iou_min=1.0)   # --regularize over all scenes
     drift = dict(objects=0, kept=0, vanished=0, iou_sum=0.0, iou_min=1.0)   # --simplify_check over all scenes
@@ -642,6 +748,11 @@ def main(argv=None):
             out = inf.predict(scene, objects=True, min_area=args.min_area, connectivity=args.connectivity, outlines=True,
                               max_rings=args.max_rings, max_vertices=args.max_vertices, simplify=args.simplify, **split)
             simplified, iou, shapes, regular, regular_iou = None, None, None, None, None
+            conf = {}                         # stage -> (host rows, counts) of its `SceneConflicts`
+            if args.conflicts:            # appended after the validity entries, in the same order
+                stages_c = ["raw"] + (["simplified"] if args.simplify is not None else []) + (["regular"] if args.regularize else [])
+                out, found_c = out[:-len(stages_c)], out[-len(stages_c):]
+                conf = {stage: read_conflicts(v) for stage, v in zip(stages_c, found_c)}
             valid_rows = {}                   # stage -> host rows of its `SceneValidity`
             if args.validity:             # appended last of all: raw, then simplified, then regularised
                 stages_v = ["raw"] + (["simplified"] if args.simplify is not None else []) + (["regular"] if args.regularize else [])
@@ -664,9 +775,9 @@ def main(argv=None):
             check_split(name, out[-2])
             written_v = valid_rows.get("simplified" if simplified is not None else "raw")   # of the coordinates that are written
             bad_v = not_valid_ids(valid_rows["simplified"]) if args.simplify_valid else None
+            main_path = os.path.join(args.out_dir, "objects", name + ".geojson")
             if shapes is None:
-                cut_off += len(save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified,
-                                             iou, args.simplify_min_iou, None, written_v, bad_v))
+                cut_off += len(save_polygons(main_path, out[-2], out[-1], simplified, iou, args.simplify_min_iou, None, written_v, bad_v))
             else:
                 props, hull_rings, rect_rings = object_shapes(name, out[-2], shapes)
                 skipped = save_polygons(os.path.join(args.out_dir, "objects", name + ".geojson"), out[-2], out[-1], simplified, iou,
@@ -678,15 +789,47 @@ def main(argv=None):
                 shape_sums = dict(objects=shape_sums["objects"] + len(kept),
                                   solidity=shape_sums["solidity"] + sum(v["solidity"] for v in kept),
                                   rectangularity=shape_sums["rectangularity"] + sum(v["rectangularity"] for v in kept))
+            most = max(int(out[-2].counts[1]), 1)
+            if args.conflicts:            # the main file: fall back and check again, then the properties of what is written
+                written_stage = "simplified" if simplified is not None else "raw"
+                rows_c, counts_c = conf[written_stage]
+                rounds, left = None, ()
+                if args.simplify_clean:
+                    rounds, left, last = clean_file(
+                        main_path, lambda ids: save_polygons(main_path, out[-2], out[-1], simplified, iou, args.simplify_min_iou,
+                                                             props if shapes is not None else None, written_v, set(bad_v or ()) | ids),
+                        in_conflict_ids(rows_c), 0, args.clean_rounds, most, device)
+                    if last is not None:
+                        rows_c, counts_c = read_conflicts(last)
+                add_conflict_properties(main_path, rows_c)
+                for stage, (rows_s, counts_s) in conf.items():
+                    if stage == written_stage:
+                        add_conflicts(conflict_sums, stage, name, rows_c, counts_c, rounds, left)
+                    elif stage != "regular":
+                        add_conflicts(conflict_sums, stage, name, rows_s, counts_s)
             if regular is not None:
                 if int(regular.counts[4]) & (L.OUTLINE_ST_BAD_COUNTS | L.REGULAR_ST_BAD_ROW):
                     raise SystemExit(f"{name}: --regularize: c3d_rings_regularize status {int(regular.counts[4])}")
                 if args.regularize_min_iou is not None:
                     regular_iou = simplify_ious(out[-2], regular_fill)[0]
-                main_path = os.path.join(args.out_dir, "objects", name + ".geojson")
-                done, fallback, ids = save_regular(os.path.join(args.out_dir, "objects", name + ".regular.geojson"), main_path, out[-1],
-                                                   regular, regular_iou, args.regularize_min_iou, valid_rows.get("regular"),
-                                                   not_valid_ids(valid_rows["regular"]) if args.regularize_valid else None)
+                regular_path = os.path.join(args.out_dir, "objects", name + ".regular.geojson")
+                bad_r = not_valid_ids(valid_rows["regular"]) if args.regularize_valid else None
+                done, fallback, ids = save_regular(regular_path, main_path, out[-1], regular, regular_iou, args.regularize_min_iou,
+                                                   valid_rows.get("regular"), bad_r)
+                if args.conflicts:
+                    rows_c, counts_c = conf["regular"]
+                    rounds, left, kept = None, (), [(done, fallback, ids)]
+                    if args.regularize_clean:
+                        rounds, left, last = clean_file(
+                            regular_path, lambda bad: kept.append(save_regular(regular_path, main_path, out[-1], regular, regular_iou,
+                                                                               args.regularize_min_iou, valid_rows.get("regular"),
+                                                                               set(bad_r or ()) | bad)),
+                            in_conflict_ids(rows_c), REGULAR_FRAC_BITS, args.clean_rounds, most, device)
+                        done, fallback, ids = kept[-1]
+                        if last is not None:
+                            rows_c, counts_c = read_conflicts(last)
+                    add_conflict_properties(regular_path, rows_c)
+                    add_conflicts(conflict_sums, "regular", name, rows_c, counts_c, rounds, left)
                 ious = [float(regular_iou[k - 1]) for k in ids] if regular_iou is not None else []
                 squared = dict(objects=squared["objects"] + len(ids), regular=squared["regular"] + done,
                                fallback=squared["fallback"] + fallback, iou_sum=squared["iou_sum"] + sum(ious),
@@ -768,6 +911,17 @@ def main(argv=None):
         print(f"validity[{stage}]: objects = {c['objects']} valid = {c['checked'] - c['invalid']} invalid = {c['invalid']} "
               f"unchecked = {c['objects'] - c['checked']} crossings = {c['crossings']} overlaps = {c['overlaps']}" +
               (f" (unchecked: {', '.join(v['unchecked'])})" if v["unchecked"] else ""))
+    for stage, v in conflict_sums.items():
+        c = v["counts"]
+        print(f"conflicts[{stage}]: objects = {c['objects']} clean = {c['checked'] - c['in_conflict']} in_conflict = {c['in_conflict']} "
+              f"unchecked = {c['objects'] - c['checked']} crossings = {c['crossings']} overlaps = {c['overlaps']} "
+              f"shared_walls = {c['shared_walls']}" +
+              (f" rounds = {v['rounds']} remaining = {len(v['remaining'])}" if v["rounds"] is not None else "") +
+              (f" (unchecked: {', '.join(v['unchecked'])})" if v["unchecked"] else ""))
+    still = [n for v in conflict_sums.values() for n in v["remaining"]]
+    if still:
+        raise SystemExit(f"{len(still)} objects are still in conflict after --clean_rounds {args.clean_rounds}: {', '.join(still)}; "
+                         f"raise --clean_rounds")
     if cut_off:
         raise SystemExit(f"{cut_off} objects have no polygon: their rings did not fit; raise --max_rings / --max_vertices")
     if not scored:
@@ -841,6 +995,16 @@ def build_parser():
                    "crosses or overlaps itself, or could not be checked, keeps its raw vertices")
     p.add_argument("--regularize_valid", action="store_true", help="--regularize: implies --validity; an object whose regularised "
                    "polygon crosses or overlaps itself, or could not be checked, keeps its simplified rings")
+    p.add_argument("--conflicts", action="store_true", help="--polygons: also compare the polygons of different objects on the device "
+                   "(c3d_rings_conflicts): `conflicts`, `conflict_with` and `shared_walls` on every feature, of the coordinates that "
+                   "are written, and a closing `conflicts[stage]:` line for the raw, the simplified and the regularised rings")
+    p.add_argument("--simplify_clean", action="store_true", help="--simplify: implies --conflicts; an object whose polygon crosses "
+                   "another object's, or overlaps it in the same direction, keeps its raw vertices; the written table is checked "
+                   "again until it is clean")
+    p.add_argument("--regularize_clean", action="store_true", help="--regularize: implies --conflicts; such an object keeps in "
+                   "objects/<name>.regular.geojson what the main file writes for it")
+    p.add_argument("--clean_rounds", type=int, default=8, metavar="N", help="--simplify_clean, --regularize_clean: at most N rounds of "
+                   "fall back and check again; objects still in conflict then end the run with an error")
     p.add_argument("--label_polygons", default="", metavar="FILE", help="BCD, BDA: the ground truth as polygons, a GeoJSON FeatureCollection "
                    "in pixel coordinates or an xBD label JSON, instead of label rasters; with --file_root a directory of <name>.json / "
                    "<name>.geojson.  Filled on the device (c3d_rings_fill); one ground-truth object per feature")

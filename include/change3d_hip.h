@@ -1024,7 +1024,7 @@ int c3d_rings_polis(const int32_t* rings_p, const int32_t* vertices_p, const int
  * traced rings are valid.  What this does NOT decide:
  *   - a ring that passes from one side of another ring to its other side exactly through a vertex is counted as touches only;
  *   - whether a hole still lies inside its shell is not examined;
- *   - edges of different ids are never compared.
+ *   - edges of different ids are never compared (c3d_rings_conflicts does that).
  * Inputs (device): the table; max_id_work >= 0, the most edge pairs one id may cost (there is no spatial index: this cap stands
  * in for one, as max_pair_work does in c3d_rings_polis; a bounding-box reject in front of the four products is the only pruning
  * and changes no count).
@@ -1052,6 +1052,76 @@ int64_t c3d_rings_valid_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_
 int c3d_rings_valid(const int32_t* rings, const int32_t* vertices, const int32_t* counts_in, int32_t max_rings,
                     int32_t max_vertices, int32_t frac_bits, int32_t max_ids, int64_t max_id_work, int64_t* valid,
                     int64_t* counts, int64_t* totals, void* ws, void* stream);
+
+/* Polygon conflicts between objects (csrc/scene_conflicts.hip): for every object id of ONE ring table the proper crossings,
+ * collinear overlaps and touches of its edges with the edges of every OTHER id, while the table stays in HBM.  One memset and 14
+ * launches on `stream`, nothing is read back by the host, no workgroup waits for another, every loop is capped, and no workspace
+ * word is read before the call wrote it.  Everything is an integer, as in c3d_rings_valid, and every sum is an integer atomic or
+ * a ballot count; nothing depends on the order in which the device lists edges or fills cells: the result is exact, equal from
+ * run to run and on a dirty workspace, and independent of the grid that finds the pairs.  The rule:
+ *   table, rows used, INCOMPLETE ids, K, edges, DEGENERATE, live edges, m
+ *               word for word those of c3d_rings_valid, which are those of c3d_rings_polis for one side, RING_LIMIT included.
+ *               The edges of an incomplete id take part in nothing
+ *   pairs       every unordered pair of live edges (a, b) of id i and (c, d) of id j with i != j, both ids complete.  Pairs of
+ *               one id are never looked at (c3d_rings_valid does that)
+ *   classes     with o1 .. o4 as in c3d_rings_valid, the first class that applies:
+ *                 cross     o1 o2 < 0 and o3 o4 < 0
+ *                 same      all four are zero, the collinear segments share more than one point (the t / L test of
+ *                           c3d_rings_valid) and (b-a).(d-c) > 0
+ *                 opposite  the same with (b-a).(d-c) < 0
+ *                 touch     the segments share exactly one point: touch_vv if it is an end point of both edges, touch_ve if an
+ *                           end point of one lies strictly inside the other.  There is no adjacency across ids: every such pair
+ *                           counts
+ *                 nothing   otherwise
+ *   verdict     an id <= K is checked iff it is complete, m >= 1 and work <= max_work (below).  It is IN CONFLICT iff it is
+ *               checked and cross + same > 0.  `opposite` is the shared wall of two pieces that meet and is reported only.
+ *               Touches are reported only: 4-connected components meet corner to corner.  `same` means that both interiors lie
+ *               on the same side of a common stretch; that reading assumes that every ring keeps its object on the side where
+ *               c3d_scene_outlines puts it (a table whose rings were reversed turns shared walls into `same`)
+ * What this does NOT decide:
+ *   - a boundary that passes from one side of another id's boundary to its other side exactly through a vertex is touches only;
+ *   - an object that lies wholly inside another without any edge contact is not seen;
+ *   - nothing is said about an id against itself.
+ * Raw traced rings never conflict: two directed pixel edges of different labels cannot cross, and a shared wall runs in opposite
+ * directions.
+ *   work        the implementation bins the live edges into a uniform grid of square cells of 2^s units whose origin is the
+ *               lower corner of the bounding box of all live edges; an edge is entered in every cell its own bounding box
+ *               covers.  s is the smallest shift in [0, 25] for which entries <= out[4] * n and cells <= out[5] * max(n, 1)
+ *               (c3d_rings_conflicts_limits), n = the live edges of the complete ids; one cell always satisfies both, and n <=
+ *               max_vertices, so both also hold against max_vertices.  work = the sum over the cells of n_c (n_c - 1) / 2 with
+ *               n_c the entries of cell c: a function of the input only.  If work >
+ *               max_work no pair is evaluated.  A pair of entries of a cell is evaluated iff the ids differ, the edges' bounding
+ *               boxes meet and the cell holds the lower corner of the boxes' intersection, so every pair is evaluated once
+ * Inputs (device): the table; max_work >= 0.
+ * Outputs (all written by the call):
+ *   conflict   i64 [max_ids][8], row id-1 = (flag, partner, m, cross, same, opposite, touch_vv, touch_ve); flag 0 checked, 1
+ *              empty (no live edge), 2 incomplete, 3 over max_work, which then holds for every id that would otherwise be
+ *              checked.  partner = the smallest other id with which this id has a cross or same pair, 0 if none.  The counts are
+ *              this id's edges against all other ids, so an edge pair appears in two rows.  m is 0 for an incomplete id; for
+ *              flags 2 and 3 the pair counts and partner are 0.  Rows past K are 0
+ *   counts     i64 [8] = (checked, in conflict, empty, incomplete, over work, sum cross, sum same, status) over the ids 1 .. K;
+ *              each edge pair is counted once in the sums; status = counts[4] of the table as it came
+ *   info       i64 [8] = (live edges of complete ids, s, cells_x, cells_y, entries, work, sum opposite, sum touch_vv + touch_ve),
+ *              pairs once.  Elements 1 .. 5 describe the grid and are the implementation's; the others are fixed by the rule
+ *   totals     i64 [8] or NULL: counts[0..6] are ADDED into it and status is OR-ed into totals[7] by one thread at the end of
+ *              the last launch, so calls on one stream accumulate in stream order.  The caller zeroes it once
+ *   ws         c3d_rings_conflicts_ws_bytes(...) bytes, 256-byte aligned, a function of the three maxima alone; a dirty one
+ *              gives the same result
+ * Tiers.  A cell of at most out[0] entries runs in one wave: a lane per entry, the other entry by shuffle.  A larger cell is cut
+ * into chunks of out[1] entries; the job (cell, chunk i) of a cell of c chunks compares chunk i with the chunks i, i+1, .., i +
+ * floor(c/2) (mod c), staged through LDS out[2] entries at a time, so one crowded cell spreads over the compute units.
+ * Registration is by bounding box: a long diagonal edge enters every cell of its box, which shows in `entries`; max_work stands
+ * in for a finer index.
+ * Refused before anything is enqueued (C3D_E_BADARG): a NULL pointer other than totals / stream, frac_bits outside [0, 8],
+ * a max below 1, max_work < 0.
+ * c3d_rings_conflicts_limits: out[0] = the most entries of a cell in the wave tier, out[1] = the entries of a chunk, out[2] = the
+ * entries of an LDS tile, out[3] = RING_LIMIT, out[4] = the entry budget and out[5] = the cell budget per live edge (so per
+ * vertex).  Host only.                                                                                                                       */
+void c3d_rings_conflicts_limits(int32_t out[6]);
+int64_t c3d_rings_conflicts_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_ids);   /* < 0: C3D_E_* */
+int c3d_rings_conflicts(const int32_t* rings, const int32_t* vertices, const int32_t* counts_in, int32_t max_rings,
+                        int32_t max_vertices, int32_t frac_bits, int32_t max_ids, int64_t max_work, int64_t* conflict,
+                        int64_t* counts, int64_t* info, int64_t* totals, void* ws, void* stream);
 
 /* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
  * in HBM.  The rule:
