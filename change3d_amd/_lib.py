@@ -214,6 +214,9 @@ SIGNATURES = {
     "c3d_rings_conflicts_limits": (None, [C.POINTER(i32)]),
     "c3d_rings_conflicts_ws_bytes": (i64, [i32, i32, i32]),
     "c3d_rings_conflicts": (i32, [vp, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp]),
+    "c3d_outlines_simplify_shared_limits": (None, [C.POINTER(i32)]),
+    "c3d_outlines_simplify_shared_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "c3d_outlines_simplify_shared": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
     "c3d_scene_edt_ws_bytes": (i64, [i32, i32]),
     "c3d_scene_edt_tile": (i32, [C.POINTER(i32)]),
     "c3d_scene_edt": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),

@@ -29,6 +29,13 @@ a ring table and a vertex list; it is enqueued behind the labelling, before the 
 simplified by `c3d_outlines_simplify` (Douglas-Peucker, `tol` in pixels), enqueued behind the tracing, before the same one
 synchronisation.  Its rows are `(id, start, n_vertices, 2 * area, perimeter, x, y, raw n_vertices)`.
 
+`predict(..., simplify=tol, simplify_shared=True)` puts a `SceneSharedOutlines` in that place instead: the rings cut at the points
+where three or more regions of the label map meet and simplified once per arc between two such nodes
+(`c3d_outlines_simplify_shared`), so that two neighbours -- the pieces of `split=R` above all -- share their wall vertex for
+vertex.  Its first three fields are those of the simplified `SceneOutlines`, and every later stage takes it unchanged; `left` is
+the label on the other side of the edge leaving each vertex, `info` counts nodes, arcs and collapsed rings.  Still the same one
+synchronisation.
+
 `predict(..., simplify=tol, simplify_check=True)` appends a `SceneFill` after that: the simplified rings filled back into a
 label map of the scene's size (`c3d_rings_fill`, centre sampling, even-odd per id) and joined to the raw objects with
 `c3d_objects_match` at the lowest threshold, 0.5 -- per object what the simplification cost: its partner, intersection and union
@@ -93,6 +100,11 @@ class SceneSplitObjects(SceneObjects):
 # [max_vertices, 2] = (vx, vy) lattice points, ring after ring; counts i32 [5] = (rings found, rows written, vertices found,
 # vertices written, status: _lib.OUTLINE_ST_*)
 SceneOutlines = namedtuple("SceneOutlines", "rings vertices counts")
+# `predict(..., simplify=tol, simplify_shared=True)`: rings, vertices and counts as the simplified SceneOutlines has them (vertices
+# has twice the rows, (x, y) of a row is the ring's first vertex); left i32 [2 max_vertices] = the label left of the edge that
+# leaves each vertex, the object being on the right; info i32 [8] = (nodes inserted, node vertices, arcs, closed arcs, arcs with a
+# neighbour, collapsed rings, 0, 0)
+SceneSharedOutlines = namedtuple("SceneSharedOutlines", "rings vertices counts left info")
 # the simplified rings filled back into pixels (`c3d_rings_fill`) and joined to the raw objects (`c3d_objects_match`, prediction =
 # the raw objects): labels, table [max_objects, 8] and counts [2] as in SceneObjects; info i32 [4] = (status, ring rows used, K,
 # 0); match = (match_raw i32 [max_objects, 4], match_filled i32 [max_objects, 4], conf, counts i64 [6], sum_iou f64 [1])
@@ -236,6 +248,9 @@ class SceneInferencer:
     `simplify=tol` (with `outlines=True`) appends one more `SceneOutlines`: the rings simplified with a tolerance of `tol`
     pixels in [0, 1024] (`ops.outlines_simplify`); column 3 of its rows is twice the signed area of the simplified ring and
     column 7 the ring's raw vertex count.  With `simplify=None` the result is the one without the argument.
+    `simplify_shared=True` (with `simplify=tol`) puts a `SceneSharedOutlines` there instead (`ops.outlines_simplify_shared`): walls
+    between objects are simplified once for both neighbours; `simplify_check`, `shapes`, `regularize`, `validity` and `conflicts`
+    take it unchanged.  With `simplify_shared=False` the launches are the ones without the argument.
     `simplify_check=True` (with `simplify=tol`) appends a `SceneFill`: the simplified rings filled back into pixels
     (`ops.rings_fill`) and matched to the raw objects (`ops.objects_match`, raw objects first, threshold 0.5): row id-1 of
     `match[0]` is (partner id, intersection, union, covered) of raw object `id`.  With `simplify_check=False` the launches are
@@ -315,7 +330,7 @@ class SceneInferencer:
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
                 max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False, shapes=False,
-                regularize=False, regularize_check=False, validity=False, conflicts=False):
+                regularize=False, regularize_check=False, validity=False, conflicts=False, simplify_shared=False):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
         if validity and not outlines:
@@ -337,6 +352,8 @@ class SceneInferencer:
             if not outlines:
                 raise ValueError("simplify=tol simplifies the outlines of the objects: it needs outlines=True")
             ops.simplify_tol2_q(simplify)               # raises outside [0, 1024] before anything is enqueued
+        if simplify_shared and simplify is None:
+            raise ValueError("simplify_shared=True chooses how simplify=tol simplifies: it needs simplify")
         if simplify_check and simplify is None:
             raise ValueError("simplify_check=True measures what simplify=tol cost: it needs simplify")
         if regularize and simplify is None:
@@ -420,10 +437,14 @@ class SceneInferencer:
                                                              max_rings=max_rings, max_vertices=max_vertices)),)
                 raw = result[-1]
                 if simplify is not None:
-                    result += (SceneOutlines(*ops.outlines_simplify(*result[-1], simplify)),)
-                    simple = result[-1]
+                    if simplify_shared:
+                        result += (SceneSharedOutlines(*ops.outlines_simplify_shared(labels, counts, *raw, simplify,
+                                                                                     max_objects=max_objects)),)
+                    else:
+                        result += (SceneOutlines(*ops.outlines_simplify(*raw, simplify)),)
+                    simple = result[-1][:3]             # what every later stage takes
                     if simplify_check:
-                        f_labels, f_table, f_counts, _, _, f_info = ops.rings_fill(*result[-1], Hs, Ws, max_objects=max_objects)
+                        f_labels, f_table, f_counts, _, _, f_info = ops.rings_fill(*simple, Hs, Ws, max_objects=max_objects)
                         match = ops.objects_match(labels, table, counts, f_labels, f_table, f_counts, n_cls=1, iou_thr=0.5)
                         result += (SceneFill(f_labels, f_table, f_counts, f_info, match),)
                 hull = ops.rings_hull(*raw, max_objects=max_objects) if shapes or regularize else None   # one call for both

@@ -977,6 +977,51 @@ def outlines_simplify(rings, vertices, counts, tol, ws=None):
     return rings_out, vertices_out, out
 
 
+def outlines_simplify_shared_limits():
+    """(most augmented vertices of a ring that one wave simplifies, most of a ring whose state one workgroup keeps in LDS)."""
+    out = (L.C.c_int32 * 2)()
+    L.lib().c3d_outlines_simplify_shared_limits(out)
+    return int(out[0]), int(out[1])
+
+
+def outlines_simplify_shared(labels, counts_obj, rings, vertices, counts, tol, max_objects=65536, max_vertices_out=None, ws=None):
+    """c3d_outlines_simplify_shared on the `labels` i32 [Hs, Ws] and `counts_obj` i32 [2] of `scene_objects` / `scene_split` and the
+    `rings`, `vertices` and `counts` that `scene_outlines` wrote for them: every wall between two objects is cut at the points
+    where three or more regions meet and simplified once for both neighbours, with the tolerance `tol` in pixels, by the integer
+    rule of include/change3d_hip.h.  Returns `(rings_out i32 [max_rings, 8] = (id, start', n', area2', perimeter, x', y', n),
+    vertices_out i32 [max_vertices_out, 2], counts_out i32 [5], left i32 [max_vertices_out] = the label left of the edge that
+    leaves each vertex, info i32 [8] = (nodes inserted, node vertices, arcs, closed arcs, arcs with a neighbour, collapsed rings,
+    0, 0))`, all on the device; nothing is read back.  `max_vertices_out` defaults to twice the rows of `vertices`, which
+    always suffices for a complete table.  Vertex and left rows past counts_out[3] are not initialised."""
+    tol2_q = simplify_tol2_q(tol)
+    for t in (labels, counts_obj, rings, vertices, counts):
+        require_gpu(t, "outlines_simplify_shared input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert labels.dim() == 2 and counts_obj.numel() == 2
+    assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    Hs, Ws = int(labels.shape[0]), int(labels.shape[1])
+    max_rings, max_vertices = int(rings.shape[0]), int(vertices.shape[0])
+    max_out = 2 * max_vertices if max_vertices_out is None else int(max_vertices_out)
+    nbytes = L.lib().c3d_outlines_simplify_shared_ws_bytes(Hs, Ws, max_rings, max_vertices)
+    if nbytes < 0 or max_out < 1 or int(max_objects) < 1:
+        raise L.Change3DHipError(f"c3d_outlines_simplify_shared refuses a {Hs} x {Ws} scene with max_objects = {max_objects}, max_rings = "
+                                 f"{max_rings}, max_vertices = {max_vertices}, max_vertices_out = {max_out} (code "
+                                 f"{nbytes if nbytes < 0 else -1})")
+    dev = rings.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    rings_out = torch.empty((max_rings, 8), dtype=torch.int32, device=dev)
+    vertices_out = torch.empty((max_out, 2), dtype=torch.int32, device=dev)
+    left = torch.empty(max_out, dtype=torch.int32, device=dev)
+    out = torch.empty(5, dtype=torch.int32, device=dev)
+    info = torch.empty(8, dtype=torch.int32, device=dev)
+    _launch("c3d_outlines_simplify_shared", (max_rings + max_vertices) * 128, L.lib().c3d_outlines_simplify_shared, _p(labels),
+            _p(counts_obj), Hs, Ws, int(max_objects), _p(rings), _p(vertices), _p(counts), max_rings, max_vertices, tol2_q, max_out,
+            _p(rings_out), _p(vertices_out), _p(left), _p(out), _p(info), _p(ws), _stream())
+    return rings_out, vertices_out, out, left, info
+
+
 def rings_fill_limits():
     """(most rows and columns of an id's pixel box that one wave fills, rows of a band of a larger box); host only."""
     out = (C.c_int32 * 2)()

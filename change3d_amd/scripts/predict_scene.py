@@ -30,7 +30,14 @@ into pixels (`c3d_rings_fill`: a pixel belongs to a polygon iff its centre lies 
 joined to the raw objects (`c3d_objects_match`, whose partners are unique because a pair needs an IoU above 0.5: an object that
 drifted further has no partner and the IoU 0).  Every feature gets an `iou` property and the run ends with a line `simplify: tol
 objects kept vanished iou_mean iou_min`: `kept` counts the objects whose partner is their own id, `vanished` those without a
-pixel after the fill.  `--simplify_min_iou F` implies the check and leaves every object whose IoU is not above F on its raw
+pixel after the fill.  `--simplify_shared` (with `--simplify`) simplifies every wall between two objects once for both
+(`c3d_outlines_simplify_shared`): the rings are cut at the points where three or more regions of the label map meet, each arc
+between two such nodes is simplified on its own, and both neighbours get the same vertices.  Every feature gets `neighbours`, the
+sorted ids on the other side of its walls, and `collapsed`; an object whose outline collapsed or changed the sign of its area is
+written with `"geometry": null`, a hole that did is left out, and nothing ever falls back to raw vertices -- which is why the flag
+is refused together with `--simplify_min_iou`, `--simplify_valid` and `--simplify_clean`.  The run ends with a line `shared: tol
+= .. objects = .. nodes = .. arcs = .. shared_arcs = .. collapsed = ..`.  With `--regularize` the squared rings no longer share
+their walls.  `--simplify_min_iou F` implies the check and leaves every object whose IoU is not above F on its raw
 vertices, in every ring.
 
 `--shapes` (with `--polygons`) describes every object's shape, on the device (`c3d_rings_hull` on the raw rings): each feature
@@ -219,7 +226,8 @@ def not_valid_ids(rows):
     return {k + 1 for k, row in enumerate(np.asarray(rows).tolist()) if not validity_properties(row)["valid"]}
 
 
-def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=None, extra=None, validity=None, not_valid=None):
+def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=None, extra=None, validity=None, not_valid=None,
+                     shared=None):
     """(FeatureCollection dict, ids left out) from host arrays: `table` [rows, 8] of the objects, `rings` [ring rows, 8] and
     `vertices` [vertices written, 2] of their outlines.  An object is complete iff it has one ring of positive area, every
     ring of it has its vertices (start >= 0) and the signed areas add up to the table's area -- a hole ring cut off by
@@ -233,7 +241,11 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
     `extra`: id -> further properties of that object's feature (`--shapes`).
     `validity` [rows, 8]: the rows of `c3d_rings_valid` on the stage that is written (the simplified one with `simplified`);
     every feature gets `valid`, `crossings`, `overlaps` and `touches`.  `not_valid` (with `simplified`): ids that keep their raw
-    vertices in every ring, as an object below `min_iou` does."""
+    vertices in every ring, as an object below `min_iou` does.
+    `shared` (with `simplified` = the rings and vertices of `c3d_outlines_simplify_shared`): its `left` labels.  No ring ever
+    falls back to its raw vertices then, since that would break the sharing: an object whose outline collapsed (fewer than 3
+    vertices, or a doubled area that is zero or changed its sign) is written with "geometry": null, a hole that did is left out,
+    and every feature gets `neighbours`, the sorted ids on the other side of its walls, and `collapsed`."""
     table, rings, vertices = np.asarray(table), np.asarray(rings), np.asarray(vertices)
     if simplified is not None:
         rings_s, vertices_s = np.asarray(simplified[0]).tolist(), np.asarray(simplified[1])
@@ -248,12 +260,22 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
             skipped.append(k + 1)
             continue
         coords, n_raw, n_out = [], 0, 0
+        neighbours, collapsed, gone = set(), False, False
         drifted = simplified is not None and iou is not None and min_iou is not None and not float(iou[k]) > min_iou
         drifted = drifted or (simplified is not None and not_valid is not None and k + 1 in not_valid)
         for r in outline + [r for r in own if r[3] <= 0]:  # the outline, then the holes in ring order
             ring = vertices[r[1]:r[1] + r[2]].tolist()
             n_raw += len(ring)
-            if simplified is not None and not drifted:
+            if shared is not None:
+                s = rings_s[r[8]]
+                if 0 <= s[1] and s[1] + s[2] <= len(vertices_s):      # also of a ring that collapsed: the wall is still shared
+                    neighbours.update(int(v) for v in shared[s[1]:s[1] + s[2]] if v > 0)
+                if s[1] < 0 or s[1] + s[2] > len(vertices_s) or s[2] < 3 or s[3] == 0 or (s[3] > 0) != (r[3] > 0):
+                    collapsed = True
+                    gone = gone or r[3] > 0
+                    continue
+                ring = vertices_s[s[1]:s[1] + s[2]].tolist()
+            elif simplified is not None and not drifted:
                 s = rings_s[r[8]]
                 if s[1] >= 0 and s[1] + s[2] <= len(vertices_s) and s[3] != 0 and (s[3] > 0) == (r[3] > 0):
                     ring = vertices_s[s[1]:s[1] + s[2]].tolist()
@@ -264,11 +286,14 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
             properties.update(vertices_raw=n_raw, vertices=n_out)
             if iou is not None:
                 properties.update(iou=round(float(iou[k]), 4))
+        if shared is not None:
+            properties.update(neighbours=sorted(neighbours), collapsed=collapsed)
         if extra is not None:
             properties.update(extra.get(k + 1, {}))
         if validity is not None:
             properties.update(validity_properties(validity[k] if k < len(validity) else EMPTY_ROW))
-        features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords}, "properties": properties})
+        geometry = None if gone else {"type": "Polygon", "coordinates": coords}
+        features.append({"type": "Feature", "geometry": geometry, "properties": properties})
     return {"type": "FeatureCollection", "features": features}, skipped
 
 
@@ -323,7 +348,7 @@ def doc_table(doc, frac_bits, device):
     written, on `device`: one ring per linear ring without its closing vertex, coordinates times 2^frac_bits."""
     rows, verts = [], []
     for feature in doc["features"]:
-        for ring in feature["geometry"]["coordinates"]:
+        for ring in (feature["geometry"] or {"coordinates": []})["coordinates"]:
             rows.append([feature["properties"]["id"], len(verts), len(ring) - 1, 0, 0, 0, 0, 0])
             verts += [[int(round(x * (1 << frac_bits))), int(round(y * (1 << frac_bits)))] for x, y in ring[:-1]]
     rings = torch.tensor(rows or [[0] * 8], dtype=torch.int32, device=device).reshape(-1, 8)
@@ -382,10 +407,14 @@ def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=No
     left out."""
     ring_rows, written = int(outlines.counts[1]), int(outlines.counts[3])
     rows = int(objects.counts[1])
+    shared = None
     if simplified is not None:
+        if hasattr(simplified, "left"):                   # a SceneSharedOutlines of --simplify_shared
+            shared = simplified.left[:int(simplified.counts[3])].cpu().numpy()
         simplified = (simplified.rings[:ring_rows].cpu().numpy(), simplified.vertices[:int(simplified.counts[3])].cpu().numpy())
     doc, skipped = polygons_geojson(objects.table[:rows].cpu().numpy(), outlines.rings[:ring_rows].cpu().numpy(),
-                                    outlines.vertices[:written].cpu().numpy(), simplified, iou, min_iou, extra, validity, not_valid)
+                                    outlines.vertices[:written].cpu().numpy(), simplified, iou, min_iou, extra, validity, not_valid,
+                                    shared)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
         json.dump(doc, f)
@@ -426,12 +455,16 @@ def regular_geojson(doc, rings, regular, iou=None, min_iou=None, validity=None, 
                 break
             ring = (v / scale).tolist()
             coords.append(ring + ring[:1])
+        ok = ok and feature["geometry"] is not None       # a collapsed outline of --simplify_shared: nothing to square or to keep
         properties = dict(feature["properties"], regular=ok)
         if iou is not None:
             properties["iou"] = round(float(iou[k - 1]), 4)
         if validity is not None:
             properties.update(validity_properties(validity[k - 1] if k - 1 < len(validity) else EMPTY_ROW))
         done += ok
+        if feature["geometry"] is None:
+            features.append({"type": "Feature", "geometry": None, "properties": properties})
+            continue
         features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": coords if ok else feature["geometry"]["coordinates"]},
                          "properties": properties})
     return {"type": "FeatureCollection", "features": features}, done, len(features) - done
@@ -639,6 +672,11 @@ def parse_args(argv=None):
         args.simplify_check = True
     if args.simplify_check and args.simplify is None:
         parser.error("--simplify_check and --simplify_min_iou measure what --simplify cost: they need --simplify")
+    if args.simplify_shared and args.simplify is None:
+        parser.error("--simplify_shared chooses how --simplify simplifies: it needs --simplify")
+    if args.simplify_shared and (args.simplify_min_iou is not None or args.simplify_valid or args.simplify_clean):
+        parser.error("--simplify_shared shares every wall between its two objects: a fall-back of single objects to their raw vertices "
+                     "(--simplify_min_iou, --simplify_valid, --simplify_clean) would break that")
     if args.regularize_min_iou is not None and not args.regularize:
         parser.error("--regularize_min_iou is the fallback threshold of --regularize: it needs --regularize")
     if args.regularize and (not args.polygons or args.simplify is None):
@@ -727,6 +765,8 @@ def main(argv=None):
     split = {} if args.split_objects is None else dict(split=args.split_objects, split_rounds=args.split_rounds)
     if args.simplify_check:
         split["simplify_check"] = True
+    if args.simplify_shared:
+        split["simplify_shared"] = True
     if args.shapes:
         split["shapes"] = True
     if args.regularize:
@@ -736,6 +776,7 @@ def main(argv=None):
         split["validity"] = True
     if args.conflicts:
         split["conflicts"] = True
+    shared_sums = dict(objects=0, nodes=0, arcs=0, shared_arcs=0, collapsed=0)   # --simplify_shared over all scenes
     conflict_sums = {}                                    # --conflicts over all scenes: stage -> counts, objects by name
     validity_sums = {}                                    # --validity over all scenes: stage -> counts, unchecked objects by name
     squared =dict(objects=0, regular=0, fallback=0, iou_sum=0.0, iou_min=1.0)   # --regularize over all scenes
@@ -772,6 +813,13 @@ def main(argv=None):
                              iou_sum=drift["iou_sum"] + float(iou.sum()), iou_min=min([drift["iou_min"]] + iou.tolist()))
             if args.simplify is not None:
                 out, simplified = out[:-1], out[-1]
+            if args.simplify_shared:
+                if int(simplified.counts[4]) & (L.OUTLINE_ST_BAD_COUNTS | L.SIMPLIFY_ST_BAD_INPUT):
+                    raise SystemExit(f"{name}: --simplify_shared: c3d_outlines_simplify_shared status {int(simplified.counts[4])}")
+                _, nodes, arcs, _, shared_arcs, collapsed, _, _ = (int(v) for v in simplified.info.cpu().tolist())
+                shared_sums = dict(objects=shared_sums["objects"] + int(out[-2].counts[1]), nodes=shared_sums["nodes"] + nodes,
+                                   arcs=shared_sums["arcs"] + arcs, shared_arcs=shared_sums["shared_arcs"] + shared_arcs,
+                                   collapsed=shared_sums["collapsed"] + collapsed)
             check_split(name, out[-2])
             written_v = valid_rows.get("simplified" if simplified is not None else "raw")   # of the coordinates that are written
             bad_v = not_valid_ids(valid_rows["simplified"]) if args.simplify_valid else None
@@ -897,6 +945,9 @@ def main(argv=None):
     if args.simplify_check:
         print(f"simplify: tol = {args.simplify:g} objects = {drift['objects']} kept = {drift['kept']} vanished = {drift['vanished']} "
               f"iou_mean = {drift['iou_sum'] / max(drift['objects'], 1):.4f} iou_min = {drift['iou_min'] if drift['objects'] else 0.0:.4f}")
+    if args.simplify_shared:
+        print(f"shared: tol = {args.simplify:g} objects = {shared_sums['objects']} nodes = {shared_sums['nodes']} "
+              f"arcs = {shared_sums['arcs']} shared_arcs = {shared_sums['shared_arcs']} collapsed = {shared_sums['collapsed']}")
     if args.shapes:
         n_shapes = max(shape_sums["objects"], 1)
         print(f"shapes: objects = {shape_sums['objects']} solidity_mean = {shape_sums['solidity'] / n_shapes:.4f} "
@@ -975,6 +1026,10 @@ def build_parser():
     p.add_argument("--max_vertices", type=int, default=None, help="--polygons: rows of the vertex list (default: 16 per ring row)")
     p.add_argument("--simplify", type=simplify_tolerance, default=None, metavar="TOL", help="--polygons: simplify the rings on the "
                    "device (Douglas-Peucker) with this tolerance in pixels, in [0, 1024]")
+    p.add_argument("--simplify_shared", action="store_true", help="--simplify: cut the rings where three or more regions meet and simplify "
+                   "every wall once for both neighbours; features get `neighbours` and `collapsed`, a collapsed outline is written "
+                   "with a null geometry, and the run ends with a `shared:` line.  Not with --simplify_min_iou, --simplify_valid or "
+                   "--simplify_clean")
     p.add_argument("--simplify_check", action="store_true", help="--simplify: fill the simplified polygons back into pixels on the device "
                    "and join them to the raw objects: an `iou` per feature and a closing `simplify:` line")
     p.add_argument("--simplify_min_iou", type=unit_interval, default=None, metavar="F", help="--simplify: implies --simplify_check; an "

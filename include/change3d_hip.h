@@ -1123,6 +1123,80 @@ int c3d_rings_conflicts(const int32_t* rings, const int32_t* vertices, const int
                         int32_t max_vertices, int32_t frac_bits, int32_t max_ids, int64_t max_work, int64_t* conflict,
                         int64_t* counts, int64_t* info, int64_t* totals, void* ws, void* stream);
 
+/* Shared-wall simplification (csrc/scene_shared.hip): the traced rings of a label map that is still in HBM, cut at the lattice
+ * points where three or more regions meet and simplified once per arc between two such nodes, so that the wall of A against B
+ * is the wall of B against A, vertex for vertex, and an island's outline is the reverse of the hole it sits in.  A sibling of
+ * c3d_outlines_simplify, which simplifies ring by ring and knows nothing of labels; that call is unchanged.  Integers only,
+ * nothing is rounded, two runs agree bit for bit.  One memset and 10 launches on `stream`, nothing is read back, no workgroup
+ * waits for another.  The rule:
+ *   labels      l(y, x) = labels[y][x] if the pixel is in the scene and 1 <= value <= rows, else 0; rows = clamp(counts_obj[1],
+ *               0, max_objects), as c3d_scene_outlines defines it
+ *   nodes       for a lattice point (vx, vy) let a = l(vy-1, vx-1), b = l(vy-1, vx), c = l(vy, vx-1), d = l(vy, vx).  Its degree
+ *               is [a != b] + [c != d] + [a != c] + [b != d]; it is a node iff degree >= 3.  Degree 4 includes the diagonal
+ *               pinch a == d != b == c
+ *   augmented   for every stored edge v[k] -> v[k+1] (v[n] = v[0]): v[k], then every lattice point strictly inside the edge that
+ *               is a node, in travel order: a wall that runs straight through a T-junction gets the junction as a vertex, since
+ *               the neighbours on the other side have their corner there.  Every augmented vertex carries `node` and `left` =
+ *               the label left of the unit edge leaving it, the object on the right and y down: travelling +x it is l(y-1, x),
+ *               +y l(y, x), -x l(y, x-1), -y l(y-1, x-1).  Between two nodes every lattice point has degree 2, so `left` is
+ *               constant along an arc
+ *   start       a ring with nodes starts at its first node in stored (augmented) order; one without at its vertex with the
+ *               smallest (vy, vx), which is unique since such a ring visits no lattice point twice
+ *   arcs        run between cyclically consecutive nodes; all nodes are kept.  A ring without nodes is one arc from its start to
+ *               itself.  An arc whose two ends are the same lattice point is closed
+ *   per arc     Douglas-Peucker with the segment distance num / den and the strict 16 num > tol2_q den of
+ *               c3d_outlines_simplify.  The farthest vertex of a chord has the largest num; ties go to the smallest (vy, vx),
+ *               NOT to the index: with the symmetric distance this makes the result independent of the direction of travel.  A
+ *               chord whose two ends coincide always splits (in a traced ring only the chord of a whole closed arc is one; its
+ *               num is |p - N|^2): a closed arc with interior vertices always keeps M, its interior vertex farthest from its
+ *               node N, and goes on with the chains N..M and M..N.  If neither chain keeps anything the closed arc also keeps T,
+ *               its interior vertex with the largest |cross(M - N, p - N)|, same tie, iff that cross product is not 0: a ring
+ *               with at most one node never loses its area.  Open arcs have no such guard: it could not be decided identically
+ *               from both sides
+ * What follows from it:
+ *   - every dropped vertex lies within tol of the kept chord that spans it
+ *   - the twin property: for every output edge p -> q of id i with left = j > 0 the table holds the edge q -> p of id j with
+ *     left = i, equally often (for a complete table of the same labels)
+ *   - at tol2_q == 0 the output is the augmented ring, rotated to its start
+ *   - a ring with two or more nodes may collapse (n' < 3 or area2' == 0); that is counted in info[5] and never repaired
+ *   - chords of DIFFERENT arcs may still cross, and a neck narrower than the tolerance that collapses onto one line puts its two
+ *     neighbours on that line from both sides: c3d_rings_conflicts finds both.  Neither is decided here
+ * Inputs (device): labels i32 [Hs][Ws] and counts_obj i32 [2] of c3d_scene_objects / c3d_scene_split; rings, vertices, counts as
+ * c3d_scene_outlines wrote them for those labels (alignment as for c3d_outlines_simplify); tol2_q as in c3d_outlines_simplify.
+ * Outputs (must not alias the inputs):
+ *   rings_out     i32 [max_rings][8], 16-byte aligned, input row order: (id, start', n', area2', perimeter, x', y', n); (x', y')
+ *                 = the first output vertex = the ring's start; area2' as c3d_outlines_simplify defines it.  Rows past the last 0
+ *   vertices_out  i32 [max_vertices_out][2], 8-byte aligned;  left_out i32 [max_vertices_out] = `left` of the edge leaving that
+ *                 vertex.  Rows past counts_out[3] are left as they were
+ *   counts_out    i32 [5] = (rings found, rows written, vertices kept, vertices written, status).  The table goes unchanged
+ *                 into c3d_rings_fill, _hull, _valid, _conflicts, _polis and _regularize
+ *   info          i32 [8] = (straight-through nodes inserted, node vertices, arcs, closed arcs, arcs with left > 0, collapsed
+ *                 rings among the written ones, 0, 0); the first five over all simplified rows
+ *   ws            c3d_outlines_simplify_shared_ws_bytes(Hs, Ws, max_rings, max_vertices) bytes (24 per ring row, 66 per vertex row:
+ *                 room for 2 max_vertices augmented vertices; a quarter byte per lattice point for the two node bitmaps),
+ *                 256-byte aligned; the call zeroes what it needs of it
+ * Rows that are not simplified get start' = -1, n' = 0, area2' = 0 and keep the input's x, y:
+ *   start < 0        passed through, no new status bit
+ *   bad input        n < 4, start + n above the written vertices, a vertex outside [0, Ws] x [0, Hs], an edge that is zero or
+ *                    not parallel to an axis, or augmented rings of this and all earlier valid rows that add up to more than
+ *                    2 max_vertices: C3D_SIMPLIFY_ST_BAD_INPUT
+ *   no room          truncation is prefix-shaped as in c3d_scene_outlines: a ring with start' + n' > max_vertices_out, and
+ *                    every ring after it; counts_out[2] > counts_out[3] and C3D_OUTLINE_ST_TRUNCATED.  Every straight-through
+ *                    node is a corner of some other ring, so 2 * (vertices written by the outlines call) always suffices
+ * Nothing is read or written out of range.  Input status C3D_OUTLINE_ST_BAD_COUNTS: counts_out = (0, 0, 0, 0,
+ * C3D_OUTLINE_ST_BAD_COUNTS), all ring rows and info 0.
+ * Refused before anything is enqueued: a NULL pointer, Hs, Ws, max_objects, max_rings, max_vertices or max_vertices_out < 1,
+ * max_objects or max_vertices above 2^30, tol2_q out of range (C3D_E_BADARG); Hs or Ws above 16384 (C3D_E_UNSUPPORTED).
+ * c3d_outlines_simplify_shared_limits: out[0] = the most augmented vertices of a ring that one wave simplifies, out[1] = the most
+ * of a ring whose state one workgroup keeps in LDS; larger rings keep it in `ws`.  The results do not depend on the tier.       */
+void c3d_outlines_simplify_shared_limits(int32_t out[2]);
+int64_t c3d_outlines_simplify_shared_ws_bytes(int32_t Hs, int32_t Ws, int32_t max_rings, int32_t max_vertices);   /* < 0: C3D_E_* */
+int c3d_outlines_simplify_shared(const int32_t* labels, const int32_t* counts_obj, int32_t Hs, int32_t Ws, int32_t max_objects,
+                                 const int32_t* rings, const int32_t* vertices, const int32_t* counts, int32_t max_rings,
+                                 int32_t max_vertices, int64_t tol2_q, int32_t max_vertices_out, int32_t* rings_out,
+                                 int32_t* vertices_out, int32_t* left_out, int32_t* counts_out, int32_t* info, void* ws,
+                                 void* stream);
+
 /* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
  * in HBM.  The rule:
  *   sites       the pixels with mask == 0; with C3D_EDT_INVERT (bit 0 of flags) the pixels with mask != 0
