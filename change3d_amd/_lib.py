@@ -217,6 +217,10 @@ SIGNATURES = {
     "c3d_outlines_simplify_shared_limits": (None, [C.POINTER(i32)]),
     "c3d_outlines_simplify_shared_ws_bytes": (i64, [i32, i32, i32, i32]),
     "c3d_outlines_simplify_shared": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "c3d_outlines_simplify_safe_limits": (None, [C.POINTER(i32)]),
+    "c3d_outlines_simplify_safe_ws_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "c3d_outlines_simplify_safe": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp]),
     "c3d_scene_edt_ws_bytes": (i64, [i32, i32]),
     "c3d_scene_edt_tile": (i32, [C.POINTER(i32)]),
     "c3d_scene_edt": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),

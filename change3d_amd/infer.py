@@ -36,6 +36,13 @@ vertex.  Its first three fields are those of the simplified `SceneOutlines`, and
 the label on the other side of the edge leaving each vertex, `info` counts nodes, arcs and collapsed rings.  Still the same one
 synchronisation.
 
+`predict(..., simplify=tol, simplify_shared=True, simplify_safe=True)` puts a `SceneSafeOutlines` there: the same call in rounds
+(`c3d_outlines_simplify_safe`), in which every arc that takes part in a defect of the output -- chords that cross or overlap, a
+vertex inside another edge, a ring that collapsed or flipped -- gets a smaller tolerance of its own until a round finds nothing
+or `safe_rounds` rounds have run.  It is a `SceneSharedOutlines` with `.level`, the level of the arc of the edge leaving each
+vertex, and `.safe` i64 [8], whose last element says whether the loop converged.  The rounds are launched ahead: still the same
+one synchronisation.
+
 `predict(..., simplify=tol, simplify_check=True)` appends a `SceneFill` after that: the simplified rings filled back into a
 label map of the scene's size (`c3d_rings_fill`, centre sampling, even-odd per id) and joined to the raw objects with
 `c3d_objects_match` at the lowest threshold, 0.5 -- per object what the simplification cost: its partner, intersection and union
@@ -105,6 +112,21 @@ SceneOutlines = namedtuple("SceneOutlines", "rings vertices counts")
 # leaves each vertex, the object being on the right; info i32 [8] = (nodes inserted, node vertices, arcs, closed arcs, arcs with a
 # neighbour, collapsed rings, 0, 0)
 SceneSharedOutlines = namedtuple("SceneSharedOutlines", "rings vertices counts left info")
+
+
+class SceneSafeOutlines(SceneSharedOutlines):
+    """The `SceneSharedOutlines` of `predict(..., simplify_shared=True, simplify_safe=True)`: the same five fields, so everything
+    that takes a `SceneSharedOutlines` takes it, plus `.level` i32 [2 max_vertices] = the level of the arc of the edge leaving
+    each vertex and `.safe` i64 [8] = (rounds run, rounds that raised, arcs with level > 0, arcs at the cap, defective pairs in
+    round 0, in the last round, defective rings in round 0, status: `ops.outlines_simplify_safe`) of `c3d_outlines_simplify_safe`.  The two are attributes
+    of the instance, as `SceneSplitObjects.info` is: `_replace`, `_make` and slices give a plain tuple of the five fields."""
+
+    def __new__(cls, rings, vertices, counts, left, info, level, safe):
+        self = super().__new__(cls, rings, vertices, counts, left, info)
+        self.level, self.safe = level, safe
+        return self
+
+
 # the simplified rings filled back into pixels (`c3d_rings_fill`) and joined to the raw objects (`c3d_objects_match`, prediction =
 # the raw objects): labels, table [max_objects, 8] and counts [2] as in SceneObjects; info i32 [4] = (status, ring rows used, K,
 # 0); match = (match_raw i32 [max_objects, 4], match_filled i32 [max_objects, 4], conf, counts i64 [6], sum_iou f64 [1])
@@ -251,6 +273,9 @@ class SceneInferencer:
     `simplify_shared=True` (with `simplify=tol`) puts a `SceneSharedOutlines` there instead (`ops.outlines_simplify_shared`): walls
     between objects are simplified once for both neighbours; `simplify_check`, `shapes`, `regularize`, `validity` and `conflicts`
     take it unchanged.  With `simplify_shared=False` the launches are the ones without the argument.
+    `simplify_safe=True` (with `simplify_shared=True`) puts a `SceneSafeOutlines` there (`ops.outlines_simplify_safe`): the shared
+    call in at most `safe_rounds` rounds (default 8, in [1, 64]) that give the arcs of every defect a smaller tolerance; its
+    `.safe[7]` is 0 iff a round found nothing.  With `simplify_safe=False` the launches are the ones without the argument.
     `simplify_check=True` (with `simplify=tol`) appends a `SceneFill`: the simplified rings filled back into pixels
     (`ops.rings_fill`) and matched to the raw objects (`ops.objects_match`, raw objects first, threshold 0.5): row id-1 of
     `match[0]` is (partner id, intersection, union, covered) of raw object `id`.  With `simplify_check=False` the launches are
@@ -330,7 +355,8 @@ class SceneInferencer:
     @torch.no_grad()
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
                 max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False, shapes=False,
-                regularize=False, regularize_check=False, validity=False, conflicts=False, simplify_shared=False):
+                regularize=False, regularize_check=False, validity=False, conflicts=False, simplify_shared=False, simplify_safe=False,
+                safe_rounds=None):
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
         if validity and not outlines:
@@ -354,6 +380,14 @@ class SceneInferencer:
             ops.simplify_tol2_q(simplify)               # raises outside [0, 1024] before anything is enqueued
         if simplify_shared and simplify is None:
             raise ValueError("simplify_shared=True chooses how simplify=tol simplifies: it needs simplify")
+        if simplify_safe and not simplify_shared:
+            raise ValueError("simplify_safe=True refines the arcs of simplify_shared=True: it needs simplify_shared")
+        if safe_rounds is not None and not simplify_safe:
+            raise ValueError("safe_rounds limits the rounds of simplify_safe=True: it needs simplify_safe")
+        if simplify_safe:
+            safe_rounds = 8 if safe_rounds is None else int(safe_rounds)
+            if not 1 <= safe_rounds <= 64:
+                raise ValueError(f"safe_rounds must lie in [1, 64], got {safe_rounds}")
         if simplify_check and simplify is None:
             raise ValueError("simplify_check=True measures what simplify=tol cost: it needs simplify")
         if regularize and simplify is None:
@@ -437,7 +471,10 @@ class SceneInferencer:
                                                              max_rings=max_rings, max_vertices=max_vertices)),)
                 raw = result[-1]
                 if simplify is not None:
-                    if simplify_shared:
+                    if simplify_safe:
+                        result += (SceneSafeOutlines(*ops.outlines_simplify_safe(labels, counts, *raw, simplify, max_rounds=safe_rounds,
+                                                                                 max_objects=max_objects)),)
+                    elif simplify_shared:
                         result += (SceneSharedOutlines(*ops.outlines_simplify_shared(labels, counts, *raw, simplify,
                                                                                      max_objects=max_objects)),)
                     else:

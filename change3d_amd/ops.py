@@ -1022,6 +1022,59 @@ def outlines_simplify_shared(labels, counts_obj, rings, vertices, counts, tol, m
     return rings_out, vertices_out, out, left, info
 
 
+def outlines_simplify_safe_limits():
+    """(the two tier limits of the Douglas-Peucker as in `outlines_simplify_shared_limits`, most entries of a cell in the detector's
+    wave tier, entries of a chunk, entry budget and cell budget per live edge); host only."""
+    out = (C.c_int32 * 6)()
+    L.lib().c3d_outlines_simplify_safe_limits(out)
+    return tuple(int(v) for v in out)
+
+
+def outlines_simplify_safe(labels, counts_obj, rings, vertices, counts, tol, max_rounds=8, max_work=2 ** 32, max_objects=65536,
+                           max_vertices_out=None, ws=None):
+    """c3d_outlines_simplify_safe: `outlines_simplify_shared` in rounds with a tolerance per arc.  The arcs that take part in a
+    defect of the output (two edges that cross or overlap, a vertex inside another edge, a ring that collapsed or flipped) get a
+    quarter of their squared tolerance and every ring is simplified again, until a round finds nothing or `max_rounds` rounds
+    have run, by the integer rule of include/change3d_hip.h.  Returns `(rings_out, vertices_out, counts_out, left, info, level,
+    safe)`: the first five as `outlines_simplify_shared` returns them (info[6], info[7] = the shift and the work of the last
+    round's grid), `level` i32 [max_vertices_out] = the level of the arc of the edge that leaves each vertex, `safe` i64 [8] =
+    (rounds run, rounds that raised, arcs with level > 0, arcs at the cap, defective pairs in round 0, in the last round,
+    defective rings in round 0, status: 0 converged, 1 not converged, 2 defects left, 3 over `max_work`).  All on the device;
+    nothing is read back, the rounds are launched ahead."""
+    tol2_q = simplify_tol2_q(tol)
+    for t in (labels, counts_obj, rings, vertices, counts):
+        require_gpu(t, "outlines_simplify_safe input")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert labels.dim() == 2 and counts_obj.numel() == 2
+    assert rings.dim() == 2 and rings.shape[1] == 8 and vertices.dim() == 2 and vertices.shape[1] == 2 and counts.numel() == 5
+    if not 1 <= int(max_rounds) <= 64:
+        raise ValueError(f"max_rounds = {max_rounds} is outside [1, 64]")
+    if int(max_work) < 0:
+        raise ValueError(f"max_work = {max_work} is negative")
+    Hs, Ws = int(labels.shape[0]), int(labels.shape[1])
+    max_rings, max_vertices = int(rings.shape[0]), int(vertices.shape[0])
+    max_out = 2 * max_vertices if max_vertices_out is None else int(max_vertices_out)
+    nbytes = L.lib().c3d_outlines_simplify_safe_ws_bytes(Hs, Ws, max_rings, max_vertices, max_out) if max_out >= 1 else -1
+    if nbytes < 0 or int(max_objects) < 1:
+        raise L.Change3DHipError(f"c3d_outlines_simplify_safe refuses a {Hs} x {Ws} scene with max_objects = {max_objects}, max_rings = "
+                                 f"{max_rings}, max_vertices = {max_vertices}, max_vertices_out = {max_out} (code {min(nbytes, -1)})")
+    dev = rings.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_cuda
+    rings_out = torch.empty((max_rings, 8), dtype=torch.int32, device=dev)
+    vertices_out = torch.empty((max_out, 2), dtype=torch.int32, device=dev)
+    left = torch.empty(max_out, dtype=torch.int32, device=dev)
+    level = torch.empty(max_out, dtype=torch.int32, device=dev)
+    out = torch.empty(5, dtype=torch.int32, device=dev)
+    info = torch.empty(8, dtype=torch.int32, device=dev)
+    safe = torch.empty(8, dtype=torch.int64, device=dev)
+    _launch("c3d_outlines_simplify_safe", (max_rings + max_vertices) * 128, L.lib().c3d_outlines_simplify_safe, _p(labels),
+            _p(counts_obj), Hs, Ws, int(max_objects), _p(rings), _p(vertices), _p(counts), max_rings, max_vertices, tol2_q, int(max_rounds),
+            int(max_work), max_out, _p(rings_out), _p(vertices_out), _p(left), _p(level), _p(out), _p(info), _p(safe), _p(ws), _stream())
+    return rings_out, vertices_out, out, left, info, level, safe
+
+
 def rings_fill_limits():
     """(most rows and columns of an id's pixel box that one wave fills, rows of a band of a larger box); host only."""
     out = (C.c_int32 * 2)()

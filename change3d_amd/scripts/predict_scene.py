@@ -37,7 +37,13 @@ sorted ids on the other side of its walls, and `collapsed`; an object whose outl
 written with `"geometry": null`, a hole that did is left out, and nothing ever falls back to raw vertices -- which is why the flag
 is refused together with `--simplify_min_iou`, `--simplify_valid` and `--simplify_clean`.  The run ends with a line `shared: tol
 = .. objects = .. nodes = .. arcs = .. shared_arcs = .. collapsed = ..`.  With `--regularize` the squared rings no longer share
-their walls.  `--simplify_min_iou F` implies the check and leaves every object whose IoU is not above F on its raw
+their walls.  `--simplify_safe` (implies `--simplify_shared`, and is refused where that flag is) repairs what the shared rule
+leaves: `c3d_outlines_simplify_safe` runs it in at most `--safe_rounds N` rounds (default 8) and gives every arc that takes part
+in a defect -- edges that cross or overlap, a vertex inside another edge, a ring that collapsed or flipped -- a smaller tolerance
+of its own, the same for both neighbours.  Every feature gets `refined`, the number of its arcs with a level above 0, and the run
+ends with a line `safe: tol = .. rounds = .. raised = .. arcs_refined = .. arcs_raw = .. defects = <pairs in round 0> -> <in the
+last round>` (rounds and raised: the most of any scene).  A scene that did not converge ends the run with an error that names
+`--safe_rounds`, or the work cap.  `--simplify_min_iou F` implies the check and leaves every object whose IoU is not above F on its raw
 vertices, in every ring.
 
 `--shapes` (with `--polygons`) describes every object's shape, on the device (`c3d_rings_hull` on the raw rings): each feature
@@ -227,7 +233,7 @@ def not_valid_ids(rows):
 
 
 def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=None, extra=None, validity=None, not_valid=None,
-                     shared=None):
+                     shared=None, refined=None):
     """(FeatureCollection dict, ids left out) from host arrays: `table` [rows, 8] of the objects, `rings` [ring rows, 8] and
     `vertices` [vertices written, 2] of their outlines.  An object is complete iff it has one ring of positive area, every
     ring of it has its vertices (start >= 0) and the signed areas add up to the table's area -- a hole ring cut off by
@@ -245,7 +251,10 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
     `shared` (with `simplified` = the rings and vertices of `c3d_outlines_simplify_shared`): its `left` labels.  No ring ever
     falls back to its raw vertices then, since that would break the sharing: an object whose outline collapsed (fewer than 3
     vertices, or a doubled area that is zero or changed its sign) is written with "geometry": null, a hole that did is left out,
-    and every feature gets `neighbours`, the sorted ids on the other side of its walls, and `collapsed`."""
+    and every feature gets `neighbours`, the sorted ids on the other side of its walls, and `collapsed`.
+    `refined` (with `shared`, of `c3d_outlines_simplify_safe`) = (level [vertices], node [vertices]) of the simplified vertices:
+    every feature gets `refined`, the number of its arcs -- which start at the node vertices of a ring, or at the first vertex of a
+    ring without one -- whose level is above 0."""
     table, rings, vertices = np.asarray(table), np.asarray(rings), np.asarray(vertices)
     if simplified is not None:
         rings_s, vertices_s = np.asarray(simplified[0]).tolist(), np.asarray(simplified[1])
@@ -260,7 +269,7 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
             skipped.append(k + 1)
             continue
         coords, n_raw, n_out = [], 0, 0
-        neighbours, collapsed, gone = set(), False, False
+        neighbours, collapsed, gone, n_refined = set(), False, False, 0
         drifted = simplified is not None and iou is not None and min_iou is not None and not float(iou[k]) > min_iou
         drifted = drifted or (simplified is not None and not_valid is not None and k + 1 in not_valid)
         for r in outline + [r for r in own if r[3] <= 0]:  # the outline, then the holes in ring order
@@ -270,6 +279,9 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
                 s = rings_s[r[8]]
                 if 0 <= s[1] and s[1] + s[2] <= len(vertices_s):      # also of a ring that collapsed: the wall is still shared
                     neighbours.update(int(v) for v in shared[s[1]:s[1] + s[2]] if v > 0)
+                    if refined is not None and s[2] > 0:
+                        up, node = refined[0][s[1]:s[1] + s[2]] > 0, refined[1][s[1]:s[1] + s[2]]
+                        n_refined += int((up & node).sum()) if node.any() else int(up[0])
                 if s[1] < 0 or s[1] + s[2] > len(vertices_s) or s[2] < 3 or s[3] == 0 or (s[3] > 0) != (r[3] > 0):
                     collapsed = True
                     gone = gone or r[3] > 0
@@ -288,6 +300,8 @@ def polygons_geojson(table, rings, vertices, simplified=None, iou=None, min_iou=
                 properties.update(iou=round(float(iou[k]), 4))
         if shared is not None:
             properties.update(neighbours=sorted(neighbours), collapsed=collapsed)
+            if refined is not None:
+                properties.update(refined=n_refined)
         if extra is not None:
             properties.update(extra.get(k + 1, {}))
         if validity is not None:
@@ -401,20 +415,35 @@ def simplify_ious(objects, fill):
     return iou, kept, vanished
 
 
+def node_vertices(objects, vertices):
+    """bool [n] on the device: which of the lattice points `vertices` i32 [n, 2] = (vx, vy) are nodes of the label map of
+    `objects`, by the rule of c3d_outlines_simplify_shared: the four labels round the point differ across three of its four
+    sides or more."""
+    rows = objects.counts[1].clamp(0, objects.table.shape[0])
+    lab = torch.where((objects.labels >= 1) & (objects.labels <= rows), objects.labels, torch.zeros_like(objects.labels))
+    lab = torch.nn.functional.pad(lab, (1, 1, 1, 1))          # l(y, x) is lab[y + 1, x + 1]
+    vx, vy = vertices[:, 0].long(), vertices[:, 1].long()
+    a, b, c, d = lab[vy, vx], lab[vy, vx + 1], lab[vy + 1, vx], lab[vy + 1, vx + 1]
+    return (a != b).int() + (c != d).int() + (a != c).int() + (b != d).int() >= 3
+
+
 def save_polygons(path, objects, outlines, simplified=None, iou=None, min_iou=None, extra=None, validity=None, not_valid=None):
     """objects/<name>.geojson; the one read-back of the rings (`simplified`: the second `SceneOutlines` of
     `predict(..., simplify=tol)`, read back with them; `iou`, `min_iou`: see `polygons_geojson`).  Returns the ids that were
     left out."""
     ring_rows, written = int(outlines.counts[1]), int(outlines.counts[3])
     rows = int(objects.counts[1])
-    shared = None
+    shared, refined = None, None
     if simplified is not None:
         if hasattr(simplified, "left"):                   # a SceneSharedOutlines of --simplify_shared
             shared = simplified.left[:int(simplified.counts[3])].cpu().numpy()
+        if hasattr(simplified, "level"):                  # a SceneSafeOutlines of --simplify_safe
+            n_out = int(simplified.counts[3])
+            refined = (simplified.level[:n_out].cpu().numpy(), node_vertices(objects, simplified.vertices[:n_out]).cpu().numpy())
         simplified = (simplified.rings[:ring_rows].cpu().numpy(), simplified.vertices[:int(simplified.counts[3])].cpu().numpy())
     doc, skipped = polygons_geojson(objects.table[:rows].cpu().numpy(), outlines.rings[:ring_rows].cpu().numpy(),
                                     outlines.vertices[:written].cpu().numpy(), simplified, iou, min_iou, extra, validity, not_valid,
-                                    shared)
+                                    shared, refined)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
         json.dump(doc, f)
@@ -672,6 +701,13 @@ def parse_args(argv=None):
         args.simplify_check = True
     if args.simplify_check and args.simplify is None:
         parser.error("--simplify_check and --simplify_min_iou measure what --simplify cost: they need --simplify")
+    if args.safe_rounds is not None and not args.simplify_safe:
+        parser.error("--safe_rounds limits the rounds of --simplify_safe: it needs --simplify_safe")
+    if args.simplify_safe:
+        args.simplify_shared = True
+        args.safe_rounds = 8 if args.safe_rounds is None else args.safe_rounds
+        if not 1 <= args.safe_rounds <= 64:
+            parser.error(f"--safe_rounds must lie in [1, 64], got {args.safe_rounds}")
     if args.simplify_shared and args.simplify is None:
         parser.error("--simplify_shared chooses how --simplify simplifies: it needs --simplify")
     if args.simplify_shared and (args.simplify_min_iou is not None or args.simplify_valid or args.simplify_clean):
@@ -767,6 +803,8 @@ def main(argv=None):
         split["simplify_check"] = True
     if args.simplify_shared:
         split["simplify_shared"] = True
+    if args.simplify_safe:
+        split.update(simplify_safe=True, safe_rounds=args.safe_rounds)
     if args.shapes:
         split["shapes"] = True
     if args.regularize:
@@ -777,6 +815,7 @@ def main(argv=None):
     if args.conflicts:
         split["conflicts"] = True
     shared_sums = dict(objects=0, nodes=0, arcs=0, shared_arcs=0, collapsed=0)   # --simplify_shared over all scenes
+    safe_sums = dict(rounds=0, raised=0, refined=0, raw=0, first=0, last=0)      # --simplify_safe over all scenes
     conflict_sums = {}                                    # --conflicts over all scenes: stage -> counts, objects by name
     validity_sums = {}                                    # --validity over all scenes: stage -> counts, unchecked objects by name
     squared =dict(objects=0, regular=0, fallback=0, iou_sum=0.0, iou_min=1.0)   # --regularize over all scenes
@@ -820,6 +859,20 @@ def main(argv=None):
                 shared_sums = dict(objects=shared_sums["objects"] + int(out[-2].counts[1]), nodes=shared_sums["nodes"] + nodes,
                                    arcs=shared_sums["arcs"] + arcs, shared_arcs=shared_sums["shared_arcs"] + shared_arcs,
                                    collapsed=shared_sums["collapsed"] + collapsed)
+            if args.simplify_safe:
+                rounds, raised, refined, at_cap, first, last, _, status = (int(v) for v in simplified.safe.cpu().tolist())
+                if status == 3:
+                    raise SystemExit(f"{name}: --simplify_safe: the edge grid of round {rounds - 1} is above the work cap of "
+                                     f"c3d_outlines_simplify_safe (work {int(simplified.info[7])}): the outlines were not checked")
+                if status == 2:
+                    raise SystemExit(f"{name}: --simplify_safe: {last} defective pairs are left after {rounds} rounds and no arc can be "
+                                     f"refined further: the rings do not belong to the label map, and more rounds cannot help")
+                if status != 0:
+                    raise SystemExit(f"{name}: --simplify_safe did not converge in {rounds} rounds ({last} defective pairs left, status "
+                                     f"{status}): raise --safe_rounds (now {args.safe_rounds})")
+                safe_sums = dict(rounds=max(safe_sums["rounds"], rounds), raised=max(safe_sums["raised"], raised),
+                                 refined=safe_sums["refined"] + refined, raw=safe_sums["raw"] + at_cap, first=safe_sums["first"] + first,
+                                 last=safe_sums["last"] + last)
             check_split(name, out[-2])
             written_v = valid_rows.get("simplified" if simplified is not None else "raw")   # of the coordinates that are written
             bad_v = not_valid_ids(valid_rows["simplified"]) if args.simplify_valid else None
@@ -948,6 +1001,9 @@ def main(argv=None):
     if args.simplify_shared:
         print(f"shared: tol = {args.simplify:g} objects = {shared_sums['objects']} nodes = {shared_sums['nodes']} "
               f"arcs = {shared_sums['arcs']} shared_arcs = {shared_sums['shared_arcs']} collapsed = {shared_sums['collapsed']}")
+    if args.simplify_safe:
+        print(f"safe: tol = {args.simplify:g} rounds = {safe_sums['rounds']} raised = {safe_sums['raised']} "
+              f"arcs_refined = {safe_sums['refined']} arcs_raw = {safe_sums['raw']} defects = {safe_sums['first']} -> {safe_sums['last']}")
     if args.shapes:
         n_shapes = max(shape_sums["objects"], 1)
         print(f"shapes: objects = {shape_sums['objects']} solidity_mean = {shape_sums['solidity'] / n_shapes:.4f} "
@@ -1030,6 +1086,11 @@ def build_parser():
                    "every wall once for both neighbours; features get `neighbours` and `collapsed`, a collapsed outline is written "
                    "with a null geometry, and the run ends with a `shared:` line.  Not with --simplify_min_iou, --simplify_valid or "
                    "--simplify_clean")
+    p.add_argument("--simplify_safe", action="store_true", help="--simplify_shared in rounds (c3d_outlines_simplify_safe): the arcs of "
+                   "every crossing, overlap, vertex inside another edge and collapsed ring get a smaller tolerance of their own until a "
+                   "round finds nothing.  Implies --simplify_shared; every feature gets `refined`, and the run ends with a `safe:` line")
+    p.add_argument("--safe_rounds", type=int, default=None, help="--simplify_safe: the most rounds, in [1, 64] (default 8); a scene "
+                   "that needs more ends the run with an error")
     p.add_argument("--simplify_check", action="store_true", help="--simplify: fill the simplified polygons back into pixels on the device "
                    "and join them to the raw objects: an `iou` per feature and a closing `simplify:` line")
     p.add_argument("--simplify_min_iou", type=unit_interval, default=None, metavar="F", help="--simplify: implies --simplify_check; an "

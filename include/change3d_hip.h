@@ -1197,6 +1197,95 @@ int c3d_outlines_simplify_shared(const int32_t* labels, const int32_t* counts_ob
                                  int32_t* vertices_out, int32_t* left_out, int32_t* counts_out, int32_t* info, void* ws,
                                  void* stream);
 
+/* Crossing-free shared walls (csrc/scene_safe.hip): c3d_outlines_simplify_shared run in rounds with a tolerance per arc.  A
+ * defect of the output -- two chords that cross, a neck that collapsed onto one line, a ring that lost or flipped its area --
+ * is repaired locally: the arcs that take part in it get a quarter of their squared tolerance, every other arc keeps the
+ * caller's.  Both neighbours of a wall see the same change, so the twin property survives, and at tolerance 0 an arc is its raw
+ * augmented vertices, which never form a defect.  All of it is integers: exact, equal from run to run and on a dirty workspace.
+ * c3d_outlines_simplify_shared, c3d_rings_conflicts and c3d_rings_valid are unchanged.  The rule:
+ *   inputs      those of c3d_outlines_simplify_shared, and max_rounds in [1, 64].  Labels, nodes, augmentation, start, arcs and
+ *               the per-arc Douglas-Peucker are word for word that call's, but that the arc's own tolerance stands where tol2_q
+ *               stands there (the closed-arc guards M and T are decided without any tolerance, there and here)
+ *   arc key     key(v, dir) = 4 * (vy * (Ws + 1) + vx) + dir with the four unit directions numbered as c3d_scene_outlines numbers
+ *               sides: +x 0, +y 1, -x 2, -y 3.  An arc from lattice point s to lattice point e has the key min(key(s, first unit
+ *               step), key(e, reverse of the last unit step)); a ring without nodes has s = e = its start.  A unit edge of the
+ *               lattice lies on at most one wall, so two arcs share a key iff they are twins, or an island and the hole it sits in
+ *   level       every arc has a level L >= 0, kept by key, 0 at first.  Its tolerance is tol2_q >> (2 L).  L_cap = the smallest L
+ *               for which that is 0: there the arc is its raw augmented vertices.  tol2_q = 0 has L_cap = 0
+ *   round       simplify every ring with the current levels; find the defects of the result; raise
+ *   edges       every written output ring takes part, whatever its n'.  Its edges are v[k] -> v[(k + 1) mod n'].  An edge is live
+ *               iff its ends differ, belongs to the arc of its start vertex, and two edges are adjacent iff they are in the same
+ *               ring row and their indices differ by 1 modulo n'
+ *   pair        an unordered pair of distinct live edges (a, b) of id i and (c, d) of id j, o1 .. o4 as in c3d_rings_valid, is
+ *               DEFECTIVE iff it is a cross (o1 o2 < 0 and o3 o4 < 0); or collinear and shares more than one point (the t / L
+ *               test of c3d_rings_valid; adjacent pairs are tested) unless i != j and (b-a).(d-c) < 0, which is a shared wall; or
+ *               the segments share exactly one point, the pair is not adjacent, and that point is an end of one edge strictly
+ *               inside the other (touch_ve).  Vertex-vertex touches are never a defect.  A defective pair marks the arcs of both
+ *               edges
+ *   ring        a written ring is DEFECTIVE iff n' < 3 or the sign of area2' is not the sign of column 3 of its input row.  It
+ *               marks all its arcs
+ *   raise       every marked arc with L < L_cap gets L + 1
+ *   loop        at most max_rounds rounds.  The call stops after the first round that marks nothing
+ *               (C3D_SAFE_ST_CONVERGED); after a round that marks something and raises nothing (C3D_SAFE_ST_DEFECTS_LEFT);
+ *               after round max_rounds - 1 if it raised something (C3D_SAFE_ST_NOT_CONVERGED); after a round whose grid work
+ *               (below) exceeds max_work, in which no pair is evaluated and nothing is raised (C3D_SAFE_ST_OVER_WORK).  The
+ *               output is always that of the last simplify step that ran
+ * Why it ends: levels only rise and are bounded by L_cap.  For a table that belongs to its labels two raw arcs never form a
+ * defective pair: raw traced rings do not cross, shared walls run in opposite directions, and every straight-through junction is
+ * an inserted node, so no vertex lies inside a raw edge.  A ring whose arcs are all raw keeps its area.  So every defect involves
+ * an arc below L_cap, and that arc is raised: DEFECTS_LEFT needs a table that does not belong to its labels.
+ * What is NOT promised: defects are what the pair rule sees.  A change of the cyclic order of the chords round a node is caught
+ * only where it shows as one of those pairs or as a flipped ring; an object that moves wholly inside another without any contact
+ * of edges is not seen (as in c3d_rings_conflicts).
+ * What follows from it:
+ *   - the twin property of c3d_outlines_simplify_shared holds in every round
+ *   - at tol2_q == 0 the output is that of c3d_outlines_simplify_shared, in one round
+ *   - if round 0 marks nothing, rings_out, vertices_out, left_out and counts_out are those of c3d_outlines_simplify_shared
+ *   - on a converged output c3d_rings_valid reports 0 crossings, 0 overlaps and 0 touch_ve for every checked id,
+ *     c3d_rings_conflicts 0 cross, 0 same and 0 touch_ve, and info[5] (collapsed) is 0
+ * Outputs (must not alias the inputs; all taken from the last round that ran):
+ *   rings_out, vertices_out, left_out, counts_out   as in c3d_outlines_simplify_shared; the prefix-shaped truncation at
+ *                 max_vertices_out (at most 2^29 here) is decided in each round's scatter
+ *   level_out     i32 [max_vertices_out]: the level of the arc of the edge leaving that vertex.  Rows of vertices_out, left_out
+ *                 and level_out past counts_out[3] mean nothing: they are as they were, or an earlier round's where that round
+ *                 wrote more (a truncated table only); nothing is written past max_vertices_out
+ *   info          i32 [8] as there; info[6] = the shift s and info[7] = min(work, 2^31 - 1) of the last round's grid, which
+ *                 are the implementation's
+ *   safe          i64 [8] = (rounds run, rounds that raised, arcs with L > 0, arcs at L_cap, defective pairs in round 0,
+ *                 defective pairs in the last round run, defective rings in round 0, status).  Pairs are counted once each, arcs
+ *                 once per key, and the two arc counts are those of the levels that the last simplify step read.  In a round
+ *                 over max_work the pairs count as 0
+ *   work          the detector bins the live output edges into the grid of c3d_rings_conflicts (cells of 2^s units from the
+ *                 lower corner of the box of all live edges, an edge in every cell its box covers, the smallest s in [0, 25] with
+ *                 entries <= out[4] n and cells <= out[5] max(n, 1), n = the live edges); work = the sum over the cells of
+ *                 n_c (n_c - 1) / 2.  A pair of entries of a cell is evaluated iff the boxes meet and the cell holds the lower
+ *                 corner of their intersection, pairs of one id included: every pair once
+ *   ws            c3d_outlines_simplify_safe_ws_bytes(...) bytes, 256-byte aligned: the shared call's (24 per ring row, 66 per
+ *                 vertex row), 10 more per vertex row (direction and key of every augmented vertex), 4 per lattice point for the
+ *                 level store (a byte per key: level, a `present` and a `mark` bit), and 76 per row of max_vertices_out for the
+ *                 edge list and the grid.  The call zeroes what it needs of it
+ * Two memsets and 7 + 16 max_rounds launches on `stream`: bitmaps, validation, offsets and the augmented rings with their arc
+ * keys are built once; the rounds are launched ahead and every launch of a round after the stopping one returns at once on a
+ * device word.  Nothing is read back, no workgroup waits for another, every loop is capped.  Every ring is simplified again in
+ * every round.  Rows that are not simplified, bad input, BAD_COUNTS: as in c3d_outlines_simplify_shared; safe is then (1, 0, ..).
+ * Refused before anything is enqueued: what c3d_outlines_simplify_shared refuses, a NULL level_out or safe, max_rounds outside
+ * [1, 64], max_work < 0, max_vertices_out above 2^29 (C3D_E_BADARG); Hs or Ws above 16384 (C3D_E_UNSUPPORTED).
+ * c3d_outlines_simplify_safe_limits: out[0], out[1] = the two tier limits of the Douglas-Peucker as in
+ * c3d_outlines_simplify_shared_limits; out[2] = the most entries of a cell in the detector's wave tier, out[3] = the entries of a
+ * chunk and of an LDS tile, out[4] = the entry budget and out[5] = the cell budget per live edge.  Host only.                  */
+#define C3D_SAFE_ST_CONVERGED 0
+#define C3D_SAFE_ST_NOT_CONVERGED 1
+#define C3D_SAFE_ST_DEFECTS_LEFT 2
+#define C3D_SAFE_ST_OVER_WORK 3
+void c3d_outlines_simplify_safe_limits(int32_t out[6]);
+int64_t c3d_outlines_simplify_safe_ws_bytes(int32_t Hs, int32_t Ws, int32_t max_rings, int32_t max_vertices,
+                                            int32_t max_vertices_out);   /* < 0: C3D_E_* */
+int c3d_outlines_simplify_safe(const int32_t* labels, const int32_t* counts_obj, int32_t Hs, int32_t Ws, int32_t max_objects,
+                               const int32_t* rings, const int32_t* vertices, const int32_t* counts, int32_t max_rings,
+                               int32_t max_vertices, int64_t tol2_q, int32_t max_rounds, int64_t max_work, int32_t max_vertices_out,
+                               int32_t* rings_out, int32_t* vertices_out, int32_t* left_out, int32_t* level_out, int32_t* counts_out,
+                               int32_t* info, int64_t* safe, void* ws, void* stream);
+
 /* Distance transform (csrc/scene_edt.hip): the exact squared Euclidean distance transform of a u8 map [Hs][Ws] that is already
  * in HBM.  The rule:
  *   sites       the pixels with mask == 0; with C3D_EDT_INVERT (bit 0 of flags) the pixels with mask != 0
