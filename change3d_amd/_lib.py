@@ -111,6 +111,7 @@ POLIS_ST_BAD_PARTNER = 512                               # C3D_POLIS_ST_BAD_PART
 EDT_INVERT, EDT_BORDER, EDT_FAR = 1, 2, 0x3fffffff       # C3D_EDT_*: flag bits of c3d_scene_edt, and its "no site within the cap"
 BOUNDARY_R2_MAX = 1024 * 1024                            # C3D_BOUNDARY_R2_MAX
 SPLIT_ST_NOT_CONVERGED, SPLIT_ST_BAD_LABELS = 1, 2       # C3D_SPLIT_ST_*: bits of c3d_scene_split's info[0]
+SIEVE_ST_NOT_CONVERGED, SIEVE_ST_TABLE_FULL, SIEVE_ST_BAD_LABELS = 1, 2, 4   # C3D_SIEVE_ST_*: bits of c3d_regions_sieve's info[0]
 
 
 class CapMetricsArgs(C.Structure):
@@ -229,6 +230,11 @@ SIGNATURES = {
     "c3d_scene_split_ws_bytes": (i64, [i32, i32, i32]),
     "c3d_scene_split_tile": (i32, [C.POINTER(i32)]),
     "c3d_scene_split": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "c3d_scene_regions_ws_bytes": (i64, [i32, i32]),
+    "c3d_scene_regions_tile": (i32, [vp, vp]),
+    "c3d_scene_regions": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "c3d_regions_sieve_ws_bytes": (i64, [i32, i32, C.POINTER(i64)]),
+    "c3d_regions_sieve": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp]),
     "c3d_cap_embed_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_embed_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
     "c3d_cap_dropout": (i32, [vp, vp, i64, i32, f32, C.c_uint64, i32, vp]),

@@ -29,6 +29,7 @@ __device__ __forceinline__ void c3d_detail_wave_area_add(uint32_t* area, int r) 
 
 int64_t c3d_detail_label_ws_bytes(int64_t N, int n_cls);   // what c3d_scene_label_ws_bytes returns for N pixels
 int64_t c3d_detail_area_offset();                          // byte offset of the u32 [N] of areas
+int64_t c3d_detail_ssum_offset(int64_t N);                 // byte offset of the u64 score sums, one per table row
 
 // The memsets: header and areas, and the score sums and votes of the rows that can be used.  hist / n_cls as the entry got them.
 int c3d_detail_objects_clear(void* ws, int64_t N, const uint8_t* cls_map, const float* score, int n_cls, uint32_t* hist,
@@ -39,6 +40,26 @@ int c3d_detail_objects_clear(void* ws, int64_t N, const uint8_t* cls_map, const 
 // (the instrumented build of c3d_scene_objects; 3 everywhere else).
 int c3d_detail_label_roots(const uint8_t* mask, int32_t* L, uint32_t* err, uint32_t* area, int Hs, int Ws, int conn8, int phases,
                            hipStream_t st);
+
+// Launch 3 alone, for a caller with union-find phases of its own (csrc/scene_regions.hip): every L[p] >= 0 becomes its root,
+// `area` u32 [N], zeroed, gets the pixel count at every root.
+int c3d_detail_label_flatten(int32_t* L, uint32_t* err, uint32_t* area, int N, hipStream_t st);
+
+// The keyed labelling of csrc/scene_regions.hip (three launches): L[p] = the smallest linear index of p's region of equal
+// nonzero key, -1 where key is 0; areas as above.  `stop` NULL: launch 3 is c3d_detail_label_flatten.  `stop` a device word:
+// every launch returns at once when it is nonzero (the rounds of csrc/scene_sieve.hip), and the flatten is a gated twin.
+int c3d_detail_region_roots(const uint8_t* key, int32_t* L, uint32_t* err, uint32_t* area, int Hs, int Ws, int conn8,
+                            const uint32_t* stop, hipStream_t st);
+
+// A scene of N pixels holds at most ceil(N / 2) components of a mask, which is what the label workspace is laid out for, but
+// N regions of a key map (a 4-connected checkerboard of two keys).  The region workspace is the label workspace of one
+// class with the score sums grown to N rows; c3d_detail_region_clear is c3d_detail_objects_clear on it.
+int64_t c3d_detail_region_ws_bytes(int64_t N);
+int c3d_detail_region_clear(void* ws, int64_t N, const float* score, int max_objects, hipStream_t st);
+
+// table[k][5] = key[table[k][6]] for the rows k < counts[1], and object_key (may be NULL) = key where labels > 0, else 0.
+int c3d_detail_region_keys(const uint8_t* key, const int32_t* labels, int32_t* table, const int32_t* counts, uint8_t* object_key,
+                           int Hs, int Ws, int max_objects, hipStream_t st);
 
 // Launches 4..9 (count, scan, number, relabel_stats, finalise, paint) on a root map: L[p] = the index of the first pixel of
 // p's object (L[r] == r there), -1 elsewhere, with the area of every object at its root in the workspace.

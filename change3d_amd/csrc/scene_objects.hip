@@ -420,6 +420,7 @@ extern "C" int c3d_scene_label_tile(int32_t* th, int32_t* tw) {
 // ---- the stages as host functions (scene_detail.h): c3d_scene_objects below, and csrc/scene_split.hip
 int64_t c3d_detail_label_ws_bytes(int64_t N, int n_cls) { return workspace_plan(N, n_cls).bytes; }
 int64_t c3d_detail_area_offset() { return workspace_plan(1, 1).area; }
+int64_t c3d_detail_ssum_offset(int64_t N) { return workspace_plan(N, 1).ssum; }
 
 // header and area; the sums and votes of the rows that can be used.  The table needs none: number_roots writes the rows of
 // the objects, finalise zeroes the others.
@@ -453,6 +454,10 @@ int c3d_detail_label_roots(const uint8_t* mask, int32_t* L, uint32_t* err, uint3
   if (phases == 2) return 0;
   if (area) return c3d_launch_lds<label_flatten_kernel<true>>(dim3(grid_for(N, 256)), dim3(256), 0, st, L, area, err, N, N);
   return c3d_launch_lds<label_flatten_kernel<false>>(dim3(grid_for(N, 256)), dim3(256), 0, st, L, area, err, N, N);
+}
+
+int c3d_detail_label_flatten(int32_t* L, uint32_t* err, uint32_t* area, int N, hipStream_t st) {
+  return c3d_launch_lds<label_flatten_kernel<true>>(dim3(grid_for(N, 256)), dim3(256), 0, st, L, area, err, N, N);
 }
 
 int c3d_detail_objects_tail(const uint8_t* cls_map, const float* score, int Hs, int Ws, int min_area, int n_cls, int first_class,

@@ -103,6 +103,31 @@ class SceneSplitObjects(SceneObjects):
         self = super().__new__(cls, labels, table, counts, object_cls, hist)
         self.info = info
         return self
+
+
+REGION_MODES = ("pre", "post", "transition")
+
+
+class SceneRegionObjects(SceneObjects):
+    """The `SceneObjects` of `predict(objects=True, regions=mode)` (SCD): the regions of equal class of a class map instead of the
+    components of the change mask, in the same five fields (`table[:, 5]` is the region's key, exact; `object_cls` is the key
+    painted over the kept regions; `hist` is None), plus `.key_map` u8 [Hs, Ws], the map that was labelled -- the sieved one
+    with `sieve=N` --, and `.info` i32 [8] of `c3d_regions_sieve` (zeros without `sieve`).  The key is the class of the chosen
+    side, or `pre * num_class + post` for `"transition"` (`region_classes` decodes it)."""
+
+    def __new__(cls, labels, table, counts, object_cls, hist, key_map, info):
+        self = super().__new__(cls, labels, table, counts, object_cls, hist)
+        self.key_map = key_map
+        self.info = info
+        return self
+
+
+def region_classes(key, mode, num_class):
+    """(from, to) of a region key (an int or an integer array): the class on its own side and 0 on the other for `"pre"` /
+    `"post"`, `key // num_class` and `key % num_class` for `"transition"`."""
+    if mode == "transition":
+        return key // num_class, key % num_class
+    return (key, key * 0) if mode == "pre" else (key * 0, key)
 # rings i32 [max_rings, 8] = (id, start, n_vertices, area, perimeter, x, y, 0) in the order of their starting edge; vertices i32
 # [max_vertices, 2] = (vx, vy) lattice points, ring after ring; counts i32 [5] = (rings found, rows written, vertices found,
 # vertices written, status: _lib.OUTLINE_ST_*)
@@ -285,6 +310,13 @@ class SceneInferencer:
     with `.info` = (status, seeds, rounds used, 0) that outlines, simplification, votes and `ObjectEvaluator` take unchanged.
     `split_rounds` (default 32) limits the growth rounds: `info[0] & SPLIT_ST_NOT_CONVERGED` says that it was too small.  With
     `split=None` the launches are the ones without the argument.
+    `regions="pre" | "post" | "transition"` (SCD, with `objects=True`, not with `split`) labels the regions of equal class of a
+    class map instead of the components of the change mask (`ops.scene_regions`): the key map is `pre_cls`, `post_cls` or
+    `pre_cls * num_class + post_cls` (num_class <= 16), the appended object a `SceneRegionObjects`, a `SceneObjects` with
+    `.key_map` and `.info` whose labels every later stage takes unchanged.  `min_area` still drops; `sieve=N` (in [1, 2^20])
+    has the regions below N pixels absorbed by the neighbour with the longest border first (`ops.regions_sieve`), in at most
+    `sieve_rounds` (default 8) rounds: `info[0] & SIEVE_ST_NOT_CONVERGED` says that it was too small.  With `regions=None` the
+    launches are the ones without the argument.
     `shapes=True` (with `outlines=True`) appends a `SceneShapes` last: the convex hull and the minimum-area rectangle of every
     object (`ops.rings_hull`), taken from the raw rings -- also with `simplify=tol` -- and from the pieces with `split=R`.  Its
     `hulls` rows are a ring table that `ops.rings_fill` takes.  With `shapes=False` the launches are the ones without it.
@@ -356,7 +388,27 @@ class SceneInferencer:
     def predict(self, scene_u8, objects=False, min_area=1, connectivity=8, max_objects=65536, outlines=False, max_rings=None,
                 max_vertices=None, simplify=None, split=None, split_rounds=None, simplify_check=False, shapes=False,
                 regularize=False, regularize_check=False, validity=False, conflicts=False, simplify_shared=False, simplify_safe=False,
-                safe_rounds=None):
+                safe_rounds=None, regions=None, sieve=None, sieve_rounds=None):
+        if regions is not None:
+            if regions not in REGION_MODES:
+                raise ValueError(f"regions must be one of {REGION_MODES}, got {regions!r}")
+            if self.task != "scd":
+                raise ValueError(f"regions={regions!r} labels the class maps of SCD: the task is {self.task}")
+            if not objects:
+                raise ValueError("regions=mode chooses what objects=True labels: it needs objects=True")
+            if split is not None:
+                raise ValueError("regions=mode and split=R both replace the labelling: give one of them")
+            if regions == "transition" and self.num_class > 16:
+                raise ValueError(f"regions='transition' keys a region by pre * num_class + post in a byte: num_class = "
+                                 f"{self.num_class} is above 16")
+        if sieve is None and sieve_rounds is not None:
+            raise ValueError("sieve_rounds limits the rounds of sieve=N: it needs sieve")
+        if sieve is not None:
+            if regions is None:
+                raise ValueError("sieve=N absorbs the small regions of regions=mode: it needs regions")
+            sieve_rounds = 8 if sieve_rounds is None else int(sieve_rounds)
+            if not 1 <= int(sieve) <= 2 ** 20 or not 1 <= sieve_rounds <= 65536:
+                raise ValueError(f"sieve must lie in [1, 2^20] and sieve_rounds in [1, 65536], got {sieve} and {sieve_rounds}")
         if outlines and not objects:
             raise ValueError("outlines=True traces the objects of the map: it needs objects=True")
         if validity and not outlines:
@@ -457,7 +509,21 @@ class SceneInferencer:
             result = (heads[0].cls, heads[1].cls, heads[2].cls)
             found = dict(mask=heads[2].cls, cls_map=heads[1].cls, n_cls=self.num_class)
         if objects:
-            if split is not None:
+            if regions is not None:
+                if regions == "transition":             # < 256 with num_class <= 16
+                    key_map = (heads[0].cls.to(torch.int16) * self.num_class + heads[1].cls).to(torch.uint8)
+                else:
+                    key_map = heads[0].cls if regions == "pre" else heads[1].cls
+                info = torch.zeros(8, dtype=torch.int32, device=dev)
+                if sieve is not None:
+                    labels, table, _, key_map, counts, info = ops.regions_sieve(key_map, int(sieve), connectivity=connectivity,
+                                                                                max_rounds=sieve_rounds, max_objects=max_objects)
+                    object_key = key_map                # every nonzero pixel lies in a region with a label
+                if sieve is None or int(min_area) > 1:  # min_area drops, as everywhere
+                    labels, table, _, object_key, counts = ops.scene_regions(key_map, connectivity=connectivity, min_area=min_area,
+                                                                             max_objects=max_objects)
+                result += (SceneRegionObjects(labels, table, counts, object_key, None, key_map, info),)
+            elif split is not None:
                 labels, table, hist, object_cls, counts, info = ops.scene_split(
                     found.pop("mask"), split, first_class=1, connectivity=connectivity, min_area=min_area, max_objects=max_objects,
                     max_rounds=split_rounds, **found)

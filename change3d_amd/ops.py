@@ -1483,6 +1483,74 @@ def scene_split(mask, r, cls_map=None, score=None, connectivity=8, min_area=1, n
     return labels, table, hist, object_cls, counts, info
 
 
+def scene_regions_tile():
+    """(th, tw) of the LDS tile of c3d_scene_regions' local phase; host only."""
+    th, tw = C.c_int32(0), C.c_int32(0)
+    L.check(L.lib().c3d_scene_regions_tile(C.byref(th), C.byref(tw)), "c3d_scene_regions_tile")
+    return th.value, tw.value
+
+
+def _region_score(score, key_map):
+    if score is not None:
+        assert score.dtype == torch.float32 and score.shape == key_map.shape and score.is_contiguous() and score.is_cuda
+
+
+def scene_regions(key_map, score=None, connectivity=8, min_area=1, max_objects=65536, want_object_key=True, ws=None):
+    """c3d_scene_regions on the u8 map `key_map` [Hs, Ws]: the connected components of equal nonzero key.  Returns `(labels i32
+    [Hs, Ws], table i32 [max_objects, 8], None, object_key u8 [Hs, Ws] or None, counts i32 [2])`, the 5-tuple of
+    `scene_objects`, all on the device; nothing is read back.  Column 5 of a table row is the region's key."""
+    Hs, Ws = _u8_map(key_map, "scene_regions key map")
+    _region_score(score, key_map)
+    if int(max_objects) < 1:
+        raise L.Change3DHipError(f"c3d_scene_regions refuses max_objects = {max_objects}")
+    dev = key_map.device
+    ws = _scene_ws(ws, L.lib().c3d_scene_regions_ws_bytes(Hs, Ws), dev, "c3d_scene_regions", Hs, Ws)
+    labels = torch.empty((Hs, Ws), dtype=torch.int32, device=dev)
+    table = torch.empty((int(max_objects), 8), dtype=torch.int32, device=dev)
+    object_key = torch.empty((Hs, Ws), dtype=torch.uint8, device=dev) if want_object_key else None
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _launch("c3d_scene_regions", Hs * Ws * 40, L.lib().c3d_scene_regions, _p(key_map), _p(score), Hs, Ws, int(connectivity),
+            int(min_area), int(max_objects), _p(labels), _p(table), _p(object_key), _p(counts), _p(ws), _stream())
+    return labels, table, None, object_key, counts
+
+
+def regions_sieve_plan(Hs, Ws, table_capacity=0):
+    """c3d_regions_sieve_ws_bytes: (workspace bytes, table capacity); `table_capacity` 0 asks for the one that cannot overflow."""
+    cap = C.c_int64(int(table_capacity))
+    nbytes = L.lib().c3d_regions_sieve_ws_bytes(int(Hs), int(Ws), C.byref(cap))
+    if nbytes < 0:
+        raise L.Change3DHipError(f"c3d_regions_sieve refuses a {Hs} x {Ws} scene with a table of {table_capacity} slots (code {nbytes})")
+    return int(nbytes), int(cap.value)
+
+
+def regions_sieve(key_map, min_area, score=None, connectivity=8, max_rounds=8, max_objects=65536, table_capacity=0, ws=None):
+    """c3d_regions_sieve on the u8 map `key_map` [Hs, Ws]: regions below `min_area` pixels are absorbed by the neighbour they
+    share the longest border with, in rounds.  Returns `(labels, table, None, key_out u8 [Hs, Ws], counts, info i32 [8])`:
+    `scene_regions(key_out)` and `info` = (status, rounds, regions moved, pixels changed, small regions left, regions of the
+    input, most table entries of a round, 0), all on the device; nothing is read back.  A status with `SIEVE_ST_NOT_CONVERGED`
+    asks for a larger `max_rounds`, one with `SIEVE_ST_TABLE_FULL` for a larger `table_capacity`."""
+    Hs, Ws = _u8_map(key_map, "regions_sieve key map")
+    _region_score(score, key_map)
+    if not 1 <= int(min_area) <= 2 ** 20:
+        raise ValueError(f"min_area must lie in [1, 2^20], got {min_area}")
+    if not 1 <= int(max_rounds) <= 65536:
+        raise ValueError(f"max_rounds must lie in [1, 65536], got {max_rounds}")
+    if int(max_objects) < 1:
+        raise L.Change3DHipError(f"c3d_regions_sieve refuses max_objects = {max_objects}")
+    nbytes, cap = regions_sieve_plan(Hs, Ws, table_capacity)
+    dev = key_map.device
+    ws = _scene_ws(ws, nbytes, dev, "c3d_regions_sieve", Hs, Ws)
+    key_out = torch.empty((Hs, Ws), dtype=torch.uint8, device=dev)
+    labels = torch.empty((Hs, Ws), dtype=torch.int32, device=dev)
+    table = torch.empty((int(max_objects), 8), dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    info = torch.empty(8, dtype=torch.int32, device=dev)
+    _launch("c3d_regions_sieve", Hs * Ws * 80, L.lib().c3d_regions_sieve, _p(key_map), _p(score), Hs, Ws, int(connectivity),
+            int(min_area), int(max_rounds), int(max_objects), cap, _p(key_out), _p(labels), _p(table), _p(counts), _p(info), _p(ws),
+            _stream())
+    return labels, table, None, key_out, counts, info
+
+
 def build_clip(pre, post, frames, clip, B, K, H, W):
     _launch("c3d_build_clip", clip.numel() * 8, L.lib().c3d_build_clip, _p(pre), _p(post), _p(frames), _p(clip), B, K, H, W,
             _stream())

@@ -149,7 +149,7 @@ if ROOT not in sys.path:
 from change3d_amd.data.dataset import BCDDataset, BDADataset, SCDDataset, read_label, read_rgb  # noqa: E402
 from change3d_amd import _lib as L  # noqa: E402
 from change3d_amd import ops, vector_labels  # noqa: E402
-from change3d_amd.infer import REGULAR_FRAC_BITS, SceneInferencer  # noqa: E402
+from change3d_amd.infer import REGULAR_FRAC_BITS, SceneInferencer, region_classes  # noqa: E402
 from change3d_amd.model.trainer import Trainer  # noqa: E402
 from change3d_amd.boundary_metrics import BoundaryEvaluator  # noqa: E402
 from change3d_amd.object_metrics import ObjectEvaluator  # noqa: E402
@@ -203,15 +203,17 @@ def save_png(path, array):
     Image.fromarray(array).save(path)
 
 
-def save_objects(path, objects):
-    """One CSV line per table row; the one read-back of the table.  Returns (found, written)."""
+def save_objects(path, objects, regions=None, num_class=0):
+    """One CSV line per table row; the one read-back of the table.  Returns (found, written).  `regions` (the mode of
+    `--regions`): `cls` is the region's key, and every line ends with the `from` and `to` classes it stands for."""
     found, rows = (int(v) for v in objects.counts.cpu())
     table = objects.table[:rows].cpu().numpy()
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
-        f.write("id,area,x0,y0,x1,y1,cls,score\n")
+        f.write("id,area,x0,y0,x1,y1,cls,score" + (",from,to" if regions else "") + "\n")
         for k, (area, x0, y0, x1, y1, cls, _, score_q) in enumerate(table.tolist()):
-            f.write(f"{k + 1},{area},{x0},{y0},{x1},{y1},{cls},{score_q / 65535:.4f}\n")
+            ends = ",{},{}".format(*region_classes(cls, regions, num_class)) if regions else ""
+            f.write(f"{k + 1},{area},{x0},{y0},{x1},{y1},{cls},{score_q / 65535:.4f}{ends}\n")
     if found > rows:
         print(f"{path}: {found} objects found, the table holds the first {rows} (max_objects)")
     return found, rows
@@ -663,8 +665,56 @@ def split_rounds(text):
 def check_split(name, objects):
     """Ends the run when the growth of `--split_objects` did not reach its fixed point on this scene."""
     info = getattr(objects, "info", None)
+    if hasattr(objects, "key_map"):                       # the regions of --regions: their info is the sieve's (check_sieve)
+        return
     if info is not None and int(info[0]) & L.SPLIT_ST_NOT_CONVERGED:
         raise SystemExit(f"{name}: the pieces of --split_objects were still growing after {int(info[2])} rounds; raise --split_rounds")
+
+
+def sieve_area(text):
+    v = int(text)
+    if not 1 <= v <= 2 ** 20:
+        raise ArgumentTypeError(f"--sieve must lie in [1, 2^20] pixels, got {text}")
+    return v
+
+
+def sieve_rounds(text):
+    v = int(text)
+    if not 1 <= v <= 65536:
+        raise ArgumentTypeError(f"--sieve_rounds must lie in [1, 65536], got {text}")
+    return v
+
+
+def check_sieve(name, objects, rounds):
+    """Ends the run when the sieve of `--sieve` stopped short on this scene."""
+    status = int(objects.info[0])
+    if status & L.SIEVE_ST_TABLE_FULL:
+        Hs, Ws = objects.labels.shape
+        raise SystemExit(f"{name}: --sieve: the border table of c3d_regions_sieve overflowed at its capacity of "
+                         f"{ops.regions_sieve_plan(Hs, Ws)[1]} slots")
+    if status & L.SIEVE_ST_NOT_CONVERGED:
+        raise SystemExit(f"{name}: --sieve: small regions were still moving after {int(objects.info[1])} rounds; raise --sieve_rounds "
+                         f"(now {rounds})")
+    if status:
+        raise SystemExit(f"{name}: --sieve: c3d_regions_sieve status {status}")
+
+
+def add_region_properties(path, regions, num_class):
+    """`from` and `to` on every feature of a .geojson of this run, decoded from its `cls` (the region's key)."""
+    with open(path) as f:
+        doc = json.load(f)
+    for feature in doc["features"]:
+        a, b = region_classes(feature["properties"]["cls"], regions, num_class)
+        feature["properties"].update({"from": a, "to": b})
+    with open(path, "w") as f:
+        json.dump(doc, f)
+
+
+def region_key_map(pre, post, change, regions, num_class):
+    """The key map of `--regions` from label maps on the device, as `SceneInferencer.predict(regions=..)` keys the prediction."""
+    pre, post = pre * change, post * change
+    key = pre * num_class + post if regions == "transition" else (pre if regions == "pre" else post)
+    return key.to(torch.uint8).contiguous()
 
 
 def iou_threshold(text):
@@ -745,6 +795,19 @@ def parse_args(argv=None):
         parser.error("--split_objects splits the objects of the map: it needs --objects")
     if args.split_rounds is not None and args.split_objects is None:
         parser.error("--split_rounds is the round limit of --split_objects: it needs --split_objects")
+    if args.regions is not None:
+        if args.task != "SCD":
+            parser.error("--regions labels the class maps of --task SCD")
+        if not args.objects:
+            parser.error("--regions chooses what --objects labels: it needs --objects")
+        if args.split_objects is not None:
+            parser.error("--regions and --split_objects both replace the labelling: give one of them")
+        if args.regions == "transition" and num_classes(args) > 16:
+            parser.error("--regions transition keys a region by from * num_class + to in a byte: it serves at most 16 classes")
+    if args.sieve is not None and args.regions is None:
+        parser.error("--sieve absorbs the small regions of --regions: it needs --regions")
+    if args.sieve_rounds is not None and args.sieve is None:
+        parser.error("--sieve_rounds is the round limit of --sieve: it needs --sieve")
     if args.polygon_scores and not (args.label_polygons and args.polygons):
         parser.error("--polygon_scores compares the polygons of the map with labelled ones: it needs --label_polygons and --objects --polygons")
     return args
@@ -772,7 +835,8 @@ def main(argv=None):
     def score_objects(name, objects, gt_mask, gt_cls=None, gt=None):
         nonlocal object_eval
         if object_eval is None:
-            object_eval = ObjectEvaluator(n_cls=num_class, iou_thr=args.iou_thr, connectivity=args.connectivity, device=device)
+            object_eval = ObjectEvaluator(n_cls=1 if args.regions == "transition" else num_class, iou_thr=args.iou_thr,
+                                          connectivity=args.connectivity, device=device)
         if gt is not None:                                # polygon labels are objects already: no relabelling
             match_p, match_g = object_eval.update_labeled(objects, gt.labels, gt.table, gt.counts)
         else:
@@ -799,6 +863,9 @@ def main(argv=None):
         boundary_eval.update(mask.to(torch.uint8), gt_mask.to(torch.uint8))
 
     split = {} if args.split_objects is None else dict(split=args.split_objects, split_rounds=args.split_rounds)
+    if args.regions is not None:
+        split.update(regions=args.regions, sieve=args.sieve, sieve_rounds=args.sieve_rounds)
+    region_sums = dict(objects=0, moved=0, pixels=0, rounds=0)                   # --regions over all scenes
     if args.simplify_check:
         split["simplify_check"] = True
     if args.simplify_shared:
@@ -935,6 +1002,11 @@ def main(argv=None):
                 squared = dict(objects=squared["objects"] + len(ids), regular=squared["regular"] + done,
                                fallback=squared["fallback"] + fallback, iou_sum=squared["iou_sum"] + sum(ious),
                                iou_min=min([squared["iou_min"]] + ious))
+            if args.regions is not None:  # after every rewrite of the files above
+                written = [main_path] + ([regular_path] if regular is not None else []) + \
+                          ([main_path[:-len(".geojson")] + ext for ext in (".hulls.geojson", ".rects.geojson")] if shapes is not None else [])
+                for path in written:
+                    add_region_properties(path, args.regions, num_class)
             if args.polygon_scores:
                 stages = [("raw", out[-1], 0)] + ([("simplified", simplified, 0)] if simplified is not None else []) + \
                          ([("regularised", regular, REGULAR_FRAC_BITS)] if regular is not None else [])
@@ -984,13 +1056,31 @@ def main(argv=None):
         else:
             for sub, m in zip(("pred1", "pred2", "change"), out[:3]):
                 save_png(os.path.join(args.out_dir, sub, name + ".png"), m.cpu().numpy() * (255 if sub == "change" else 1))
-            if args.objects:             # the objects of the change mask; cls: the majority class of pred2 inside
+            if args.regions is not None:  # the regions of a class map; cls: the key.  The map that was vectorised goes out too
+                found = out[-1]
+                if args.sieve is not None:
+                    check_sieve(name, found, args.sieve_rounds or 8)
+                save_objects(os.path.join(args.out_dir, "objects", name + ".csv"), found, args.regions, num_class)
+                key_map = found.key_map.cpu().numpy()
+                if args.regions == "transition":
+                    for side, m in zip(("from", "to"), region_classes(key_map, args.regions, num_class)):
+                        save_png(os.path.join(args.out_dir, "regions", f"{name}.{side}.png"), m)
+                else:
+                    save_png(os.path.join(args.out_dir, "regions", name + ".png"), key_map)
+                info = found.info.cpu().tolist()
+                region_sums = dict(objects=region_sums["objects"] + int(found.counts[1]), moved=region_sums["moved"] + info[2],
+                                   pixels=region_sums["pixels"] + info[3], rounds=max(region_sums["rounds"], info[1]))
+            elif args.objects:           # the objects of the change mask; cls: the majority class of pred2 inside
                 save_objects(os.path.join(args.out_dir, "objects", name + ".csv"), out[-1])
             if label is not None:        # reference scripts/train_SCD.py:216-217: the class labels count inside the change only
                 lab = torch.from_numpy(np.ascontiguousarray(label)).to(device).long()
                 meter.update(out[0], lab[..., 0] * lab[..., 2])
                 meter.update(out[1], lab[..., 1] * lab[..., 2])
-                if args.objects:         # the objects of the change label; cls: the majority class of label2 inside
+                if args.regions is not None:   # the regions of the label maps in the same mode, not sieved
+                    gt_key = region_key_map(lab[..., 0], lab[..., 1], (lab[..., 2] > 0).long(), args.regions, num_class)
+                    g_labels, g_table, _, _, g_counts = ops.scene_regions(gt_key, connectivity=args.connectivity, want_object_key=False)
+                    score_objects(name, out[-1], None, gt=SimpleNamespace(labels=g_labels, table=g_table, counts=g_counts))
+                elif args.objects:       # the objects of the change label; cls: the majority class of label2 inside
                     score_objects(name, out[-1], lab[..., 2] > 0, lab[..., 1])
                 score_boundary(out[2], lab[..., 2] > 0)
                 scored += 1
@@ -1004,6 +1094,9 @@ def main(argv=None):
     if args.simplify_safe:
         print(f"safe: tol = {args.simplify:g} rounds = {safe_sums['rounds']} raised = {safe_sums['raised']} "
               f"arcs_refined = {safe_sums['refined']} arcs_raw = {safe_sums['raw']} defects = {safe_sums['first']} -> {safe_sums['last']}")
+    if args.regions is not None:
+        print(f"regions: mode = {args.regions} objects = {region_sums['objects']} moved = {region_sums['moved']} "
+              f"pixels = {region_sums['pixels']} rounds = {region_sums['rounds']}")
     if args.shapes:
         n_shapes = max(shape_sums["objects"], 1)
         print(f"shapes: objects = {shape_sums['objects']} solidity_mean = {shape_sums['solidity'] / n_shapes:.4f} "
@@ -1043,7 +1136,7 @@ def main(argv=None):
         result = meter.scores()
         print(f"Fscd: {result[0] * 100:.2f} IoU: {result[1] * 100:.2f} Sek: {result[2] * 100:.2f}")
     if object_eval is not None:
-        print_object_scores(object_eval, per_class=args.task == "BDA")
+        print_object_scores(object_eval, per_class=args.task == "BDA" or args.regions in ("pre", "post"))
     if boundary_eval is not None:
         print_boundary_scores(boundary_eval)
     if polygon_evals:
@@ -1137,6 +1230,12 @@ def build_parser():
                    "(c3d_scene_split): erode the mask by R pixels, in [1, 1024], and grow what is left back inside the mask, so that "
                    "objects joined by a neck narrower than about 2 R come apart.  Only the prediction is split: the labels that "
                    "--objects scores against stay whole components")
+    p.add_argument("--regions", choices=["pre", "post", "transition"], default=None, help="--task SCD --objects: label the regions "
+                   "of equal class of the pre or the post class map, or of their from-to transitions (c3d_scene_regions), instead of the "
+                   "components of the change mask: cls is the key, from / to the classes, regions/<name>.png the map")
+    p.add_argument("--sieve", type=sieve_area, default=None, metavar="N", help="--regions: absorb every region below N pixels into "
+                   "the neighbour it shares the longest border with, on the device (c3d_regions_sieve); --min_area drops instead")
+    p.add_argument("--sieve_rounds", type=sieve_rounds, default=None, metavar="R", help="--sieve: the most rounds, default 8")
     p.add_argument("--split_rounds", type=split_rounds, default=None, metavar="N", help="--split_objects: the most growth rounds, "
                    "in [1, 65536] (default 32); a scene that needs more ends the run with an error")
     p.add_argument("--pretrained", default="./pretrained/X3D_L.pyth")

@@ -1377,6 +1377,76 @@ int c3d_scene_split(const uint8_t* mask, const uint8_t* cls_map, const float* sc
                     int32_t* labels, int32_t* table, uint32_t* hist, uint8_t* object_cls, int32_t* counts, int32_t* info, void* ws,
                     void* stream);
 
+/* Class regions of a scene map (csrc/scene_regions.hip): the connected components of EQUAL nonzero key of a u8 key map that is
+ * already in HBM.  Two pixels belong to one region iff a path of 4-adjacent (connectivity 4) or 8-adjacent (connectivity 8)
+ * pixels of the same key joins them; key 0 is background.  This is scipy.ndimage.label(key == k, structure) for every k, taken
+ * together.  At connectivity 8 two regions of different keys may both pass through one lattice point (A B / B A); that is
+ * allowed and is what the rule above defines.
+ *   key       u8 [Hs][Ws];  score f32 [Hs][Ws] or NULL;  Hs * Ws < 2^31
+ *   labels, table, counts and the min_area / max_objects / truncation behaviour are exactly those of c3d_scene_objects with
+ *             "component" read as "region": regions are numbered 1 .. N in raster order of their first pixel over ALL keys
+ *             together; row = (area, x0, y0, x1, y1, cls, first, score_q) with cls = the region's key, exact, 1 .. 255 (it is
+ *             not a vote)
+ *   object_key u8 [Hs][Ws] or NULL: the key where labels > 0, else 0
+ *   ws        c3d_scene_regions_ws_bytes(Hs, Ws) bytes, 256-byte aligned
+ *   identity  on a key map of 0 / 1 every output equals c3d_scene_objects on it as a mask without a class map, except column 5
+ * Integer arithmetic and integer atomics only: two runs agree bit for bit, and a dirty workspace gives the same result.  Nine
+ * launches and at most two memsets on `stream`: the keyed local and seam phases, then the flatten and the tail of
+ * c3d_scene_objects (count, scan, number, relabel_stats, finalise), then the keys.  Nothing is read back, no workgroup waits
+ * for another, every walk is capped as there (counts[0] = -1 at the cap).  Refused before anything is enqueued: what
+ * c3d_scene_objects refuses.
+ * c3d_scene_regions_tile: the extent of the LDS tile of the keyed local phase.  Host only.                                  */
+int64_t c3d_scene_regions_ws_bytes(int32_t Hs, int32_t Ws);                   /* < 0: C3D_E_* */
+int c3d_scene_regions_tile(int32_t* th, int32_t* tw);
+int c3d_scene_regions(const uint8_t* key, const float* score, int32_t Hs, int32_t Ws, int32_t connectivity, int32_t min_area,
+                      int32_t max_objects, int32_t* labels, int32_t* table, uint8_t* object_key, int32_t* counts, void* ws,
+                      void* stream);
+
+/* The sieve of a key map (csrc/scene_sieve.hip): regions below min_area are absorbed by the neighbour they share the longest
+ * border with, in rounds, on the device.  All integers; tests/sieve_reference.py restates it.  One ROUND on the current map K:
+ *   1 Take the regions of K as c3d_scene_regions does.  Each is identified by its root, the linear index of its first pixel,
+ *     and has an area.  A region is SMALL iff area < min_area.  If none is small, stop: converged.
+ *   2 For every small region r and every pixel side between a pixel of r and a 4-adjacent pixel q of the scene outside r, add 1
+ *     to border(r, n), n = the region of q, or BG if K[q] == 0.  Always 4-adjacency: a border is counted in pixel sides.
+ *     Sides on the scene's edge count for nobody.  (A 4-adjacent pixel of equal key is always in r, so n never has r's key.)
+ *   3 The target t(r) is the neighbour with the largest (border, area(n), -root(n)), compared lexicographically; BG has area =
+ *     the number of zero pixels of K and root = -1, so BG wins a full tie.  A small region without a neighbour has no target.
+ *   4 r MOVES iff it has a target and t(r) is BG, or t(r) is not small, or (area(t), root(t)) > (area(r), root(r)).  This
+ *     breaks every cycle; the small region with the smallest (area, root) that has a target always moves, so a round that has
+ *     something to do does something.
+ *   5 Every pixel of a moving region takes the key of the END of its chain r -> t(r) -> t(t(r)) -> ..: the first region that
+ *     does not move, or 0 for BG.  If nothing moves, stop: converged (a small region that fills its surroundings stays).
+ *   6 The next round runs on the new map: regions of equal key that an absorbed speck used to separate are one from then on.
+ * The call stops when it has converged; or when max_rounds rounds have moved something and the map after them still has a
+ * region that would move (C3D_SIEVE_ST_NOT_CONVERGED); or when a round's border table did not fit (C3D_SIEVE_ST_TABLE_FULL):
+ * that round moves nothing and the output is the map before it, so no result depends on arrival order.
+ *   key, score, connectivity, max_objects   as in c3d_scene_regions;  min_area in [1, 2^20];  max_rounds in [1, 65536]
+ *   table_capacity  slots of the border table, a power of two in [16, 2^31], as c3d_regions_sieve_ws_bytes returned it: 0 there
+ *             asks for the one that cannot overflow (twice the ordered pairs that the pixel sides of the scene can hold; a
+ *             region pair is one entry however long its border).  A smaller one overflows for certain when a round has more
+ *             pairs than slots; probes are capped at 4096
+ *   key_out   u8 [Hs][Ws], the final map; must not alias key
+ *   labels, table, counts   exactly c3d_scene_regions(key_out, min_area = 1)
+ *   info      i32 [8] = (status, rounds that moved something, regions moved over all rounds, pixels whose key changed, small
+ *             regions left, regions of the input, most table entries of a round, 0).  C3D_SIEVE_ST_BAD_LABELS: a capped walk
+ *             reached its cap (counts[0] = -1 as well)
+ *   identity  min_area <= 1 gives key_out == key, info[1] == 0 and the outputs of c3d_scene_regions
+ *   ws        c3d_regions_sieve_ws_bytes(Hs, Ws, &table_capacity) bytes, 256-byte aligned
+ * Integer atomics only (maxima, counts, one compare-and-swap that never spins): two runs agree bit for bit, a dirty workspace
+ * gives the same result.  Launches on `stream`: at most four memsets and a copy, max_rounds + 1 rounds of nine launches (the
+ * last round only finds out whether something would still move) -- every kernel of a round after the stopping one returns at
+ * once on a device word, and the grids are sized by the compute units and the pixels --, the tail of c3d_scene_objects (5),
+ * the keys and info.  Nothing is read back, no workgroup waits for another, every loop is capped.  Refused before anything is
+ * enqueued: what c3d_scene_regions refuses, a NULL or aliasing key_out, a NULL info, min_area / max_rounds / table_capacity
+ * outside their ranges (C3D_E_BADARG).                                                                                      */
+#define C3D_SIEVE_ST_NOT_CONVERGED 1
+#define C3D_SIEVE_ST_TABLE_FULL 2
+#define C3D_SIEVE_ST_BAD_LABELS 4
+int64_t c3d_regions_sieve_ws_bytes(int32_t Hs, int32_t Ws, int64_t* table_capacity);   /* < 0: C3D_E_* */
+int c3d_regions_sieve(const uint8_t* key, const float* score, int32_t Hs, int32_t Ws, int32_t connectivity, int32_t min_area,
+                      int32_t max_rounds, int32_t max_objects, int64_t table_capacity, uint8_t* key_out, int32_t* labels,
+                      int32_t* table, int32_t* counts, int32_t* info /* [8] */, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Residual-stage step driver: ONE call enqueues every kernel of `blocks[i](x)` for a whole X3D residual
  * stage (reference model/x3d.py:331-412 = ResStage of ResBlocks, driven by `self.x3d.blocks[i](x)` at
