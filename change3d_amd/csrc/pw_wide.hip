@@ -323,6 +323,7 @@ int launch_wide(const c3d_pw_args& a, hipStream_t st) {
   const size_t lds = (size_t)(WB_M + WB_N) * KL * sizeof(typename MM::lds_t) + (size_t)WB_M * (WB_N + 4) * 4 +
                      (size_t)WB_SLOTS * WB_N * 3 * 8 + (size_t)3 * a.Kp * 4;
   dim3 grid((unsigned)((a.M + WB_M - 1) / WB_M), (unsigned)((a.Np + WB_N - 1) / WB_N));
+  c3d_note_launch(reinterpret_cast<const void*>(&pw_wide_kernel<T, PRO, EPI>));
   pw_wide_kernel<T, PRO, EPI><<<grid, 256, lds, st>>>(a);
   C3D_CHECK_LAUNCH();
   return 0;
@@ -471,6 +472,7 @@ int launch_wide_wgrad(const c3d_pw_wgrad_args& a, hipStream_t st) {
   int64_t rows = (a.M + split - 1) / split;
   rows = (rows + WG_R - 1) / WG_R * WG_R;
   split = (a.M + rows - 1) / rows;
+  c3d_note_launch(reinterpret_cast<const void*>(&pw_wide_wgrad_kernel<T>));
   pw_wide_wgrad_kernel<T><<<dim3(gn, gk, (unsigned)split), 256, 0, st>>>(a, rows);
   C3D_CHECK_LAUNCH();
   return 0;

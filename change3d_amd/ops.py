@@ -329,10 +329,13 @@ def _ws(device, n_floats):
 
 def pw_wgrad(p, q, dw, *, M, K, N, dw_sn, dw_sk, dtype, p2=None, p_coef=None, q_mode=PRO_NONE, q_ss=None,
              q_gate=None, rows_per_sample=0, row_mode=ROWS_DENSE, rpg=0, gstride=0, H=0, W=0, dy=0, dx=0,
-             q_ptr=None, dw_ptr=None, taps=0, dw_tap_stride=0, chain_ws=None):
+             q_ptr=None, dw_ptr=None, taps=0, dw_tap_stride=0, chain_ws=None, p_fin=None):
     """chain_ws: a caller-owned workspace tensor (c3d_pw_wgrad_ws_floats(N, K) floats) -> a CHAINED launch (c3d_pw_wgrad_args.chain):
-    its partials stay pending in chain_ws until the next chained launch or pw_wgrad_flush(); alternate two workspaces."""
+    its partials stay pending in chain_ws until the next chained launch or pw_wgrad_flush(); alternate two workspaces.
+    p_fin: a c3d_bn_fin (L.BnFin) whose completed sums give the AFFINE2 coefficients of p (c3d_pw_wgrad_args.p_fin), as pw_gemm's fin."""
     a = L.PwWgradArgs()
+    if p_fin is not None:
+        a.p_fin = p_fin
     a.p, a.p2 = _p(p), _p(p2)
     a.q = q_ptr if q_ptr is not None else _p(q)
     a.dw = dw_ptr if dw_ptr is not None else _p(dw)

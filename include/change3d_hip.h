@@ -98,6 +98,8 @@ typedef struct c3d_pw_args {
   const float* epi_gate; /* SWISH_SE_BWD: gate[B][Np] or NULL (=1)                           */
   const float* epi_q;    /* SWISH_SE_BWD: mean[Np],rstd[Np] of that BN (centred sum t1*bhat)  */
   double* stats;         /* STATS: [C3D_STAT_STRIPES][2][N]; SWISH_SE_BWD: [B][Np][3]         */
+                         /* (SWISH_SE_BWD, block-tiled kernel: a workgroup adds its rows in 2^-40 fixed point, so   */
+                         /* the three sums over one workgroup's <= 64 rows of a sample must stay within +-8.4e6)    */
   int64_t M;             /* output rows                                                      */
   int64_t gstride;       /* C3D_ROWS_FRAME: elements between consecutive row groups          */
   int64_t rows_per_sample; /* output rows per batch sample (gate / per-sample sums)          */
