@@ -23,12 +23,14 @@
 //
 // One memset (the workspace) and four launches on one stream, no host read, no grid barrier, no loop that waits for another
 // workgroup, every loop bounded, no float atomics.  A label outside the rows of its table is counted nowhere.
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 #pragma clang fp contract(off)   // inter > thr * union and inter / union are the two float64 operations, as written
 
 namespace {
+
+using namespace c3d_wave;
 
 typedef unsigned long long u64;
 
@@ -164,10 +166,6 @@ __global__ __launch_bounds__(256) void pair_count_kernel(const int32_t* __restri
   }
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 // covered[id - 1][3] += inter over the lanes of a wave: one add for the object of the first lane, one per lane for the rest
 __device__ __forceinline__ void add_covered(int32_t* match, bool valid, int id, uint32_t inter, int lane) {
@@ -176,7 +174,7 @@ __device__ __forceinline__ void add_covered(int32_t* match, bool valid, int id, 
   const int leader = __ffsll((long long)m) - 1;
   const int id0 = __shfl(id, leader);
   const bool same = valid && id == id0;
-  const uint32_t sum = wave_sum_u(same ? inter : 0u);                  // <= Hs * Ws < 2^31
+  const uint32_t sum = wave_sum32(same ? inter : 0u);                  // <= Hs * Ws < 2^31
   if (lane == leader) atomicAdd(reinterpret_cast<uint32_t*>(match + (int64_t)(id0 - 1) * 4 + 3), sum);
   else if (valid && !same) atomicAdd(reinterpret_cast<uint32_t*>(match + (int64_t)(id - 1) * 4 + 3), inter);
 }

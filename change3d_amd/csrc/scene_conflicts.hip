@@ -2,7 +2,8 @@
 // of live edges of DIFFERENT ids, while the table stays in HBM.  The rule is the header's (include/change3d_hip.h); this file
 // is one way to compute it.  The all-pairs walk across ids is quadratic in the edges of the whole scene, so the edges are
 // binned into a uniform grid of square cells and only the entries of one cell are compared.  The rows pass, the ids scan and
-// the pair predicate are those of csrc/scene_valid.hip (csrc/scene_rings.h).  Everything is an integer, every sum an integer
+// the pair predicate are those of csrc/scene_valid.hip (csrc/scene_rings.h); the grid build (4 .. 8) is csrc/scene_grid.h's, which the
+// detector of csrc/scene_safe.hip runs too.  Everything is an integer, every sum an integer
 // atomic or a ballot count, and nothing depends on the order in which entries land in a cell.  No workgroup waits for
 // another, nothing is read back, every loop is capped.
 //
@@ -30,21 +31,18 @@
 #include <climits>
 #include <type_traits>
 
+#include "scene_grid.h"
 #include "scene_rings.h"
 
 namespace {
 
 using namespace c3d_rings;
+using namespace c3d_grid;
 
-constexpr int WAVE_LIMIT = 64;                             // entries of a cell in the wave tier: a lane each
-constexpr int CHUNK = 256;                                 // entries of a chunk: a thread each
+constexpr int WAVE_LIMIT = CELL_WAVE_LIMIT;                // entries of a cell in the wave tier: a lane each
 constexpr int TILE = 256;                                  // entries of an LDS tile: 20 bytes each; a chunk is one tile
-constexpr int BUDGET_E = 2;                                // entries the grid may hold per live edge, so per vertex of max_vertices
-constexpr int BUDGET_C = 4;                                // cells the grid may have per live edge, so per vertex of max_vertices
-constexpr int N_SHIFT = 26;                                // candidate shifts 0 .. 25: extents stay below 2^25, so s = 25 is one cell
 constexpr int BLOCK_T = 256;
 constexpr int MAX_GRID = 4096;
-constexpr int BIAS = 1 << 24;                              // above every |coordinate|: biased values are positive, 0 means none
 constexpr u64 NO_PARTNER = ~0ull;
 
 // 32-bit words of the workspace header (512 bytes, zeroed by the call's memset); WS_K, WS_JOBS and WS_BIG are scene_rings.h's
@@ -54,6 +52,11 @@ enum { WS_EDGES = 4, WS_LO_X = 5, WS_LO_Y = 6, WS_HI_X = 7, WS_HI_Y = 8, WS_SHIF
 enum { WQ_WORK = 0, WQ_ENTRIES = 1, WQ_SUM = 2 /* cross, same, opposite, vv, ve */, WQ_COST = 8 /* N_SHIFT of them */ };
 enum { COL_FLAG = 0, COL_PARTNER = 1, COL_M = 2, COL_CROSS = 3, COL_SAME = 4, COL_OPP = 5, COL_VV = 6, COL_VE = 7 };
 enum { HIT_CROSS = 0, HIT_SAME = 1, HIT_OPP = 2, HIT_VV = 3, HIT_VE = 4, HIT_NONE = 5 };
+// where scene_grid.h finds the grid's words in this header
+struct Words {
+  enum { LO_X = WS_LO_X, LO_Y = WS_LO_Y, HI_X = WS_HI_X, HI_Y = WS_HI_Y, SHIFT = WS_SHIFT, CX = WS_CX, CY = WS_CY, X0 = WS_X0, Y0 = WS_Y0,
+         AT = WS_AT, JOBS = WS_JOBS, Q_WORK = WQ_WORK, Q_ENTRIES = WQ_ENTRIES, Q_COST = WQ_COST };
+};
 
 struct Tab : Rows {
   uint32_t* id_live;                                       // [max_ids] live edges of the id
@@ -86,8 +89,7 @@ Plan plan_of(int64_t max_rings, int64_t max_vertices, int64_t max_ids) {
   // the caps keep every index in 32 bits
   t.cap_e = BUDGET_E * max_vertices < 0xFFFFFFF0ll ? BUDGET_E * max_vertices : 0xFFFFFFF0ll;
   t.cap_c = BUDGET_C * max_vertices < 0x7FFFFFF0ll ? BUDGET_C * max_vertices : 0x7FFFFFF0ll;
-  // a cell above WAVE_LIMIT entries has ceil(n / CHUNK) jobs: at most entries / CHUNK + entries / (WAVE_LIMIT + 1) in all
-  t.cap_j = t.cap_e / CHUNK + t.cap_e / (WAVE_LIMIT + 1) + 1;
+  t.cap_j = jobs_cap(t.cap_e);
   take(t.id_rings, max_ids * 4);                           // zeroed part first
   take(t.id_verts, max_ids * 8);
   take(t.id_flags, max_ids * 4);
@@ -115,30 +117,10 @@ void bind(Tab& t, char* base) {
   rebase(t.cell_n, base); rebase(t.cell_at, base); rebase(t.entry, base); rebase(t.jobs, base);
 }
 
-__device__ __forceinline__ u64* quad(uint32_t* header) { return reinterpret_cast<u64*>(header + 16); }
-__device__ __forceinline__ const u64* quad(const uint32_t* header) { return reinterpret_cast<const u64*>(header + 16); }
 __device__ __forceinline__ uint32_t edges_of(const Tab& s, const uint32_t* header) {
   return min(header[WS_EDGES], (uint32_t)s.max_vertices);
 }
 __device__ __forceinline__ bool over_work(const Tab& s, const uint32_t* header) { return quad(header)[WQ_WORK] > (u64)s.max_work; }
-
-// the grid as the later launches read it
-struct Grid {
-  int shift, x0, y0;
-  uint32_t cx, cy;
-};
-__device__ __forceinline__ Grid grid_of(const uint32_t* header) {
-  Grid g;
-  g.shift = (int)header[WS_SHIFT]; g.x0 = (int)header[WS_X0]; g.y0 = (int)header[WS_Y0];
-  g.cx = header[WS_CX]; g.cy = header[WS_CY];
-  return g;
-}
-// the cells (x0 .. x1, y0 .. y1) that the bounding box of e covers; e lies inside the box of all edges, so no index leaves the grid
-__device__ __forceinline__ void span_of(const Grid& g, int4 e, uint32_t& x0, uint32_t& x1, uint32_t& y0, uint32_t& y1) {
-  x0 = (uint32_t)(min(e.x, e.z) - g.x0) >> g.shift; x1 = (uint32_t)(max(e.x, e.z) - g.x0) >> g.shift;
-  y0 = (uint32_t)(min(e.y, e.w) - g.y0) >> g.shift; y1 = (uint32_t)(max(e.y, e.w) - g.y0) >> g.shift;
-  x1 = min(x1, g.cx - 1u); y1 = min(y1, g.cy - 1u);        // cannot bind: the box was taken over these edges
-}
 
 // ---------------------------------------------------------------------------------------------------------- 1, 2: shared
 __global__ __launch_bounds__(256) void conflicts_rows_kernel(Tab s, uint32_t* __restrict__ header) { rows_pass(s, header); }
@@ -226,123 +208,24 @@ __global__ __launch_bounds__(256) void conflicts_edges_big_kernel(Tab s, uint32_
   box_out(box, header);
 }
 
-// --------------------------------------------------------------------------------------------------------------- 4: cost
-// Per candidate s the entries that s would cost.  A sum only has to tell "within the budget" from "above it": an edge adds at
-// most budget + 1 and a wave keeps its sum at or below that, so with at most 4 MAX_GRID waves no 64-bit counter overflows.
-__device__ __forceinline__ u64 entry_budget(const Tab& s, uint32_t n) { return min((u64)BUDGET_E * n, (u64)s.cap_e); }
-__device__ __forceinline__ u64 cell_budget(const Tab& s, uint32_t n) { return min((u64)BUDGET_C * max(n, 1u), (u64)s.cap_c); }
+// ------------------------------------------------------------------------------------------------- 4 .. 8: scene_grid.h
+// the list holds live edges only, all of them: no filter
 __global__ __launch_bounds__(256) void conflicts_cost_kernel(Tab s, uint32_t* __restrict__ header) {
   const uint32_t n = edges_of(s, header);
-  const int lane = threadIdx.x & 63;
-  if ((uint32_t)blockIdx.x * 256u >= n) return;             // the grid is sized by max_vertices
-  const int x0 = BIAS - (int)header[WS_LO_X], y0 = BIAS - (int)header[WS_LO_Y];
-  const u64 top = entry_budget(s, n) + 1ull;
-  u64 cost[N_SHIFT];
-#pragma unroll
-  for (int k = 0; k < N_SHIFT; ++k) cost[k] = 0;
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const int4 e = s.e_xy[i];
-    const uint32_t ax = (uint32_t)(min(e.x, e.z) - x0), bx = (uint32_t)(max(e.x, e.z) - x0);
-    const uint32_t ay = (uint32_t)(min(e.y, e.w) - y0), by = (uint32_t)(max(e.y, e.w) - y0);
-#pragma unroll
-    for (int k = 0; k < N_SHIFT; ++k) {
-      const u64 c = (u64)((bx >> k) - (ax >> k) + 1u) * (u64)((by >> k) - (ay >> k) + 1u);   // below 2^50
-      cost[k] = min(cost[k] + min(c, top), top);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < N_SHIFT; ++k) {
-    u64 v = cost[k];
-    for (int o = 32; o > 0; o >>= 1) v = min(v + shfl64(v, lane ^ o), top);
-    if (lane == 0 && v) atomicAdd(quad(header) + WQ_COST + k, v);
-  }
+  cost_pass<Words, false>(cells_of(s), header, n, n);
 }
-
-// ------------------------------------------------------------------------------------------------------------- 5: choose
 __global__ __launch_bounds__(64) void conflicts_choose_kernel(Tab s, uint32_t* __restrict__ header) {
-  const int k = threadIdx.x;
-  const uint32_t n = edges_of(s, header);
-  int x0 = 0, y0 = 0;
-  uint32_t wx = 0, wy = 0;                                 // the extent of the box: below 2^25
-  if (n) {
-    x0 = BIAS - (int)header[WS_LO_X]; y0 = BIAS - (int)header[WS_LO_Y];
-    wx = (uint32_t)((int)header[WS_HI_X] - BIAS - x0); wy = (uint32_t)((int)header[WS_HI_Y] - BIAS - y0);
-  }
-  bool ok = false;
-  u64 cells = 0, cost = 0;
-  if (k < N_SHIFT) {
-    cells = (u64)((wx >> k) + 1u) * (u64)((wy >> k) + 1u);
-    cost = quad(header)[WQ_COST + k];
-    ok = cost <= entry_budget(s, n) && cells <= cell_budget(s, n);
-  }
-  const u64 fit = __ballot(ok);
-  const int pick = fit ? __ffsll((long long)fit) - 1 : N_SHIFT - 1;   // s = 25 always fits: one cell, an entry per edge
-  if (k == pick) {
-    header[WS_SHIFT] = (uint32_t)pick;
-    header[WS_CX] = (wx >> pick) + 1u;
-    header[WS_CY] = (wy >> pick) + 1u;
-    header[WS_X0] = (uint32_t)x0;
-    header[WS_Y0] = (uint32_t)y0;
-    quad(header)[WQ_ENTRIES] = min(cost, entry_budget(s, n));
-  }
+  choose_pass<Words>(cells_of(s), header, edges_of(s, header));
 }
-
-// -------------------------------------------------------------------------------------------------------------- 6: count
 __global__ __launch_bounds__(256) void conflicts_count_kernel(Tab s, const uint32_t* __restrict__ header) {
-  const uint32_t n = edges_of(s, header);
-  const Grid g = grid_of(header);
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    uint32_t x0, x1, y0, y1;
-    span_of(g, s.e_xy[i], x0, x1, y0, y1);
-    for (uint32_t y = y0; y <= y1; ++y)                    // at most cap_e cells in all: the chosen s is within the budget
-      for (uint32_t x = x0; x <= x1; ++x) atomicAdd(s.cell_n + ((u64)y * g.cx + x), 1u);
-  }
+  count_pass<Words, false>(cells_of(s), header, edges_of(s, header));
 }
-
-// ------------------------------------------------------------------------------------------------------------- 7: starts
 __global__ __launch_bounds__(256) void conflicts_starts_kernel(Tab s, uint32_t* __restrict__ header) {
-  const Grid g = grid_of(header);
-  const u64 cells = (u64)g.cx * g.cy;                      // at most cap_c
-  const int lane = threadIdx.x & 63;
-  u64 work = 0;
-  for (u64 c0 = ((u64)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; c0 < cells; c0 += (u64)gridDim.x * 256) {   // uniform over the wave
-    const u64 c = c0 + lane;
-    const uint32_t cnt = c < cells ? s.cell_n[c] : 0u;
-    uint32_t inc = cnt;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t t = (uint32_t)__shfl((int)inc, lane >= d ? lane - d : lane);
-      if (lane >= d) inc += t;
-    }
-    uint32_t base = 0;
-    if (lane == 63 && inc) base = atomicAdd(header + WS_AT, inc);
-    base = (uint32_t)__shfl((int)base, 63);
-    if (c < cells) s.cell_at[c] = base + inc - cnt;
-    work += (u64)cnt * (u64)(cnt ? cnt - 1u : 0u) / 2ull;   // cnt < 2^31: an edge enters a cell once
-    if (cnt > (uint32_t)WAVE_LIMIT) {
-      const uint32_t chunks = (cnt + CHUNK - 1) / CHUNK;
-      const uint32_t at = atomicAdd(header + WS_JOBS, chunks);
-      for (uint32_t i = 0; i < chunks; ++i)                // at most cap_e / CHUNK + 1 steps
-        if ((u64)at + i < (u64)s.cap_j) s.jobs[at + i] = make_uint2((uint32_t)c, i);   // cannot fail: see plan_of
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) work += shfl64(work, lane ^ o);
-  if (lane == 0 && work) atomicAdd(quad(header) + WQ_WORK, work);
+  starts_pass<Words>(cells_of(s), header);
 }
-
-// ------------------------------------------------------------------------------------------------------------ 8: scatter
 __global__ __launch_bounds__(256) void conflicts_scatter_kernel(Tab s, const uint32_t* __restrict__ header) {
   if (over_work(s, header)) return;
-  const uint32_t n = edges_of(s, header);
-  const Grid g = grid_of(header);
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    uint32_t x0, x1, y0, y1;
-    span_of(g, s.e_xy[i], x0, x1, y0, y1);
-    for (uint32_t y = y0; y <= y1; ++y)
-      for (uint32_t x = x0; x <= x1; ++x) {
-        const uint32_t at = atomicAdd(s.cell_at + ((u64)y * g.cx + x), 1u);
-        if ((u64)at < (u64)s.cap_e) s.entry[at] = i;       // cannot fail: the counts are those of kernel 6
-      }
-  }
+  fill_pass<Words, false>(cells_of(s), header, edges_of(s, header));
 }
 
 // --------------------------------------------------------------------------------------------------------------- 9: rows
@@ -424,7 +307,7 @@ __device__ __forceinline__ void tally_out(uint32_t (&tally)[5], uint32_t* header
 
 __global__ __launch_bounds__(256) void conflicts_wave_kernel(Tab s, uint32_t* __restrict__ header, u64* __restrict__ conflict) {
   if (over_work(s, header)) return;
-  const Grid g = grid_of(header);
+  const Grid g = grid_of<Words>(header);
   const u64 cells = (u64)g.cx * g.cy;
   const int lane = threadIdx.x & 63;
   uint32_t tally[5] = {0, 0, 0, 0, 0};
@@ -472,7 +355,7 @@ __global__ __launch_bounds__(BLOCK_T) void conflicts_jobs_kernel(Tab s, uint32_t
   extern __shared__ int4 t_edge[];                         // [TILE], then u32 [TILE]
   uint32_t* t_id = reinterpret_cast<uint32_t*>(t_edge + TILE);
   if (over_work(s, header)) return;
-  const Grid g = grid_of(header);
+  const Grid g = grid_of<Words>(header);
   const int tid = threadIdx.x;
   const u64 n_jobs = min((u64)header[WS_JOBS], (u64)s.cap_j);
   uint32_t tally[5] = {0, 0, 0, 0, 0};

@@ -27,6 +27,64 @@ __device__ __forceinline__ void c3d_detail_wave_area_add(uint32_t* area, int r) 
   if (open) atomicAdd(area + r, 1u);
 }
 
+// ------------------------------------------------------------------------------------------------ the union-find walks
+// of the labelling kernels (csrc/scene_objects.hip, csrc/scene_regions.hip): parent pointers towards the smaller index, a
+// root points at itself.  Every walk is capped and sets the error word where the cap is reached.
+constexpr int C3D_DETAIL_TILE = 64 * 64;                   // cells of the LDS tile of a local phase: the cap of a walk inside it
+
+__device__ __forceinline__ int ld_agent(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int ld_wg(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// root of `a` in the LDS tile; parents are read while other waves lower them, which only shortens the walk
+__device__ __forceinline__ int lds_find(const int32_t* lab, int a, uint32_t* err) {
+  for (int step = 0; step <= C3D_DETAIL_TILE; ++step) {
+    const int p = ld_wg(lab + a);
+    if (p == a) return a;
+    a = p;
+  }
+  atomicOr(err, 1u);
+  return a;
+}
+
+__device__ __forceinline__ void lds_unite(int32_t* lab, int a, int b, uint32_t* err) {
+  for (int step = 0; step <= C3D_DETAIL_TILE; ++step) {
+    a = lds_find(lab, a, err);
+    b = lds_find(lab, b, err);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(lab + a, b);
+    if (old == a) return;
+    a = old;
+  }
+  atomicOr(err, 1u);
+}
+
+// Parents are read with agent-scope atomic loads: a plain load could see an older parent from another XCD's L2.  Even that
+// would be correct -- a stale "root" fails its atomicMin (old != a) and the loop goes on from `old` -- but the walk is shorter
+// with current values.
+__device__ __forceinline__ int g_find(const int32_t* L, int a, int cap, uint32_t* err) {
+  for (int step = 0; step <= cap; ++step) {
+    const int p = ld_agent(L + a);
+    if (p == a) return a;
+    a = p;
+  }
+  atomicOr(err, 1u);
+  return a;
+}
+
+__device__ __forceinline__ void g_unite(int32_t* L, int a, int b, int cap, uint32_t* err) {
+  for (int step = 0; step <= cap; ++step) {
+    a = g_find(L, a, cap, err);
+    b = g_find(L, b, cap, err);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(L + a, b);                   // device scope: performed at the memory side, seen by every XCD
+    if (old == a) return;
+    a = old;
+  }
+  atomicOr(err, 1u);
+}
+
 int64_t c3d_detail_label_ws_bytes(int64_t N, int n_cls);   // what c3d_scene_label_ws_bytes returns for N pixels
 int64_t c3d_detail_area_offset();                          // byte offset of the u32 [N] of areas
 int64_t c3d_detail_ssum_offset(int64_t N);                 // byte offset of the u64 score sums, one per table row

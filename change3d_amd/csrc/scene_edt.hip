@@ -26,10 +26,12 @@
 // (blockIdx.z picks the mask; capped at d2), boundary_band (the band counts, the contour maps Pc / Gc as u8), the three again
 // on the two contour maps with INVERT and a cap of tau2 -- the row pass then counts the hits over the OTHER contour map in place
 // of storing distances -- and boundary_finalise, one thread, which writes `counts` and adds them into `totals`.
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
+
+using namespace c3d_wave;
 
 typedef unsigned long long u64;
 
@@ -99,10 +101,6 @@ __global__ __launch_bounds__(256) void edt_cols_kernel(const Jobs jobs, int Hs, 
   }
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 // acc[k] += the sum of v[k] over the workgroup of 256, k < K: one atomic per workgroup and count, none where the sum is 0 --
 // a few thousand adds to one address cost more than the pass they end.  A workgroup's sum stays below 2^32 (its pixels do).
@@ -111,7 +109,7 @@ __device__ __forceinline__ void block_add(u64* acc, const uint32_t (&v)[K], uint
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    const uint32_t sum = wave_sum_u(v[k]);
+    const uint32_t sum = wave_sum32(v[k]);
     if (lane == 0) s_part[wave * K + k] = sum;
   }
   __syncthreads();

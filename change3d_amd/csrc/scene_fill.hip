@@ -27,10 +27,12 @@
 //   8 finish    rows without a pixel, cls, the rows past K, counts_obj, info
 #include <climits>
 
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
+
+using namespace c3d_wave;
 
 typedef unsigned long long u64;
 
@@ -69,21 +71,6 @@ Workspace workspace_plan(int64_t max_rings, int64_t max_objects) {
   return w;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int wave_min32(int v) {
-  for (int d = 32; d; d >>= 1) {
-    const int o = __shfl_xor(v, d);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_max32(int v) {
-  for (int d = 32; d; d >>= 1) {
-    const int o = __shfl_xor(v, d);
-    v = o > v ? o : v;
-  }
-  return v;
-}
 
 // The smallest column x in [lo, hi] whose centre lies right of the edge on this row, hi + 1 if none does.  The predicate is
 // P(x): (2x + 1) * sdy > A with sdy = 2^f * (Y1 - Y0) > 0 and A = X0 * dy + dx * (Cy - Y0); it is false below the answer and

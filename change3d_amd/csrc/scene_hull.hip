@@ -30,10 +30,12 @@
 //               walked again by 9, which needs no room at all
 #include <climits>
 
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
+
+using namespace c3d_wave;
 
 typedef unsigned long long u64;
 typedef unsigned __int128 u128;
@@ -82,25 +84,8 @@ Workspace workspace_plan(int64_t max_rings, int64_t max_vertices, int64_t max_ob
   return w;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int wave_max32(int v) {
-  for (int d = 32; d; d >>= 1) {
-    const int o = __shfl_xor(v, d);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_minu32(uint32_t v) {
-  for (int d = 32; d; d >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)v, d);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-  for (int d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-  return v;
-}
+// 64-bit reductions by the xor shuffle, which the walks below use on pairs of words too: another shuffle pattern than
+// scene_wave.h's, so these three stay here
 __device__ __forceinline__ u64 shfl_xor64(u64 v, int d) {
   const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
   return ((u64)hi << 32) | lo;
@@ -396,7 +381,7 @@ __global__ __launch_bounds__(256) void hull_wave_kernel(const int32_t* __restric
       pos += n;
     }
     // the walk
-    const uint32_t h0 = wave_minu32(p);
+    const uint32_t h0 = wave_min32u(p);
     uint32_t cur = h0, mine = NONE;                        // mine = hull vertex `lane`
     int m = 0;
     for (int step = 0; step < WAVE_LIMIT; ++step) {        // a hull has no more vertices than the id has points

@@ -36,13 +36,16 @@
 // earlier in raster order, or by p's own vertical edge, which that column never skips: the induction is well founded.
 #include <climits>
 
-#include "common.h"
+#include "scene_wave.h"
 #include "scene_detail.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
 
+using namespace c3d_wave;
+
 constexpr int TH = 64, TW = 64;                            // tile of the local phase: a wave is a row
+static_assert(TH * TW == C3D_DETAIL_TILE, "the walks of scene_detail.h are capped by the tile");
 constexpr int CHUNK = 1024;                                // pixels per chunk of the numbering scan
 constexpr int MAX_GRID = 256 * 8;
 
@@ -64,59 +67,6 @@ Workspace workspace_plan(int64_t N, int n_cls) {
   w.hist = w.ssum + up(w.cap * 8);
   w.bytes = w.hist + up(w.cap * 4 * n_cls);
   return w;
-}
-
-__device__ __forceinline__ int ld_agent(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ld_wg(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// root of `a` in the LDS tile; parents are read while other waves lower them, which only shortens the walk
-__device__ __forceinline__ int lds_find(const int32_t* lab, int a, uint32_t* err) {
-  for (int step = 0; step <= TH * TW; ++step) {
-    const int p = ld_wg(lab + a);
-    if (p == a) return a;
-    a = p;
-  }
-  atomicOr(err, 1u);
-  return a;
-}
-
-__device__ __forceinline__ void lds_unite(int32_t* lab, int a, int b, uint32_t* err) {
-  for (int step = 0; step <= TH * TW; ++step) {
-    a = lds_find(lab, a, err);
-    b = lds_find(lab, b, err);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(lab + a, b);
-    if (old == a) return;
-    a = old;
-  }
-  atomicOr(err, 1u);
-}
-
-// Parents are read with agent-scope atomic loads: a plain load could see an older parent from another XCD's L2.  Even that
-// would be correct -- a stale "root" fails its atomicMin (old != a) and the loop goes on from `old` -- but the walk is shorter
-// with current values.
-__device__ __forceinline__ int g_find(const int32_t* L, int a, int cap, uint32_t* err) {
-  for (int step = 0; step <= cap; ++step) {
-    const int p = ld_agent(L + a);
-    if (p == a) return a;
-    a = p;
-  }
-  atomicOr(err, 1u);
-  return a;
-}
-
-__device__ __forceinline__ void g_unite(int32_t* L, int a, int b, int cap, uint32_t* err) {
-  for (int step = 0; step <= cap; ++step) {
-    a = g_find(L, a, cap, err);
-    b = g_find(L, b, cap, err);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(L + a, b);                   // device scope: performed at the memory side, seen by every XCD
-    if (old == a) return;
-    a = old;
-  }
-  atomicOr(err, 1u);
 }
 
 __global__ __launch_bounds__(256) void label_local_kernel(const uint8_t* __restrict__ mask, int32_t* __restrict__ L,
@@ -296,18 +246,6 @@ __global__ __launch_bounds__(256) void number_roots_kernel(const int32_t* __rest
   }
 }
 
-__device__ __forceinline__ int wave_min(int v) {
-  for (int d = 32; d; d >>= 1) { const int o = __shfl_xor(v, d); v = o < v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int d = 32; d; d >>= 1) { const int o = __shfl_xor(v, d); v = o > v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 // 16-bit fixed point of a probability: NaN and negatives count as 0 (fmaxf returns the operand that is a number)
 __device__ __forceinline__ uint32_t score_fixed(float p) { return __float2uint_rn(fminf(fmaxf(p, 0.0f), 1.0f) * 65535.0f); }
@@ -334,9 +272,9 @@ __global__ __launch_bounds__(256) void relabel_stats_kernel(int32_t* __restrict_
     if (!m) continue;
     const int id0 = __shfl(id, __ffsll((long long)m) - 1);
     if (__ballot(in && id != id0) == 0) {                  // one object in this wave: reduce first, one lane does the atomics
-      const int x0 = wave_min(in ? x : INT_MAX), y0 = wave_min(in ? y : INT_MAX);
-      const int x1 = wave_max(in ? x : -1), y1 = wave_max(in ? y : -1);
-      const uint32_t qs = wave_sum(q);                     // <= 64 * 65535
+      const int x0 = wave_min32(in ? x : INT_MAX), y0 = wave_min32(in ? y : INT_MAX);
+      const int x1 = wave_max32(in ? x : -1), y1 = wave_max32(in ? y : -1);
+      const uint32_t qs = wave_sum32(q);                   // <= 64 * 65535
       int32_t* row = table + (int64_t)(id0 - 1) * 8;
       if (lane == 0) {
         atomicMin(row + 1, x0); atomicMin(row + 2, y0); atomicMax(row + 3, x1); atomicMax(row + 4, y1);

@@ -34,10 +34,12 @@
 // one smallest corner key, its first occurrence in the window is the ring's start edge, and A wins ties.
 #include <climits>
 
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
+
+using namespace c3d_wave;
 
 constexpr int CHUNK = 1024;                                // pixels per chunk of the scans
 constexpr int MAX_GRID = 256 * 8;
@@ -124,10 +126,6 @@ __device__ __forceinline__ int successor(const int32_t* __restrict__ L, const ui
   return e < edges ? (int)e : -1;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 // exclusive prefix of v over the 256 threads; `all` = the sum.  part: 4 words of LDS; the caller syncs before reusing it
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* part, uint32_t* all) {
@@ -163,7 +161,7 @@ __global__ __launch_bounds__(256) void mark_kernel(const int32_t* __restrict__ L
         n += (uint32_t)__popc(v & 15u);
       }
     }
-    n = wave_sum(n);
+    n = wave_sum32(n);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
     __syncthreads();
     if (threadIdx.x == 0) chunks[c] = part[0] + part[1] + part[2] + part[3];
@@ -283,8 +281,8 @@ __global__ __launch_bounds__(256) void ring_count_kernel(const int32_t* __restri
       const int64_t i = c * CHUNK + k * 256 + threadIdx.x;
       if (i < N) for_ring_starts(L, info, off, fin, H, W, i, conn8, edges, header + WS_ERR, [&](int, uint32_t, int n) { ++nr; nv += (uint32_t)n; });
     }
-    nr = wave_sum(nr);
-    nv = wave_sum(nv);
+    nr = wave_sum32(nr);
+    nv = wave_sum32(nv);
     if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = nr; part[4 + (threadIdx.x >> 6)] = nv; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -405,7 +403,7 @@ __global__ __launch_bounds__(256) void emit_kernel(const uint8_t* __restrict__ i
       const int leader = __ffsll((long long)mk) - 1;
       const int r0 = __shfl(r, leader);
       if (__ballot(act && r != r0) == 0) {                 // one ring on this side of the wave's pixels
-        const uint32_t a = wave_sum(act ? (uint32_t)term : 0u);
+        const uint32_t a = wave_sum32(act ? (uint32_t)term : 0u);
         if (r0 != acc_r) {
           flush();
           acc_r = r0;

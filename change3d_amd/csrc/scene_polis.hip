@@ -23,10 +23,12 @@
 //   8 totals   one workgroup: counts and sums in ascending p (256 interleaved partial sums, then a fixed tree), totals
 #include <climits>
 
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
+
+using namespace c3d_wave;
 
 typedef unsigned long long u64;
 
@@ -134,16 +136,11 @@ struct Sides {
   Side s[2];
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int rows_of(const Side& s) {
   return (s.counts[4] & C3D_OUTLINE_ST_BAD_COUNTS) ? 0 : clampi(s.counts[1], 0, s.max_rings);
 }
 __device__ __forceinline__ bool coord_ok(const Side& s, int2 p) {
   return p.x >= -s.coord_max && p.x <= s.coord_max && p.y >= -s.coord_max && p.y <= s.coord_max;
-}
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-  return ((u64)hi << 32) | lo;
 }
 __device__ __forceinline__ double shfl_d(double v, int src) {
   return __longlong_as_double((long long)shfl64((u64)__double_as_longlong(v), src));

@@ -27,56 +27,8 @@
 namespace {
 
 constexpr int TH = 64, TW = 64;                            // tile of the local phase: a wave is a row
+static_assert(TH * TW == C3D_DETAIL_TILE, "the walks of scene_detail.h are capped by the tile");
 constexpr int LOCAL_LDS = TH * TW * 4 + TH * TW;           // parents, then keys
-
-__device__ __forceinline__ int ld_agent(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ld_wg(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-__device__ __forceinline__ int lds_find(const int32_t* lab, int a, uint32_t* err) {
-  for (int step = 0; step <= TH * TW; ++step) {
-    const int p = ld_wg(lab + a);
-    if (p == a) return a;
-    a = p;
-  }
-  atomicOr(err, 1u);
-  return a;
-}
-
-__device__ __forceinline__ void lds_unite(int32_t* lab, int a, int b, uint32_t* err) {
-  for (int step = 0; step <= TH * TW; ++step) {
-    a = lds_find(lab, a, err);
-    b = lds_find(lab, b, err);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(lab + a, b);
-    if (old == a) return;
-    a = old;
-  }
-  atomicOr(err, 1u);
-}
-
-__device__ __forceinline__ int g_find(const int32_t* L, int a, int cap, uint32_t* err) {
-  for (int step = 0; step <= cap; ++step) {
-    const int p = ld_agent(L + a);
-    if (p == a) return a;
-    a = p;
-  }
-  atomicOr(err, 1u);
-  return a;
-}
-
-__device__ __forceinline__ void g_unite(int32_t* L, int a, int b, int cap, uint32_t* err) {
-  for (int step = 0; step <= cap; ++step) {
-    a = g_find(L, a, cap, err);
-    b = g_find(L, b, cap, err);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(L + a, b);                   // device scope: seen by every XCD
-    if (old == a) return;
-    a = old;
-  }
-  atomicOr(err, 1u);
-}
 
 __global__ __launch_bounds__(256) void region_local_kernel(const uint8_t* __restrict__ key, int32_t* __restrict__ L,
                                                            uint32_t* __restrict__ err, const uint32_t* __restrict__ stop, int Hs,

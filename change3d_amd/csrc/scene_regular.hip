@@ -21,10 +21,12 @@
 //                  the ring's own place start' (the same code, other pointers)
 #include <climits>
 
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
+
+using namespace c3d_wave;
 
 typedef unsigned long long u64;
 typedef __int128 i128;
@@ -61,13 +63,8 @@ Workspace workspace_plan(int64_t max_rings, int64_t max_vertices) {
   return w;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int64_t absl(int64_t v) { return v < 0 ? -v : v; }
 __device__ __forceinline__ bool coord_ok(int2 p) { return p.x >= 0 && p.x <= COORD_MAX && p.y >= 0 && p.y <= COORD_MAX; }
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-  return ((u64)hi << 32) | lo;
-}
 
 // what the call reads of its two count vectors
 struct Limits {

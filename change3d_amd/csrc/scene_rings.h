@@ -6,12 +6,12 @@
 #pragma once
 #include <climits>
 
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 namespace c3d_rings {
 
-typedef unsigned long long u64;
+using namespace c3d_wave;
 
 constexpr int RING_LIMIT = 16384;                          // rings of an id whose order the gather step restores
 constexpr int BIG_RING = 4096;                             // a longer ring is checked and copied by many workgroups
@@ -42,16 +42,11 @@ struct Rows {
   uint32_t* id_start;                                      // [max_ids] start among the edges
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int rows_of(const Rows& s) {
   return (s.counts[4] & C3D_OUTLINE_ST_BAD_COUNTS) ? 0 : clampi(s.counts[1], 0, s.max_rings);
 }
 __device__ __forceinline__ bool coord_ok(const Rows& s, int2 p) {
   return p.x >= -s.coord_max && p.x <= s.coord_max && p.y >= -s.coord_max && p.y <= s.coord_max;
-}
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-  return ((u64)hi << 32) | lo;
 }
 __device__ __forceinline__ int sign_of(double v) { return (v > 0.0) - (v < 0.0); }
 

@@ -25,10 +25,12 @@
 //                 the kept ring, the ring row; rows past the table are zeroed
 #include <climits>
 
-#include "common.h"
+#include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
 namespace {
+
+using namespace c3d_wave;
 
 typedef unsigned long long u64;
 
@@ -68,51 +70,9 @@ Workspace workspace_plan(int64_t max_rings, int64_t max_vertices) {
   return w;
 }
 
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-  return ((u64)hi << 32) | lo;
-}
 __device__ __forceinline__ u64 shfl_down64(u64 v, int d) {
   const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)v, d), hi = (uint32_t)__shfl_down((int)(uint32_t)(v >> 32), d);
   return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 wave_max64(u64 v) {
-  for (int d = 32; d; d >>= 1) {
-    const u64 o = shfl64(v, (int)((threadIdx.x & 63) ^ d));
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_min32(int v) {
-  for (int d = 32; d; d >>= 1) {
-    const int o = __shfl_xor(v, d);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-// exclusive prefix of v over the workgroup's threads; `all` = the sum.  part: one word of LDS per wave; the caller syncs
-// before reusing it
-__device__ __forceinline__ u64 block_excl_scan64(u64 v, u64* part, u64* all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-  u64 inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const u64 t = shfl64(inc, lane >= d ? lane - d : lane);
-    if (lane >= d) inc += t;
-  }
-  if (lane == 63) part[wave] = inc;
-  __syncthreads();
-  u64 before = 0, sum = 0;
-  for (int w = 0; w < waves; ++w) {
-    before += w < wave ? part[w] : 0ull;
-    sum += part[w];
-  }
-  *all = sum;
-  return before + inc - v;
 }
 
 __device__ __forceinline__ bool coord_ok(int2 p) { return p.x >= 0 && p.x <= COORD_MAX && p.y >= 0 && p.y <= COORD_MAX; }
