@@ -29,15 +29,16 @@
 // A pair of entries of one cell is evaluated iff the ids differ, the bounding boxes meet, and the cell holds the lower corner
 // of the boxes' intersection: that point lies in both boxes, so exactly one cell that holds both edges evaluates the pair.
 #include <climits>
-#include <type_traits>
 
 #include "scene_grid.h"
+#include "scene_host.h"
 #include "scene_rings.h"
 
 namespace {
 
 using namespace c3d_rings;
 using namespace c3d_grid;
+using c3d_host::grid_for;
 
 constexpr int WAVE_LIMIT = CELL_WAVE_LIMIT;                // entries of a cell in the wave tier: a lane each
 constexpr int TILE = 256;                                  // entries of an LDS tile: 20 bytes each; a chunk is one tile
@@ -45,8 +46,9 @@ constexpr int BLOCK_T = 256;
 constexpr int MAX_GRID = 4096;
 constexpr u64 NO_PARTNER = ~0ull;
 
-// 32-bit words of the workspace header (512 bytes, zeroed by the call's memset); WS_K, WS_JOBS and WS_BIG are scene_rings.h's
-enum { WS_EDGES = 4, WS_LO_X = 5, WS_LO_Y = 6, WS_HI_X = 7, WS_HI_Y = 8, WS_SHIFT = 9, WS_CX = 10, WS_CY = 11, WS_X0 = 12,
+// 32-bit words of the workspace header (512 bytes, zeroed by the call's memset): the largest id of a row, the jobs, the long
+// rings, the live edges, the grid's words
+enum { WS_K = 1, WS_JOBS = 2, WS_BIG = 3, WS_EDGES = 4, WS_LO_X = 5, WS_LO_Y = 6, WS_HI_X = 7, WS_HI_Y = 8, WS_SHIFT = 9, WS_CX = 10, WS_CY = 11, WS_X0 = 12,
        WS_Y0 = 13, WS_AT = 14 };
 // 64-bit words of the header, counted from byte 64
 enum { WQ_WORK = 0, WQ_ENTRIES = 1, WQ_SUM = 2 /* cross, same, opposite, vv, ve */, WQ_COST = 8 /* N_SHIFT of them */ };
@@ -71,18 +73,14 @@ struct Tab : Rows {
 };
 
 struct Plan {
-  Tab t;                                                   // offsets until bind() adds the base
+  Tab t;
   int64_t zero_bytes, bytes;
 };
 
-Plan plan_of(int64_t max_rings, int64_t max_vertices, int64_t max_ids) {
+// ws: the workspace, or nullptr where only the sizes are asked for
+Plan plan_of(void* ws, int64_t max_rings, int64_t max_vertices, int64_t max_ids) {
   Plan pl{};
-  auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-  int64_t at = 512;
-  auto take = [&](auto*& p, int64_t bytes) {
-    p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(at);
-    at += up(bytes);
-  };
+  c3d_host::Layout l{static_cast<char*>(ws), 512};
   Tab& t = pl.t;
   // both budgets hold for one cell whatever the table holds (at most max_vertices live edges, one entry each), and a grid
   // within the budgets of the live edges is within those of max_vertices, so the sizes are a function of the maxima alone;
@@ -90,31 +88,28 @@ Plan plan_of(int64_t max_rings, int64_t max_vertices, int64_t max_ids) {
   t.cap_e = BUDGET_E * max_vertices < 0xFFFFFFF0ll ? BUDGET_E * max_vertices : 0xFFFFFFF0ll;
   t.cap_c = BUDGET_C * max_vertices < 0x7FFFFFF0ll ? BUDGET_C * max_vertices : 0x7FFFFFF0ll;
   t.cap_j = jobs_cap(t.cap_e);
-  take(t.id_rings, max_ids * 4);                           // zeroed part first
-  take(t.id_verts, max_ids * 8);
-  take(t.id_flags, max_ids * 4);
-  take(t.id_live, max_ids * 4);
-  take(t.cell_n, t.cap_c * 4);
-  pl.zero_bytes = at;
-  take(t.kind, max_rings);
-  take(t.big, max_rings * 4);
-  take(t.id_list, max_ids * 4);
-  take(t.id_start, max_ids * 4);
-  take(t.e_xy, max_vertices * 16);
-  take(t.e_id, max_vertices * 4);
-  take(t.cell_at, t.cap_c * 4);
-  take(t.entry, t.cap_e * 4);
-  take(t.jobs, t.cap_j * 8);
-  pl.bytes = at;
+  l.take(t.id_rings, max_ids * 4);                           // zeroed part first
+  l.take(t.id_verts, max_ids * 8);
+  l.take(t.id_flags, max_ids * 4);
+  l.take(t.id_live, max_ids * 4);
+  l.take(t.cell_n, t.cap_c * 4);
+  pl.zero_bytes = l.at;
+  l.take(t.kind, max_rings);
+  l.take(t.big, max_rings * 4);
+  l.take(t.id_list, max_ids * 4);
+  l.take(t.id_start, max_ids * 4);
+  l.take(t.e_xy, max_vertices * 16);
+  l.take(t.e_id, max_vertices * 4);
+  l.take(t.cell_at, t.cap_c * 4);
+  l.take(t.entry, t.cap_e * 4);
+  l.take(t.jobs, t.cap_j * 8);
+  pl.bytes = l.at;
   t.max_rings = (int)max_rings; t.max_vertices = (int)max_vertices; t.max_ids = (int)max_ids;
+  if (ws) {
+    t.top = static_cast<uint32_t*>(ws) + WS_K;
+    t.n_big = static_cast<uint32_t*>(ws) + WS_BIG;
+  }
   return pl;
-}
-
-template <class T> void rebase(T*& p, char* base) { p = reinterpret_cast<T*>(base + reinterpret_cast<intptr_t>(p)); }
-void bind(Tab& t, char* base) {
-  rebase(t.kind, base); rebase(t.big, base); rebase(t.id_rings, base); rebase(t.id_verts, base); rebase(t.id_flags, base);
-  rebase(t.id_list, base); rebase(t.id_start, base); rebase(t.id_live, base); rebase(t.e_xy, base); rebase(t.e_id, base);
-  rebase(t.cell_n, base); rebase(t.cell_at, base); rebase(t.entry, base); rebase(t.jobs, base);
 }
 
 __device__ __forceinline__ uint32_t edges_of(const Tab& s, const uint32_t* header) {
@@ -123,13 +118,11 @@ __device__ __forceinline__ uint32_t edges_of(const Tab& s, const uint32_t* heade
 __device__ __forceinline__ bool over_work(const Tab& s, const uint32_t* header) { return quad(header)[WQ_WORK] > (u64)s.max_work; }
 
 // ---------------------------------------------------------------------------------------------------------- 1, 2: shared
-__global__ __launch_bounds__(256) void conflicts_rows_kernel(Tab s, uint32_t* __restrict__ header) { rows_pass(s, header); }
-__global__ __launch_bounds__(256) void conflicts_check_big_kernel(Tab s, const uint32_t* __restrict__ header) {
-  check_big_pass(s, header);
-}
-__global__ __launch_bounds__(SCAN_T) void conflicts_ids_kernel(Tab s, const uint32_t* __restrict__ header) {
+__global__ __launch_bounds__(256) void conflicts_rows_kernel(Tab s) { rows_pass(s); }
+__global__ __launch_bounds__(256) void conflicts_check_big_kernel(Tab s) { check_big_pass(s); }
+__global__ __launch_bounds__(SCAN_T) void conflicts_ids_kernel(Tab s) {
   extern __shared__ u64 part_ids[];                        // [2][SCAN_T / 64]
-  ids_pass(s, header, reinterpret_cast<u64(*)[SCAN_T / 64]>(part_ids));
+  ids_pass(s, reinterpret_cast<u64(*)[SCAN_T / 64]>(part_ids));
 }
 
 // -------------------------------------------------------------------------------------------------------------- 3: edges
@@ -459,11 +452,6 @@ __global__ __launch_bounds__(256) void conflicts_tail_kernel(Tab s, const uint32
   }
 }
 
-unsigned grid_for(int64_t items, int per_block) {
-  int64_t g = (items + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : (g > MAX_GRID ? MAX_GRID : g));
-}
-
 int refuse(int32_t max_rings, int32_t max_vertices, int32_t max_ids) {
   if (max_rings < 1 || max_vertices < 1 || max_ids < 1) return C3D_E_BADARG;
   return 0;
@@ -484,7 +472,7 @@ extern "C" void c3d_rings_conflicts_limits(int32_t out[6]) {
 extern "C" int64_t c3d_rings_conflicts_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_ids) {
   const int rc = refuse(max_rings, max_vertices, max_ids);
   if (rc) return rc;
-  return plan_of(max_rings, max_vertices, max_ids).bytes;
+  return plan_of(nullptr, max_rings, max_vertices, max_ids).bytes;
 }
 
 extern "C" int c3d_rings_conflicts(const int32_t* rings, const int32_t* vertices, const int32_t* counts_in, int32_t max_rings,
@@ -494,30 +482,28 @@ extern "C" int c3d_rings_conflicts(const int32_t* rings, const int32_t* vertices
   if (frac_bits < 0 || frac_bits > 8 || max_work < 0) return C3D_E_BADARG;
   int rc = refuse(max_rings, max_vertices, max_ids);
   if (rc) return rc;
-  Plan pl = plan_of(max_rings, max_vertices, max_ids);
+  const Plan pl = plan_of(ws, max_rings, max_vertices, max_ids);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
   Tab s = pl.t;
-  bind(s, base);
   s.rings = rings; s.vertices = reinterpret_cast<const int2*>(vertices); s.counts = counts_in;
   s.coord_max = (int64_t)COORD_UNIT << frac_bits;
   s.max_work = max_work;
-  uint32_t* header = reinterpret_cast<uint32_t*>(base);
+  uint32_t* header = static_cast<uint32_t*>(ws);
   const uint32_t* hdr = header;
   u64* rows = reinterpret_cast<u64*>(conflict);
 
   // the header, the per-id sums and the cell counts: every other word of the workspace is written by the call before the call
   // reads it
-  hipError_t e = hipMemsetAsync(base, 0, (size_t)pl.zero_bytes, st);
+  hipError_t e = hipMemsetAsync(ws, 0, (size_t)pl.zero_bytes, st);
   if (e != hipSuccess) return (int)e;
   // the ring, id, edge and cell counts are known on the device only: grids are sized by the maxima and surplus workgroups return
-  const unsigned g_rows = grid_for(max_rings, 4), g_edge = grid_for(max_vertices, 256), g_cell = grid_for(s.cap_c, 256);
-  const unsigned g_big = grid_for(max_vertices, 4 * 256) < 1024u ? grid_for(max_vertices, 4 * 256) : 1024u;
-  rc = c3d_launch_lds<conflicts_rows_kernel>(dim3(g_rows), dim3(256), 0, st, s, header);
+  const unsigned g_rows = grid_for(max_rings, 4, MAX_GRID), g_edge = grid_for(max_vertices, 256, MAX_GRID);
+  const unsigned g_cell = grid_for(s.cap_c, 256, MAX_GRID), g_big = grid_for(max_vertices, 4 * 256, 1024);
+  rc = c3d_launch_lds<conflicts_rows_kernel>(dim3(g_rows), dim3(256), 0, st, s);
   if (rc) return rc;
-  rc = c3d_launch_lds<conflicts_check_big_kernel>(dim3(g_big), dim3(256), 0, st, s, hdr);
+  rc = c3d_launch_lds<conflicts_check_big_kernel>(dim3(g_big), dim3(256), 0, st, s);
   if (rc) return rc;
-  rc = c3d_launch_lds<conflicts_ids_kernel>(dim3(1), dim3(SCAN_T), 2 * (SCAN_T / 64) * 8, st, s, hdr);
+  rc = c3d_launch_lds<conflicts_ids_kernel>(dim3(1), dim3(SCAN_T), 2 * (SCAN_T / 64) * 8, st, s);
   if (rc) return rc;
   rc = c3d_launch_lds<conflicts_edges_kernel>(dim3(g_rows), dim3(256), 0, st, s, header);
   if (rc) return rc;
@@ -533,11 +519,11 @@ extern "C" int c3d_rings_conflicts(const int32_t* rings, const int32_t* vertices
   if (rc) return rc;
   rc = c3d_launch_lds<conflicts_scatter_kernel>(dim3(g_edge), dim3(256), 0, st, s, hdr);
   if (rc) return rc;
-  rc = c3d_launch_lds<conflicts_init_kernel>(dim3(grid_for(max_ids, 256)), dim3(256), 0, st, s, hdr, rows);
+  rc = c3d_launch_lds<conflicts_init_kernel>(dim3(grid_for(max_ids, 256, MAX_GRID)), dim3(256), 0, st, s, hdr, rows);
   if (rc) return rc;
   rc = c3d_launch_lds<conflicts_wave_kernel>(dim3(g_cell), dim3(256), 0, st, s, header, rows);
   if (rc) return rc;
-  rc = c3d_launch_lds<conflicts_jobs_kernel>(dim3(grid_for(s.cap_j, 1)), dim3(BLOCK_T), (size_t)TILE * 20, st, s, header, rows);
+  rc = c3d_launch_lds<conflicts_jobs_kernel>(dim3(grid_for(s.cap_j, 1, MAX_GRID)), dim3(BLOCK_T), (size_t)TILE * 20, st, s, header, rows);
   if (rc) return rc;
   return c3d_launch_lds<conflicts_tail_kernel>(dim3(1), dim3(256), 5 * 256 * 8, st, s, hdr, conflict, counts, info, totals);
 }

@@ -27,12 +27,13 @@
 //   8 finish    rows without a pixel, cls, the rows past K, counts_obj, info
 #include <climits>
 
-#include "scene_wave.h"
-#include "../../include/change3d_hip.h"
+#include "scene_groups.h"
+#include "scene_host.h"
 
 namespace {
 
-using namespace c3d_wave;
+using namespace c3d_groups;                                // the group, scan and scatter passes (steps 2-4)
+using c3d_host::grid_for;
 
 typedef unsigned long long u64;
 
@@ -42,35 +43,38 @@ constexpr int EXTENT_MAX = 16384;                          // scene rows / colum
 constexpr int COORD_UNITS = 32768;                         // |coordinate| <= COORD_UNITS << frac_bits
 constexpr int FRAC_MAX = 8;
 constexpr int BLOCK_T = 512;                               // threads of a band's workgroup
-constexpr int SMALL_RING = 16;                             // most vertices of a ring that one lane walks alone
 constexpr int TABLE_STEPS = 16;                            // steps of 64 pixels that a wave of the table pass walks
-constexpr int SCAN_T = 1024, SCAN_ROWS = 8;
 constexpr int MAX_GRID = 8192;
 constexpr int LIST_GRID = 128;                             // workgroups that share the list of large ids, per band
-constexpr int ROW_SKIP = 0, ROW_USED = 1;
 
 // words of the workspace header (256 bytes, zeroed by the call's memset)
 enum { WS_STATUS = 0, WS_USED = 1, WS_K = 2, WS_LARGE = 3 };
 
-struct Workspace {
-  int64_t box, cnt, off, cursor, large, grouped, yrange, valid, bytes;   // byte offsets
+struct Plan {
+  Groups g;
+  int4* box;                                               // [max_objects] the pixels the id's rings can reach
+  uint32_t* large;                                         // [max_objects] the ids whose box exceeds BOX_LIMIT, in any order
+  int2* yrange;                                            // [max_rings] the rows a ring can toggle a bit on
+  int64_t bytes;
 };
 
-Workspace workspace_plan(int64_t max_rings, int64_t max_objects) {
-  Workspace w;
-  auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-  w.box = 256;
-  w.cnt = w.box + up(max_objects * 16);
-  w.off = w.cnt + up(max_objects * 4);
-  w.cursor = w.off + up(max_objects * 4);
-  w.large = w.cursor + up(max_objects * 4);
-  w.grouped = w.large + up(max_objects * 4);
-  w.yrange = w.grouped + up(max_rings * 4);
-  w.valid = w.yrange + up(max_rings * 8);
-  w.bytes = w.valid + up(max_rings);
-  return w;
+// ws: the workspace, or nullptr where only the sizes are asked for
+Plan plan_of(void* ws, int64_t max_rings, int64_t max_vertices, int64_t max_objects) {
+  Plan pl{};
+  c3d_host::Layout l{static_cast<char*>(ws), 256};
+  l.take(pl.box, max_objects * 16);
+  l.take(pl.g.cnt, max_objects * 4);
+  l.take(pl.g.off, max_objects * 4);
+  l.take(pl.g.cursor, max_objects * 4);
+  l.take(pl.large, max_objects * 4);
+  l.take(pl.g.grouped, max_rings * 4);
+  l.take(pl.yrange, max_rings * 8);
+  l.take(pl.g.valid, max_rings);
+  pl.bytes = l.at;
+  pl.g.max_rings = (int)max_rings; pl.g.max_vertices = (int)max_vertices; pl.g.max_objects = (int)max_objects;
+  if (ws) pl.g.top = static_cast<uint32_t*>(ws) + WS_K;
+  return pl;
 }
-
 
 // The smallest column x in [lo, hi] whose centre lies right of the edge on this row, hi + 1 if none does.  The predicate is
 // P(x): (2x + 1) * sdy > A with sdy = 2^f * (Y1 - Y0) > 0 and A = X0 * dy + dx * (Cy - Y0); it is false below the answer and
@@ -129,11 +133,6 @@ __global__ __launch_bounds__(256) void fill_init_kernel(int4* __restrict__ box, 
   }
 }
 
-__device__ __forceinline__ int rows_of(const int32_t* counts, int max_rings) {
-  if (counts[4] & C3D_OUTLINE_ST_BAD_COUNTS) return 0;
-  return clampi(counts[1], 0, max_rings);
-}
-
 // the box of the pixels whose centre can lie inside a ring with these coordinate extremes, clipped to the scene: Xmin < Cx <=
 // Xmax and Ymin <= Cy < Ymax in doubled coordinates.  False: none (a ring wholly left or right of the scene changes no parity)
 __device__ __forceinline__ bool pixel_box(int xmin, int ymin, int xmax, int ymax, int f, int Hs, int Ws, int4* out) {
@@ -151,162 +150,68 @@ __device__ __forceinline__ void box_atomics(int* b, int4 v) {
   if (v.w > b[3]) atomicMax(b + 3, v.w);
 }
 
-// 64 ring rows per wave and step: a small ring is read by its own lane, a larger one by the whole wave.  What the rows of a
-// wave add to the same word -- the used count, K, the ring count and the box of an id -- goes out as one atomic per wave
-// (a checkerboard is half a million rings of ONE id).
-__global__ __launch_bounds__(256) void fill_group_kernel(const int32_t* __restrict__ rings, const int2* __restrict__ vertices,
-                                                         const int32_t* __restrict__ counts, int max_rings, int max_vertices,
-                                                         int max_objects, int f, int Hs, int Ws, int* __restrict__ box,
-                                                         uint32_t* __restrict__ cnt, int2* __restrict__ yrange,
-                                                         uint8_t* __restrict__ valid, uint32_t* __restrict__ header) {
-  const int lane = threadIdx.x & 63, rows = rows_of(counts, max_rings);
-  const int64_t vlimit = clampi(counts[3], 0, max_vertices);
-  const int cmax = COORD_UNITS << f;
-  for (int base = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 64; base < rows; base += gridDim.x * 256) {   // uniform over the wave
-    const int r = base + lane;
-    const bool in = r < rows;
-    int id = 0, start = -1, n = 0;
-    if (in) {
-      id = rings[(int64_t)r * 8];
-      start = rings[(int64_t)r * 8 + 1];
-      n = rings[(int64_t)r * 8 + 2];
-    }
-    const bool look = in && start >= 0;                    // start < 0: the simplifier's pass-through
-    const bool id_ok = id >= 1 && id <= max_objects, range_ok = look && n >= 0 && (int64_t)start + n <= vlimit;
-    int xmin = INT_MAX, xmax = INT_MIN, ymin = INT_MAX, ymax = INT_MIN;
-    bool bad = false;
-    if (range_ok && n <= SMALL_RING) {
-      for (int k = 0; k < n; ++k) {
-        const int2 p = vertices[(int64_t)start + k];
-        bad |= p.x < -cmax || p.x > cmax || p.y < -cmax || p.y > cmax;
-        xmin = p.x < xmin ? p.x : xmin;
-        xmax = p.x > xmax ? p.x : xmax;
-        ymin = p.y < ymin ? p.y : ymin;
-        ymax = p.y > ymax ? p.y : ymax;
-      }
-    }
-    u64 big = __ballot(range_ok && n > SMALL_RING);
-    for (int step = 0; step < 64 && big; ++step) {         // uniform: the shuffles see every lane
-      const int src = __ffsll((long long)big) - 1;
-      big &= big - 1;
-      const int64_t s0 = __shfl(start, src);
-      const int n0 = __shfl(n, src);
-      int ax = INT_MAX, bx = INT_MIN, ay = INT_MAX, by = INT_MIN;
-      bool b0 = false;
-      for (int k = lane; k < n0; k += 64) {
-        const int2 p = vertices[s0 + k];
-        b0 |= p.x < -cmax || p.x > cmax || p.y < -cmax || p.y > cmax;
-        ax = p.x < ax ? p.x : ax;
-        bx = p.x > bx ? p.x : bx;
-        ay = p.y < ay ? p.y : ay;
-        by = p.y > by ? p.y : by;
-      }
-      ax = wave_min32(ax);
-      ay = wave_min32(ay);
-      bx = wave_max32(bx);
-      by = wave_max32(by);
-      const bool any_bad = __any(b0) != 0;
-      if (lane == src) { xmin = ax; ymin = ay; xmax = bx; ymax = by; bad = any_bad; }
-    }
-    const bool ring_ok = range_ok && !bad, used = look && id_ok && ring_ok;
-    if (in) valid[r] = used ? ROW_USED : ROW_SKIP;
+// what the group pass checks and adds up here: coordinates inside +-(COORD_UNITS << f), the coordinate box of every ring,
+// the pixel box of every id; the used rows are counted on the way
+struct GroupPolicy {
+  int f, Hs, Ws;
+  int* box;
+  int2* yrange;
+  uint32_t* header;
+  struct Ring {
+    int xmin, ymin, xmax, ymax;
+  };
+  struct Sum {
+    bool has_box;
+    int4 pb;
+  };
+  __device__ __forceinline__ Ring empty() const { return Ring{INT_MAX, INT_MAX, INT_MIN, INT_MIN}; }
+  __device__ __forceinline__ bool vertex(Ring& r, int2 p) const {
+    const int cmax = COORD_UNITS << f;
+    r.xmin = p.x < r.xmin ? p.x : r.xmin;
+    r.xmax = p.x > r.xmax ? p.x : r.xmax;
+    r.ymin = p.y < r.ymin ? p.y : r.ymin;
+    r.ymax = p.y > r.ymax ? p.y : r.ymax;
+    return p.x >= -cmax && p.x <= cmax && p.y >= -cmax && p.y <= cmax;
+  }
+  __device__ __forceinline__ void merge(Ring& r) const {
+    r.xmin = wave_min32(r.xmin);
+    r.ymin = wave_min32(r.ymin);
+    r.xmax = wave_max32(r.xmax);
+    r.ymax = wave_max32(r.ymax);
+  }
+  __device__ __forceinline__ void status(bool look, bool id_ok, bool ring_ok, bool used) const {
     const bool no_id = __any(look && !id_ok) != 0, no_ring = __any(look && !ring_ok) != 0;
-    const int n_used = __popcll(__ballot(used)), k_max = wave_max32(used ? id : 0);
-    if (lane == 0) {
+    const int n_used = __popcll(__ballot(used));
+    if ((threadIdx.x & 63) == 0) {
       if (no_id || no_ring) atomicOr(header + WS_STATUS, (uint32_t)((no_id ? C3D_FILL_ST_BAD_ID : 0) | (no_ring ? C3D_FILL_ST_BAD_RING : 0)));
       if (n_used) atomicAdd(header + WS_USED, (uint32_t)n_used);
-      if ((uint32_t)k_max > header[WS_K]) atomicMax(header + WS_K, (uint32_t)k_max);
-    }
-    int4 pb = make_int4(0, 0, -1, -1);
-    const bool has_box = used && n >= 3 && pixel_box(xmin, ymin, xmax, ymax, f, Hs, Ws, &pb);
-    if (used) yrange[r] = has_box ? make_int2(pb.y, pb.w) : make_int2(1, 0);   // the rows this ring can toggle a bit on
-    bool open = used;
-    for (int round = 0; round < 2; ++round) {              // one set of atomics per wave for its two most frequent ids
-      const u64 m = __ballot(open);
-      if (!m) break;
-      const int leader = __ffsll((long long)m) - 1, id0 = __shfl(id, leader);
-      const bool same = open && id == id0, sb = same && has_box;
-      const int c = __popcll(__ballot(same));
-      const int4 u = make_int4(wave_min32(sb ? pb.x : INT_MAX), wave_min32(sb ? pb.y : INT_MAX), wave_max32(sb ? pb.z : INT_MIN),
-                               wave_max32(sb ? pb.w : INT_MIN));
-      if (lane == leader) {
-        atomicAdd(cnt + (id0 - 1), (uint32_t)c);
-        if (u.x <= u.z) box_atomics(box + (int64_t)(id0 - 1) * 4, u);
-      }
-      if (same) open = false;
-    }
-    if (open) {
-      atomicAdd(cnt + (id - 1), 1u);
-      if (has_box) box_atomics(box + (int64_t)(id - 1) * 4, pb);
     }
   }
+  __device__ __forceinline__ Sum ring(int r, int n, bool used, const Ring& c) const {
+    Sum v{false, make_int4(0, 0, -1, -1)};
+    v.has_box = used && n >= 3 && pixel_box(c.xmin, c.ymin, c.xmax, c.ymax, f, Hs, Ws, &v.pb);
+    if (used) yrange[r] = v.has_box ? make_int2(v.pb.y, v.pb.w) : make_int2(1, 0);   // the rows this ring can toggle a bit on
+    return v;
+  }
+  __device__ __forceinline__ Sum fold(bool same, const Sum& v) const {
+    const bool sb = same && v.has_box;
+    const int4 u = make_int4(wave_min32(sb ? v.pb.x : INT_MAX), wave_min32(sb ? v.pb.y : INT_MAX), wave_max32(sb ? v.pb.z : INT_MIN),
+                             wave_max32(sb ? v.pb.w : INT_MIN));
+    return Sum{u.x <= u.z, u};
+  }
+  __device__ __forceinline__ void add(int id, const Sum& v) const {
+    if (v.has_box) box_atomics(box + (int64_t)(id - 1) * 4, v.pb);
+  }
+};
+__global__ __launch_bounds__(256) void fill_group_kernel(Groups g, int f, int Hs, int Ws, int* __restrict__ box, int2* __restrict__ yrange,
+                                                         uint32_t* __restrict__ header) {
+  group_pass(g, GroupPolicy{f, Hs, Ws, box, yrange, header});
 }
-
-// off[i] = rings of the ids before i + 1, for the ids up to K.  One workgroup.
-__global__ __launch_bounds__(SCAN_T) void fill_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
-                                                           const uint32_t* __restrict__ header) {
-  const int max_objects = (int)header[WS_K];               // the ids above K own no ring and are never looked up
+__global__ __launch_bounds__(SCAN_T) void fill_scan_kernel(Groups g) {
   extern __shared__ uint32_t part[];                       // [SCAN_T / 64]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t running = 0;
-  for (int base = 0; base < max_objects; base += SCAN_T * SCAN_ROWS) {
-    uint32_t n[SCAN_ROWS], mine = 0;
-    for (int j = 0; j < SCAN_ROWS; ++j) {
-      const int i = base + (int)threadIdx.x * SCAN_ROWS + j;
-      n[j] = i < max_objects ? cnt[i] : 0u;
-      mine += n[j];
-    }
-    uint32_t inc = mine;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t t = (uint32_t)__shfl((int)inc, lane >= d ? lane - d : lane);
-      if (lane >= d) inc += t;
-    }
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < SCAN_T / 64; ++w) {
-      before += w < wave ? part[w] : 0u;
-      all += part[w];
-    }
-    uint32_t at = running + before + inc - mine;
-    for (int j = 0; j < SCAN_ROWS; ++j) {
-      const int i = base + (int)threadIdx.x * SCAN_ROWS + j;
-      if (i < max_objects) off[i] = at;
-      at += n[j];
-    }
-    running += all;
-    __syncthreads();
-  }
+  scan_pass(g, part);
 }
-
-__global__ __launch_bounds__(256) void fill_scatter_kernel(const int32_t* __restrict__ rings, const int32_t* __restrict__ counts,
-                                                           int max_rings, const uint8_t* __restrict__ valid,
-                                                           const uint32_t* __restrict__ off, uint32_t* __restrict__ cursor,
-                                                           uint32_t* __restrict__ grouped) {
-  const int rows = rows_of(counts, max_rings), lane = threadIdx.x & 63;
-  for (int base = blockIdx.x * 256; base < rows; base += gridDim.x * 256) {   // whole waves stay together
-    const int r = base + (int)threadIdx.x;
-    bool open = r < rows && valid[r] == ROW_USED;
-    const int id = open ? rings[(int64_t)r * 8] : 0;       // 1 .. max_objects: the group kernel checked it
-    uint32_t slot = 0xFFFFFFFFu;
-    for (int round = 0; round < 2; ++round) {              // one claim per wave for its two most frequent ids
-      const u64 m = __ballot(open);
-      if (!m) break;
-      const int leader = __ffsll((long long)m) - 1, id0 = __shfl(id, leader);
-      const bool same = open && id == id0;
-      const u64 sm = __ballot(same);
-      uint32_t first = 0;
-      if (lane == leader) first = atomicAdd(cursor + (id0 - 1), (uint32_t)__popcll(sm));
-      first = (uint32_t)__shfl((int)first, leader);
-      if (same) {
-        slot = off[id0 - 1] + first + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
-        open = false;
-      }
-    }
-    if (open) slot = off[id - 1] + atomicAdd(cursor + (id - 1), 1u);
-    if (slot < (uint32_t)max_rings) grouped[slot] = (uint32_t)r;   // the used rows number at most max_rings
-  }
-}
+__global__ __launch_bounds__(256) void fill_scatter_kernel(Groups g) { scatter_pass(g); }
 
 // ------------------------------------------------------------------------------------------------- one wave per id
 __global__ __launch_bounds__(256) void fill_wave_kernel(const int32_t* __restrict__ rings, const int2* __restrict__ vertices,
@@ -429,21 +334,17 @@ __global__ __launch_bounds__(BLOCK_T) void fill_block_kernel(const int32_t* __re
       for (int base = 0; base < wpr; base += 64) {
         const int j = base + lane;
         u64 v = j < wpr ? line[j] : 0ull;
-        const uint32_t odd = (uint32_t)__popcll(v) & 1u;
-        uint32_t inc = odd;
-        for (int d = 1; d < 64; d <<= 1) {
-          const uint32_t t = (uint32_t)__shfl((int)inc, lane >= d ? lane - d : lane);
-          if (lane >= d) inc ^= t;
-        }
+        uint32_t all;                                      // the parity of a sum of parities is their xor
+        const uint32_t before = wave_excl_scan32((uint32_t)__popcll(v) & 1u, &all);
         v ^= v << 1;
         v ^= v << 2;
         v ^= v << 4;
         v ^= v << 8;
         v ^= v << 16;
         v ^= v << 32;
-        if (carry ^ inc ^ odd) v = ~v;
+        if (carry ^ (before & 1u)) v = ~v;
         if (j < wpr) line[j] = v;
-        carry ^= (uint32_t)__shfl((int)inc, 63);
+        carry ^= all & 1u;
       }
     }
     __syncthreads();
@@ -567,11 +468,6 @@ __global__ __launch_bounds__(256) void fill_finish_kernel(const int32_t* __restr
   }
 }
 
-unsigned grid_for(int64_t items, int per_block) {
-  int64_t g = (items + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : (g > MAX_GRID ? MAX_GRID : g));
-}
-
 int refuse(int32_t max_rings, int32_t max_vertices, int32_t max_objects, int32_t Hs, int32_t Ws) {
   if (max_rings < 1 || max_vertices < 1 || max_objects < 1 || Hs < 1 || Ws < 1) return C3D_E_BADARG;
   if (Hs > EXTENT_MAX || Ws > EXTENT_MAX) return C3D_E_UNSUPPORTED;
@@ -589,7 +485,7 @@ extern "C" void c3d_rings_fill_limits(int32_t out[2]) {
 extern "C" int64_t c3d_rings_fill_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_objects, int32_t Hs, int32_t Ws) {
   const int rc = refuse(max_rings, max_vertices, max_objects, Hs, Ws);
   if (rc) return rc;
-  return workspace_plan(max_rings, max_objects).bytes;
+  return plan_of(nullptr, max_rings, max_vertices, max_objects).bytes;
 }
 
 extern "C" int c3d_rings_fill(const int32_t* rings, const int32_t* vertices, const int32_t* counts, int32_t max_rings,
@@ -600,38 +496,32 @@ extern "C" int c3d_rings_fill(const int32_t* rings, const int32_t* vertices, con
   if (frac_bits < 0 || frac_bits > FRAC_MAX) return C3D_E_BADARG;
   int rc = refuse(max_rings, max_vertices, max_objects, Hs, Ws);
   if (rc) return rc;
-  const Workspace w = workspace_plan(max_rings, max_objects);
+  const Plan pl = plan_of(ws, max_rings, max_vertices, max_objects);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  uint32_t* header = reinterpret_cast<uint32_t*>(base);
-  int4* box = reinterpret_cast<int4*>(base + w.box);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(base + w.cnt);
-  uint32_t* off = reinterpret_cast<uint32_t*>(base + w.off);
-  uint32_t* cursor = reinterpret_cast<uint32_t*>(base + w.cursor);
-  uint32_t* large = reinterpret_cast<uint32_t*>(base + w.large);
-  uint32_t* grouped = reinterpret_cast<uint32_t*>(base + w.grouped);
-  int2* yrange = reinterpret_cast<int2*>(base + w.yrange);
-  uint8_t* valid = reinterpret_cast<uint8_t*>(base + w.valid);
-  const int2* v_in = reinterpret_cast<const int2*>(vertices);
+  uint32_t* header = static_cast<uint32_t*>(ws);
+  Groups g = pl.g;
+  g.rings = rings; g.vertices = reinterpret_cast<const int2*>(vertices); g.counts = counts;
+  int4* box = pl.box;
+  uint32_t *cnt = g.cnt, *off = g.off, *large = pl.large, *grouped = g.grouped;
+  int2* yrange = pl.yrange;
+  const int2* v_in = g.vertices;
   const int f = frac_bits;
 
   // the header and the labels; every other word of the workspace is written by the call before the call reads it
-  hipError_t e = hipMemsetAsync(base, 0, 256, st);
+  hipError_t e = hipMemsetAsync(ws, 0, 256, st);
   if (e != hipSuccess) return (int)e;
   e = hipMemsetAsync(labels, 0, (size_t)Hs * (size_t)Ws * 4, st);
   if (e != hipSuccess) return (int)e;
   // ring and id counts are known on the device only: grids are sized by the limits and surplus waves and workgroups return
-  const unsigned g_ids = grid_for(max_objects, 256), g_idw = grid_for(max_objects, 4);
-  rc = c3d_launch_lds<fill_init_kernel>(dim3(g_ids), dim3(256), 0, st, box, cnt, cursor, table, (int)max_objects);
+  const unsigned g_ids = grid_for(max_objects, 256, MAX_GRID), g_idw = grid_for(max_objects, 4, MAX_GRID);
+  const unsigned g_rows = grid_for(max_rings, 256, MAX_GRID);
+  rc = c3d_launch_lds<fill_init_kernel>(dim3(g_ids), dim3(256), 0, st, box, cnt, g.cursor, table, (int)max_objects);
   if (rc) return rc;
-  rc = c3d_launch_lds<fill_group_kernel>(dim3(grid_for(max_rings, 256)), dim3(256), 0, st, rings, v_in, counts, (int)max_rings,
-                                         (int)max_vertices, (int)max_objects, f, (int)Hs, (int)Ws, reinterpret_cast<int*>(box), cnt,
-                                         yrange, valid, header);
+  rc = c3d_launch_lds<fill_group_kernel>(dim3(g_rows), dim3(256), 0, st, g, f, (int)Hs, (int)Ws, reinterpret_cast<int*>(box), yrange, header);
   if (rc) return rc;
-  rc = c3d_launch_lds<fill_scan_kernel>(dim3(1), dim3(SCAN_T), SCAN_T / 64 * 4, st, (const uint32_t*)cnt, off, (const uint32_t*)header);
+  rc = c3d_launch_lds<fill_scan_kernel>(dim3(1), dim3(SCAN_T), SCAN_T / 64 * 4, st, g);
   if (rc) return rc;
-  rc = c3d_launch_lds<fill_scatter_kernel>(dim3(grid_for(max_rings, 256)), dim3(256), 0, st, rings, counts, (int)max_rings,
-                                           (const uint8_t*)valid, (const uint32_t*)off, cursor, grouped);
+  rc = c3d_launch_lds<fill_scatter_kernel>(dim3(g_rows), dim3(256), 0, st, g);
   if (rc) return rc;
   rc = c3d_launch_lds<fill_wave_kernel>(dim3(g_idw), dim3(256), 0, st, rings, v_in, (const int4*)box, (const uint32_t*)cnt,
                                         (const uint32_t*)off, (const uint32_t*)grouped, large, header, f, (int)Ws, labels);
@@ -643,7 +533,7 @@ extern "C" int c3d_rings_fill(const int32_t* rings, const int32_t* vertices, con
                                          (const uint32_t*)cnt, (const uint32_t*)off, (const uint32_t*)grouped, (const int2*)yrange,
                                          (const uint32_t*)large, (const uint32_t*)header, f, (int)Ws, labels);
   if (rc) return rc;
-  rc = c3d_launch_lds<fill_table_kernel>(dim3(grid_for((int64_t)Hs * Ws, 256 * TABLE_STEPS)), dim3(256), 0, st, (const int32_t*)labels, (int)Hs,
+  rc = c3d_launch_lds<fill_table_kernel>(dim3(grid_for((int64_t)Hs * Ws, 256 * TABLE_STEPS, MAX_GRID)), dim3(256), 0, st, (const int32_t*)labels, (int)Hs,
                                          (int)Ws, (int)max_objects, id_cls, table, mask, cls_map);
   if (rc) return rc;
   return c3d_launch_lds<fill_finish_kernel>(dim3(g_ids), dim3(256), 0, st, counts, (const uint32_t*)header, id_cls, (int)max_objects,

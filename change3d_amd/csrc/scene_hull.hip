@@ -30,12 +30,13 @@
 //               walked again by 9, which needs no room at all
 #include <climits>
 
-#include "scene_wave.h"
-#include "../../include/change3d_hip.h"
+#include "scene_groups.h"
+#include "scene_host.h"
 
 namespace {
 
-using namespace c3d_wave;
+using namespace c3d_groups;                                // the group, scan and scatter passes (steps 2-4)
+using c3d_host::grid_for;
 
 typedef unsigned long long u64;
 typedef unsigned __int128 u128;
@@ -49,13 +50,10 @@ constexpr int HULL_CAP = 4096;
 constexpr int BLOCK_T = 1024;                              // threads of an id's workgroup: a step of the walk is latency
 constexpr int WAVES = BLOCK_T / 64;
 constexpr int COORD_MAX = 16384;
-constexpr int SMALL_RING = 16;                             // most vertices of a ring that one lane walks alone
 constexpr int MID_RING = 2048;                             // most vertices of a ring that one wave walks; all threads beyond
 constexpr int BIG_LIST = 1024;                             // larger rings of an id that the workgroup lists in LDS per sweep
-constexpr int SCAN_T = 1024, SCAN_ROWS = 8;
 constexpr int MAX_GRID = 8192;
 constexpr int LIST_GRID = 256;                             // workgroups that share the list of large ids
-constexpr int ROW_SKIP = 0, ROW_USED = 1;
 constexpr uint32_t NONE = 0xFFFFFFFFu;                     // no point; a point is y << 16 | x, so that the order is (y, x)
 
 // LDS of the block kernel: candidates, hull, the list of larger rings, then the scratch of the reductions
@@ -64,24 +62,32 @@ constexpr int LDS_BYTES = LDS_LIMIT * 4 + HULL_CAP * 4 + BIG_LIST * 8 + 8 * 8 + 
 // words of the workspace header (256 bytes, zeroed by the call's memset)
 enum { WS_STATUS = 0, WS_K = 1, WS_LARGE = 2, WS_STAGED = 4 };   // WS_STAGED: a u64, the hull vertices staged so far
 
-struct Workspace {
-  int64_t npts, cnt, off, cursor, large, stage_at, grouped, valid, stage, bytes;   // byte offsets
+struct Plan {
+  Groups g;
+  u64* npts;                                               // [max_objects] points of the id
+  uint32_t* large;                                         // [max_objects] the ids above WAVE_LIMIT points, in any order
+  uint32_t* stage_at;                                      // [max_objects] where the id's hull starts in `stage`
+  uint32_t* stage;                                         // [max_vertices] hulls kept by the first block pass
+  int64_t bytes;
 };
 
-Workspace workspace_plan(int64_t max_rings, int64_t max_vertices, int64_t max_objects) {
-  Workspace w;
-  auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-  w.npts = 256;
-  w.cnt = w.npts + up(max_objects * 8);
-  w.off = w.cnt + up(max_objects * 4);
-  w.cursor = w.off + up(max_objects * 4);
-  w.large = w.cursor + up(max_objects * 4);
-  w.stage_at = w.large + up(max_objects * 4);
-  w.grouped = w.stage_at + up(max_objects * 4);
-  w.valid = w.grouped + up(max_rings * 4);
-  w.stage = w.valid + up(max_rings);
-  w.bytes = w.stage + up(max_vertices * 4);
-  return w;
+// ws: the workspace, or nullptr where only the sizes are asked for
+Plan plan_of(void* ws, int64_t max_rings, int64_t max_vertices, int64_t max_objects) {
+  Plan pl{};
+  c3d_host::Layout l{static_cast<char*>(ws), 256};
+  l.take(pl.npts, max_objects * 8);
+  l.take(pl.g.cnt, max_objects * 4);
+  l.take(pl.g.off, max_objects * 4);
+  l.take(pl.g.cursor, max_objects * 4);
+  l.take(pl.large, max_objects * 4);
+  l.take(pl.stage_at, max_objects * 4);
+  l.take(pl.g.grouped, max_rings * 4);
+  l.take(pl.g.valid, max_rings);
+  l.take(pl.stage, max_vertices * 4);
+  pl.bytes = l.at;
+  pl.g.max_rings = (int)max_rings; pl.g.max_vertices = (int)max_vertices; pl.g.max_objects = (int)max_objects;
+  if (ws) pl.g.top = static_cast<uint32_t*>(ws) + WS_K;
+  return pl;
 }
 
 // 64-bit reductions by the xor shuffle, which the walks below use on pairs of words too: another shuffle pattern than
@@ -200,138 +206,33 @@ __global__ __launch_bounds__(256) void hull_init_kernel(u64* __restrict__ npts, 
   }
 }
 
-__device__ __forceinline__ int rows_of(const int32_t* counts, int max_rings) {
-  if (counts[4] & C3D_OUTLINE_ST_BAD_COUNTS) return 0;
-  return clampi(counts[1], 0, max_rings);
-}
-
-// 64 ring rows per wave and step: a small ring is read by its own lane, a larger one by the whole wave.  What the rows of a
-// wave add to the same word goes out as one atomic per wave (a checkerboard is half a million rings of ONE id).
-__global__ __launch_bounds__(256) void hull_group_kernel(const int32_t* __restrict__ rings, const int2* __restrict__ vertices,
-                                                         const int32_t* __restrict__ counts, int max_rings, int max_vertices,
-                                                         int max_objects, u64* __restrict__ npts, uint32_t* __restrict__ cnt,
-                                                         uint8_t* __restrict__ valid, uint32_t* __restrict__ header) {
-  const int lane = threadIdx.x & 63, rows = rows_of(counts, max_rings);
-  const int64_t vlimit = clampi(counts[3], 0, max_vertices);
-  for (int base = (blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 64; base < rows; base += gridDim.x * 256) {   // uniform over the wave
-    const int r = base + lane;
-    const bool in = r < rows;
-    int id = 0, start = -1, n = 0;
-    if (in) {
-      id = rings[(int64_t)r * 8];
-      start = rings[(int64_t)r * 8 + 1];
-      n = rings[(int64_t)r * 8 + 2];
-    }
-    const bool look = in && start >= 0;                    // start < 0: a ring that had no room, skipped silently
-    const bool id_ok = id >= 1 && id <= max_objects, range_ok = look && n >= 0 && (int64_t)start + n <= vlimit;
-    bool bad = false;
-    if (range_ok && n <= SMALL_RING)
-      for (int k = 0; k < n; ++k) bad |= !coord_ok(vertices[(int64_t)start + k]);
-    u64 big = __ballot(range_ok && n > SMALL_RING);
-    for (int step = 0; step < 64 && big; ++step) {         // uniform: the shuffles see every lane
-      const int src = __ffsll((long long)big) - 1;
-      big &= big - 1;
-      const int64_t s0 = __shfl(start, src);
-      const int n0 = __shfl(n, src);
-      bool b0 = false;
-      for (int k = lane; k < n0; k += 64) b0 |= !coord_ok(vertices[s0 + k]);
-      const bool any_bad = __any(b0) != 0;
-      if (lane == src) bad = any_bad;
-    }
-    const bool used = look && id_ok && range_ok && !bad;
-    if (in) valid[r] = used ? ROW_USED : ROW_SKIP;
+// what the group pass checks and adds up here: coordinates inside the scene, the points of every id
+struct GroupPolicy {
+  u64* npts;
+  uint32_t* header;
+  struct Ring {};                                          // nothing is kept per ring but its n
+  typedef u64 Sum;
+  __device__ __forceinline__ Ring empty() const { return Ring{}; }
+  __device__ __forceinline__ bool vertex(Ring&, int2 v) const { return coord_ok(v); }
+  __device__ __forceinline__ void merge(Ring&) const {}
+  __device__ __forceinline__ void status(bool look, bool, bool, bool used) const {
     const bool any_skipped = __any(look && !used) != 0;
-    const int k_max = wave_max32(used ? id : 0);
-    if (lane == 0) {
-      if (any_skipped) atomicOr(header + WS_STATUS, (uint32_t)C3D_HULL_ST_BAD_ROW);
-      if ((uint32_t)k_max > header[WS_K]) atomicMax(header + WS_K, (uint32_t)k_max);
-    }
-    bool open = used;
-    for (int round = 0; round < 2; ++round) {              // one set of atomics per wave for its two most frequent ids
-      const u64 m = __ballot(open);
-      if (!m) break;
-      const int leader = __ffsll((long long)m) - 1, id0 = __shfl(id, leader);
-      const bool same = open && id == id0;
-      const int c = __popcll(__ballot(same));
-      const u64 pts = wave_sum64(same ? (u64)n : 0ull);
-      if (lane == leader) {
-        atomicAdd(cnt + (id0 - 1), (uint32_t)c);
-        if (pts) atomicAdd(npts + (id0 - 1), pts);
-      }
-      if (same) open = false;
-    }
-    if (open) {
-      atomicAdd(cnt + (id - 1), 1u);
-      if (n) atomicAdd(npts + (id - 1), (u64)n);
-    }
+    if ((threadIdx.x & 63) == 0 && any_skipped) atomicOr(header + WS_STATUS, (uint32_t)C3D_HULL_ST_BAD_ROW);
   }
+  __device__ __forceinline__ Sum ring(int, int n, bool, const Ring&) const { return (u64)n; }
+  __device__ __forceinline__ Sum fold(bool same, Sum n) const { return wave_sum64(same ? n : 0ull); }
+  __device__ __forceinline__ void add(int id, Sum pts) const {
+    if (pts) atomicAdd(npts + (id - 1), pts);
+  }
+};
+__global__ __launch_bounds__(256) void hull_group_kernel(Groups g, u64* __restrict__ npts, uint32_t* __restrict__ header) {
+  group_pass(g, GroupPolicy{npts, header});
 }
-
-// off[i] = rings of the ids before i + 1, for the ids up to K.  One workgroup.
-__global__ __launch_bounds__(SCAN_T) void hull_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
-                                                           const uint32_t* __restrict__ header) {
-  const int K = (int)header[WS_K];                         // the ids above K own no ring and are never looked up
+__global__ __launch_bounds__(SCAN_T) void hull_scan_kernel(Groups g) {
   extern __shared__ uint32_t part[];                       // [SCAN_T / 64]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t running = 0;
-  for (int base = 0; base < K; base += SCAN_T * SCAN_ROWS) {
-    uint32_t n[SCAN_ROWS], mine = 0;
-    for (int j = 0; j < SCAN_ROWS; ++j) {
-      const int i = base + (int)threadIdx.x * SCAN_ROWS + j;
-      n[j] = i < K ? cnt[i] : 0u;
-      mine += n[j];
-    }
-    uint32_t inc = mine;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t t = (uint32_t)__shfl((int)inc, lane >= d ? lane - d : lane);
-      if (lane >= d) inc += t;
-    }
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < SCAN_T / 64; ++w) {
-      before += w < wave ? part[w] : 0u;
-      all += part[w];
-    }
-    uint32_t at = running + before + inc - mine;
-    for (int j = 0; j < SCAN_ROWS; ++j) {
-      const int i = base + (int)threadIdx.x * SCAN_ROWS + j;
-      if (i < K) off[i] = at;
-      at += n[j];
-    }
-    running += all;
-    __syncthreads();
-  }
+  scan_pass(g, part);
 }
-
-__global__ __launch_bounds__(256) void hull_scatter_kernel(const int32_t* __restrict__ rings, const int32_t* __restrict__ counts,
-                                                           int max_rings, const uint8_t* __restrict__ valid,
-                                                           const uint32_t* __restrict__ off, uint32_t* __restrict__ cursor,
-                                                           uint32_t* __restrict__ grouped) {
-  const int rows = rows_of(counts, max_rings), lane = threadIdx.x & 63;
-  for (int base = blockIdx.x * 256; base < rows; base += gridDim.x * 256) {   // whole waves stay together
-    const int r = base + (int)threadIdx.x;
-    bool open = r < rows && valid[r] == ROW_USED;
-    const int id = open ? rings[(int64_t)r * 8] : 0;       // 1 .. max_objects: the group kernel checked it
-    uint32_t slot = 0xFFFFFFFFu;
-    for (int round = 0; round < 2; ++round) {              // one claim per wave for its two most frequent ids
-      const u64 m = __ballot(open);
-      if (!m) break;
-      const int leader = __ffsll((long long)m) - 1, id0 = __shfl(id, leader);
-      const bool same = open && id == id0;
-      const u64 sm = __ballot(same);
-      uint32_t first = 0;
-      if (lane == leader) first = atomicAdd(cursor + (id0 - 1), (uint32_t)__popcll(sm));
-      first = (uint32_t)__shfl((int)first, leader);
-      if (same) {
-        slot = off[id0 - 1] + first + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
-        open = false;
-      }
-    }
-    if (open) slot = off[id - 1] + atomicAdd(cursor + (id - 1), 1u);
-    if (slot < (uint32_t)max_rings) grouped[slot] = (uint32_t)r;   // the used rows number at most max_rings
-  }
-}
+__global__ __launch_bounds__(256) void hull_scatter_kernel(Groups g) { scatter_pass(g); }
 
 // ------------------------------------------------------------------------------------------------- one wave per id
 // WRITE false: the hull row (all but start) and the rectangle row of every id up to K, the list of the larger ids, zeros
@@ -655,7 +556,7 @@ __global__ __launch_bounds__(SCAN_T) void hull_starts_kernel(const int32_t* __re
   u64& s_written = spart[SCAN_T / 64];
   uint32_t& s_ids = *reinterpret_cast<uint32_t*>(spart + SCAN_T / 64 + 1);
   const int K = (int)header[WS_K];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   if (threadIdx.x == 0) { s_written = ~0ull; s_ids = 0; }
   __syncthreads();
   u64 running = 0;
@@ -668,22 +569,10 @@ __global__ __launch_bounds__(SCAN_T) void hull_starts_kernel(const int32_t* __re
       with_points += i < K && npts[i] != 0;
       mine += n[j];
     }
-    u64 inc = mine;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int src = lane >= d ? lane - d : lane;
-      const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)inc, src), hi = (uint32_t)__shfl((int)(uint32_t)(inc >> 32), src);
-      if (lane >= d) inc += ((u64)hi << 32) | lo;
-    }
-    if (lane == 63) spart[wave] = inc;
     with_points = wave_sum32(with_points);
     if (lane == 0 && with_points) atomicAdd(&s_ids, with_points);
-    __syncthreads();
-    u64 before = 0, all = 0;
-    for (int w = 0; w < SCAN_T / 64; ++w) {
-      before += w < wave ? spart[w] : 0ull;
-      all += spart[w];
-    }
-    u64 at = running + before + inc - mine;
+    u64 all;
+    u64 at = running + block_excl_scan64(mine, spart, &all);
     for (int j = 0; j < SCAN_ROWS; ++j) {
       const int i = base + (int)threadIdx.x * SCAN_ROWS + j;
       if (i < K && n[j]) {
@@ -712,11 +601,6 @@ __global__ __launch_bounds__(SCAN_T) void hull_starts_kernel(const int32_t* __re
   }
 }
 
-unsigned grid_for(int64_t items, int per_block) {
-  int64_t g = (items + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : (g > MAX_GRID ? MAX_GRID : g));
-}
-
 int refuse(int32_t max_rings, int32_t max_vertices, int32_t max_objects) {
   if (max_rings < 1 || max_vertices < 1 || max_objects < 1) return C3D_E_BADARG;
   return 0;
@@ -733,7 +617,7 @@ extern "C" void c3d_rings_hull_limits(int32_t out[2]) {
 extern "C" int64_t c3d_rings_hull_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_objects) {
   const int rc = refuse(max_rings, max_vertices, max_objects);
   if (rc) return rc;
-  return workspace_plan(max_rings, max_vertices, max_objects).bytes;
+  return plan_of(nullptr, max_rings, max_vertices, max_objects).bytes;
 }
 
 extern "C" int c3d_rings_hull(const int32_t* rings, const int32_t* vertices, const int32_t* counts, int32_t max_rings,
@@ -743,38 +627,31 @@ extern "C" int c3d_rings_hull(const int32_t* rings, const int32_t* vertices, con
   if (max_hull_vertices < 1) return C3D_E_BADARG;
   int rc = refuse(max_rings, max_vertices, max_objects);
   if (rc) return rc;
-  const Workspace w = workspace_plan(max_rings, max_vertices, max_objects);
+  const Plan pl = plan_of(ws, max_rings, max_vertices, max_objects);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  uint32_t* header = reinterpret_cast<uint32_t*>(base);
-  u64* npts = reinterpret_cast<u64*>(base + w.npts);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(base + w.cnt);
-  uint32_t* off = reinterpret_cast<uint32_t*>(base + w.off);
-  uint32_t* cursor = reinterpret_cast<uint32_t*>(base + w.cursor);
-  uint32_t* large = reinterpret_cast<uint32_t*>(base + w.large);
-  uint32_t* grouped = reinterpret_cast<uint32_t*>(base + w.grouped);
-  uint8_t* valid = reinterpret_cast<uint8_t*>(base + w.valid);
-  uint32_t* stage_at = reinterpret_cast<uint32_t*>(base + w.stage_at);
-  uint32_t* stage = reinterpret_cast<uint32_t*>(base + w.stage);
+  uint32_t* header = static_cast<uint32_t*>(ws);
+  Groups g = pl.g;
+  g.rings = rings; g.vertices = reinterpret_cast<const int2*>(vertices); g.counts = counts;
+  u64* npts = pl.npts;
+  uint32_t *cnt = g.cnt, *off = g.off, *large = pl.large, *grouped = g.grouped, *stage_at = pl.stage_at, *stage = pl.stage;
   u64* stage_ctr = reinterpret_cast<u64*>(header + WS_STAGED);
-  const int2* v_in = reinterpret_cast<const int2*>(vertices);
+  const int2* v_in = g.vertices;
   int2* hv = reinterpret_cast<int2*>(hull_vertices);
 
   // only the header: every other word of the workspace is written by the call before the call reads it
-  hipError_t e = hipMemsetAsync(base, 0, 256, st);
+  hipError_t e = hipMemsetAsync(ws, 0, 256, st);
   if (e != hipSuccess) return (int)e;
   // ring and id counts are known on the device only: grids are sized by the limits and surplus waves and workgroups return
-  const unsigned g_ids = grid_for(max_objects, 256), g_idw = grid_for(max_objects, 4), g_rows = grid_for(max_rings, 256);
+  const unsigned g_ids = grid_for(max_objects, 256, MAX_GRID), g_idw = grid_for(max_objects, 4, MAX_GRID);
+  const unsigned g_rows = grid_for(max_rings, 256, MAX_GRID);
   const unsigned g_list = (unsigned)(max_objects < LIST_GRID ? max_objects : LIST_GRID);
-  rc = c3d_launch_lds<hull_init_kernel>(dim3(g_ids), dim3(256), 0, st, npts, cnt, cursor, (int)max_objects);
+  rc = c3d_launch_lds<hull_init_kernel>(dim3(g_ids), dim3(256), 0, st, npts, cnt, g.cursor, (int)max_objects);
   if (rc) return rc;
-  rc = c3d_launch_lds<hull_group_kernel>(dim3(g_rows), dim3(256), 0, st, rings, v_in, counts, (int)max_rings, (int)max_vertices,
-                                         (int)max_objects, npts, cnt, valid, header);
+  rc = c3d_launch_lds<hull_group_kernel>(dim3(g_rows), dim3(256), 0, st, g, npts, header);
   if (rc) return rc;
-  rc = c3d_launch_lds<hull_scan_kernel>(dim3(1), dim3(SCAN_T), SCAN_T / 64 * 4, st, (const uint32_t*)cnt, off, (const uint32_t*)header);
+  rc = c3d_launch_lds<hull_scan_kernel>(dim3(1), dim3(SCAN_T), SCAN_T / 64 * 4, st, g);
   if (rc) return rc;
-  rc = c3d_launch_lds<hull_scatter_kernel>(dim3(g_rows), dim3(256), 0, st, rings, counts, (int)max_rings, (const uint8_t*)valid,
-                                           (const uint32_t*)off, cursor, grouped);
+  rc = c3d_launch_lds<hull_scatter_kernel>(dim3(g_rows), dim3(256), 0, st, g);
   if (rc) return rc;
   rc = c3d_launch_lds<hull_wave_kernel<false>>(dim3(g_idw), dim3(256), 0, st, rings, v_in, (const u64*)npts, (const uint32_t*)cnt,
                                                (const uint32_t*)off, (const uint32_t*)grouped, large, header, (int)max_objects,

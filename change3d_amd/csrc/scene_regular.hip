@@ -21,6 +21,7 @@
 //                  the ring's own place start' (the same code, other pointers)
 #include <climits>
 
+#include "scene_host.h"
 #include "scene_wave.h"
 #include "../../include/change3d_hip.h"
 
@@ -52,7 +53,7 @@ struct Workspace {
 
 Workspace workspace_plan(int64_t max_rings, int64_t max_vertices) {
   Workspace w;
-  auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+  auto up = c3d_host::up256;
   w.np = 256;
   w.startp = w.np + up(max_rings * 4);
   w.large = w.startp + up(max_rings * 4);
@@ -255,7 +256,6 @@ __global__ __launch_bounds__(SCAN_T) void regular_scan_kernel(const int32_t* __r
   extern __shared__ u64 part[];                            // [SCAN_T / 64], then where the first row that does not fit
   u64& s_cut = part[SCAN_T / 64];                          // would have started
   const Limits l = limits_of(counts, counts_hull, max_rings, max_vertices, max_objects, max_hull_vertices);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0) s_cut = ~0ull;
   __syncthreads();
   u64 running = 0;
@@ -267,19 +267,8 @@ __global__ __launch_bounds__(SCAN_T) void regular_scan_kernel(const int32_t* __r
       n[j] = r < l.rows ? np[r] : 0;
       mine += (u64)n[j];
     }
-    u64 inc = mine;
-    for (int d = 1; d < 64; d <<= 1) {
-      const u64 t = shfl64(inc, lane >= d ? lane - d : lane);
-      if (lane >= d) inc += t;
-    }
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    u64 before = 0, all = 0;
-    for (int w = 0; w < SCAN_T / 64; ++w) {
-      before += w < wave ? part[w] : 0ull;
-      all += part[w];
-    }
-    u64 at = running + before + inc - mine;
+    u64 all;
+    u64 at = running + block_excl_scan64(mine, part, &all);
     for (int j = 0; j < SCAN_ROWS; ++j) {
       const int r = base + (int)threadIdx.x * SCAN_ROWS + j;
       if (r < l.rows) {
@@ -503,11 +492,6 @@ __global__ __launch_bounds__(BLOCK_T) void regular_write_block_kernel(const int3
   }
 }
 
-unsigned grid_for(int64_t items, int per_block) {
-  int64_t g = (items + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : (g > MAX_GRID ? MAX_GRID : g));
-}
-
 int refuse(int32_t max_rings, int32_t max_vertices, int32_t max_objects) {
   if (max_rings < 1 || max_vertices < 1 || max_objects < 1) return C3D_E_BADARG;
   return 0;
@@ -555,7 +539,7 @@ extern "C" int c3d_rings_regularize(const int32_t* rings, const int32_t* vertice
   hipError_t e = hipMemsetAsync(base, 0, 256, st);
   if (e != hipSuccess) return (int)e;
   // the ring count is known on the device only: grids are sized by max_rings and surplus waves and workgroups return
-  const unsigned g_wave = grid_for(max_rings, 4), g_block = grid_for(max_rings, 1);
+  const unsigned g_wave = c3d_host::grid_for(max_rings, 4, MAX_GRID), g_block = c3d_host::grid_for(max_rings, 1, MAX_GRID);
   rc = c3d_launch_lds<regular_count_wave_kernel>(dim3(g_wave), dim3(256), 0, st, rings, v_in, counts, (int)max_rings, (int)max_vertices,
                                                  hulls, hv, rects, counts_hull, (int)max_objects, (int)max_hull_vertices, np, kind, large,
                                                  header);

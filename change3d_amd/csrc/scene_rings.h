@@ -1,8 +1,10 @@
-// What csrc/scene_valid.hip and csrc/scene_conflicts.hip share: the pass that marks the used rows of a ring table, the
-// incomplete ids and K, the scan that settles which ids are complete and where their edges go, and the class of a pair of
-// live edges.  The rule is the header's (include/change3d_hip.h, c3d_rings_valid); both files include this one and neither
-// keeps a copy.  Everything is an integer: coordinate differences stay below 2^25 and every cross or dot product below 2^51,
-// so the doubles that carry them are exact and only their signs and orders are used.
+// What the consumers of a ring table share (csrc/scene_polis.hip for each of its two sides, csrc/scene_valid.hip,
+// csrc/scene_conflicts.hip): the pass that marks the used rows of a table, the incomplete ids and K, the scan that settles
+// which ids are complete and where their edges go, the passes that regroup the rows into per-id edge lists (place, gather),
+// and the class of a pair of live edges.  The rule is the header's (include/change3d_hip.h, c3d_rings_valid); the files
+// include this one and none keeps a copy: their __global__ kernels are thin wrappers around the ..._pass bodies below.
+// Everything is an integer: coordinate differences stay below 2^25 and every cross or dot product below 2^51, so the doubles
+// that carry them are exact and only their signs and orders are used.
 #pragma once
 #include <climits>
 
@@ -22,9 +24,6 @@ enum : uint8_t { ROW_SKIP = 0, ROW_USED = 1 };             // ROW_USED: valid, n
 enum { ID_INCOMPLETE = 1 };
 enum { PAIR_NONE = 0, PAIR_CROSS = 1, PAIR_OVERLAP = 2, PAIR_VV = 3, PAIR_VE = 4 };
 
-// words of the workspace header (zeroed by the call's memset) that the shared passes use
-enum { WS_K = 1, WS_JOBS = 2, WS_BIG = 3 };                // the largest id of a row, the jobs, the long rings
-
 // the table and the workspace arrays of the shared passes; a file's own view derives from it
 struct Rows {
   const int32_t* rings;
@@ -32,6 +31,9 @@ struct Rows {
   const int32_t* counts;
   int max_rings, max_vertices, max_ids;
   int64_t coord_max;                                       // 32768 << frac_bits
+  // two words of the workspace header (zeroed by the call's memset), wherever the file keeps them
+  uint32_t* top;                                           // the largest id of a row
+  uint32_t* n_big;                                         // the rings above BIG_RING
   // workspace
   uint8_t* kind;                                           // [max_rings]
   uint32_t* big;                                           // [max_rings] the rows of the rings above BIG_RING, in any order
@@ -82,7 +84,7 @@ __device__ __forceinline__ bool live_of(int4 e) { return e.x != e.z || e.y != e.
 // --------------------------------------------------------------------------------------------------------------- rows
 // A wave per ring row (256 threads, r uniform over the wave): classifies the row and adds it to its id (ring count, vertex
 // count, the incomplete mark); the rings above BIG_RING vertices are only listed.
-__device__ __forceinline__ void rows_pass(const Rows& s, uint32_t* __restrict__ header) {
+__device__ __forceinline__ void rows_pass(const Rows& s) {
   const int rows = rows_of(s), lane = threadIdx.x & 63;
   const int64_t vlimit = clampi(s.counts[3], 0, s.max_vertices);
   // what a wave adds to an id is kept in registers while the id stays the same (the holes of a scene-filling object are
@@ -101,7 +103,7 @@ __device__ __forceinline__ void rows_pass(const Rows& s, uint32_t* __restrict__ 
         bad = __any(out);
       }
       // a longer ring is counted now and checked by the next kernel: a bad coordinate there makes the id incomplete
-      if (!bad && n > BIG_RING && lane == 0) s.big[atomicAdd(header + WS_BIG, 1u)] = (uint32_t)r;
+      if (!bad && n > BIG_RING && lane == 0) s.big[atomicAdd(s.n_big, 1u)] = (uint32_t)r;
       top = id > top ? id : top;
       if (bad) {
         if (lane == 0) atomicOr(s.id_flags + (id - 1), (uint32_t)ID_INCOMPLETE);
@@ -127,13 +129,14 @@ __device__ __forceinline__ void rows_pass(const Rows& s, uint32_t* __restrict__ 
       atomicAdd(s.id_rings + (held - 1), held_rings);
       atomicAdd(s.id_verts + (held - 1), held_verts);
     }
-    if (top) atomicMax(header + WS_K, (uint32_t)top);
+    if (top) atomicMax(s.top, (uint32_t)top);
   }
 }
 
 // the coordinates of the rings above BIG_RING vertices, which rows_pass only lists: many workgroups of 256, a chunk each
-__device__ __forceinline__ void check_big_pass(const Rows& s, const uint32_t* __restrict__ header) {
-  const uint32_t n_big = min(header[WS_BIG], (uint32_t)s.max_rings);
+__device__ __forceinline__ uint32_t big_of(const Rows& s) { return min(*s.n_big, (uint32_t)s.max_rings); }
+__device__ __forceinline__ void check_big_pass(const Rows& s) {
+  const uint32_t n_big = big_of(s);
   for (uint32_t li = 0; li < n_big; ++li) {
     const int r = (int)s.big[li];
     const int id = s.rings[(int64_t)r * 8], n = s.rings[(int64_t)r * 8 + 2];
@@ -148,9 +151,10 @@ __device__ __forceinline__ void check_big_pass(const Rows& s, const uint32_t* __
 // One workgroup of SCAN_T threads, `part` = u64 [2][SCAN_T / 64] of LDS: exclusive scans over the ids up to the largest one
 // seen.  An id with more than RING_LIMIT rings, or whose edges no longer fit below max_vertices (only tables whose rows share
 // vertices get there), becomes incomplete and takes no room.
-__device__ __forceinline__ void ids_pass(const Rows& s, const uint32_t* __restrict__ header, u64 (*part)[SCAN_T / 64]) {
+__device__ __forceinline__ int top_of(const Rows& s) { return clampi((int)*s.top, 0, s.max_ids); }
+__device__ __forceinline__ void ids_pass(const Rows& s, u64 (*part)[SCAN_T / 64]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int top = clampi((int)header[WS_K], 0, s.max_ids);   // the ids above it have no row: their words stay 0
+  const int top = top_of(s);                               // the ids above it have no row: their words stay 0
   u64 run_r = 0, run_v = 0;
   for (int base = 0; base < top; base += SCAN_T) {
     const int i = base + (int)threadIdx.x;
@@ -191,6 +195,93 @@ __device__ __forceinline__ void ids_pass(const Rows& s, const uint32_t* __restri
     run_r += ar;
     run_v += av;
     __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------ place, gather
+// The rows regrouped into one edge list per id, in row order.  What is written per edge is the file's: a writer W with
+//   w.edge(at, before, n, a, b)   edge (a, b) of a ring of n edges that starts `before` edges into its id; `at` = its place
+//                                 among the edges of all ids; returns whether the file counts the edge (W::COUNTS only)
+//   w.counted(id, c)              one lane per wave and ring: c edges of the id were counted (W::COUNTS only)
+struct Lists : Rows {
+  uint2* list;                                             // [max_rings] (ring row, its n) grouped by id
+  uint32_t* row_at;                                        // [max_rings] where a ring above BIG_RING goes within its id
+  uint32_t* id_claim;                                      // [max_ids]
+};
+
+// a thread per row: claims a slot in the ring list of its id (the order of the list varies and is never used)
+__device__ __forceinline__ void place_pass(const Lists& s) {
+  const int rows = rows_of(s);
+  for (int r = blockIdx.x * 256 + (int)threadIdx.x; r < rows; r += gridDim.x * 256) {
+    if (s.kind[r] != ROW_USED) continue;
+    const int id = s.rings[(int64_t)r * 8];
+    const uint32_t k = s.id_rings[id - 1];                 // 0: the id became incomplete
+    if (!k) continue;
+    const uint32_t slot = atomicAdd(s.id_claim + (id - 1), 1u);
+    if (slot < k) s.list[(u64)s.id_list[id - 1] + slot] = make_uint2((uint32_t)r, (uint32_t)s.rings[(int64_t)r * 8 + 2]);
+  }
+}
+
+// a wave per row (256 threads): the row's place among the edges of its id = the n of the listed rings with a smaller row
+// index (an integer sum); then its edges go to that place.  A ring above BIG_RING only gets its place here
+template <class W>
+__device__ __forceinline__ void gather_pass(const Lists& s, const W& w) {
+  const int rows = rows_of(s), lane = threadIdx.x & 63;
+  for (int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6); r < rows; r += gridDim.x * 4) {   // r is uniform over the wave
+    if (s.kind[r] != ROW_USED) continue;
+    const int id = s.rings[(int64_t)r * 8], n = s.rings[(int64_t)r * 8 + 2];
+    const int64_t start = s.rings[(int64_t)r * 8 + 1];
+    const int k = (int)s.id_rings[id - 1];                 // at most RING_LIMIT
+    if (!k) continue;
+    const uint2* list = s.list + s.id_list[id - 1];
+    u64 before = 0;                                        // edges of the id's rings with a smaller row index
+    for (int j = lane; j < k; j += 64) {
+      const uint2 q = list[j];
+      if (q.x < (uint32_t)r) before += (u64)q.y;
+    }
+    before = wave_sum64(before);
+    const u64 total = s.id_verts[id - 1];
+    if (before + (u64)n > total) continue;                 // cannot happen: the sums are those of rows_pass
+    if (n > BIG_RING) {                                    // copied by gather_big_pass
+      if (lane == 0) s.row_at[r] = (uint32_t)before;
+      continue;
+    }
+    const u64 at = (u64)s.id_start[id - 1] + before;       // id_start + total <= max_vertices
+    if constexpr (W::COUNTS) {
+      uint32_t c = 0;
+      for (int j0 = 0; j0 < n; j0 += 64) {                 // uniform trip count: the ballot sees every lane
+        const int j = j0 + lane;
+        bool hit = false;
+        if (j < n) hit = w.edge(at + j, before, n, s.vertices[start + j], s.vertices[start + (j + 1 < n ? j + 1 : 0)]);
+        c += (uint32_t)__popcll(__ballot(hit));
+      }
+      if (c && lane == 0) w.counted(id, c);
+    } else {
+      for (int j = lane; j < n; j += 64) w.edge(at + j, before, n, s.vertices[start + j], s.vertices[start + (j + 1 < n ? j + 1 : 0)]);
+    }
+  }
+}
+
+// the same for the rings above BIG_RING, whose place gather_pass left in row_at: many workgroups of 256, a chunk each
+template <class W>
+__device__ __forceinline__ void gather_big_pass(const Lists& s, const W& w) {
+  const uint32_t n_big = big_of(s);
+  for (uint32_t li = 0; li < n_big; ++li) {
+    const int r = (int)s.big[li];
+    if (s.kind[r] != ROW_USED) continue;
+    const int id = s.rings[(int64_t)r * 8], n = s.rings[(int64_t)r * 8 + 2];
+    const int64_t start = s.rings[(int64_t)r * 8 + 1];
+    if (!s.id_rings[id - 1]) continue;                     // the id became incomplete
+    const u64 before = s.row_at[r];
+    if (before + (u64)n > s.id_verts[id - 1]) continue;    // cannot happen
+    const u64 at = (u64)s.id_start[id - 1] + before;
+    uint32_t c = 0;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256)
+      c += w.edge(at + j, before, n, s.vertices[start + j], s.vertices[start + (j + 1 < n ? j + 1 : 0)]) ? 1u : 0u;
+    if constexpr (W::COUNTS) {
+      c = wave_sum32(c);
+      if (c && (threadIdx.x & 63) == 0) w.counted(id, c);
+    }
   }
 }
 

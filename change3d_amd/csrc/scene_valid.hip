@@ -5,8 +5,8 @@
 // are exact and only their signs and orders are used.  No workgroup waits for another, nothing is read back, every loop is
 // capped, and every sum is an integer atomic or a ballot count, whose result does not depend on their order.
 //
-// Steps 1-4 regroup the rows into per-id edge lists as csrc/scene_polis.hip does for each of its two sides (one side here, no
-// common unit; DESIGN.md says why the steps are repeated and not shared):
+// Steps 1-4 regroup the rows into per-id edge lists; their bodies are csrc/scene_rings.h's, shared by every consumer of a
+// ring table:
 //
 //   1 rows     a wave per ring row: classifies the row and adds it to its id (ring count, vertex count, the incomplete mark)
 //     check    the coordinates of the rings above BIG_RING vertices, which kernel 1 only lists: many workgroups, a chunk each
@@ -25,14 +25,14 @@
 //              ballot) or the sums of the id's jobs; writes the last four columns of the row
 //   8 tail     one workgroup: counts and totals
 #include <climits>
-#include <type_traits>
 
+#include "scene_host.h"
 #include "scene_rings.h"
 
 namespace {
 
-using namespace c3d_rings;                                 // the rows pass, the ids scan and pair_class: shared with
-                                                           // csrc/scene_conflicts.hip
+using namespace c3d_rings;
+using c3d_host::grid_for;
 
 constexpr int WAVE_LIMIT = 64;                             // edges of an id in the wave tier: a lane each
 constexpr int CHUNK = 256;                                 // edges of a chunk: a thread each
@@ -42,11 +42,10 @@ constexpr int MAX_GRID = 4096;
 
 enum : uint8_t { TIER_NONE = 0, TIER_WAVE = 1, TIER_JOB = 2 };
 
-// the workspace header is 256 bytes, zeroed by the call's memset; its words are those of scene_rings.h
-struct Tab : Rows {
-  uint2* list;                                             // [max_rings] (ring row, its n) grouped by id
-  uint32_t* row_at;                                        // [max_rings] where such a ring's edges go within its id
-  uint32_t* id_claim;                                      // [max_ids]
+// words of the workspace header (256 bytes, zeroed by the call's memset)
+enum { WS_K = 1, WS_JOBS = 2, WS_BIG = 3 };                // the largest id of a row, the jobs, the long rings
+
+struct Tab : Lists {
   uint32_t* id_degen;                                      // [max_ids] edges with a == b
   u64* acc;                                                // [max_ids][4] what the jobs add up: cross, overlap, vv, ve
   int4* edges;                                             // [max_vertices] (a.x, a.y, b.x, b.y) grouped by id
@@ -56,49 +55,41 @@ struct Tab : Rows {
 };
 
 struct Plan {
-  Tab t;                                                   // offsets until bind() adds the base
+  Tab t;
   int64_t zero_bytes, job_cap, bytes;
 };
 
-Plan plan_of(int64_t max_rings, int64_t max_vertices, int64_t max_ids) {
+// ws: the workspace, or nullptr where only the sizes are asked for
+Plan plan_of(void* ws, int64_t max_rings, int64_t max_vertices, int64_t max_ids) {
   Plan pl{};
-  auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-  int64_t at = 256;
-  auto take = [&](auto*& p, int64_t bytes) {
-    p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(at);
-    at += up(bytes);
-  };
+  c3d_host::Layout l{static_cast<char*>(ws), 256};
   Tab& t = pl.t;
-  take(t.id_rings, max_ids * 4);                           // zeroed part first
-  take(t.id_verts, max_ids * 8);
-  take(t.id_flags, max_ids * 4);
-  take(t.id_claim, max_ids * 4);
-  take(t.id_degen, max_ids * 4);
-  take(t.acc, max_ids * 32);
-  pl.zero_bytes = at;
-  take(t.kind, max_rings);
-  take(t.list, max_rings * 8);
-  take(t.big, max_rings * 4);
-  take(t.row_at, max_rings * 4);
-  take(t.id_list, max_ids * 4);
-  take(t.id_start, max_ids * 4);
-  take(t.edges, max_vertices * 16);
-  take(t.meta, max_vertices * 8);
-  take(t.tier, max_ids);
-  take(t.job_start, max_ids * 8);
+  l.take(t.id_rings, max_ids * 4);                         // zeroed part first
+  l.take(t.id_verts, max_ids * 8);
+  l.take(t.id_flags, max_ids * 4);
+  l.take(t.id_claim, max_ids * 4);
+  l.take(t.id_degen, max_ids * 4);
+  l.take(t.acc, max_ids * 32);
+  pl.zero_bytes = l.at;
+  l.take(t.kind, max_rings);
+  l.take(t.list, max_rings * 8);
+  l.take(t.big, max_rings * 4);
+  l.take(t.row_at, max_rings * 4);
+  l.take(t.id_list, max_ids * 4);
+  l.take(t.id_start, max_ids * 4);
+  l.take(t.edges, max_vertices * 16);
+  l.take(t.meta, max_vertices * 8);
+  l.take(t.tier, max_ids);
+  l.take(t.job_start, max_ids * 8);
   // the chunks of the ids add up to at most this whatever the table holds: the edges of all ids fit in max_vertices
   pl.job_cap = (max_vertices + CHUNK - 1) / CHUNK + max_ids;
-  pl.bytes = at;
+  pl.bytes = l.at;
   t.max_rings = (int)max_rings; t.max_vertices = (int)max_vertices; t.max_ids = (int)max_ids;
+  if (ws) {
+    t.top = static_cast<uint32_t*>(ws) + WS_K;
+    t.n_big = static_cast<uint32_t*>(ws) + WS_BIG;
+  }
   return pl;
-}
-
-template <class T> void rebase(T*& p, char* base) { p = reinterpret_cast<T*>(base + reinterpret_cast<intptr_t>(p)); }
-void bind(Tab& t, char* base) {
-  rebase(t.kind, base); rebase(t.list, base); rebase(t.big, base); rebase(t.row_at, base); rebase(t.id_rings, base);
-  rebase(t.id_verts, base); rebase(t.id_flags, base); rebase(t.id_claim, base); rebase(t.id_degen, base); rebase(t.acc, base);
-  rebase(t.id_list, base); rebase(t.id_start, base); rebase(t.edges, base); rebase(t.meta, base); rebase(t.tier, base);
-  rebase(t.job_start, base);
 }
 
 // edges at the places i and j of an id's list, with the packed (place of the ring, n) of each
@@ -108,111 +99,42 @@ __device__ __forceinline__ bool adjacent_of(uint32_t i, u64 mi, uint32_t j, u64 
   return d == 1u || d == n - 1u;
 }
 
-// --------------------------------------------------------------------------------------------------------------- 1: rows
-__global__ __launch_bounds__(256) void valid_rows_kernel(Tab s, uint32_t* __restrict__ header) {
-  rows_pass(s, header);
-}
-
-__global__ __launch_bounds__(256) void valid_check_big_kernel(Tab s, const uint32_t* __restrict__ header) {
-  check_big_pass(s, header);
-}
-
-// ---------------------------------------------------------------------------------------------------------------- 2: ids
-// An id with more than RING_LIMIT rings, or whose edges no longer fit below max_vertices (only tables whose rows share
-// vertices get there), becomes incomplete and takes no room.
-__global__ __launch_bounds__(SCAN_T) void valid_ids_kernel(Tab s, const uint32_t* __restrict__ header) {
+// ------------------------------------------------------------------------------------------- 1 - 4: scene_rings.h's passes
+__global__ __launch_bounds__(256) void valid_rows_kernel(Tab s) { rows_pass(s); }
+__global__ __launch_bounds__(256) void valid_check_big_kernel(Tab s) { check_big_pass(s); }
+__global__ __launch_bounds__(SCAN_T) void valid_ids_kernel(Tab s) {
   extern __shared__ u64 part_ids[];                        // [2][SCAN_T / 64]
-  ids_pass(s, header, reinterpret_cast<u64(*)[SCAN_T / 64]>(part_ids));
+  ids_pass(s, reinterpret_cast<u64(*)[SCAN_T / 64]>(part_ids));
 }
 
-// -------------------------------------------------------------------------------------------------------------- 3: place
-__global__ __launch_bounds__(256) void valid_place_kernel(Tab s, const uint32_t* __restrict__ header, int64_t* __restrict__ valid) {
-  const int rows = rows_of(s);
+__global__ __launch_bounds__(256) void valid_place_kernel(Tab s, int64_t* __restrict__ valid) {
   // the rows past the last id: 8 words each, a thread per word
   const int64_t words = (int64_t)s.max_ids * 8;
-  for (int64_t w = (int64_t)clampi((int)header[WS_K], 0, s.max_ids) * 8 + (int64_t)blockIdx.x * 256 + threadIdx.x; w < words;
-       w += (int64_t)gridDim.x * 256)
+  for (int64_t w = (int64_t)top_of(s) * 8 + (int64_t)blockIdx.x * 256 + threadIdx.x; w < words; w += (int64_t)gridDim.x * 256)
     valid[w] = 0;
-  for (int r = blockIdx.x * 256 + (int)threadIdx.x; r < rows; r += gridDim.x * 256) {
-    if (s.kind[r] != ROW_USED) continue;
-    const int id = s.rings[(int64_t)r * 8];
-    const uint32_t k = s.id_rings[id - 1];                 // 0: the id became incomplete
-    if (!k) continue;
-    const uint32_t slot = atomicAdd(s.id_claim + (id - 1), 1u);
-    if (slot < k) s.list[(u64)s.id_list[id - 1] + slot] = make_uint2((uint32_t)r, (uint32_t)s.rings[(int64_t)r * 8 + 2]);
-  }
+  place_pass(s);
 }
 
-// ------------------------------------------------------------------------------------------------------------- 4: gather
-__global__ __launch_bounds__(256) void valid_gather_kernel(Tab s) {
-  const int rows = rows_of(s), lane = threadIdx.x & 63;
-  for (int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6); r < rows; r += gridDim.x * 4) {   // r is uniform over the wave
-    if (s.kind[r] != ROW_USED) continue;
-    const int id = s.rings[(int64_t)r * 8], n = s.rings[(int64_t)r * 8 + 2];
-    const int64_t start = s.rings[(int64_t)r * 8 + 1];
-    const int k = (int)s.id_rings[id - 1];                 // at most RING_LIMIT
-    if (!k) continue;
-    const uint2* list = s.list + s.id_list[id - 1];
-    u64 before = 0;                                        // edges of the id's rings with a smaller row index
-    for (int j = lane; j < k; j += 64) {
-      const uint2 q = list[j];
-      if (q.x < (uint32_t)r) before += (u64)q.y;
-    }
-    for (int o = 32; o > 0; o >>= 1) before += shfl64(before, lane ^ o);
-    const u64 total = s.id_verts[id - 1];
-    if (before + (u64)n > total) continue;                 // cannot happen: the sums are those of kernel 1
-    if (n > BIG_RING) {                                    // copied by the next kernel
-      if (lane == 0) s.row_at[r] = (uint32_t)before;
-      continue;
-    }
-    const u64 at = (u64)s.id_start[id - 1] + before;       // id_start + total <= max_vertices
-    const u64 meta = before | ((u64)(uint32_t)n << 32);
-    uint32_t degen = 0;
-    for (int j0 = 0; j0 < n; j0 += 64) {                   // uniform trip count: the ballot sees every lane
-      const int j = j0 + lane;
-      bool dead = false;
-      if (j < n) {
-        const int2 a = s.vertices[start + j], b = s.vertices[start + (j + 1 < n ? j + 1 : 0)];
-        s.edges[at + j] = make_int4(a.x, a.y, b.x, b.y);
-        s.meta[at + j] = meta;
-        dead = a.x == b.x && a.y == b.y;
-      }
-      degen += (uint32_t)__popcll(__ballot(dead));
-    }
-    if (degen && lane == 0) atomicAdd(s.id_degen + (id - 1), degen);
+// an edge as it is, next to it the packed (place of the ring, n) that adjacency needs; the degenerate ones are counted
+struct EdgeWriter {
+  static constexpr bool COUNTS = true;
+  int4* edges;
+  u64* meta;
+  uint32_t* id_degen;
+  __device__ __forceinline__ bool edge(u64 at, u64 before, int n, int2 a, int2 b) const {
+    edges[at] = make_int4(a.x, a.y, b.x, b.y);
+    meta[at] = before | ((u64)(uint32_t)n << 32);
+    return a.x == b.x && a.y == b.y;
   }
-}
-
-__global__ __launch_bounds__(256) void valid_gather_big_kernel(Tab s, const uint32_t* __restrict__ header) {
-  const uint32_t n_big = min(header[WS_BIG], (uint32_t)s.max_rings);
-  const int lane = threadIdx.x & 63;
-  for (uint32_t li = 0; li < n_big; ++li) {
-    const int r = (int)s.big[li];
-    if (s.kind[r] != ROW_USED) continue;
-    const int id = s.rings[(int64_t)r * 8], n = s.rings[(int64_t)r * 8 + 2];
-    const int64_t start = s.rings[(int64_t)r * 8 + 1];
-    if (!s.id_rings[id - 1]) continue;                     // the id became incomplete
-    const u64 before = s.row_at[r];
-    if (before + (u64)n > s.id_verts[id - 1]) continue;    // cannot happen
-    const u64 at = (u64)s.id_start[id - 1] + before;
-    const u64 meta = before | ((u64)(uint32_t)n << 32);
-    uint32_t degen = 0;
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-      const int2 a = s.vertices[start + j], b = s.vertices[start + (j + 1 < n ? j + 1 : 0)];
-      s.edges[at + j] = make_int4(a.x, a.y, b.x, b.y);
-      s.meta[at + j] = meta;
-      degen += (a.x == b.x && a.y == b.y) ? 1u : 0u;
-    }
-    for (int o = 32; o > 0; o >>= 1) degen += (uint32_t)__shfl((int)degen, lane ^ o);
-    if (degen && lane == 0) atomicAdd(s.id_degen + (id - 1), degen);
-  }
-}
+  __device__ __forceinline__ void counted(int id, uint32_t c) const { atomicAdd(id_degen + (id - 1), c); }
+};
+__global__ __launch_bounds__(256) void valid_gather_kernel(Tab s) { gather_pass(s, EdgeWriter{s.edges, s.meta, s.id_degen}); }
+__global__ __launch_bounds__(256) void valid_gather_big_kernel(Tab s) { gather_big_pass(s, EdgeWriter{s.edges, s.meta, s.id_degen}); }
 
 // --------------------------------------------------------------------------------------------------------------- 5: plan
 __global__ __launch_bounds__(SCAN_T) void valid_plan_kernel(Tab s, int64_t max_id_work, int64_t job_cap, uint32_t* __restrict__ header,
                                                             int64_t* __restrict__ valid) {
   extern __shared__ u64 part[];                            // [SCAN_T / 64]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int top = clampi((int)header[WS_K], 0, s.max_ids);
   u64 running = 0;
   for (int base = 0; base < top; base += SCAN_T) {
@@ -230,20 +152,10 @@ __global__ __launch_bounds__(SCAN_T) void valid_plan_kernel(Tab s, int64_t max_i
       else if (m * (m - 1) / 2 > (u64)max_id_work) flag = 3;
       else if (nv > (u64)WAVE_LIMIT) jobs = (nv + CHUNK - 1) / CHUNK;
     }
-    u64 inc = jobs;
-    for (int d = 1; d < 64; d <<= 1) {
-      const u64 t = shfl64(inc, lane >= d ? lane - d : lane);
-      if (lane >= d) inc += t;
-    }
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    u64 before = 0, all = 0;
-    for (int w = 0; w < SCAN_T / 64; ++w) {
-      before += w < wave ? part[w] : 0ull;
-      all += part[w];
-    }
+    u64 all;
+    const u64 before = block_excl_scan64(jobs, part, &all);
     if (i < top) {
-      s.job_start[i] = running + before + inc - jobs;      // the chunks of all ids stay below job_cap: see plan_of
+      s.job_start[i] = running + before;                   // the chunks of all ids stay below job_cap: see plan_of
       s.tier[i] = flag ? TIER_NONE : (jobs ? TIER_JOB : TIER_WAVE);
       int64_t* row = valid + (int64_t)i * 8;
       row[0] = flag; row[1] = rings; row[2] = (int64_t)m; row[3] = degen;
@@ -399,11 +311,6 @@ __global__ __launch_bounds__(256) void valid_tail_kernel(Tab s, const uint32_t* 
   }
 }
 
-unsigned grid_for(int64_t items, int per_block) {
-  int64_t g = (items + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : (g > MAX_GRID ? MAX_GRID : g));
-}
-
 int refuse(int32_t max_rings, int32_t max_vertices, int32_t max_ids) {
   if (max_rings < 1 || max_vertices < 1 || max_ids < 1) return C3D_E_BADARG;
   return 0;
@@ -423,7 +330,7 @@ extern "C" void c3d_rings_valid_limits(int32_t out[5]) {
 extern "C" int64_t c3d_rings_valid_ws_bytes(int32_t max_rings, int32_t max_vertices, int32_t max_ids) {
   const int rc = refuse(max_rings, max_vertices, max_ids);
   if (rc) return rc;
-  return plan_of(max_rings, max_vertices, max_ids).bytes;
+  return plan_of(nullptr, max_rings, max_vertices, max_ids).bytes;
 }
 
 extern "C" int c3d_rings_valid(const int32_t* rings, const int32_t* vertices, const int32_t* counts_in, int32_t max_rings,
@@ -433,39 +340,38 @@ extern "C" int c3d_rings_valid(const int32_t* rings, const int32_t* vertices, co
   if (frac_bits < 0 || frac_bits > 8 || max_id_work < 0) return C3D_E_BADARG;
   int rc = refuse(max_rings, max_vertices, max_ids);
   if (rc) return rc;
-  Plan pl = plan_of(max_rings, max_vertices, max_ids);
+  const Plan pl = plan_of(ws, max_rings, max_vertices, max_ids);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
   Tab s = pl.t;
-  bind(s, base);
   s.rings = rings; s.vertices = reinterpret_cast<const int2*>(vertices); s.counts = counts_in;
   s.coord_max = (int64_t)COORD_UNIT << frac_bits;
-  uint32_t* header = reinterpret_cast<uint32_t*>(base);
+  uint32_t* header = static_cast<uint32_t*>(ws);
+  const uint32_t* hdr = header;
 
   // the header, the per-id sums and what the jobs add into: every other word of the workspace is written by the call before
   // the call reads it
-  hipError_t e = hipMemsetAsync(base, 0, (size_t)pl.zero_bytes, st);
+  hipError_t e = hipMemsetAsync(ws, 0, (size_t)pl.zero_bytes, st);
   if (e != hipSuccess) return (int)e;
   // the ring and id counts are known on the device only: grids are sized by the maxima and surplus workgroups return
-  rc = c3d_launch_lds<valid_rows_kernel>(dim3(grid_for(max_rings, 4)), dim3(256), 0, st, s, header);
+  const unsigned g_rows = grid_for(max_rings, 4, MAX_GRID), g_big = grid_for(max_vertices, 4 * 256, 1024);
+  rc = c3d_launch_lds<valid_rows_kernel>(dim3(g_rows), dim3(256), 0, st, s);
   if (rc) return rc;
-  const unsigned g_big = grid_for(max_vertices, 4 * 256) < 1024u ? grid_for(max_vertices, 4 * 256) : 1024u;
-  rc = c3d_launch_lds<valid_check_big_kernel>(dim3(g_big), dim3(256), 0, st, s, (const uint32_t*)header);
+  rc = c3d_launch_lds<valid_check_big_kernel>(dim3(g_big), dim3(256), 0, st, s);
   if (rc) return rc;
-  rc = c3d_launch_lds<valid_ids_kernel>(dim3(1), dim3(SCAN_T), 2 * (SCAN_T / 64) * 8, st, s, (const uint32_t*)header);
+  rc = c3d_launch_lds<valid_ids_kernel>(dim3(1), dim3(SCAN_T), 2 * (SCAN_T / 64) * 8, st, s);
   if (rc) return rc;
   const int64_t more_rows = (int64_t)max_ids * 8 > max_rings ? (int64_t)max_ids * 8 : max_rings;
-  rc = c3d_launch_lds<valid_place_kernel>(dim3(grid_for(more_rows, 256)), dim3(256), 0, st, s, (const uint32_t*)header, valid);
+  rc = c3d_launch_lds<valid_place_kernel>(dim3(grid_for(more_rows, 256, MAX_GRID)), dim3(256), 0, st, s, valid);
   if (rc) return rc;
-  rc = c3d_launch_lds<valid_gather_kernel>(dim3(grid_for(max_rings, 4)), dim3(256), 0, st, s);
+  rc = c3d_launch_lds<valid_gather_kernel>(dim3(g_rows), dim3(256), 0, st, s);
   if (rc) return rc;
-  rc = c3d_launch_lds<valid_gather_big_kernel>(dim3(g_big), dim3(256), 0, st, s, (const uint32_t*)header);
+  rc = c3d_launch_lds<valid_gather_big_kernel>(dim3(g_big), dim3(256), 0, st, s);
   if (rc) return rc;
   rc = c3d_launch_lds<valid_plan_kernel>(dim3(1), dim3(SCAN_T), (SCAN_T / 64) * 8, st, s, max_id_work, pl.job_cap, header, valid);
   if (rc) return rc;
-  rc = c3d_launch_lds<valid_jobs_kernel>(dim3(grid_for(pl.job_cap, 1)), dim3(BLOCK_T), (size_t)TILE * 24, st, s, (const uint32_t*)header);
+  rc = c3d_launch_lds<valid_jobs_kernel>(dim3(grid_for(pl.job_cap, 1, MAX_GRID)), dim3(BLOCK_T), (size_t)TILE * 24, st, s, hdr);
   if (rc) return rc;
-  rc = c3d_launch_lds<valid_score_kernel>(dim3(grid_for(max_ids, 4)), dim3(256), 0, st, s, (const uint32_t*)header, valid);
+  rc = c3d_launch_lds<valid_score_kernel>(dim3(grid_for(max_ids, 4, MAX_GRID)), dim3(256), 0, st, s, hdr, valid);
   if (rc) return rc;
-  return c3d_launch_lds<valid_tail_kernel>(dim3(1), dim3(256), 7 * 256 * 8, st, s, (const uint32_t*)header, (const int64_t*)valid, counts, totals);
+  return c3d_launch_lds<valid_tail_kernel>(dim3(1), dim3(256), 7 * 256 * 8, st, s, hdr, (const int64_t*)valid, counts, totals);
 }

@@ -89,6 +89,23 @@ __device__ __forceinline__ u64 block_excl_scan64(u64 v, u64* part, u64* all) {
   return before + inc - v;
 }
 
+// the same for 32-bit sums.  WAVES: the waves of the workgroup where the caller knows them, so that the loop over them unrolls
+template <int WAVES = 0>
+__device__ __forceinline__ uint32_t block_excl_scan32(uint32_t v, uint32_t* part, uint32_t* all) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = WAVES ? WAVES : (int)(blockDim.x >> 6);
+  uint32_t total;
+  const uint32_t excl = wave_excl_scan32(v, &total);
+  if (lane == 63) part[wave] = total;
+  __syncthreads();
+  uint32_t before = 0, sum = 0;
+  for (int w = 0; w < waves; ++w) {
+    before += w < wave ? part[w] : 0u;
+    sum += part[w];
+  }
+  *all = sum;
+  return before + excl;
+}
+
 // exclusive prefix maximum of v (>= -1) over the workgroup's threads; `all` = the maximum.  part as above
 __device__ __forceinline__ int block_excl_max32(int v, int* part, int* all) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;

@@ -2,7 +2,8 @@
 Everything is an integer and equality is exact, value for value.  The smallest shapes that reach each path: the hand-made
 table of every pair class, two rows of the survey of noisy masks, stars on both sides of the wave tier, stars whose chunk
 counts 1..5 cover the even and the odd job schedule, the c/2 offset, a partial last chunk and the LDS tile edge, one id of
-interleaved rings, the corners of the coordinate range at three frac_bits, every flag, the work cap at and below m (m - 1) / 2,
+interleaved rings, rings on both sides of the length that many workgroups share (checked and copied, and one whose pairs are
+evaluated), an id on each side of the ring limit, the corners of the coordinate range at three frac_bits, every flag, the work cap at and below m (m - 1) / 2,
 accumulation in stream order, a dirty workspace and another stream, refusals, and three negative controls."""
 import functools
 import os
@@ -111,6 +112,44 @@ def test_stars_of_one_to_five_chunks(n):
     got = _check(c)
     assert got["valid"][0].tolist() == [0, 1, n, 0, crossings, 0, 0, 0]
     assert "valid_tail_kernel" in ops.last_kernel()
+
+
+def test_one_ring_that_many_workgroups_share_with_its_pairs_evaluated():
+    """The pure-Python restatement needs minutes for this n, so the count asserted is the constructed n (k - 1); it was
+    confirmed once on the CPU with valid_reference.count_pairs at this n, radius and frac_bits."""
+    n = LIMITS()[4] + 1
+    c, crossings = _star_case(n)
+    rc, got = _call(K.tables(c), c["frac_bits"], c["max_ids"])
+    assert rc == 0
+    assert got["valid"][0].tolist() == [0, 1, n, 0, crossings, 0, 0, 0]
+
+
+def test_rings_on_both_sides_of_the_length_that_many_workgroups_share():
+    big = LIMITS()[4]
+    rings = [K.P.polygon(big, 1, radius=20000), K.P.square(30000, 30000, 50), K.P.polygon(big + 1, 2, radius=25000),
+             K.P.polygon(2 * big + 77, 3, radius=30000)]
+    rings[3][5000] = rings[3][4999]                          # one degenerate edge deep inside a ring that many workgroups copy
+    c = K.case(rings, ids=[1, 2, 3, 1], max_ids=4)           # id 1: a ring of the limit, then one of twice that, not contiguous
+    table = K.tables(c)
+    # the long ids come out over the work cap: their rows still carry rings, m and the degenerate count of the gather
+    got = _check(c, table=table, max_id_work=6)
+    assert got["valid"].tolist() == [[3, 2, 12364, 1, 0, 0, 0, 0], [0, 1, 4, 0, 0, 0, 0, 0], [3, 1, 4097, 0, 0, 0, 0, 0], [0] * 8]
+    assert got["counts"].tolist() == [1, 0, 0, 0, 2, 0, 0, 0]
+    table[1][int(table[0][3, 1]) + 2 * big + 50, 1] = -32769   # one coordinate out of range deep inside the longest ring
+    got = _check(c, table=table, max_id_work=6)
+    assert got["valid"][0].tolist() == [2, 0, 0, 0, 0, 0, 0, 0]
+    assert got["counts"].tolist() == [1, 0, 0, 1, 1, 0, 0, 0]
+
+
+def test_an_id_on_each_side_of_the_ring_limit():
+    limit = LIMITS()[3]
+    rings, ids = [], []
+    for k in range(2 * limit + 1):                           # id 1 gets `limit` rings, id 2 one more, interleaved
+        rings.append(K.P.square(12 * ((k // 2) % 256), 60 * ((k // 2) // 256) + 30 * (k % 2), 5))
+        ids.append(2 if k == 2 * limit else 1 + k % 2)
+    got = _check(K.case(rings, ids=ids, max_ids=3), max_id_work=6)
+    assert got["valid"].tolist() == [[3, 16384, 65536, 0, 0, 0, 0, 0], [2, 0, 0, 0, 0, 0, 0, 0], [0] * 8]
+    assert got["counts"].tolist() == [0, 0, 0, 1, 1, 0, 0, 0]
 
 
 def test_both_tiers_and_every_flag_in_one_table():
