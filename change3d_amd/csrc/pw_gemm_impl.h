@@ -183,8 +183,8 @@ __device__ __forceinline__ int64_t row_offset(const c3d_pw_args& a, uint32_t um)
     const uint32_t r = um - g * (uint32_t)a.rpg;
     return (int64_t)g * a.gstride + (int64_t)r * a.Kp;
   }
-  // STRIDE2: m = (bt, ho, wo) over output [BT][H/2][W/2]
-  const uint32_t Wo = (uint32_t)a.W >> 1, Ho = (uint32_t)a.H >> 1;
+  // STRIDE2: m = (bt, ho, wo) over output [BT][(H+1)/2][(W+1)/2] -- the plan's (H - 1) / 2 + 1, odd extents included
+  const uint32_t Wo = ((uint32_t)a.W + 1u) >> 1, Ho = ((uint32_t)a.H + 1u) >> 1;
   const uint32_t wo = um % Wo;
   const uint32_t t = um / Wo;
   const uint32_t ho = t % Ho;
@@ -893,7 +893,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
               const uint32_t h = t % (uint32_t)a.H;
               const uint32_t bt = t / (uint32_t)a.H;
               if (((w | h) & 1u) == 0u) {
-                const int64_t roff = (((int64_t)bt * (a.H >> 1) + (h >> 1)) * (a.W >> 1) + (w >> 1)) * Np + v_o * 8;
+                const int64_t roff = (((int64_t)bt * ((a.H + 1) >> 1) + (h >> 1)) * ((a.W + 1) >> 1) + (w >> 1)) * Np + v_o * 8;
                 float rv[8];
                 Vec8<T>::load(E1 + roff, rv);
 #pragma unroll

@@ -76,7 +76,7 @@ __device__ __forceinline__ int64_t q_row_offset(const c3d_pw_wgrad_args& a, int6
     const uint32_t r = (uint32_t)m - g * (uint32_t)a.rpg;
     return (int64_t)g * a.gstride + (int64_t)r * a.Kp;
   }
-  const uint32_t Wo = (uint32_t)a.W >> 1, Ho = (uint32_t)a.H >> 1;
+  const uint32_t Wo = ((uint32_t)a.W + 1u) >> 1, Ho = ((uint32_t)a.H + 1u) >> 1;   // the plan's (H - 1) / 2 + 1
   const uint32_t um = (uint32_t)m;
   const uint32_t wo = um % Wo;
   const uint32_t t = um / Wo;

@@ -21,7 +21,7 @@ constexpr int WB_SLOTS = 5;                              // batch samples a 64-r
 
 __device__ __forceinline__ int64_t wide_row_offset(const c3d_pw_args& a, int64_t m) {
   if (a.row_mode == C3D_ROWS_STRIDE2) {
-    const int64_t Wo = a.W >> 1, Ho = a.H >> 1;
+    const int64_t Wo = (a.W + 1) >> 1, Ho = (a.H + 1) >> 1;   // the plan's (H - 1) / 2 + 1, odd extents included
     const int64_t wo = m % Wo, t = m / Wo, ho = t % Ho, bt = t / Ho;
     return ((bt * a.H + 2 * ho) * a.W + 2 * wo) * a.Kp;
   }
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256) void pw_wide_kernel(const c3d_pw_args a) {
           const int64_t w_ = m % a.W, t_ = m / a.W, h_ = t_ % a.H, bt = t_ / a.H;
           if (((w_ | h_) & 1) == 0) {
             float rv[8];
-            Vec8<T>::load(E1 + ((bt * (a.H >> 1) + (h_ >> 1)) * (a.W >> 1) + (w_ >> 1)) * Np + c0, rv);
+            Vec8<T>::load(E1 + ((bt * ((a.H + 1) >> 1) + (h_ >> 1)) * ((a.W + 1) >> 1) + (w_ >> 1)) * Np + c0, rv);
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] += rv[j];
           }

@@ -249,6 +249,14 @@ struct FoldPlan {
 inline int make_fold_plan(const c3d_stage_desc* d, const Plan& P, FoldPlan& Q) {
   const int n = d->n_blocks;
   Q.f.resize(n); Q.e.resize(n);
+  // A geometry the eval launches cannot take is refused here, at the caller's first contact with it (c3d_stage_fold_bytes), not
+  // by a launch in the middle of the pass: the narrow pointwise kernel (channel counts up to 224) takes one SE gate per 16-row
+  // sub-tile, so conv_c of an SE block needs T * Ho * Wo to be a multiple of 16 (c3d_pw_gemm answers C3D_E_BADARG otherwise,
+  // after conv_a and conv_b ran)
+  for (int i = 0; i < n; ++i) {
+    const BlkGeom& G = P.g[i];
+    if (G.se && G.Cip <= 224 && G.Cop <= 224 && (((int64_t)d->T * G.Ho * G.Wo) & 15)) return C3D_E_UNSUPPORTED;
+  }
   Carver cf;
   for (int i = 0; i < n; ++i) {
     const BlkGeom& G = P.g[i];

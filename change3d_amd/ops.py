@@ -716,6 +716,12 @@ class StageBinding:
 def stage_fold_sizes(binding):
     a, b = C.c_int64(), C.c_int64()
     rc = L.lib().c3d_stage_fold_bytes(C.byref(binding.desc), C.byref(a), C.byref(b))
+    if rc == -2:   # C3D_E_UNSUPPORTED
+        binding.sizes()   # make_plan's own refusal (a tensor too large for the narrow kernels) raises with its own message
+        d = binding.desc  # else make_fold_plan's (csrc/stage_plan.h)
+        raise L.Change3DHipError(
+            f"the folded-BatchNorm inference path does not take the stage geometry B={d.B} T={d.T} {d.H}x{d.W}: an SE block of "
+            f"up to 224 channels needs T*Ho*Wo (output rows per sample) to be a multiple of 16")
     if rc != 0:
         raise L.Change3DHipError(f"c3d_stage_fold_bytes failed with code {rc}")
     return int(a.value), int(b.value)
